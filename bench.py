@@ -21,7 +21,9 @@ Secondary legs (rank 0 of a 1-GPU run only, after the timed region): BASELINE co
 configs[2] (D=512 full rank), configs[3] (MultivariateT + DIS), configs[4] (logistic regression), the optimiser loop,
 the CPU baseline and the parity check.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --steps K times exactly K headline evaluations; --dump-outputs DIR writes what the
+last of them returned (the value and the gradient, float64 .npy) for comparing two builds output for output: the
+target, theta and noise are seeded, so the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -93,8 +95,9 @@ def timed_blocks(run_block, sync, group, steps, min_total_s=MIN_TIMED_S, max_blo
     return times
 
 
-def fullrank_leg(eng, vb, _lib, group, d, steps, warmup, scaling='weak', slot0=40, ring=8, profile=True):
-    """FullRankGaussian + ExclusiveKL on the correlated-Gaussian target with the parameter resident on the device."""
+def fullrank_leg(eng, vb, _lib, group, d, steps, warmup, scaling='weak', slot0=40, ring=8, profile=True, max_blocks=1):
+    """FullRankGaussian + ExclusiveKL on the correlated-Gaussian target with the parameter resident on the device.
+    ``max_blocks=1`` (the headline): exactly ``steps`` timed evaluations, one block."""
     world, rank = group.world, group.rank
     if scaling == 'strong':
         from viabel_amd.objectives import shard_rows
@@ -115,7 +118,8 @@ def fullrank_leg(eng, vb, _lib, group, d, steps, warmup, scaling='weak', slot0=4
     eng.sync()
     run(warmup)
     eng.sync()
-    times = timed_blocks(run, eng.sync, group, steps)
+    times = timed_blocks(run, eng.sync, group, steps, max_blocks=max_blocks)
+    value, grad = eng.fullrank_get(d)            # what the last timed evaluation returns to a caller
     kern = {}
     if profile:
         # per-kernel durations: the same K steps once more with hipExtLaunchKernel start / stop events on the three
@@ -134,7 +138,6 @@ def fullrank_leg(eng, vb, _lib, group, d, steps, warmup, scaling='weak', slot0=4
             n_l, _, ms = eng.profile_read(reset=True, kernel=k)
             kern[name] = (n_l, 1e3 * ms / max(1, n_l))
         eng.profile_enable(False)
-    value, grad = eng.fullrank_get(d)
     sec_per_step = statistics.median(times) / steps
     fl = fr_flops(n_rows, d)
     per_kernel = {}
@@ -145,7 +148,7 @@ def fullrank_leg(eng, vb, _lib, group, d, steps, warmup, scaling='weak', slot0=4
     whole_tf = fl['total'] / sec_per_step / 1e12
     return {
         'sec_per_step': sec_per_step, 'block_seconds': times, 'n_rows': n_rows, 'n_total': n_total,
-        '_model': model, '_theta': theta,
+        '_model': model, '_theta': theta, '_grad': grad,
         'value': value, 'grad_norm': float(np.linalg.norm(grad)), 'per_kernel': per_kernel,
         'whole_evaluation': {'flops_executed': fl['total'], 'us_per_eval': 1e6 * sec_per_step, 'achieved': whole_tf,
                              'frac': whole_tf / FP64_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
@@ -1348,6 +1351,8 @@ def main():
     ap.add_argument('--no-profile', action='store_true', help='no per-kernel HIP events in the timed region')
     ap.add_argument('--launch-timeout', type=float, default=1500.0,
                     help='self-launched ranks (--gpus N > 1 without a launcher) are killed after this many seconds')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed evaluation returned (value.npy, grad.npy: float64) to DIR')
     ap.add_argument('--probe-transport', choices=['rccl', 'ipc', 'host'], default=None,
                     help='internal: a child of second_transport_probe (runs transport_legs under that transport)')
     args = ap.parse_args()
@@ -1404,6 +1409,12 @@ def main():
         other_mode = 'strong' if args.scaling == 'weak' else 'weak'
         other = fullrank_leg(eng, vb, _lib, group, FR_D, args.steps, args.warmup, scaling=other_mode, profile=False)
         other['scaling'] = other_mode
+    grad = head.pop('_grad')      # (a pinned block: back to the pool before the secondary legs)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'value.npy'), np.asarray(head['value'], dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, 'grad.npy'), np.asarray(grad, dtype=np.float64))
+    del grad
 
     tlegs, sharded, transports = None, None, None
     if world > 1 and not no_rccl:          # collective legs: every rank runs them
@@ -1501,11 +1512,11 @@ def main():
             import contextlib
             import io
             out['c2_fullrank_d512'] = {k: v for k, v in fullrank_leg(
-                eng, vb, _lib, group, 512, max(args.steps, 200), args.warmup, profile=True).items()
+                eng, vb, _lib, group, 512, max(args.steps, 200), args.warmup, profile=True, max_blocks=200).items()
                 if k in ('whole_evaluation', 'per_kernel', 'value', 'grad_norm')}
             # the same evaluation at D = 256: the sub-30-us GEMMs of C3's shape class
             out['fullrank_d256'] = {k: v for k, v in fullrank_leg(
-                eng, vb, _lib, group, 256, max(args.steps, 200), args.warmup, profile=True).items()
+                eng, vb, _lib, group, 256, max(args.steps, 200), args.warmup, profile=True, max_blocks=200).items()
                 if k in ('whole_evaluation', 'per_kernel', 'value', 'grad_norm')}
             out['fullrank_funnel'] = fullrank_funnel_leg(eng, vb)
             out['api_call'] = api_call_leg(eng, vb)

@@ -1,5 +1,7 @@
 """Helpers shared by the oracle tests and the GPU parity tests: load fixtures, rebuild specs."""
 import glob
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -8,6 +10,8 @@ from oracle import families as ofam
 from oracle import models as omod
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+# sha256 of every fixture's arrays as make_golden.py wrote them from the reference's own code
+DIGESTS_PATH = os.path.join(GOLDEN_DIR, 'digests.json')
 
 
 def fixtures(prefix):
@@ -71,3 +75,31 @@ def rel_err(a, b):
 
 def ids(paths):
     return [os.path.splitext(os.path.basename(p))[0] for p in paths]
+
+
+def fixture_digest(path):
+    """sha256 over a fixture's arrays (names, dtypes, shapes, bytes in key order): independent of the zip container,
+    whose member timestamps change with every write."""
+    h = hashlib.sha256()
+    with np.load(path, allow_pickle=False) as z:
+        for k in sorted(z.files):
+            a = np.ascontiguousarray(z[k])
+            h.update(('%s|%s|%s|' % (k, a.dtype.str, a.shape)).encode())
+            h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def fixture_digests(directory=GOLDEN_DIR):
+    """{fixture name: digest} of every ``*.npz`` in ``directory``."""
+    return {os.path.basename(p)[:-4]: fixture_digest(p) for p in sorted(glob.glob(os.path.join(directory, '*.npz')))}
+
+
+def write_digests(digests, path=DIGESTS_PATH):
+    with open(path, 'w') as f:
+        json.dump(digests, f, indent=1, sort_keys=True)
+        f.write('\n')
+
+
+def read_digests(path=DIGESTS_PATH):
+    with open(path) as f:
+        return json.load(f)

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Generate golden vectors for the BBVI hot path from the upstream reference itself.
 
-Runs ONLY in the build container (needs the read-only reference tree); writes
-``tests/golden/*.npz``.  The reference's Python is imported through the
-container-only shims of ``_ref_stubs.py`` (autograd/paragami/pystan are absent
-here); see that file for exactly what is real reference code (all forward
+Needs a checkout of the upstream reference (``--reference DIR``, the directory
+that holds its ``viabel`` package); writes ``tests/golden/*.npz`` and their
+digests, ``tests/golden/digests.json``.  The reference's Python is imported
+through the shims of ``_ref_stubs.py`` (autograd/paragami/pystan need not be
+installed); see that file for exactly what is real reference code (all forward
 arithmetic, the RGE control-variate algebra, DIS tempering/bisection,
 alpha-divergence weights) and what is supplied (finite-difference / analytic
 derivatives in place of autograd).
@@ -14,7 +15,7 @@ reference's outputs (samples, log densities, objective value, gradient), plus a
 ``provenance`` string.  ``tests/test_oracle_golden.py`` checks the numpy oracle
 against them; the GPU parity tests check the HIP engine against the same files.
 
-Usage:  python tests/golden/make_golden.py
+Usage:  python tests/golden/make_golden.py --reference DIR [--check] [generator ...]
 """
 import os
 import sys
@@ -25,11 +26,19 @@ import scipy.stats
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 
-import _ref_stubs  # noqa: E402
+if '--reference' not in sys.argv[1:-1]:
+    sys.exit(__doc__.strip().splitlines()[-1])
+_i = sys.argv.index('--reference')
+REFERENCE_ROOT = os.path.abspath(sys.argv.pop(_i + 1))
+sys.argv.pop(_i)
 
-_ref_stubs.install('/root/reference')
+import _ref_stubs  # noqa: E402
+import _golden     # noqa: E402  (tests/_golden.py: the fixture digests)
+
+_ref_stubs.install(REFERENCE_ROOT)
 
 from viabel import approximations as ref_approx  # noqa: E402  (the reference)
 from viabel import objectives as ref_obj         # noqa: E402
@@ -793,8 +802,8 @@ if __name__ == '__main__':
                       lowrank_alpha_dis=gen_lowrank_alpha_dis, dis_priors=gen_dis_priors)
     picked = sys.argv[1:]          # e.g. `make_golden.py psis optimizers` regenerates only those fixtures
     if picked and picked[0] == '--check':
-        # regenerate everything into a scratch directory and diff against the committed fixtures (drift guard, run by
-        # tests/test_oracle_golden.py wherever the reference tree exists)
+        # regenerate everything into a scratch directory and diff against the committed fixtures and their digests
+        # (tests/test_oracle_golden.py checks the committed fixtures against those digests without the reference)
         import tempfile
         with tempfile.TemporaryDirectory() as tmp:
             OUT_DIR = tmp
@@ -802,6 +811,10 @@ if __name__ == '__main__':
                 GENERATORS[name]()
             diffs = compare_with_committed(tmp, SAVED) if not picked[1:] else [
                 d for d in compare_with_committed(tmp, SAVED) if 'no generator' not in d]
+            if not picked[1:]:
+                fresh = _golden.fixture_digests(tmp)
+                if fresh != _golden.read_digests():
+                    diffs.append('digests.json: does not match the regenerated fixtures')
         for d in diffs:
             print('DRIFT ' + d)
         print('checked %d fixtures: %s' % (len(SAVED), 'no drift' if not diffs else '%d differences' % len(diffs)))
@@ -813,4 +826,5 @@ if __name__ == '__main__':
         picked = list(GENERATORS)
     for name in picked:
         GENERATORS[name]()
+    _golden.write_digests(_golden.fixture_digests(HERE))
     print('wrote %d fixtures to %s' % (len(SAVED), HERE))
