@@ -385,6 +385,31 @@ int vb_elbo_grad_lowrank(vb_ctx* ctx, int slot_eps, int slot_z, int64_t n, int64
 int vb_elbo_sums_lowrank(vb_ctx* ctx, int slot_eps, int slot_z, int64_t n, int64_t d, int64_t k, const double* theta,
                          double* out);
 
+/* ---- RealNVP normalizing flow (NVPFlow, viabel/approximations.py:452-550) ---------------------------------
+ * One handle per flow object holds its masks, architecture and workspace (two flows on one context never share state).
+ * vb_flow_create: d columns, k coupling layers, masks (k x d, entries 0 / 1, row i belongs to layer i), the t-net's and the
+ * s-net's widths (n_t + 1 and n_s + 1 entries, first and last d).  theta layout (p doubles, vb_flow_param_dim): for each
+ * coupling layer its t-net then its s-net; within a net, per dense layer W ([in][out], row-major) then b.  Hidden layers
+ * tanh, the s-net's last layer tanh, the t-net's last layer the identity.  vb_flow_destroy frees one handle (vb_destroy
+ * frees those still alive).
+ * vb_flow_elbo_grad: ExclusiveKL of the flow over the prior draws in `slot` (this rank's n rows of the prior's base noise,
+ * n x d); prior_family VB_FAMILY_MF_GAUSSIAN or VB_FAMILY_MF_STUDENT_T (prior_df), prior_param [mu | log_sigma] (2 d).
+ * out = [value | grad (p)], value = -mean [log p(x) - log p0(z0) + sum s], all-reduced over a sharded job's ranks.
+ * flags 0: the total theta-gradient of that value (the reference's intended plain form; its objectives.py:163 raises);
+ * VB_FLAG_PATH_DERIV: the path-derivative form, -mean (dx/dtheta)' [grad log p(x) - grad_x log q(x)] with theta held
+ * fixed inside log q (objectives.py:156-159).
+ * vb_flow_sample: forward pass only, for the diagnostics: samples x (n x d, may be NULL), log q (n) and, when log_p is not
+ * NULL, the bound model's log p (n) of the prior draws in `slot`; processed in row chunks.                            */
+typedef struct vb_flow vb_flow;
+int vb_flow_create(vb_ctx* ctx, int64_t d, int64_t k, const double* masks, int64_t n_t, const int64_t* widths_t,
+                   int64_t n_s, const int64_t* widths_s, vb_flow** out);
+int vb_flow_destroy(vb_ctx* ctx, vb_flow* flow);
+int vb_flow_param_dim(vb_ctx* ctx, const vb_flow* flow, int64_t* p);
+int vb_flow_elbo_grad(vb_ctx* ctx, vb_flow* flow, int slot, int64_t n, int64_t n_total, int prior_family,
+                      double prior_df, const double* prior_param, const double* theta, unsigned flags, double* out);
+int vb_flow_sample(vb_ctx* ctx, vb_flow* flow, int slot, int64_t n, int prior_family, double prior_df,
+                   const double* prior_param, const double* theta, double* x, double* log_q, double* log_p);
+
 /* ---- Importance weights and Pareto smoothing (diagnostics) ----------------------------
  * vb_log_weights_meanfield: log p(z_n) - log q(z_n; theta) for the samples z = mu + sigma * eps of
  * the noise staged in `slot` -- samples_and_log_weights, viabel/convenience.py:176-179.  The

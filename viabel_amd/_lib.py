@@ -222,6 +222,15 @@ SIGNATURES = {
     'vb_profile_read_kernel': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
                                               ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double),
                                               ctypes.c_int]),
+    'vb_flow_create': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, ctypes.c_int64, _c_int64_p,
+                                      ctypes.c_int64, _c_int64_p, ctypes.POINTER(ctypes.c_void_p)]),
+    'vb_flow_destroy': (ctypes.c_int, [_ctx_p, ctypes.c_void_p]),
+    'vb_flow_param_dim': (ctypes.c_int, [_ctx_p, ctypes.c_void_p, _c_int64_p]),
+    'vb_flow_elbo_grad': (ctypes.c_int, [_ctx_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                         ctypes.c_int, ctypes.c_double, _c_double_p, _c_double_p, ctypes.c_uint,
+                                         _c_double_p]),
+    'vb_flow_sample': (ctypes.c_int, [_ctx_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                      ctypes.c_double, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
 }
 
 _lib = None
@@ -902,6 +911,44 @@ class Engine:
                                               _dptr(weights), ctypes.byref(w_sum), ctypes.byref(w_logq),
                                               _dptr(d_mu), _dptr(gram)))
         return w_sum.value, w_logq.value, d_mu, gram
+
+    # ------------------------------------------------------------------ NVPFlow
+    def flow_create(self, d, masks, widths_t, widths_s):
+        """A handle holding one flow's masks, architecture and workspace on this context (``vb_flow_create``)."""
+        masks = _f64(masks)
+        wt = np.ascontiguousarray(widths_t, dtype=np.int64)
+        ws = np.ascontiguousarray(widths_s, dtype=np.int64)
+        h = ctypes.c_void_p()
+        self._check(self._lib.vb_flow_create(self._ctx, int(d), int(masks.shape[0]), _dptr(masks), wt.size - 1,
+                                             wt.ctypes.data_as(_c_int64_p), ws.size - 1, ws.ctypes.data_as(_c_int64_p),
+                                             ctypes.byref(h)))
+        return h.value
+
+    def flow_destroy(self, handle):
+        if getattr(self, '_ctx', None):
+            self._check(self._lib.vb_flow_destroy(self._ctx, handle))
+
+    def flow_elbo_grad(self, handle, slot, n, n_total, prior_family, prior_df, prior_param, theta, flags):
+        """``(value, grad)`` of ExclusiveKL for the flow over the prior draws in ``slot`` (``vb_flow_elbo_grad``)."""
+        prior_param = _f64(prior_param)
+        theta = _f64(theta)
+        out = pinned_array(1 + theta.size)
+        self._check(self._lib.vb_flow_elbo_grad(self._ctx, handle, slot, int(n), int(n_total), int(prior_family),
+                                                float(prior_df), _dptr(prior_param), _dptr(theta), int(flags),
+                                                _dptr(out)))
+        return float(out[0]), out[1:]
+
+    def flow_sample(self, handle, slot, n, d, prior_family, prior_df, prior_param, theta, want_x=True, want_log_p=False):
+        """``(x or None, log q, log p or None)`` of the flow's forward pass over the prior draws in ``slot``."""
+        prior_param = _f64(prior_param)
+        theta = _f64(theta)
+        x = np.empty((n, d), dtype=np.float64) if want_x else None
+        log_q = np.empty(n, dtype=np.float64)
+        log_p = np.empty(n, dtype=np.float64) if want_log_p else None
+        self._check(self._lib.vb_flow_sample(self._ctx, handle, slot, int(n), int(prior_family), float(prior_df),
+                                             _dptr(prior_param), _dptr(theta), _dptr(x) if want_x else None,
+                                             _dptr(log_q), _dptr(log_p) if want_log_p else None))
+        return x, log_q, log_p
 
     # ------------------------------------------------------------------ ExclusiveKL, full rank
     def elbo_grad_fullrank(self, slot, n, d, theta, flags=0, n_total=None):

@@ -27,7 +27,10 @@ from scipy import special as _special
 from . import _lib
 from ._legacy_rng import LegacyRandomState
 
-__all__ = ['ApproximationFamily', 'MFGaussian', 'MFStudentT', 'MultivariateT', 'FullRankGaussian', 'LRGaussian']
+import weakref
+
+__all__ = ['ApproximationFamily', 'MFGaussian', 'MFStudentT', 'MultivariateT', 'FullRankGaussian', 'LRGaussian',
+           'NVPFlow']
 
 _LOG_2PI = float(np.log(2.0 * np.pi))
 
@@ -683,3 +686,174 @@ def _philox_host_copy(family, n_samples, seed):
     else:
         eng.noise_generate(slot, n_samples, family.dim, seed, 0, kind=kind, df=df)
     return eng.noise_get_host(slot, n_samples, family.dim)
+
+
+# ------------------------------------------------------------------------------------------
+def _net_shapes(layers, dim, name):
+    shapes = [tuple(int(v) for v in layer) for layer in layers]
+    if not shapes or any(len(sh) != 2 or sh[0] <= 0 or sh[1] <= 0 for sh in shapes):
+        raise ValueError('{}: every layer must be a positive [in, out] pair'.format(name))
+    if shapes[0][0] != dim or shapes[-1][1] != dim:
+        raise ValueError('{}: the first layer must take {} inputs and the last give {} outputs'.format(name, dim, dim))
+    for a, b in zip(shapes[:-1], shapes[1:]):
+        if a[1] != b[0]:
+            raise ValueError('{}: consecutive layer widths do not chain ({} then {})'.format(name, a, b))
+    return shapes
+
+
+def _free_engine_flows(handles):
+    for eng_ref, h in handles:
+        eng = eng_ref()
+        if eng is not None:
+            try:
+                eng.flow_destroy(h)
+            except Exception:
+                pass
+
+
+class NVPFlow(ApproximationFamily):
+    """RealNVP normalizing flow (``approximations.py:452-550``): ``K`` affine coupling layers over a mean-field prior.
+
+    Coupling layer ``i`` with mask ``m = mask[i]`` maps ``x`` to ``y + (1 - m) (x exp(s) + t)``, where ``y = m x``,
+    ``s = s_i(y) (1 - m)`` and ``t = t_i(y) (1 - m)``; ``s_i`` / ``t_i`` are dense networks (``x W + b``) with tanh hidden
+    layers, a tanh last layer for ``s`` and an identity last layer for ``t``.  Samples are ``g(z0)`` with ``z0`` drawn by
+    ``prior.sample(prior_param, n)`` (the prior's own generator, ``'numpy'`` or ``'philox'``); ``log_density`` runs the
+    inverse ``f`` and returns ``prior.log_density(prior_param, z) - sum s``.
+
+    Flat layout (paragami free flattening in insertion order): for each coupling layer its t-net then its s-net, within a
+    net per dense layer ``W`` (``[in, out]``, row-major) then ``b``.  ``fold`` / ``flatten`` convert to and from the
+    nested ``{'0t': {'0': W, '0_b': b, ...}, '0s': {...}, ...}`` form.  ``seed`` is accepted and unused, as in the
+    reference.  Under ``ExclusiveKL`` the objective runs on the HIP engine (``vb_flow.hip``)."""
+
+    def __init__(self, layers_t, layers_s, mask, prior, prior_param, dim, activation=np.tanh, seed=1,
+                 mc_samples=10000):
+        if not isinstance(prior, (MFGaussian, MFStudentT)):
+            raise NotImplementedError('NVPFlow: the prior must be an MFGaussian or an MFStudentT; got {}'.format(
+                type(prior).__name__))
+        if not (activation is np.tanh or activation == 'tanh'):
+            raise NotImplementedError('NVPFlow: only the tanh activation is implemented')
+        dim = int(dim)
+        if prior.dim != dim:
+            raise ValueError('NVPFlow: prior dimension {} != dim {}'.format(prior.dim, dim))
+        if len(layers_t) != len(layers_s):
+            raise ValueError('NVPFlow: layers_t and layers_s must have the same number of layers')
+        mask = np.asarray(mask, dtype=np.float64)
+        if mask.ndim != 2 or mask.shape[1] != dim or mask.shape[0] < 1:
+            raise ValueError('NVPFlow: mask must be K x {}'.format(dim))
+        if not np.all((mask == 0.0) | (mask == 1.0)):
+            raise ValueError('NVPFlow: mask entries must be 0 or 1')
+        prior_param = np.asarray(prior_param, dtype=np.float64)
+        if prior_param.shape != (prior.var_param_dim,):
+            raise ValueError('NVPFlow: prior_param must have length {}'.format(prior.var_param_dim))
+        self._shapes_t = _net_shapes(layers_t, dim, 'layers_t')
+        self._shapes_s = _net_shapes(layers_s, dim, 'layers_s')
+        self.prior = prior
+        self.prior_param = prior_param
+        self.mask = mask
+        self.mc_samples = mc_samples
+        self._rs = LegacyRandomState(seed)           # the reference's own unused generator (approximations.py:487)
+        self._layout = []                            # (key, net, layer, 'W' / 'b', offset, shape)
+        off = 0
+        for i in range(mask.shape[0]):
+            for net, shapes in (('t', self._shapes_t), ('s', self._shapes_s)):
+                for l, (a, b) in enumerate(shapes):
+                    self._layout.append((str(i) + net, str(l), off, (a, b)))
+                    off += a * b
+                    self._layout.append((str(i) + net, str(l) + '_b', off, (b,)))
+                    off += b
+        self._handles = []                           # (engine weakref, handle) of the device copies of this flow
+        weakref.finalize(self, _free_engine_flows, self._handles)
+        super().__init__(dim, off, False, False)
+
+    # -- layout ------------------------------------------------------------------------------
+    def fold(self, var_param):
+        """The nested parameter dict of a flat ``var_param``."""
+        var_param = np.asarray(var_param, dtype=np.float64)
+        if var_param.shape != (self.var_param_dim,):
+            raise ValueError('var_param must have shape ({},)'.format(self.var_param_dim))
+        out = {}
+        for key, name, off, shape in self._layout:
+            out.setdefault(key, {})[name] = var_param[off:off + int(np.prod(shape))].reshape(shape).copy()
+        return out
+
+    def flatten(self, params):
+        """Inverse of ``fold``."""
+        flat = np.empty(self.var_param_dim)
+        for key, name, off, shape in self._layout:
+            v = np.asarray(params[key][name], dtype=np.float64)
+            if v.shape != shape:
+                raise ValueError('{}[{}] must have shape {}'.format(key, name, shape))
+            flat[off:off + v.size] = v.ravel()
+        return flat
+
+    @property
+    def num_couplings(self):
+        return self.mask.shape[0]
+
+    # -- host forward / inverse --------------------------------------------------------------
+    def _net(self, p, shapes, x, last_tanh):
+        for l in range(len(shapes)):
+            x = x @ p[str(l)] + p[str(l) + '_b']
+            if l + 1 < len(shapes) or last_tanh:
+                x = np.tanh(x)
+        return x
+
+    def _g(self, var_param, z):
+        p = self.fold(var_param)
+        x = z
+        for i in range(self.num_couplings):
+            m = self.mask[i]
+            y = m * x
+            s = self._net(p[str(i) + 's'], self._shapes_s, y, True) * (1 - m)
+            t = self._net(p[str(i) + 't'], self._shapes_t, y, False) * (1 - m)
+            x = y + (1 - m) * (x * np.exp(s) + t)
+        return x
+
+    def _f(self, var_param, x):
+        p = self.fold(var_param)
+        z = x
+        log_det = np.zeros(x.shape[0])
+        for i in reversed(range(self.num_couplings)):
+            m = self.mask[i]
+            y = m * z
+            s = self._net(p[str(i) + 's'], self._shapes_s, y, True) * (1 - m)
+            t = self._net(p[str(i) + 't'], self._shapes_t, y, False) * (1 - m)
+            z = (1 - m) * (z - t) * np.exp(-s) + y
+            log_det -= s.sum(axis=1)
+        return z, log_det
+
+    # -- reference API -----------------------------------------------------------------------
+    def sample(self, var_param, n_samples, seed=None):
+        z0 = self.prior.sample(self.prior_param, int(n_samples), seed=seed)
+        return self._g(var_param, z0)
+
+    def log_density(self, var_param, x):
+        z, log_det = self._f(var_param, _as_rows(x))
+        return self.prior.log_density(self.prior_param, z) + log_det
+
+    def mean_and_cov(self, var_param):
+        samples = self.sample(var_param, self.mc_samples)
+        return np.mean(samples, axis=0), np.cov(samples.T)
+
+    def _pth_moment(self, var_param, p):
+        raise NotImplementedError
+
+    def supports_pth_moment(self, p):
+        return False
+
+    # -- engine hooks ------------------------------------------------------------------------
+    def _device_handle(self, eng):
+        """This flow's handle on ``eng`` (created on first use, freed with the flow or the engine)."""
+        for ref, h in self._handles:
+            if ref() is eng:
+                return h
+        widths_t = [self._shapes_t[0][0]] + [b for _, b in self._shapes_t]
+        widths_s = [self._shapes_s[0][0]] + [b for _, b in self._shapes_s]
+        h = eng.flow_create(self.dim, self.mask, widths_t, widths_s)
+        self._handles[:] = [(r, x) for r, x in self._handles if r() is not None]
+        self._handles.append((weakref.ref(eng), h))
+        return h
+
+    def _device_prior(self):
+        family, df = self.prior._device_family()
+        return family, df, self.prior_param

@@ -10,10 +10,10 @@ import numpy as np
 
 from . import _lib
 from ._psis import psislw
-from .approximations import MFGaussian, MFStudentT
+from .approximations import MFGaussian, MFStudentT, NVPFlow
 from .diagnostics import all_diagnostics
 from .models import CallableModel, DeviceModel, SourceModel
-from .objectives import ExclusiveKL
+from .objectives import ExclusiveKL, _stage_prior_noise
 from .optimization import FASO, RAABBVI, RMSProp
 
 __all__ = ['bbvi', 'vi_diagnostics', 'psis_correction', 'samples_and_log_weights']
@@ -151,5 +151,24 @@ def _on_device_weights(model, approx):
 def samples_and_log_weights(var_param, model, approx, n_samples):
     """Samples from the approximation and their importance log weights (``convenience.py:176-179``);
     the model log density is evaluated on the GPU."""
+    if isinstance(approx, NVPFlow) and isinstance(model, DeviceModel):
+        # the flow's forward pass and the model on the device over the prior draws approx.sample would consume; log q
+        # from the forward pass (log p0(z0) - sum s), which equals the inverse pass's up to rounding
+        var_param = np.asarray(var_param, dtype=np.float64)
+        if var_param.shape != (approx.var_param_dim,):
+            raise ValueError('var_param must have shape ({},)'.format(approx.var_param_dim))
+        eng = _lib.default_engine()
+        eng.set_model(model.device_spec())
+        handle = approx._device_handle(eng)
+        n_ranks, rank = eng.n_ranks, eng.rank
+        eng.n_ranks, eng.rank = 1, 0          # (every process draws all of its own diagnostics samples)
+        try:
+            _stage_prior_noise(eng, approx.prior, n_samples, _DIAG_SLOT)
+        finally:
+            eng.n_ranks, eng.rank = n_ranks, rank
+        family, df, prior_param = approx._device_prior()
+        samples, log_q, log_p = eng.flow_sample(handle, _DIAG_SLOT, n_samples, approx.dim, family, df, prior_param,
+                                                var_param, want_x=True, want_log_p=True)
+        return samples, log_p - log_q
     samples = approx.sample(var_param, n_samples)
     return samples, model(samples) - approx.log_density(var_param, samples)

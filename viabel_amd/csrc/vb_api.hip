@@ -525,6 +525,7 @@ int vb_destroy(vb_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)sync_streams(ctx);
   user_model_release(ctx);
+  flow_release_all(ctx);
   vb_comm_destroy(ctx);
   if (ctx->pipe.pre) {
     (void)hipStreamDestroy(ctx->pipe.pre);

@@ -270,6 +270,7 @@ struct vb_ctx {
   vb::DeviceBuffer mvt_elbo;            // multivariate-t ExclusiveKL: root, mean, row scales
   vb::DeviceBuffer lr_work;             // low-rank Gaussian family: workspace of the streaming pipeline
   vb::DeviceBuffer lr_obj;              // low-rank Gaussian under DIS / alpha: samples, residuals, Woodbury vectors
+  std::vector<vb_flow*> flows;          // NVPFlow handles alive on this context (vb_flow.hip; freed by vb_destroy)
   int64_t lr_n = 0, lr_d = 0, lr_k = 0, lr_n_total = 0;   // shape of the low-rank DIS state (0: none)
   struct TemperPrior {                  // vb_dis_set_temper_prior: a tempering prior other than the refresh's own argument
     int kind = 0;                       // VB_PRIOR_*
@@ -577,6 +578,7 @@ int temper_prior_rows(vb_ctx* ctx, const double* X, int64_t ld, int64_t n, int64
 int temper_prior_set(vb_ctx* ctx, int kind, int64_t d, double df, const double* loc, const double* scale, double log_det_l);
 int user_model_set_callback(vb_ctx* ctx, int64_t dim, vb_model_callback fn, void* user);
 int pipe_init(vb_ctx* ctx);
+void flow_release_all(vb_ctx* ctx);     // vb_destroy: the NVPFlow handles still alive (vb_flow.hip)
 
 // per-row log weights and AlphaDivergence (vb_rowstats.hip)
 int rowstats_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, const double* theta_src,

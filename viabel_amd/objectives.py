@@ -23,7 +23,8 @@ from scipy import linalg as _sla
 from scipy import special as _special
 
 from . import _lib
-from .approximations import MFGaussian, MFStudentT, FullRankGaussian, MultivariateT, LRGaussian, symmetric_eig, symmetric_root
+from .approximations import (MFGaussian, MFStudentT, FullRankGaussian, MultivariateT, LRGaussian, NVPFlow, symmetric_eig,
+                             symmetric_root)
 from .models import DeviceModel, SourceModel, as_device_model
 
 __all__ = [
@@ -44,6 +45,21 @@ def shard_rows(n, n_ranks, rank):
     base, extra = divmod(n, n_ranks)
     begin = rank * base + min(rank, extra)
     return begin, begin + base + (1 if rank < extra else 0)
+
+
+def _stage_prior_noise(eng, prior, n_samples, slot, seed=None):
+    """This rank's rows of a mean-field family's base draws (a flow's prior) into ``slot``; returns ``(begin, end)``."""
+    begin, end = shard_rows(n_samples, eng.n_ranks, eng.rank)
+    if prior.rng == 'philox':
+        kind, df = prior._philox_kind()
+        if seed is None:
+            eng.noise_generate(slot, end - begin, prior.dim, prior._seed, prior._next_philox_stream(), row_offset=begin,
+                               kind=kind, df=df)
+        else:
+            eng.noise_generate(slot, end - begin, prior.dim, seed, 0, row_offset=begin, kind=kind, df=df)
+    else:
+        prior._stage_base_noise(eng, slot, n_samples, begin, end, seed)
+    return begin, end
 
 
 def _claim_engine_state(eng, kind, owner):
@@ -370,6 +386,11 @@ class ExclusiveKL(StochasticVariationalObjective):
                 raise NotImplementedError('the RGE control variates treat var_param as [mean | log-scale] '
                                           '(objectives.py:196-198) and do not apply to MultivariateT')
             objective_and_grad = self._mvt_exclusive_kl(approx)
+        elif isinstance(approx, NVPFlow):
+            if cv_mode != 0:
+                raise NotImplementedError('the RGE control variates treat var_param as [mean | log-scale] '
+                                          '(objectives.py:196-198) and do not apply to NVPFlow')
+            objective_and_grad = self._flow_exclusive_kl(approx, flags)
         elif isinstance(approx, LRGaussian):
             if cv_mode != 0:
                 raise NotImplementedError('the RGE control variates treat var_param as [mean | log-scale] '
@@ -426,6 +447,8 @@ class ExclusiveKL(StochasticVariationalObjective):
         is linear in theta (sum of the log scales), so the first term has the Hessian of the entropy-form objective --
         the device difference above.  The second term depends on the noise only through a handful of moments and its
         Hessian at ``theta = theta_s`` is written out (``_path_logq_hvp``)."""
+        if isinstance(self.approx, NVPFlow):
+            raise NotImplementedError('the Hessian-vector product is not implemented for NVPFlow')
         approx = self.approx
         if self.hessian_approx_method is not None:
             raise AttributeError("'ExclusiveKL' object has no attribute '_hvp'")      # what the reference raises (:275)
@@ -549,6 +572,28 @@ class ExclusiveKL(StochasticVariationalObjective):
         (``vb_fit_history_mean``): the same additions in the same order as numpy's, without its pass over ``rows`` iterates on
         the host (60 x 4.2 MB at D = 1024 dense: 7 ms)."""
         return self._engine().fit_history_mean(rows, self.approx.var_param_dim)
+
+    def _flow_exclusive_kl(self, approx, flags):
+        """ExclusiveKL of an NVPFlow on the engine (``vb_flow.hip``).  The prior's base draws (its own generator,
+        ``rng='numpy'`` or ``'philox'``) are what ``approx.sample`` would consume; the path form is the reference's
+        (``objectives.py:156-159``).  The plain form (``use_path_deriv=False``, what ``bbvi`` builds) is the total
+        theta-gradient of ``-mean[log p(g(z0)) - log q(g(z0))]``.  DEVIATION: the reference's plain form calls
+        ``approx.log_density(samples)`` without ``var_param`` (``objectives.py:163``) and raises ``TypeError`` for every
+        family; here it is the estimator that call was meant to be, including the flow's log-determinant."""
+        prior = approx.prior
+
+        def objective_and_grad(var_param):
+            var_param = np.asarray(var_param, dtype=np.float64)
+            if var_param.shape != (approx.var_param_dim,):
+                raise ValueError('var_param must have shape ({},)'.format(approx.var_param_dim))
+            eng = self._engine()
+            eng.set_model(self.model.device_spec())
+            handle = approx._device_handle(eng)
+            N = self.num_mc_samples
+            begin, end = _stage_prior_noise(eng, prior, N, _NOISE_SLOT)
+            family, df, prior_param = approx._device_prior()
+            return eng.flow_elbo_grad(handle, _NOISE_SLOT, end - begin, N, family, df, prior_param, var_param, flags)
+        return objective_and_grad
 
     def _mvt_exclusive_kl(self, approx):
         """Entropy-form ELBO for the multivariate t: sampling, model gradient and the D x D contraction
