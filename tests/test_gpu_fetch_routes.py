@@ -2,6 +2,8 @@
 vb_api.hip) against the plain copies + stream synchronisation they replace (VB_FETCH_FLAGSYNC=0): the same numbers through
 another door -- bit-identical -- on every family of blocking entry points that uses them."""
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -211,3 +213,67 @@ def test_pinned_pool_stops_pinning_for_callers_that_keep_everything(env):
     assert pool._out == 0 and pool.idle_blocks() == 2      # (keep = 2: the third block was freed)
     b = pool.array(200000)
     assert pool._out == 8 * 200000 and pool.idle_blocks() == 1
+
+
+# ---- the plain-copy route with the look-ahead of numpy's streams ----------------------------------------------------------
+_NUMPY_LOOP = r"""
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+import viabel_amd as vb
+from viabel_amd import _lib
+from oracle import families as ofam
+eng = _lib.default_engine()
+D, N = 64, 8192
+rng = np.random.RandomState(3)
+model = vb.GaussianModel(0.2 * rng.randn(D), np.exp(0.1 * rng.randn(D)))
+th_mf = np.concatenate([0.1 * rng.randn(D), -0.5 + 0.1 * rng.randn(D)])
+A = rng.randn(D, D)
+th_ch = np.concatenate([0.1 * rng.randn(D), ofam.psd_to_free(0.7 * (A @ A.T / D + np.eye(D)))])
+prior = np.concatenate([np.zeros(D), 0.3 * np.ones(D)])
+objs = {
+    'ekl_mf': (vb.ExclusiveKL(vb.MFGaussian(D, seed=5), model, N), th_mf),
+    'ekl_mft': (vb.ExclusiveKL(vb.MFStudentT(D, 7.0, seed=5), model, N), th_mf),
+    'ekl_mvt': (vb.ExclusiveKL(vb.MultivariateT(D, 9.0, seed=5), model, N), th_ch),
+    'dis_mvt': (vb.DISInclusiveKL(vb.MultivariateT(D, 9.0, seed=5), model, N, ess_target=1000,
+                                  temper_prior=vb.MFGaussian(D), temper_prior_params=prior, use_resampling=True), th_ch),
+}
+out = {}
+for name, (obj, th) in objs.items():
+    np.random.seed(4)
+    before = eng.legacy_ahead_stats()[1]
+    for it in range(6):
+        v, g = obj(th)
+        out['%s_v%d' % (name, it)] = np.array(v)
+        out['%s_g%d' % (name, it)] = g.copy()
+        th = th - 0.01 * g / (1.0 + np.abs(g))
+    st = obj.approx._rs.get_state()
+    out[name + '_key'] = np.asarray(st[1])
+    out[name + '_rest'] = np.array([st[2], st[3], st[4]], dtype=np.float64)
+    out[name + '_adopted'] = np.array(eng.legacy_ahead_stats()[1] - before)
+np.savez(sys.argv[2], **out)
+"""
+
+
+def test_flagsync_off_with_numpy_look_ahead(tmp_path):
+    """VB_FETCH_FLAGSYNC=0 with the look-ahead of numpy's streams on: the look-ahead's draw copies the generator's key with
+    push_small, whose plain-copy route polls the look-ahead -- from inside the look-ahead's own enqueue, which used to start
+    the job again and recurse until the host stack ran out.  Each mode runs in a child process (a regression is a failed
+    return code, not a dead test session): values, gradients and the families' generator states equal to the mapped
+    route's, and the look-ahead really served the calls."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = {}
+    for flag in ('0', '1'):
+        env = dict(os.environ, VB_FETCH_FLAGSYNC=flag, VB_LEGACY_AHEAD='1')
+        path = str(tmp_path / ('flagsync%s.npz' % flag))
+        r = subprocess.run([sys.executable, '-c', _NUMPY_LOOP, root, path], env=env, capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, (flag, r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+        res[flag] = dict(np.load(path))
+    plain, flagged = res['0'], res['1']
+    assert sorted(plain) == sorted(flagged)
+    for key in plain:
+        if key.endswith('_adopted'):
+            assert plain[key] >= 3, (key, plain[key])
+        else:
+            np.testing.assert_array_equal(plain[key], flagged[key], err_msg=key)

@@ -551,7 +551,7 @@ int vb_destroy(vb_ctx* ctx) {
   if (ctx->pin_host) (void)hipHostFree(ctx->pin_host);
   for (DeviceBuffer* b : {&ctx->model_params, &ctx->theta, &ctx->workspace, &ctx->sums, &ctx->out,
                           &ctx->scratch, &ctx->scratch2, &ctx->rowvec, &ctx->fr_work, &ctx->fr_theta,
-                          &ctx->fr_out, &ctx->dis_state, &ctx->mvt_state, &ctx->lg_work, &ctx->user_params, &ctx->psis_lw, &ctx->psis_work, &ctx->rows_work,
+                          &ctx->fr_out, &ctx->dis_state, &ctx->mvt_state, &ctx->mvt_ekl_state, &ctx->lg_work, &ctx->user_params, &ctx->psis_lw, &ctx->psis_work, &ctx->rows_work,
                           &ctx->lr_work, &ctx->mvt_elbo, &ctx->fit_work, &ctx->glm_work, &ctx->fr_lt, &ctx->bisect_work, &ctx->chi_dev, &ctx->lr_obj, &ctx->gen_geom.buf, &ctx->tri_map, &ctx->mvt_invs, &ctx->temper.buf, &ctx->temper.work, &ctx->fz_words, &ctx->fz_items, &ctx->legacy_work, &ctx->alpha_g, &ctx->mf_one, &ctx->fetch_ticket})
     if (b->ptr) (void)hipFree(b->ptr);
   if (ctx->mvt_pin) (void)hipHostFree(ctx->mvt_pin);
@@ -948,7 +948,7 @@ static void legacy_spec_cancel(vb_ctx* ctx) {
 // enqueue the next unfinished request of the job (nothing in flight): draw kernels + the deferred finish on the speculation's stream
 static void legacy_spec_enqueue_next(vb_ctx* ctx) {
   LegacySpec& S = *ctx->legacy_spec;
-  if (!S.active || S.failed || S.in_flight >= 0 || S.n_finished >= S.n_reqs) return;
+  if (!S.active || S.failed || S.enqueuing || S.in_flight >= 0 || S.n_finished >= S.n_reqs) return;
   const int i = S.n_finished;
   const LegacyReq& r = S.reqs[i];
   const LegacyGenState& g = S.state[i];
@@ -957,6 +957,7 @@ static void legacy_spec_enqueue_next(vb_ctx* ctx) {
     return;
   }
   int rc = VB_OK;
+  S.enqueuing = true;
   {
     LegacySpecGuard guard(ctx);
     const int64_t ld = r.prog == 0 ? 1 : noise_row_stride(r.d);
@@ -978,6 +979,7 @@ static void legacy_spec_enqueue_next(vb_ctx* ctx) {
     }
     if (rc == VB_OK) rc = legacy_finish_launch(ctx, ctx->stream, S.fin, S.land_dev, ++S.seq);
   }
+  S.enqueuing = false;
   if (rc != VB_OK) {
     S.failed = true;      // (declined or failed: nothing of this request is ever adopted; the caller draws as before)
     return;
@@ -989,6 +991,7 @@ static void legacy_spec_enqueue_next(vb_ctx* ctx) {
 // called from the draw entry points and from fetch_blocking's wait.
 static void legacy_spec_poll(vb_ctx* ctx) {
   LegacySpec* Sp = ctx->legacy_spec;
+  if (Sp && Sp->enqueuing) return;      // (a wait inside the job's own draw: see LegacySpec::enqueuing)
   if (Sp && Sp->active && !Sp->failed && Sp->in_flight < 0 && Sp->n_finished < Sp->n_reqs) {
     legacy_spec_enqueue_next(ctx);      // (a job whose start was deferred to the caller's first wait: vb_legacy_round_end)
     return;

@@ -541,6 +541,9 @@ struct LegacySpec {
   bool active = false, failed = false;
   LegacyReq reqs[kMaxReqs];
   int n_reqs = 0, n_adopted = 0, n_finished = 0, in_flight = -1;
+  // set while legacy_spec_enqueue_next runs a draw under LegacySpecGuard: a wait inside that draw (push_small's plain copy
+  // with VB_FETCH_FLAGSYNC=0) polls, and that poll must not start the job again -- it would swap the streams back and recurse
+  bool enqueuing = false;
   LegacyGenState state[kMaxReqs + 1];      // state[i]: the generator before request i
   LegacyGenState head_state;               // ... and behind the host-drawn head of the request in flight
   LegacyFinish fin;

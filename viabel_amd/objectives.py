@@ -36,8 +36,12 @@ __all__ = [
 ]
 
 _NOISE_SLOT = 0
-_DIS_SLOT = 1      # DIS keeps its state samples (as base noise) in a slot of its own
+_DIS_SLOT = 1      # DIS of the dense families keeps its state samples (as base noise) in a slot of its own
 _LR_SLOT = 3       # low-rank family: the n x k block of its noise (slot 2 belongs to the diagnostics)
+# ... and so does DIS of every other family kind (0 mean-field, 1 dense, 2 low-rank): the engine keeps one DIS state per
+# kind, and a mean-field state's kept-weights steps read their residuals straight out of its slot -- a refresh of another
+# kind must not write there
+_DIS_SLOTS = {0: 4, 1: _DIS_SLOT, 2: 5}
 
 
 def shard_rows(n, n_ranks, rank):
@@ -896,7 +900,7 @@ class DISInclusiveKL(StochasticVariationalObjective):
                 or self._objective_step % self._num_resampling_batches == 0
                 or getattr(self, '_state_gen', None) != (id(eng), eng.dis_generation(kind))):
             return
-        handle = eng.dis_state_park(kind, _DIS_SLOT if kind in (0, 1) else -1)
+        handle = eng.dis_state_park(kind, _DIS_SLOTS[kind] if kind in (0, 1) else -1)   # (low-rank: no slot read)
         fin = weakref.finalize(self, eng.dis_state_drop, handle)
         fin.atexit = False      # (not at interpreter exit: the HIP runtime may be gone by then)
         self._parked = (eng, kind, handle, fin)
@@ -1007,13 +1011,13 @@ class DISInclusiveKL(StochasticVariationalObjective):
         if isinstance(approx, LRGaussian) and not 1 <= approx.k <= 64:
             raise NotImplementedError('LRGaussian under DISInclusiveKL on the HIP engine: 1 <= k <= 64')
         self._prior_spec, self._prior_arg = self._build_prior_spec(approx.dim)
-        slot = _DIS_SLOT
         if isinstance(approx, (MultivariateT, FullRankGaussian)):
-            self._objective_and_grad = self._mvt_objective(approx, slot)
+            self._objective_and_grad = self._mvt_objective(approx, _DIS_SLOTS[1])
             return
         if isinstance(approx, LRGaussian):
-            self._objective_and_grad = self._lowrank_objective(approx, slot)
+            self._objective_and_grad = self._lowrank_objective(approx, _DIS_SLOTS[2])
             return
+        slot = _DIS_SLOTS[0]
 
         def variational_objective(var_param):
             var_param = np.asarray(var_param, dtype=np.float64)
