@@ -1,6 +1,5 @@
 """Dev tool: mean-field calls on narrow shapes with the noise in memory (rng='numpy' ELBO, DIS score pass), where the
-number of row blocks decides between the streaming pass and the finalize kernel's chain of partial sums.
-VB_MF_MAX_ROW_BLOCKS=512 restores the round-3 split."""
+number of row blocks decides between the streaming pass and the finalize kernel's chain of partial sums."""
 import sys
 import time
 

@@ -41,7 +41,5 @@ for src in ('pageable', 'pinned'):
         for pinned in (False, True):
             os.environ['VB_FR_UPLOAD_PIPE'] = pipe
             _lib.pinned_array = real_pinned if pinned else (lambda k: np.empty(k, dtype=np.float64))
-            for chunks in (('3',) if pipe == '0' else ('1', '2', '3', '4')):
-                os.environ['VB_FR_UPLOAD_CHUNKS'] = chunks
-                print('theta %-8s pipe %s chunks %s pinned grad %-5s: %.1f us per blocking call'
-                      % (src, pipe, chunks, pinned, run()), flush=True)
+            print('theta %-8s pipe %s pinned grad %-5s: %.1f us per blocking call'
+                  % (src, pipe, pinned, run()), flush=True)

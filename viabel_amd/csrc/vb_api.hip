@@ -257,10 +257,7 @@ int push_small(vb_ctx* ctx, hipStream_t st, const void* host_src, size_t bytes, 
 
 int sync_streams(vb_ctx* ctx) {
   VB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->pipe.pre) {
-    VB_HIP(ctx, hipStreamSynchronize(ctx->pipe.pre));
-    VB_HIP(ctx, hipStreamSynchronize(ctx->pipe.post));
-  }
+  if (ctx->pipe.post) VB_HIP(ctx, hipStreamSynchronize(ctx->pipe.post));
   if (ctx->mvt_side) VB_HIP(ctx, hipStreamSynchronize(ctx->mvt_side));
   if (ctx->fit_copy_st) VB_HIP(ctx, hipStreamSynchronize(ctx->fit_copy_st));
   if (ctx->up_stream) {
@@ -275,14 +272,13 @@ int sync_streams(vb_ctx* ctx) {
 }
 
 // Main-stream work that writes buffers the pipeline may still be reading (noise, model parameters)
-// is ordered after everything the pipeline has in flight, and the next prep is ordered after it.
+// is ordered after everything the pipeline has in flight.
 static int main_stream_write(vb_ctx* ctx) {
   Pipeline& P = ctx->pipe;
   if (P.post_pending) {
     VB_HIP(ctx, hipStreamWaitEvent(ctx->stream, P.ev_fin[P.last_set], 0));
     P.post_pending = false;
   }
-  P.main_dirty = true;
   return VB_OK;
 }
 
@@ -527,12 +523,9 @@ int vb_destroy(vb_ctx* ctx) {
   user_model_release(ctx);
   flow_release_all(ctx);
   vb_comm_destroy(ctx);
-  if (ctx->pipe.pre) {
-    (void)hipStreamDestroy(ctx->pipe.pre);
+  if (ctx->pipe.post) {
     (void)hipStreamDestroy(ctx->pipe.post);
-    (void)hipEventDestroy(ctx->pipe.ev_main);
     for (int i = 0; i < kPipeSets; ++i) {
-      (void)hipEventDestroy(ctx->pipe.ev_prep[i]);
       (void)hipEventDestroy(ctx->pipe.ev_k1[i]);
       (void)hipEventDestroy(ctx->pipe.ev_fin[i]);
     }
@@ -1273,13 +1266,12 @@ int vb_legacy_round_end(vb_ctx* ctx, vb_legacy_rng* rng) {
   // bisection with stream synchronisations inside -- and enqueuing its first draw here costs the host ~0.15 ms (twenty-odd
   // launches) in front of the call's own first launch.  Its start waits for the caller's first wait instead (legacy_poll: in
   // front of the root's synchronisation, where the host would idle), or for the request itself.  Every other round starts at
-  // once.  VB_LEGACY_DEFER=0: always at once.
+  // once.
   // Measured and NOT done: deferring every multi-draw round (the low-rank family's two normal draws: 377-405 -> 430-449 us -- its
   // call has no wait before the final one), or any round whose last job nobody had to wait for (the dense Gaussian family:
   // 630 -> 680-700 us -- its first wait, the pageable parameter upload, is a blocking call, not a wait the host could use).
-  const char* de = getenv("VB_LEGACY_DEFER");
   const bool t_round = S.n_reqs >= 2 && S.reqs[0].prog == 0;      // chi-square first: the multivariate t
-  if (!t_round || (de && atoi(de) == 0)) legacy_spec_enqueue_next(ctx);
+  if (!t_round) legacy_spec_enqueue_next(ctx);
   return VB_OK;
 }
 
@@ -1369,8 +1361,8 @@ struct GenNoise {            // in-register noise of a single evaluation (MfCall
 
 static int mf_call(vb_ctx* ctx, int count, const int* slots, int64_t n, int64_t d, int64_t n_total,
                    int family, double df, const double* thetas, unsigned flags, int cv_mode,
-                   ResultSlot** rs, bool pipelined, bool overlap_comm = false, bool alternate = false,
-                   const GenNoise* gen = nullptr, bool blocking = false) {
+                   ResultSlot** rs, bool overlap_comm = false, const GenNoise* gen = nullptr,
+                   bool blocking = false) {
   if (!ctx || !thetas || !slots) return fail(ctx, VB_ERR_INVALID, "NULL argument");
   if (count < 1) return fail(ctx, VB_ERR_INVALID, "count must be positive");
   if (ctx->model.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model)");
@@ -1396,9 +1388,7 @@ static int mf_call(vb_ctx* ctx, int count, const int* slots, int64_t n, int64_t 
     c.df = df;
     c.flags = flags;
     c.cv_mode = cv_mode;
-    c.pipelined = pipelined;
     c.overlap_comm = overlap_comm;
-    c.alternate = alternate;
     if (gen) {
       c.gen = 1;
       c.gen_seed = gen->seed;
@@ -1406,8 +1396,7 @@ static int mf_call(vb_ctx* ctx, int count, const int* slots, int64_t n, int64_t 
       c.gen_row_offset = gen->row_offset;
     }
     ctx->done_groups = 0;
-    static const bool flagsync = !(getenv("VB_MF_FLAGSYNC") && atoi(getenv("VB_MF_FLAGSYNC")) == 0);
-    if (blocking && flagsync && count == 1) {
+    if (blocking && count == 1) {
       if (!ctx->done_host) {
         VB_HIP(ctx, hipHostMalloc((void**)&ctx->done_host, 64 * 8 * sizeof(unsigned long long), hipHostMallocMapped));
         memset(ctx->done_host, 0, 64 * 8 * sizeof(unsigned long long));
@@ -1449,7 +1438,7 @@ int vb_elbo_grad_meanfield(vb_ctx* ctx, int slot, int64_t n, int64_t d, int64_t 
                            int cv_mode, double* value, double* grad) {
   if (!ctx || !value || !grad) return fail(ctx, VB_ERR_INVALID, "NULL argument");
   ResultSlot* rs = &ctx->sync_result;
-  VB_TRY(mf_call(ctx, 1, &slot, n, d, n_total, family, df, theta, flags, cv_mode, &rs, false, false, false, nullptr, true));
+  VB_TRY(mf_call(ctx, 1, &slot, n, d, n_total, family, df, theta, flags, cv_mode, &rs, false, nullptr, true));
   VB_TRY(mf_wait_blocking(ctx));
   rs->pending = false;
   *value = rs->host[rs->p];
@@ -1478,7 +1467,7 @@ int vb_elbo_grad_meanfield_philox(vb_ctx* ctx, int slot, int64_t n, int64_t d, i
   }
   ResultSlot* rs = &ctx->sync_result;
   const GenNoise gen{seed, stream, row_offset};
-  VB_TRY(mf_call(ctx, 1, &slot, n, d, n_total, family, df, theta, flags, cv_mode, &rs, false, false, false, &gen, true));
+  VB_TRY(mf_call(ctx, 1, &slot, n, d, n_total, family, df, theta, flags, cv_mode, &rs, false, &gen, true));
   VB_TRY(mf_wait_blocking(ctx));
   rs->pending = false;
   *value = rs->host[rs->p];
@@ -1492,7 +1481,7 @@ int vb_elbo_grad_meanfield_async(vb_ctx* ctx, int slot, int64_t n, int64_t d, in
   if (!ctx) return VB_ERR_INVALID;
   VB_TRY(check_slot(ctx, rslot));
   ResultSlot* rs = &ctx->results[rslot];
-  return mf_call(ctx, 1, &slot, n, d, n_total, family, df, theta, flags, cv_mode, &rs, false);
+  return mf_call(ctx, 1, &slot, n, d, n_total, family, df, theta, flags, cv_mode, &rs);
 }
 
 int vb_elbo_grad_meanfield_batch_async(vb_ctx* ctx, int count, const int* slots, int64_t n, int64_t d,
@@ -1508,18 +1497,12 @@ int vb_elbo_grad_meanfield_batch_async(vb_ctx* ctx, int count, const int* slots,
       if (rslots[a] == rslots[b]) return fail(ctx, VB_ERR_INVALID, "result slot %d used twice", rslots[b]);
     rs[b] = &ctx->results[rslots[b]];
   }
-  // VB_PIPELINE=1 spreads prep / stream / finalize over three event-chained HIP streams.  Measured
-  // on MI355X (ROCm 7.2) the cross-stream event waits cost more than the overlap buys, so the
-  // default keeps a batch in order on the main stream; independent contexts overlap instead.
-  static const bool pipelined = getenv("VB_PIPELINE") && atoi(getenv("VB_PIPELINE")) != 0;
-  // sharded jobs overlap the all-reduce of one batch with the kernels of the next (VB_COMM_OVERLAP=0 disables)
-  static const bool overlap = !(getenv("VB_COMM_OVERLAP") && atoi(getenv("VB_COMM_OVERLAP")) == 0);
-  // VB_MF_ALT=1 (single GPU): consecutive batches alternate between two streams.  Measured +3 % throughput
-  // (157 vs 153 k evaluations/s at C1): the streaming kernel already saturates HBM, so only the small prep /
-  // finalize kernels overlap -- and two concurrent streaming kernels make per-kernel timings meaningless.  Off.
-  static const bool alt = getenv("VB_MF_ALT") && atoi(getenv("VB_MF_ALT")) != 0;
-  return mf_call(ctx, count, slots, n, d, n_total, family, df, thetas, flags, cv_mode, rs, pipelined,
-                 overlap && ctx->comm != nullptr, alt && ctx->comm == nullptr);
+  // A batch stays in order on the main stream.  Spreading prep / stream / finalize over three event-chained
+  // streams measured slower on MI355X (ROCm 7.2): the cross-stream event waits cost more than the overlap buys.
+  // Alternating consecutive batches between two streams measured +3 % throughput (157 vs 153 k evaluations/s
+  // at C1): the streaming kernel already saturates HBM, so only the small prep / finalize kernels overlap.
+  // Both were dropped.  Sharded jobs overlap the all-reduce of one batch with the kernels of the next.
+  return mf_call(ctx, count, slots, n, d, n_total, family, df, thetas, flags, cv_mode, rs, ctx->comm != nullptr);
 }
 
 int vb_result_get(vb_ctx* ctx, int rslot, double* value, double* grad, int64_t p) {
@@ -2392,9 +2375,8 @@ int vb_fit(vb_ctx* ctx, int slot, int slot_aux, int64_t n, int64_t d, int64_t n_
     c.flags = flags;
     c.cv_mode = cv_mode;
   }
-  static const bool gen_env = !(getenv("VB_FIT_GEN") && atoi(getenv("VB_FIT_GEN")) == 0);
   const bool gen_in_kernel =
-      gen_env && (ctx->model.id == VB_MODEL_GAUSS_DIAG || ctx->model.id == VB_MODEL_FUNNEL) &&
+      (ctx->model.id == VB_MODEL_GAUSS_DIAG || ctx->model.id == VB_MODEL_FUNNEL) &&
       ((family == VB_FAMILY_MF_GAUSSIAN && noise_kind == VB_NOISE_NORMAL) ||
        (family == VB_FAMILY_MF_STUDENT_T && noise_kind == VB_NOISE_STUDENT_T && noise_df == df));
   bool step_done = false, prep_done = false;
@@ -2448,8 +2430,7 @@ int vb_fit(vb_ctx* ctx, int slot, int slot_aux, int64_t n, int64_t d, int64_t n_
       VB_HIP(ctx, hipStreamWaitEvent(st, ctx->pipe.ev_fin[ctx->pipe.last_set], 0));
       ctx->pipe.post_pending = false;
     }
-    static const bool fuse_env = !(getenv("VB_FIT_STEP_UNPACK") && atoi(getenv("VB_FIT_STEP_UNPACK")) == 0);
-    if (fullrank && fuse_env && !ctx->comm) {
+    if (fullrank && !ctx->comm) {
       // dense family: the step writes mu and L' of the stepped parameter itself, the next evaluation skips its unpack
       VB_TRY(fr_step_unpack_enqueue(ctx, step, d));
       step_done = true;

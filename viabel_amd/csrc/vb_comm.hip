@@ -324,11 +324,9 @@ int vb_comm_ipc_window(vb_ctx* ctx, size_t cap_doubles, char handle[VB_IPC_HANDL
   double* w = nullptr;
   // The window -- flag words and data -- is polled and read by PEER GPUs while kernels run on both sides: fine-grained
   // (system-coherent) device memory, as RCCL allocates its own flag and buffer areas; coarse-grained hipMalloc memory is
-  // only guaranteed visible across devices at kernel boundaries.  VB_IPC_COARSE=1 keeps the plain allocation (debugging).
-  static const bool coarse = getenv("VB_IPC_COARSE") && atoi(getenv("VB_IPC_COARSE")) != 0;
-  hipError_t e = coarse ? hipMalloc((void**)&w, bytes) : hipExtMallocWithFlags((void**)&w, bytes, hipDeviceMallocFinegrained);
-  if (e != hipSuccess) return fail(ctx, VB_ERR_HIP, "IPC window (%zu bytes, %s): %s", bytes, coarse ? "coarse" : "fine-grained",
-                                   hipGetErrorString(e));
+  // only guaranteed visible across devices at kernel boundaries.
+  hipError_t e = hipExtMallocWithFlags((void**)&w, bytes, hipDeviceMallocFinegrained);
+  if (e != hipSuccess) return fail(ctx, VB_ERR_HIP, "IPC window (%zu bytes, fine-grained): %s", bytes, hipGetErrorString(e));
   unsigned* ticket = nullptr;
   unsigned* err_host = nullptr;
   void* err_dev = nullptr;

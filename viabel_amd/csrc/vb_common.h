@@ -138,17 +138,15 @@ struct NoiseSlot {
 const double* noise_row_norms(vb_ctx* ctx, NoiseSlot& s, hipStream_t st);
 int rng_row_norms(vb_ctx* ctx, hipStream_t st, const double* src, int64_t ld, int64_t n, int64_t d, double* norms);
 
-// Software pipeline over three HIP streams (prep | streaming kernel | finalize + collectives), used
-// by the asynchronous batch entry points so that consecutive batches overlap.
+// Rotating workspace sets of the mean-field evaluations, and the `post` stream on which sharded jobs run the
+// all-reduce and the epilogue so that the next batch's kernels overlap them.
 constexpr int kPipeSets = 4;
 struct Pipeline {
-  hipStream_t pre = nullptr, post = nullptr;
-  hipEvent_t ev_main = nullptr;
-  hipEvent_t ev_prep[kPipeSets] = {}, ev_k1[kPipeSets] = {}, ev_fin[kPipeSets] = {};
+  hipStream_t post = nullptr;
+  hipEvent_t ev_k1[kPipeSets] = {}, ev_fin[kPipeSets] = {};
   bool fin_valid[kPipeSets] = {};
   uint64_t seq = 0;
   int last_set = 0;
-  bool main_dirty = true;     // main-stream work was enqueued that `pre` has not been ordered after
   bool post_pending = false;  // `post` holds work the main stream has not been ordered after
 };
 
@@ -176,7 +174,7 @@ struct vb_ctx {
   vb::ResultSlot sync_result;           // used by the synchronous entry points
   // completion words of the blocking mean-field call (pinned, device-mapped): finalize workgroup g stores the call's
   // sequence number into done_host[8 g] behind its results, the host polls them instead of waking up through
-  // hipStreamSynchronize (VB_MF_FLAGSYNC=0 turns this off)
+  // hipStreamSynchronize
   unsigned long long* done_host = nullptr;
   unsigned long long* done_dev = nullptr;
   unsigned long long done_seq = 0;
@@ -412,10 +410,6 @@ struct MfCall {
   unsigned flags = 0;
   int cv_mode = 0;
   int mode = 0;        // 0: ELBO (ExclusiveKL); 1: weighted gradient only
-  bool pipelined = false;   // spread prep / stream / finalize over the three pipeline streams
-  bool alternate = false;      // single GPU, independent asynchronous batches: odd workspace sets run on the
-                               // `post` stream, even ones on the main stream, so the small prep / finalize kernels of
-                               // one batch overlap the streaming kernel of the other (no events between them)
   bool overlap_comm = false;   // sharded job: all-reduce + epilogue on the `post` stream, so the next batch's
                                // kernels run on the main stream while RCCL moves this batch's sums
   double scale = 0.0;  // mode 1

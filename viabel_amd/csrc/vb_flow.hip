@@ -357,7 +357,6 @@ int flow_order_main(vb_ctx* ctx) {
     VB_HIP(ctx, hipStreamWaitEvent(ctx->stream, P.ev_fin[P.last_set], 0));
     P.post_pending = false;
   }
-  P.main_dirty = true;
   return VB_OK;
 }
 

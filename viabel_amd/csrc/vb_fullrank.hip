@@ -118,57 +118,6 @@ struct EpiStoreZ {          // Z = acc [* rs_n] + mu - shift   (shift = 0, or th
   }
 };
 
-// The sampling product with the k range of its HEAVY column blocks cut in two (round 6; VB_FR_HSPLIT=1):
-// split 0 (k < k_half, the whole product for the columns whose k range ends there) stores Z as EpiStoreZ does; split 1
-// (k >= k_half: only the column blocks to the right of k_half have any) stores its partial products into `slab`, and
-// fr_zfix_kernel adds them to Z's right half.  Deterministic (fixed order: split 0 + split 1).
-struct EpiStoreZHeavy {
-  double* Z;
-  int64_t ldz;
-  const double* mu;
-  const double* shift;      // may be nullptr
-  double* slab;
-  int k_half;
-  __device__ void operator()(int split, int row, int col, double acc) const {
-    if (split == 0) {
-      double z = acc + mu[col];
-      if (shift) z -= shift[col];
-      Z[(int64_t)row * ldz + col] = z;
-    } else if (col >= k_half) {
-      slab[(int64_t)row * ldz + col] = acc;
-    }
-  }
-  __device__ d2v pair(int split, int row, int col, double a0, double a1) const {
-    if (split == 0) {
-      const d2v m = *reinterpret_cast<const d2v*>(mu + col);
-      d2v z = (d2v){a0 + m.x, a1 + m.y};
-      if (shift) {
-        const d2v sh = *reinterpret_cast<const d2v*>(shift + col);
-        z.x -= sh.x, z.y -= sh.y;
-      }
-      *reinterpret_cast<d2v*>(Z + (int64_t)row * ldz + col) = z;
-      return z;
-    }
-    if (col >= k_half) *reinterpret_cast<d2v*>(slab + (int64_t)row * ldz + col) = (d2v){a0, a1};
-    return (d2v){a0, a1};
-  }
-};
-
-__global__ void __launch_bounds__(256) fr_zfix_kernel(const double* __restrict__ slab, int64_t n, int d, int64_t ldz, int k_half,
-                                                      double* __restrict__ Z) {
-  const int half_pairs = (d - k_half + 1) / 2;
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= n * half_pairs) return;
-  const int64_t row = t / half_pairs;
-  const int c = k_half + 2 * (int)(t % half_pairs);
-  const int64_t idx = row * ldz + c;
-  d2v z = *reinterpret_cast<const d2v*>(Z + idx);
-  const d2v p = *reinterpret_cast<const d2v*>(slab + idx);
-  z.x += p.x;
-  if (c + 1 < d) z.y += p.y;
-  *reinterpret_cast<d2v*>(Z + idx) = z;
-}
-
 // regression targets (VB_MODEL_LOGISTIC with a VB_GLM_* likelihood): eta = Z X' -> R = dloglik / deta and the
 // log-likelihood sum, then G = R X - Z / prior_sd^2 by glm_grad_enqueue (the two GEMMs of vb_logistic.h behind the
 // sampling GEMM)
@@ -512,14 +461,6 @@ static void fr_reduce_launch(vb_ctx* ctx, hipStream_t st, const double* Cpart, i
     hipLaunchKernelGGL(fr_reduce_kernel<16>, grid, dim3(256), 0, st, Cpart, splits, slab, d, ldl, colpart, n_rb, ldz, fpart, n_fpart,
                        S, full, wpart, nb_c);
 }
-
-#ifdef VB_DBG_IDLE
-// experiment (tools/build_variant.sh idle -DVB_DBG_IDLE): one wave that sleeps for `ticks` of the 100 MHz clock
-__global__ void dbg_idle_kernel(long long ticks) {
-  const long long t0 = wall_clock64();
-  while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
-}
-#endif
 
 // ---- full-rank Gaussian: split reduction straight into the flat (paragami) layout -----------------------
 // Same pair-per-thread reduction as fr_reduce_kernel (same summation order), but entry (i, j <= i) lands at the
@@ -906,11 +847,8 @@ int fr_upload_begin(vb_ctx* ctx, const double* theta_host, int64_t d) {
   double* mu = (double*)ctx->fr_lt.ptr;
   double* Lt = mu + ldl;
   double* dev = (double*)ctx->fr_theta.ptr;
-  // chunk boundaries in column blocks of 64: equal areas of the triangle, from the bottom
-  const char* ce = getenv("VB_FR_UPLOAD_CHUNKS");      // (experiments; read per call)
-  const int want = ce ? atoi(ce) : 3;
-  int nc = want < 1 ? 1 : want > 4 ? 4 : want;
-  if (nc > tn) nc = tn;
+  // chunk boundaries in column blocks of 64: equal areas of the triangle, from the bottom (three chunks)
+  const int nc = tn < 3 ? tn : 3;
   int edge[5];
   edge[0] = tn;
   for (int c = 1; c < nc; ++c) {
@@ -1088,11 +1026,9 @@ int gram_lower_enqueue(vb_ctx* ctx, const double* A, const double* B, int64_t ld
   g3.N = d;
   g3.K = (int)n;
   g3.tri_mode = 2;
-  const char* cfg_env = getenv("VB_GRAM_CFG");      // experiments: the tile configuration of this product alone (vb_gemm_f64.h)
   const char* xcd_env = getenv("VB_GRAM_XCD");
   g3.xcd_group = xcd_env ? atoi(xcd_env) : 1;
-  gemm_f64_launch<false>(ctx->stream, g3, splits, ctx->prop.multiProcessorCount, EpiSplitSlab{Cpart, ldc, slab},
-                         cfg_env ? atoi(cfg_env) : 0);
+  gemm_f64_launch<false>(ctx->stream, g3, splits, ctx->prop.multiProcessorCount, EpiSplitSlab{Cpart, ldc, slab});
   VB_HIP(ctx, hipGetLastError());
   return VB_OK;
 }
@@ -1168,11 +1104,6 @@ int gram_splits(vb_ctx* ctx, int d, int64_t n) {
   int splits = ctx->prop.multiProcessorCount / lower_tiles;
   const int max_splits = (int)(n / 256) > 0 ? (int)(n / 256) : 1;
   if (splits > max_splits) splits = max_splits;
-  static const int forced = [] {
-    const char* e = getenv("VB_GRAM_SPLITS");
-    return e ? atoi(e) : 0;
-  }();
-  if (forced > 0 && forced < splits) splits = forced;
   return splits < 1 ? 1 : splits;
 }
 
@@ -1286,7 +1217,7 @@ static int fr_fused_enqueue(vb_ctx* ctx, hipStream_t st, int phases, GemmArgs g1
   const size_t words = 16 + 2 * (size_t)tm * tn;
   VB_TRY(ensure(ctx, ctx->fz_words, words * sizeof(unsigned)));      // (a new allocation is zeroed by ensure)
   unsigned* wbase = (unsigned*)ctx->fz_words.ptr;
-  const int64_t key[5] = {n, D, splits, phases, n_p3};      // (the group count is read once per process)
+  const int64_t key[5] = {n, D, splits, phases, n_p3};
   if (memcmp(key, ctx->fz_key, sizeof key) != 0 || !ctx->fz_items.ptr) {
     // the list, in a topological order: every Z tile heaviest k range first; then row block by row block the G tiles,
     // and behind the last row block of a split the C tiles of that split
@@ -1294,30 +1225,25 @@ static int fr_fused_enqueue(vb_ctx* ctx, hipStream_t st, int phases, GemmArgs g1
     auto push = [&host](int phase, int bx, int bz) {
       host.push_back(phase), host.push_back(bx), host.push_back(bz), host.push_back(0);
     };
-    // (VB_FR_FUSED_GROUPS = g: the row blocks in g groups, each group's Z tiles followed by its G tiles -- measured, see
+    // (the row blocks cut into groups, each group's Z tiles followed by its G tiles, was measured and dropped:
     // profiles/r04_fused_timeline.txt)
-    static const int groups_env = getenv("VB_FR_FUSED_GROUPS") ? atoi(getenv("VB_FR_FUSED_GROUPS")) : 1;
-    const int groups = groups_env < 1 ? 1 : (groups_env > tm ? tm : groups_env);
     std::vector<int> map;
     if (phases == 3 && g3.tile_map) {
       map.resize((size_t)2 * n_p3);
       VB_HIP(ctx, hipMemcpy(map.data(), g3.tile_map, map.size() * sizeof(int), hipMemcpyDeviceToHost));
     }
+    // block x of the triangular product: idx = x / tm selects the column block (heaviest first), x % tm the row block
+    for (int idx = 0; idx < tn; ++idx)
+      for (int rb = 0; rb < tm; ++rb) push(0, idx * tm + rb, 0);
     int z_next = 0;
-    for (int grp = 0; grp < groups; ++grp) {
-      const int rb0 = (int)((int64_t)tm * grp / groups), rb1 = (int)((int64_t)tm * (grp + 1) / groups);
-      // block x of the triangular product: idx = x / tm selects the column block (heaviest first), x % tm the row block
-      for (int idx = 0; idx < tn; ++idx)
-        for (int rb = rb0; rb < rb1; ++rb) push(0, idx * tm + rb, 0);
-      for (int rb = rb0; rb < rb1; ++rb) {
-        for (int cb = 0; cb < tn; ++cb) push(1, cb * tm + rb, 0);
-        while (phases == 3 && z_next < splits) {
-          const int64_t last_row = std::min<int64_t>(n, (int64_t)(z_next + 1) * g3.k_split) - 1;
-          if (last_row / 128 > rb) break;
-          for (int bx = 0; bx < n_p3; ++bx)
-            if (map.empty() || map[2 * bx] >= 0) push(2, bx, z_next);
-          ++z_next;
-        }
+    for (int rb = 0; rb < tm; ++rb) {
+      for (int cb = 0; cb < tn; ++cb) push(1, cb * tm + rb, 0);
+      while (phases == 3 && z_next < splits) {
+        const int64_t last_row = std::min<int64_t>(n, (int64_t)(z_next + 1) * g3.k_split) - 1;
+        if (last_row / 128 > rb) break;
+        for (int bx = 0; bx < n_p3; ++bx)
+          if (map.empty() || map[2 * bx] >= 0) push(2, bx, z_next);
+        ++z_next;
       }
     }
     VB_TRY(ensure(ctx, ctx->fz_items, host.size() * sizeof(int)));
@@ -1348,8 +1274,7 @@ static int fr_fused_enqueue(vb_ctx* ctx, hipStream_t st, int phases, GemmArgs g1
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fr_fused_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     configured = true;
   }
-  static const int wgs_env = getenv("VB_FR_FUSED_WGS") ? atoi(getenv("VB_FR_FUSED_WGS")) : 0;
-  const unsigned grid = (unsigned)(wgs_env > 0 ? wgs_env : 2 * n_cu);
+  const unsigned grid = (unsigned)(2 * n_cu);
   if (phases == 3) hipLaunchKernelGGL(fr_fused_kernel<3>, dim3(grid), dim3(256), lds, st, a);
   else hipLaunchKernelGGL(fr_fused_kernel<2>, dim3(grid), dim3(256), lds, st, a);
   VB_HIP(ctx, hipGetLastError());
@@ -1399,10 +1324,6 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
                 (long long)ns.n, (long long)ns.d, (long long)n, (long long)d);
   hipStream_t st = ctx->stream;
   const int D = (int)d;
-  // tile-configuration overrides of the three GEMMs (experiments; 0 = the launcher's choice)
-  static const int cfg1 = getenv("VB_FR_G1_CFG") ? atoi(getenv("VB_FR_G1_CFG")) : 0;
-  static const int cfg2 = getenv("VB_FR_G2_CFG") ? atoi(getenv("VB_FR_G2_CFG")) : 0;
-  static const int cfg3 = getenv("VB_FR_G3_CFG") ? atoi(getenv("VB_FR_G3_CFG")) : 0;
   const int64_t ldl = round_up(d, 16), ldz = round_up(d, 16);
   const int n_cu = ctx->prop.multiProcessorCount;
   const int tiles = gemm_tiles(D, 128);
@@ -1411,10 +1332,7 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
   // at least this many sample rows per split: 192 lets D = 512 take 21 splits of its 36 lower 64 x 64 tiles (756
   // workgroups on the 768 resident slots: gradient GEMM 38.9 -> 33.7 us, split reduction 8.5 -> 10.4 us; 256 rows
   // stopped it at 16 splits); D = 1024 takes 7 either way
-  static const int split_rows = getenv("VB_FR_SPLIT_ROWS") ? atoi(getenv("VB_FR_SPLIT_ROWS")) : 192;
-  const int max_splits = (int)(n / split_rows) > 0 ? (int)(n / split_rows) : 1;
-  static const int splits_env = getenv("VB_FR_SPLITS") ? atoi(getenv("VB_FR_SPLITS")) : 0;      // experiment
-  if (splits_env > 0) splits = splits_env;
+  const int max_splits = (int)(n / 192) > 0 ? (int)(n / 192) : 1;
   if (splits > max_splits) splits = max_splits;
   if (splits < 1) splits = 1;
   const int n_rb = (int)((n + 127) / 128);
@@ -1445,8 +1363,7 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
   S.off_col = 16;
   S.off_c = 16 + ldz;
   S.len = 16 + ldz + (mvt ? slab : round_up(np, 16));
-  static const bool overlap_env = !(getenv("VB_COMM_OVERLAP") && atoi(getenv("VB_COMM_OVERLAP")) == 0);
-  const bool overlap = !mvt && ctx->comm != nullptr && overlap_env;
+  const bool overlap = !mvt && ctx->comm != nullptr;
   const int64_t o_sums = carve(S.len * (overlap ? 2 : 1));
   VB_TRY(ensure(ctx, ctx->fr_work, (size_t)off * sizeof(double)));
   double* base = (double*)ctx->fr_work.ptr;
@@ -1459,11 +1376,10 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
     VB_TRY(ensure(ctx, ctx->fr_lt, (size_t)(ldz + slab) * sizeof(double)));
     mu = (double*)ctx->fr_lt.ptr;
     Lt = mu + ldz;
-    static const bool cache_env = !(getenv("VB_FR_UNPACK_CACHE") && atoi(getenv("VB_FR_UNPACK_CACHE")) == 0);
     const bool resident = theta_dev == (const double*)ctx->fr_theta.ptr;
     // ... or vb_fit's parameter, whose step kernel wrote mu and L' of the stepped value itself (fr_step_unpack_enqueue)
     const bool stepped = ctx->fr_lt_owner != nullptr && ctx->fr_lt_owner == theta_dev;
-    lt_cached = cache_env && (resident || stepped) && ctx->fr_lt_d == d;
+    lt_cached = (resident || stepped) && ctx->fr_lt_d == d;
     if (!stepped) ctx->fr_lt_owner = nullptr;
     ctx->fr_lt_d = (resident || stepped) ? d : 0;     // (a foreign parameter leaves the copy stale for the resident one)
   }
@@ -1541,23 +1457,20 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
   int fmode = 0;
   // correlated-Gaussian target under the dense Gaussian family: no pass over G and Z between the GEMMs -- sum f comes
   // out of the model GEMM's epilogue (EpiNegateF) and the column sums of G out of the gradient GEMM (EpiSplitSlabCs)
-  static const bool fast_env = !(getenv("VB_FR_FUSED_SUMS") && atoi(getenv("VB_FR_FUSED_SUMS")) == 0);
-  const bool fused_sums = fast_env && !mvt && m.id == VB_MODEL_GAUSS_FULL && !wm.roww && !row_scale &&
+  const bool fused_sums = !mvt && m.id == VB_MODEL_GAUSS_FULL && !wm.roww && !row_scale &&
                           n % kGemmBK == 0 && gemm_uses_dma(g1) && (int64_t)splits <= n_rb;
   // short shards (fewer than two 64 x 64 tiles per CU): the N x D x D products with their k range cut into `kparts`
   // pieces (see fr_zsum_kernel); the slabs of partial products live in the split area of the gradient product, which
   // is not in use yet
-  static const int kparts_env = getenv("VB_FR_KPARTS") ? atoi(getenv("VB_FR_KPARTS")) : -1;     // experiments; 1 = off
   int kparts = 1;
   const int64_t pslab = n * ldz;
-  if (!row_scale && !pd && cfg1 == 0 && cfg2 == 0 && m.id != VB_MODEL_GAUSS_DIAG) {      // (pd keeps a slab of its own there)
+  if (!row_scale && !pd && m.id != VB_MODEL_GAUSS_DIAG) {      // (pd keeps a slab of its own there)
     // measured (tools/fr_bench.py, D = 1024): 512 rows 126 -> 85 us per evaluation, 256 rows 118 -> 61 us, 1 024 rows
     // 133 -> 128 us, 2 048 rows unchanged (not split).  At D = 512 a tile's 32 slabs are no longer than a piece plus
     // the extra kernel: not split (pieces of at least 16 slabs out of at least 48).
     const long tiles64 = gemm_count_blocks(g1, 64, 64);
     if (tiles64 < 2L * n_cu && D >= 48 * kGemmBK) kparts = (int)((2L * n_cu + tiles64 - 1) / tiles64);
     if (kparts > 4) kparts = 4;
-    if (kparts_env >= 1) kparts = kparts_env;
     while (kparts > 1 && (D % (kGemmBK * kparts) != 0 || D / kparts < 16 * kGemmBK)) --kparts;
     if ((int64_t)kparts * pslab > (int64_t)(splits + 1) * slab) kparts = 1;
   }
@@ -1567,18 +1480,18 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
     const char* e = getenv("VB_FR_FUSED");
     fz_mode = e ? atoi(e) : 0;
   }
-  if (!(fused_sums && kparts == 1 && cfg1 == 0 && cfg2 == 0 && cfg3 == 0 && n % 128 == 0 && D % 64 == 0 &&
+  if (!(fused_sums && kparts == 1 && n % 128 == 0 && D % 64 == 0 &&
         (int64_t)n * ldz * 8 < ((int64_t)1 << 31)))
     fz_mode = 0;
   if ((fz_mode != 2 && fz_mode != 3) || pd) fz_mode = 0;      // (the path derivative changes G between the products)
   const unsigned sum_blocks = (unsigned)((pslab / 2 + 255) / 256);
   // Z = E L' + mu - shift into `Z` (the samples, or z - m for the correlated Gaussian target)
-  auto sample_gemm = [&](const double* shift, int cfg) {
+  auto sample_gemm = [&](const double* shift) {
     if (wm.z_ready && !shift) {      // (the caller's samples: see FrWeighted)
       Z = const_cast<double*>(wm.z_ready);
       return;
     }
-    if (up && !up_waited && kparts == 1 && cfg == 0 && !row_scale && gemm_uses_dma(g1) && up->n_chunks > 1 &&
+    if (up && !up_waited && kparts == 1 && !row_scale && gemm_uses_dma(g1) && up->n_chunks > 1 &&
         gemm_count_blocks(g1, 128, 64) < 4L * n_cu) {
       // chunk 0 (the heaviest column blocks) on the main stream behind its event; the lighter chunks on side streams
       // behind theirs (and behind everything the main stream had queued before: the noise), joined below
@@ -1602,32 +1515,18 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
       return;
     }
     (void)up_wait_all();
-    {
-      // experiment: two-way k split of the heavy column blocks only
-      const char* he = getenv("VB_FR_HSPLIT");
-      const int k_half = gemm_tiles(gemm_tiles(D, 2), kGemmBK) * kGemmBK;
-      if (he && atoi(he) != 0 && kparts == 1 && !mvt && !row_scale && gemm_uses_dma(g1) && D % 2 == 0 && D >= 384 &&
-          gemm_count_blocks(g1, 64, 64) <= 2L * n_cu && k_half % 64 == 0 && pslab <= (int64_t)(splits + 1) * slab) {
-        const int hc = atoi(he) == 2 ? 4 : 8;
-        gemm_f64_launch<true>(st, g1, 2, n_cu, EpiStoreZHeavy{Z, ldz, mu, shift, Cpart, k_half}, cfg ? cfg : hc);
-        const int64_t items = n * ((D - k_half + 1) / 2);
-        hipLaunchKernelGGL(fr_zfix_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, (const double*)Cpart, n, D, ldz,
-                           k_half, Z);
-        return;
-      }
-    }
     if (kparts > 1) {
       gemm_f64_launch<true>(st, g1, kparts, n_cu, EpiSplitSlab{Cpart, ldz, pslab});
       hipLaunchKernelGGL(fr_zsum_kernel, dim3(sum_blocks), dim3(256), 0, st, (const double*)Cpart, kparts, pslab, n, D, ldz,
                          (const double*)mu, shift, Z);
     } else {
-      gemm_f64_launch<true>(st, g1, 1, n_cu, EpiStoreZ{Z, ldz, mu, shift, row_scale}, cfg);
+      gemm_f64_launch<true>(st, g1, 1, n_cu, EpiStoreZ{Z, ldz, mu, shift, row_scale});
     }
   };
   unsigned tiles2 = 0;
   bool g_prescaled = false;      // the target's own kernel wrote G already scaled by the row weights
   // diagonal Gaussian target under the dense Gaussian family: sum f out of the sampling product's epilogue
-  const bool diag_f = fast_env && !mvt && m.id == VB_MODEL_GAUSS_DIAG && !wm.roww && !row_scale &&
+  const bool diag_f = !mvt && m.id == VB_MODEL_GAUSS_DIAG && !wm.roww && !row_scale &&
                       n % kGemmBK == 0 && gemm_uses_dma(g1) && (int64_t)splits <= n_rb;
   if (m.id == VB_MODEL_GAUSS_DIAG) VB_TRY(up_wait_all());      // (a reducing epilogue: one launch)
   if (m.id == VB_MODEL_GAUSS_DIAG && diag_f) {
@@ -1637,17 +1536,17 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
     gemm_f64_launch<true>(st, g1, 1, n_cu, EpiGaussDiag{G, ldz, mu, m.p0, m.p1, row_scale});
     fmode = 1;
   } else if (m.id == VB_MODEL_FUNNEL) {
-    sample_gemm(nullptr, 0);
+    sample_gemm(nullptr);
     VB_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(fr_funnel_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const double*)Z,
                        G, ldz, n, D, m, fpart, wm.roww);
     g_prescaled = wm.roww != nullptr;
   } else if (source) {        // the user's row kernel: G and one f per sample (summed with the other f partials)
-    sample_gemm(nullptr, 0);
+    sample_gemm(nullptr);
     VB_HIP(ctx, hipGetLastError());
     VB_TRY(user_rows_enqueue(ctx, st, Z, ldz, n, D, G, ldz, fpart));
   } else if (glm) {
-    sample_gemm(nullptr, 0);
+    sample_gemm(nullptr);
     VB_HIP(ctx, hipGetLastError());
     double* Rm = base + o_r;
     double* part = fpart + (int64_t)n_rb * cs_gx;
@@ -1687,8 +1586,8 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
       VB_TRY(up_wait_all());
       VB_TRY(fr_fused_enqueue(ctx, st, fz_mode, g1, g2, g3f, splits, Z, G, ldz, mu, m.p0, fpart, e3, &tiles2));
     } else {
-    sample_gemm(m.p0, cfg1);                         // Z - m
-    VB_HIP(ctx, hipGetLastError());
+      sample_gemm(m.p0);                         // Z - m
+      VB_HIP(ctx, hipGetLastError());
     }
     if (fz_mode >= 2 || wm.g_ready) {
     } else if (kparts > 1 && fused_sums) {
@@ -1698,19 +1597,13 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
       tiles2 = sum_blocks;
     } else {
       prof_events(ctx, &g2.ev0, &g2.ev1, 1, VB_PROF_FR_MODEL_GEMM);
-      if (fused_sums) tiles2 = gemm_f64_launch<true>(st, g2, 1, n_cu, EpiNegateF{G, ldz, Z, fpart}, cfg2);
-      else gemm_f64_launch<true>(st, g2, 1, n_cu, EpiNegate{G, ldz}, cfg2);
+      if (fused_sums) tiles2 = gemm_f64_launch<true>(st, g2, 1, n_cu, EpiNegateF{G, ldz, Z, fpart});
+      else gemm_f64_launch<true>(st, g2, 1, n_cu, EpiNegate{G, ldz});
     }
     fmode = wm.g_ready ? 0 : 2;      // (weighted sums take their value from the weights: no f here)
   }
   VB_HIP(ctx, hipGetLastError());
 
-#ifdef VB_DBG_IDLE
-  {
-    static const int idle_us = getenv("VB_FR_IDLE_US") ? atoi(getenv("VB_FR_IDLE_US")) : 0;
-    if (idle_us > 0) hipLaunchKernelGGL(dbg_idle_kernel, dim3(1), dim3(64), 0, st, (long long)idle_us * 100);
-  }
-#endif
   if (wm.roww && !g_prescaled) {   // weighted sums: scale the rows of G before anything is summed
     hipLaunchKernelGGL(fr_rowscale_kernel, dim3((unsigned)n, (unsigned)((D + 255) / 256)), dim3(256), 0, st, G, ldz, n,
                        D, wm.roww);
@@ -1729,7 +1622,7 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
   // targets whose row kernel leaves sum f behind already (funnel, source models): the column sums of G are all the pass
   // below would add, and they come out of the gradient product's LDS tiles as for the correlated Gaussian
   // (weighted sums: the same, once G is scaled -- the column sums of the gradient product's operand tiles ARE sum w g)
-  const bool cs_only = diag_f || (fast_env && !fused_sums && !mvt && (m.id == VB_MODEL_FUNNEL || source) &&
+  const bool cs_only = diag_f || (!fused_sums && !mvt && (m.id == VB_MODEL_FUNNEL || source) &&
                                  (!wm.roww || g_prescaled) &&
                                  !row_scale && n % kGemmBK == 0 && gemm_uses_dma(g3) && (int64_t)splits <= n_rb);
   // path derivative: sum f belongs to the model's G, the column sums and the gradient product to G~ = G + E L^-1.  Where
@@ -1776,13 +1669,12 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
     n_rb_red = splits;
     n_fpart_red = (int)tiles2;
   } else if (fused_sums || cs_only) {
-    static const bool map_env = !(getenv("VB_FR_TILE_MAP") && atoi(getenv("VB_FR_TILE_MAP")) == 0);
-    int cfg3_used = cfg3;
-    if (map_env && cfg3 == 0 && gemm_count_blocks(g3, 128, 64) * splits * 100 >= 190L * n_cu) {
-      cfg3_used = 2;     // the launcher's own choice for this shape (128 x 64 tiles), made here so that the list fits it
+    int cfg3 = 0;
+    if (gemm_count_blocks(g3, 128, 64) * splits * 100 >= 190L * n_cu) {
+      cfg3 = 2;     // the launcher's own choice for this shape (128 x 64 tiles), made here so that the list fits it
       VB_TRY(tri2_tile_map(ctx, D, 128, 64, &g3.tile_map, &g3.tile_blocks));
     }
-    gemm_f64_launch<false>(st, g3, splits, n_cu, EpiSplitSlabCs{Cpart, ldl, slab, colpart, ldz}, cfg3_used);
+    gemm_f64_launch<false>(st, g3, splits, n_cu, EpiSplitSlabCs{Cpart, ldl, slab, colpart, ldz}, cfg3);
     n_rb_red = splits;                  // one row of column sums per split
     if (fused_sums || diag_f) n_fpart_red = (int)tiles2;          // one partial of sum f per tile of the model GEMM
   } else {
@@ -1823,10 +1715,8 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
   VB_TRY(comm_allreduce_sum(ctx, st_post, S.sums, (size_t)S.len));
   // one workgroup per CU: 328 -> 310 us per evaluation with a one-rank communicator (64: 312, 16: 350 -- the epilogue
   // then is what the evaluation after next waits for; unlimited = 2 050 workgroups: 328)
-  static const int epi_env = getenv("VB_FR_EPI_WGS") ? atoi(getenv("VB_FR_EPI_WGS")) : -1;
-  const int epi_cap = epi_env >= 0 ? epi_env : n_cu;
   const int64_t epi_full = (np + 255) / 256;
-  const unsigned epi_grid = (unsigned)((overlap && epi_cap > 0 && epi_full > epi_cap) ? epi_cap : epi_full);
+  const unsigned epi_grid = (unsigned)((overlap && epi_full > n_cu) ? n_cu : epi_full);
   hipLaunchKernelGGL(fr_epilogue_packed_kernel, dim3(epi_grid), dim3(256), 0, st_post, S,
                      theta_dev, D, (double)n_total, (double)n_total, m.c0, out_dev, pd ? 1 : 0, wm);
   VB_HIP(ctx, hipGetLastError());

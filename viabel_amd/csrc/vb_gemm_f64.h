@@ -402,8 +402,7 @@ inline long gemm_count_blocks(const GemmArgs& g, int bm_rows, int bn_cols) {
 // flags bit 0: force the register-staged kernel
 // does a product of this shape go to the LDS-DMA kernel (which alone implements EpiColsum)?
 inline bool gemm_uses_dma(const GemmArgs& g) {
-  static const bool dma_ok = !(getenv("VB_GEMM_DMA") && atoi(getenv("VB_GEMM_DMA")) == 0);
-  return dma_ok && g.K % kGemmBK == 0 && g.M > 0 && g.N > 0;
+  return g.K % kGemmBK == 0 && g.M > 0 && g.N > 0;
 }
 
 // returns gridDim.x of the launch (the number of output tiles; reducing epilogues write one partial per tile and split)
@@ -418,8 +417,6 @@ inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu
   if (splits < 1) splits = 1;
   int ks = g.batch ? g.K : gemm_tiles(g.K, splits);   // batch mode: `splits` is the number of products
   g.k_split = gemm_tiles(ks, kGemmBK) * kGemmBK;
-  static const int cfg_env = getenv("VB_GEMM_CFG") ? atoi(getenv("VB_GEMM_CFG")) : 0;   // experiments: force a tile
-  if (cfg == 0 && cfg_env >= 1 && cfg_env <= 8) cfg = cfg_env;
   // operands straight into LDS (vb_gemm_f64_dma.h) when every k range is a whole number of slabs
   const bool dma = gemm_uses_dma(g) && !(flags & 1);
   if (g.tri_mode == 3 && (!dma || splits != 1 || g.batch)) g.tri_mode = 0;      // the zeros are multiplied instead of skipped
@@ -466,10 +463,9 @@ inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu
   const dim3 grid(g.tile_map ? (unsigned)g.tile_blocks
                              : g.bn_count ? (unsigned)(g.tiles_m * g.bn_count) : (unsigned)gemm_count_blocks(g, bm_rows, bn_cols), 1,
                   (unsigned)splits);
-  static const int prio_env = getenv("VB_GEMM_PRIO") ? atoi(getenv("VB_GEMM_PRIO")) : 1;
   // (triangular k ranges: the tiles of a CU differ in length anyway, and the alternation costs 1 - 3 us there --
-  // 4096 x 768 x 768: 55.5 -> 52.7 us, 512: 30.1 -> 29.1 us, 1024: unchanged, tools/gemm_bench.hip with VB_GEMM_PRIO=0)
-  g.prio_div = (prio_env && g.tri_mode != 1 && g.tri_mode != 3) ? n_cu : 0;
+  // 4096 x 768 x 768: 55.5 -> 52.7 us, 512: 30.1 -> 29.1 us, 1024: unchanged, tools/gemm_bench.hip with it switched off)
+  g.prio_div = (g.tri_mode != 1 && g.tri_mode != 3) ? n_cu : 0;
   if (dma) {
     if (cfg == 1) gemm_f64_dma_launch<A_KCONTIG, 4, 16, 3, Epi>(st, g, grid, epi);
     else if (cfg == 2) gemm_f64_dma_launch<A_KCONTIG, 4, 8, 3, Epi>(st, g, grid, epi);

@@ -535,8 +535,7 @@ static int lr_run(vb_ctx* ctx, const NoiseSlot& ns, const NoiseSlot& nz, int64_t
   a.G = nullptr, a.frow = nullptr;
   a.n_cb = (int)((d + kLrCols - 1) / kLrCols);
   a.Dp = a.n_cb * kLrCols;
-  const char* wg_env = getenv("VB_LR_WG_PER_CU");
-  int n_rb_target = (wg_env && *wg_env ? atoi(wg_env) : 2) * ctx->prop.multiProcessorCount / a.n_cb;
+  int n_rb_target = 2 * ctx->prop.multiProcessorCount / a.n_cb;
   if (n_rb_target < 8) n_rb_target = 8;
   int rows_per_wg = (int)((n + n_rb_target - 1) / n_rb_target);
   if (rows_per_wg > kLrMaxRows) rows_per_wg = kLrMaxRows;

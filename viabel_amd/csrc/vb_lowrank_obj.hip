@@ -268,12 +268,7 @@ LroLayout lro_layout(int64_t n, int64_t n_total, int64_t d, int64_t k) {
   L.ld = round_up(d, 16);
   L.nn = round_up(n_total, 16);
   L.n_rb = (int)((n + 127) / 128);
-  static const int rows_per_split = [] {
-    const char* e = getenv("VB_LR_SPLIT_ROWS");
-    const int v = e ? atoi(e) : 0;
-    return v >= 16 ? v : 64;
-  }();
-  int splits = (int)(n / rows_per_split);
+  int splits = (int)(n / 64);
   L.splits = splits > 32 ? 32 : (splits < 1 ? 1 : splits);
   int64_t off = 0;
   auto carve = [&off](int64_t doubles) {

@@ -1518,11 +1518,6 @@ static void launch_one(bool funnel, bool mom, bool tsc, bool gen, const Launch& 
   else launch_one_mg<VB_MODEL_GAUSS_DIAG, false>(mom, tsc, L, bp, ws, g, e, o);
 }
 
-static int env_int(const char* name, int dflt) {
-  const char* s = getenv(name);
-  return (s && *s) ? atoi(s) : dflt;
-}
-
 // Logistic-regression target: sample, two MFMA GEMMs, then the explicit-gradient streaming pass.  Fills
 // the same workspace (theta copy, column constants, prep scalars, partials) the other models fill.
 static int logistic_accumulate(vb_ctx* ctx, hipStream_t st, const ModelDev& m, const NoiseSlot& ns,
@@ -1684,22 +1679,21 @@ int mf_enqueue(vb_ctx* ctx, const MfCall& c) {
   g.n_cb = (int)((d + kMfCols - 1) / kMfCols);
   g.Dp = g.n_cb * kMfCols;
   // ~2 workgroups per CU over the whole batch; rows per workgroup a multiple of the 4 waves
-  const int target_wg = env_int("VB_MF_TARGET_WG", 2 * ctx->prop.multiProcessorCount);
+  const int target_wg = 2 * ctx->prop.multiProcessorCount;
   int n_rb_target = target_wg / g.n_cb / (c.count < 4 ? c.count : 4);
   if (n_rb_target < 8) n_rb_target = 8;
   // narrow families with the noise in memory: the finalize kernel adds one partial per row block and column in a
   // dependent chain (512 of them: 21 us at D = 64, N = 16 384 -- three times the streaming pass over those 8 MB), so a
   // small matrix is cut into at most 128 row blocks.  (Not with the noise generated in registers: that pass is bound by
   // the generator's arithmetic and wants every workgroup it can get -- MFStudentT 67 -> 106 us with the cap.)
-  if (!c.gen && n_rb_target > 128 && n * d * 8 < (int64_t)16 << 20) n_rb_target = env_int("VB_MF_MAX_ROW_BLOCKS", 128);
+  if (!c.gen && n_rb_target > 128 && n * d * 8 < (int64_t)16 << 20) n_rb_target = 128;
   n_rb_target = (n_rb_target + 7) / 8 * 8;
-  int rows_per_wg = (int)((n + n_rb_target - 1) / n_rb_target);
-  rows_per_wg = env_int("VB_MF_ROWS_PER_WG", rows_per_wg);
+  const int rows_per_wg = (int)((n + n_rb_target - 1) / n_rb_target);
   g.rows_per_wg = (int)round_up(rows_per_wg < kMfWaves ? kMfWaves : rows_per_wg, kMfWaves);
   g.n_rb = (int)((n + g.rows_per_wg - 1) / g.rows_per_wg);
   const int64_t prep_items = rows ? (n > g.Dp ? n : g.Dp) : g.Dp;
   g.n_prep = logistic ? 1 : (int)((prep_items + 255) / 256);
-  g.xcd_map = (g.n_rb % 8 == 0) ? env_int("VB_MF_XCD_MAP", 1) : 0;
+  g.xcd_map = (g.n_rb % 8 == 0) ? 1 : 0;
   g.rows = rows ? 1 : 0;
   g.df = c.df;
   g.gen = 0;
@@ -1719,7 +1713,7 @@ int mf_enqueue(vb_ctx* ctx, const MfCall& c) {
     g.gk1 = (uint32_t)(c.gen_seed >> 32) ^ (uint32_t)(c.gen_stream >> 32);
     g.gw = (uint32_t)c.gen_stream;
     g.grow0 = c.gen_row_offset;
-    if (funnel && n >= 512 && env_int("VB_MF_INLINE_ROWS", 1)) {
+    if (funnel && n >= 512) {
       // no row part in prep (nor in the previous iteration's finalize, where one workgroup would do it block after
       // block: 17 us at N = 4096): the streaming kernel does it for its own rows, and the device-resident loop stays
       // at two launches per iteration (C1: 35.0 -> 31.4 us; D = 256 / N = 1024: 23.7 -> 21.7 us).  For a handful of
@@ -1738,9 +1732,9 @@ int mf_enqueue(vb_ctx* ctx, const MfCall& c) {
   // between workgroups on different XCDs is a write-through store, a ticket and an L2-bypassing load -- a memory round
   // trip each (~2 us), three of them in sequence behind the last streaming workgroup -- where the launch boundary costs
   // ~2 us once and leaves the partial sums in an L2 every workgroup of the next kernel may hit.
-  const bool one = env_int("VB_MF_ONE", 0) && c.count == 1 && c.mode == 0 && c.cv_mode == VB_CV_NONE && !ctx->comm &&
-                   !logistic && !weighted && !c.pipelined && !c.alternate && !c.skip_prep &&
-                   (model.id == VB_MODEL_GAUSS_DIAG || funnel);
+  const char* one_env = getenv("VB_MF_ONE");      // (read per call: the tests switch it)
+  const bool one = one_env && atoi(one_env) && c.count == 1 && c.mode == 0 && c.cv_mode == VB_CV_NONE && !ctx->comm &&
+                   !logistic && !weighted && !c.skip_prep && (model.id == VB_MODEL_GAUSS_DIAG || funnel);
   if (one) {
     if (funnel && g.gen) {          // the streaming kernel forms the row scalars of its own rows, whatever n
       g.inline_rows = 1;
@@ -1788,44 +1782,15 @@ int mf_enqueue(vb_ctx* ctx, const MfCall& c) {
   }
 
   // ---- stream plan -----------------------------------------------------------------------------
-  // pipelined: prep on `pre`, the streaming kernel on the main stream, finalize (+ all-reduce,
-  // epilogue) on `post`, chained by events; otherwise everything in order on the main stream.
-  // overlap (sharded jobs, asynchronous batches): prep / streaming / finalize stay in order on the main
-  // stream; the all-reduce and the epilogue go to `post` behind ONE event, and nothing on the main stream
-  // waits for them except the re-use of this workspace set three batches later -- so RCCL moves batch i's
-  // sums while batch i+1 streams.
+  // Everything in order on the main stream.  overlap (sharded jobs, asynchronous batches): the all-reduce and the
+  // epilogue go to `post` behind ONE event, and nothing on the main stream waits for them except the re-use of this
+  // workspace set three batches later -- so RCCL moves batch i's sums while batch i+1 streams.
   Pipeline& P = ctx->pipe;
-  hipStream_t st_pre = ctx->stream, st_main = ctx->stream, st_post = ctx->stream;
-  const bool overlap = c.overlap_comm && !c.pipelined && ctx->comm != nullptr;
-  // alternate: consecutive independent batches go to two streams.  The stream is a function of the workspace
-  // set (odd -> `post`), and a set comes round again four batches later, i.e. on the same stream, so no event is
-  // needed between batches; `post` only has to be ordered after earlier main-stream work (noise uploads, blocking
-  // calls), and later main-stream writers wait for `post` through post_pending as for the other modes.
-  const bool alt = c.alternate && !c.pipelined && !overlap && ctx->comm == nullptr;
-  const bool alt_b = alt && (set & 1);
+  hipStream_t st_main = ctx->stream, st_post = ctx->stream;
+  const bool overlap = c.overlap_comm && ctx->comm != nullptr;
   if (overlap) {
     VB_TRY(pipe_init(ctx));
     if (P.fin_valid[set]) VB_HIP(ctx, hipStreamWaitEvent(ctx->stream, P.ev_fin[set], 0));   // set is free again
-  } else if (alt) {
-    VB_TRY(pipe_init(ctx));
-    if (alt_b) {
-      if (P.main_dirty) {
-        VB_HIP(ctx, hipEventRecord(P.ev_main, ctx->stream));
-        VB_HIP(ctx, hipStreamWaitEvent(P.post, P.ev_main, 0));
-        P.main_dirty = false;
-      }
-      st_pre = st_main = st_post = P.post;
-    }
-  } else if (c.pipelined) {
-    VB_TRY(pipe_init(ctx));
-    st_pre = P.pre;
-    st_post = P.post;
-    if (P.main_dirty) {   // earlier main-stream work (noise generation, uploads, ...) precedes prep
-      VB_HIP(ctx, hipEventRecord(P.ev_main, ctx->stream));
-      VB_HIP(ctx, hipStreamWaitEvent(st_pre, P.ev_main, 0));
-      P.main_dirty = false;
-    }
-    if (P.fin_valid[set]) VB_HIP(ctx, hipStreamWaitEvent(st_pre, P.ev_fin[set], 0));   // set is free again
   } else if (P.post_pending) {   // order this in-order call after everything the pipeline has in flight
     VB_HIP(ctx, hipStreamWaitEvent(ctx->stream, P.ev_fin[P.last_set], 0));
     P.post_pending = false;
@@ -1871,18 +1836,13 @@ int mf_enqueue(vb_ctx* ctx, const MfCall& c) {
     launch_one(model.id == VB_MODEL_FUNNEL, mom, tsc, g.gen != 0, L1, bp, ws, g, e1, o);
     VB_HIP(ctx, hipGetLastError());
     P.fin_valid[set] = false;
-    P.main_dirty = true;
     ctx->result_stream = st_main;
     return VB_OK;
   }
   if (!logistic && !c.skip_prep) {   // skip_prep: the previous iteration's finalize kernel has done it
-    hipLaunchKernelGGL(mf_prep_kernel, dim3((unsigned)prep_grid, (unsigned)c.count), dim3(256), 0, st_pre,
+    hipLaunchKernelGGL(mf_prep_kernel, dim3((unsigned)prep_grid, (unsigned)c.count), dim3(256), 0, st_main,
                        bp, ws, g, model);
     VB_HIP(ctx, hipGetLastError());
-  }
-  if (c.pipelined) {
-    VB_HIP(ctx, hipEventRecord(P.ev_prep[set], st_pre));
-    VB_HIP(ctx, hipStreamWaitEvent(st_main, P.ev_prep[set], 0));
   }
 
   Launch L;
@@ -1902,10 +1862,6 @@ int mf_enqueue(vb_ctx* ctx, const MfCall& c) {
   else
     launch_accum<kModelLogQ, true, false>(true, L, bp, ws, g);
   VB_HIP(ctx, hipGetLastError());
-  if (c.pipelined) {
-    VB_HIP(ctx, hipEventRecord(P.ev_k1[set], st_main));
-    VB_HIP(ctx, hipStreamWaitEvent(st_post, P.ev_k1[set], 0));
-  }
 
   EpiArgs e;
   memset(&e, 0, sizeof e);
@@ -1967,16 +1923,13 @@ int mf_enqueue(vb_ctx* ctx, const MfCall& c) {
     hipLaunchKernelGGL(mf_epilogue_kernel, dim3(1, (unsigned)c.count), dim3(256), 0, st_post, e, bp, ws);
     VB_HIP(ctx, hipGetLastError());
   }
-  if (c.pipelined || overlap || alt_b) {
+  if (overlap) {
     VB_HIP(ctx, hipEventRecord(P.ev_fin[set], st_post));
     P.fin_valid[set] = true;
     P.post_pending = true;
     P.last_set = set;
-  } else if (alt) {
-    // main-stream batch of an alternating pair: nothing on `post` depends on it
   } else {
-    P.fin_valid[set] = false;   // ordered by the main stream itself ...
-    P.main_dirty = true;        // ... which a later pipelined prep must wait for
+    P.fin_valid[set] = false;   // ordered by the main stream itself
   }
   ctx->result_stream = st_post;
   return VB_OK;
@@ -1984,12 +1937,9 @@ int mf_enqueue(vb_ctx* ctx, const MfCall& c) {
 
 int pipe_init(vb_ctx* ctx) {
   Pipeline& P = ctx->pipe;
-  if (P.pre) return VB_OK;
-  VB_HIP(ctx, hipStreamCreateWithFlags(&P.pre, hipStreamNonBlocking));
+  if (P.post) return VB_OK;
   VB_HIP(ctx, hipStreamCreateWithFlags(&P.post, hipStreamNonBlocking));
-  VB_HIP(ctx, hipEventCreateWithFlags(&P.ev_main, hipEventDisableTiming));
   for (int i = 0; i < kPipeSets; ++i) {
-    VB_HIP(ctx, hipEventCreateWithFlags(&P.ev_prep[i], hipEventDisableTiming));
     VB_HIP(ctx, hipEventCreateWithFlags(&P.ev_k1[i], hipEventDisableTiming));
     VB_HIP(ctx, hipEventCreateWithFlags(&P.ev_fin[i], hipEventDisableTiming));
   }

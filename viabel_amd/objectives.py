@@ -15,7 +15,6 @@ all-reduced on the device before the epilogue; every rank returns the same ``(va
 from abc import ABC, abstractmethod
 
 import ctypes
-import os
 import weakref
 
 import numpy as np
@@ -768,18 +767,18 @@ _ROOT_TOL = 1e-12     # ||root root - Sigma|| / ||Sigma|| accepted from the Newt
 # D = 50) gives the root and the Sylvester solve, where the device's two GEMM iterations are ~40 dependent launches
 # (0.5 ms whatever the size).  Measured per objective call (tools/mvt_root_bench.py, tools/small_shapes_bench.py):
 # D = 10: 650 -> 223 us, 50: 1042 -> 328, 100: 1593 -> 867, 160: 2100 -> 1687, 200: equal, 256: the device wins
-_HOST_ROOT_MAX_DIM = int(os.environ.get('VIABEL_AMD_HOST_ROOT_MAX_DIM', '160'))
+_HOST_ROOT_MAX_DIM = 160
 # The RESIDENT reference-identical routes of the t family (vb_dis_refresh_mvt_symroot, vb_elbo_grad_mvt_symroot[_path],
 # vb_alpha_grad_mvt_symroot) are taken for D > _RESIDENT_GATE whenever the chi-square draws are on the device (N >= 4096).
 # Measured (tools/mvt_root_gate_probe.py, N = 4096 and 16 384): they beat the host-root route at every D from 2 upwards
 # (D = 32: 0.58 against 0.83 ms, D = 160: 0.79 against 2.4 ms) -- the gate of 160 that round 4 chose for the HOST route's
 # root (LAPACK below, device iteration above) does not apply to them.
-_RESIDENT_GATE = int(os.environ.get('VIABEL_AMD_RESIDENT_GATE', '0'))
+_RESIDENT_GATE = 0
 # Below N = 4096 the chi-square draws are cheaper on the host (17 against 70 us at 1000 draws) and the host route is taken
 # with them -- unless the dimension makes the host's O(D^3) algebra the larger cost: from here on the draws are made on
 # the device whatever N, for the resident route's sake (N = 1000: host route 1.1 ms at D = 100, 2.0-2.5 ms at D = 160;
 # the resident route ~0.6 / ~0.8 ms)
-_RESIDENT_SMALL_N_MIN_DIM = int(os.environ.get('VIABEL_AMD_RESIDENT_SMALL_N_MIN_DIM', '48'))
+_RESIDENT_SMALL_N_MIN_DIM = 48
 
 
 def _device_root(eng, Sigma):
