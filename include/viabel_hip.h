@@ -399,7 +399,15 @@ int vb_elbo_sums_lowrank(vb_ctx* ctx, int slot_eps, int slot_z, int64_t n, int64
  * VB_FLAG_PATH_DERIV: the path-derivative form, -mean (dx/dtheta)' [grad log p(x) - grad_x log q(x)] with theta held
  * fixed inside log q (objectives.py:156-159).
  * vb_flow_sample: forward pass only, for the diagnostics: samples x (n x d, may be NULL), log q (n) and, when log_p is not
- * NULL, the bound model's log p (n) of the prior draws in `slot`; processed in row chunks.                            */
+ * NULL, the bound model's log p (n) of the prior draws in `slot`; processed in row chunks.
+ * vb_flow_fit: the device-resident optimiser loop (vb_fit below, same contract) for a flow handle.  Iteration k fills `slot`
+ * with this rank's rows row_offset .. row_offset + n of the prior's base noise (Philox stream first_stream + k,
+ * noise_kind / noise_df the prior's own), evaluates [value | grad] exactly as vb_flow_elbo_grad would at the device-resident
+ * theta (all-reduce included under a communicator) and applies one optimiser step; all n_iters iterations are enqueued
+ * back to back and nothing of length p crosses the bus per iteration except the logged rows.  theta (p, in / out), state,
+ * values, history (the last hist_len iterates), directions, gradients and the argument errors as vb_fit;
+ * vb_fit_history_mean serves the kept iterates afterwards.  flags: 0 or VB_FLAG_PATH_DERIV.  Callable models block once
+ * per evaluation, as in vb_fit.                                                                                          */
 typedef struct vb_flow vb_flow;
 int vb_flow_create(vb_ctx* ctx, int64_t d, int64_t k, const double* masks, int64_t n_t, const int64_t* widths_t,
                    int64_t n_s, const int64_t* widths_s, vb_flow** out);
@@ -409,6 +417,10 @@ int vb_flow_elbo_grad(vb_ctx* ctx, vb_flow* flow, int slot, int64_t n, int64_t n
                       double prior_df, const double* prior_param, const double* theta, unsigned flags, double* out);
 int vb_flow_sample(vb_ctx* ctx, vb_flow* flow, int slot, int64_t n, int prior_family, double prior_df,
                    const double* prior_param, const double* theta, double* x, double* log_q, double* log_p);
+int vb_flow_fit(vb_ctx* ctx, vb_flow* flow, int slot, int64_t n, int64_t n_total, int64_t row_offset, int prior_family,
+                double prior_df, const double* prior_param, unsigned flags, int noise_kind, double noise_df, uint64_t seed,
+                uint64_t first_stream, int opt_kind, const double hyper[4], int64_t n_iters, double* theta, double* state,
+                int has_state, double* values, double* history, int64_t hist_len, double* directions, double* gradients);
 
 /* ---- Importance weights and Pareto smoothing (diagnostics) ----------------------------
  * vb_log_weights_meanfield: log p(z_n) - log q(z_n; theta) for the samples z = mu + sigma * eps of

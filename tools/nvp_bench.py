@@ -7,7 +7,14 @@ FLOPs are counted from the shapes (every dense-layer product, 2 M N K; the targe
 the TFLOP/s and the share of the 78.6 TFLOP/s fp64 MFMA peak are whole-call figures, not kernel figures.  For context,
 torch fp64 autograd of the same objective on the CPU (16 threads).  Prints one JSON line.
 
+--fit times the optimiser loop instead: microseconds per iteration of ``RMSProp.optimize`` (host clock around a call that
+ends in a device synchronise, one warm-up fit, --fit-iters iterations per window, --reps windows) for the host loop
+(``on_device=False``) and the device-resident loop (``vb_flow_fit``), alternating within the run so that the spread
+between repeats shows; at the NVP config and at a small flow (D = 4, K = 4, hidden 16, N = 64) where launch latency is
+the cost.  --fit-legs picks the legs (host,device).
+
 Usage:  python tools/nvp_bench.py [--reps 20] [--warmup 5] [--torch-reps 2] [--out FILE]
+        python tools/nvp_bench.py --fit [--fit-iters 300] [--reps 3] [--fit-legs host,device] [--out FILE]
 """
 import argparse
 import json
@@ -50,13 +57,59 @@ def products(flow, path):
     return n + (K * per if path else 0)
 
 
+def fit_legs(args):
+    import viabel_amd as vb
+    from viabel_amd import optimization as opt
+    legs = args.fit_legs.split(',')
+    res = {'mode': 'fit', 'iters_per_window': args.fit_iters, 'legs': {}}
+    for label, d, k, width, n in (('nvp', D, K, WIDTH, N), ('small', 4, 4, 16, 64)):
+        r = np.random.RandomState(3)
+        A = r.randn(d, d)
+        model = vb.CorrelatedGaussianModel(0.3 * r.randn(d), covariance=A @ A.T / d + np.eye(d))
+        masks = np.array([[(j + i) % 2 for j in range(d)] for i in range(k)], dtype=float)
+        layers = [[d, width], [width, d]]
+
+        def window(leg, iters):
+            flow = vb.NVPFlow(layers, layers, masks, vb.MFGaussian(d, seed=7, rng='philox'), np.zeros(2 * d), d)
+            theta = 0.03 * np.random.RandomState(0).randn(flow.var_param_dim)
+            obj = vb.ExclusiveKL(flow, model, n)
+            sgo = opt.RMSProp(0.001, iterate_avg_prop=None)
+            eng = obj._engine()
+            eng.sync()
+            t0 = time.perf_counter()
+            sgo.optimize(iters, obj, theta, on_device=leg != 'host')
+            eng.sync()
+            return (time.perf_counter() - t0) / iters * 1e6
+
+        for leg in legs:
+            window(leg, max(10, args.fit_iters // 10))          # warm-up: buffers, code objects, pinned ring
+        times = {leg: [] for leg in legs}
+        for _ in range(args.reps):
+            for leg in legs:
+                times[leg].append(window(leg, args.fit_iters))
+        for leg in legs:
+            res['legs']['%s_%s' % (label, leg)] = {'us_per_iter': [round(t, 1) for t in times[leg]],
+                                                   'us_per_iter_median': float(np.median(times[leg]))}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--fit', action='store_true')
+    ap.add_argument('--fit-iters', type=int, default=300)
+    ap.add_argument('--fit-legs', default='host,device')
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--torch-reps', type=int, default=2)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.fit:
+        line = json.dumps(fit_legs(args))
+        print(line)
+        if args.out:
+            with open(args.out, 'w') as f:
+                f.write(line + '\n')
+        return
     import viabel_amd as vb
     r = np.random.RandomState(3)
     A = r.randn(D, D)

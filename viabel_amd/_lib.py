@@ -231,6 +231,11 @@ SIGNATURES = {
                                          _c_double_p]),
     'vb_flow_sample': (ctypes.c_int, [_ctx_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
                                       ctypes.c_double, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    'vb_flow_fit': (ctypes.c_int, [_ctx_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                   ctypes.c_int, ctypes.c_double, _c_double_p, ctypes.c_uint, ctypes.c_int,
+                                   ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, _c_double_p,
+                                   ctypes.c_int64, _c_double_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p,
+                                   ctypes.c_int64, _c_double_p, _c_double_p]),
 }
 
 _lib = None
@@ -949,6 +954,29 @@ class Engine:
                                              _dptr(prior_param), _dptr(theta), _dptr(x) if want_x else None,
                                              _dptr(log_q), _dptr(log_p) if want_log_p else None))
         return x, log_q, log_p
+
+    def flow_fit(self, handle, slot, n, n_total, row_offset, prior_family, prior_df, prior_param, theta, n_iters,
+                 opt_kind, hyper, *, flags=0, noise_kind=NOISE_NORMAL, noise_df=0.0, seed=1, first_stream=0,
+                 state=None, hist_len=0, log_directions=False, log_gradients=False):
+        """``n_iters`` iterations of {Philox prior noise -> flow objective -> optimiser step} enqueued back to back
+        (``vb_flow_fit``).  Returns (theta, values, history, state, directions or None, gradients or None) as ``fit``."""
+        prior_param = _f64(prior_param)
+        theta = _f64(theta).copy()
+        p = theta.size
+        hyper = _f64(np.asarray(hyper, dtype=np.float64))
+        has_state = state is not None
+        state = _f64(state).copy() if has_state else np.zeros(2 * p, dtype=np.float64)
+        values = np.empty(max(int(n_iters), 0), dtype=np.float64)
+        history = np.empty((hist_len, p), dtype=np.float64)
+        directions = np.empty((n_iters, p), dtype=np.float64) if log_directions else None
+        gradients = np.empty((n_iters, p), dtype=np.float64) if log_gradients else None
+        self._check(self._lib.vb_flow_fit(
+            self._ctx, handle, slot, int(n), int(n_total), int(row_offset), int(prior_family), float(prior_df),
+            _dptr(prior_param), int(flags), int(noise_kind), float(noise_df), int(seed), int(first_stream), int(opt_kind),
+            _dptr(hyper), int(n_iters), _dptr(theta), _dptr(state), int(has_state), _dptr(values),
+            _dptr(history) if hist_len else None, int(hist_len),
+            _dptr(directions) if log_directions else None, _dptr(gradients) if log_gradients else None))
+        return theta, values, history, state, directions, gradients
 
     # ------------------------------------------------------------------ ExclusiveKL, full rank
     def elbo_grad_fullrank(self, slot, n, d, theta, flags=0, n_total=None):

@@ -756,6 +756,8 @@ struct FitStep {
 };
 int fit_step_enqueue(vb_ctx* ctx, const FitStep& step);
 
+// noise slot `slot` sized for an n x d matrix written by someone other than vb_noise_generate (vb_api.hip)
+int noise_slot_alloc(vb_ctx* ctx, int slot, int64_t n, int64_t d);
 // Philox noise generation (vb_rng.hip)
 int rng_fill(vb_ctx* ctx, double* dst, int64_t ld, int kind, double df, uint64_t seed,
              uint64_t stream, int64_t row_offset, int64_t n, int64_t d, double* norms = nullptr);

@@ -18,6 +18,7 @@
 // straight into the gradient at the layer's offset (the flat layout keeps W and b of a layer adjacent).  Weight-gradient
 // rows of masked-out inputs are exact zeros: those columns of y are 0.  No atomics: results are bit-reproducible.
 #include "vb_common.h"
+#include "vb_fit_rows.h"
 #include "vb_gemm_f64.h"
 
 #include <cmath>
@@ -381,20 +382,31 @@ int flow_check_prior(vb_ctx* ctx, int family, double df, FlowCall& c) {
   return fail(ctx, VB_ERR_UNSUPPORTED, "NVPFlow prior must be MFGaussian or MFStudentT (family %d)", family);
 }
 
+// padded weight copies from the device-resident theta
+int flow_pack(vb_ctx* ctx, vb_flow* f) {
+  hipStream_t st = ctx->stream;
+  const double* th = (const double*)f->theta.ptr;
+  int64_t most = 0;
+  unsigned n_real = 0;       // the device table holds only the layers that exist: nets of unequal depth leave padding entries
+  for (const auto& L : f->layers) {
+    most = most > (int64_t)L.in * L.out ? most : (int64_t)L.in * L.out;
+    n_real += L.in > 0 ? 1 : 0;
+  }
+  unsigned gx = blocks_for(most);
+  gx = gx > 256 ? 256 : gx;
+  hipLaunchKernelGGL(flow_pack_kernel, dim3(gx, n_real), dim3(256), 0, st,
+                     (const vb_flow::Layer*)f->table.ptr, th, (double*)f->wpack.ptr);
+  VB_HIP(ctx, hipGetLastError());
+  return VB_OK;
+}
+
 // theta and the prior parameter to the device, padded weight copies
 int flow_upload(vb_ctx* ctx, vb_flow* f, const double* theta, const double* prior) {
   hipStream_t st = ctx->stream;
   double* th = (double*)f->theta.ptr;
   VB_HIP(ctx, hipMemcpyAsync(th, theta, (size_t)f->p * sizeof(double), hipMemcpyHostToDevice, st));
   VB_HIP(ctx, hipMemcpyAsync(th + al32(f->p), prior, (size_t)2 * f->d * sizeof(double), hipMemcpyHostToDevice, st));
-  int64_t most = 0;
-  for (const auto& L : f->layers) most = most > (int64_t)L.in * L.out ? most : (int64_t)L.in * L.out;
-  unsigned gx = blocks_for(most);
-  gx = gx > 256 ? 256 : gx;
-  hipLaunchKernelGGL(flow_pack_kernel, dim3(gx, (unsigned)f->layers.size()), dim3(256), 0, st,
-                     (const vb_flow::Layer*)f->table.ptr, (const double*)th, (double*)f->wpack.ptr);
-  VB_HIP(ctx, hipGetLastError());
-  return VB_OK;
+  return flow_pack(ctx, f);
 }
 
 // forward pass g over the rows of the call: x_0 .. x_K, y_i, s_i, hidden activations, log p0
@@ -616,22 +628,15 @@ int vb_flow_param_dim(vb_ctx* ctx, const vb_flow* flow, int64_t* p) {
   return VB_OK;
 }
 
-int vb_flow_elbo_grad(vb_ctx* ctx, vb_flow* flow, int slot, int64_t n, int64_t n_total, int prior_family,
-                      double prior_df, const double* prior_param, const double* theta, unsigned flags, double* out) {
-  if (!ctx || !out) return fail(ctx, VB_ERR_INVALID, "NULL argument");
-  if (ctx->model.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model)");
-  if (flags & ~VB_FLAG_PATH_DERIV) return fail(ctx, VB_ERR_UNSUPPORTED, "NVPFlow: unknown flags %u", flags);
-  if (n_total < n) return fail(ctx, VB_ERR_INVALID, "n_total must be >= n");
-  FlowCall c;
-  VB_TRY(flow_call_setup(ctx, flow, slot, n, prior_family, prior_df, prior_param, theta, c));
-  if (ctx->model.dim != flow->d) return fail(ctx, VB_ERR_INVALID, "model dimension %d != flow dimension %lld",
-                                             ctx->model.dim, (long long)flow->d);
-  vb_flow* f = flow;
-  VB_TRY(flow_ensure_work(ctx, f, n));
+namespace vb {
+namespace {
+
+// [value | grad (p)] of ExclusiveKL over the call's rows at the device-resident theta (f->theta, packed) into `dout`,
+// all-reduced over a sharded job's ranks: what vb_flow_elbo_grad copies out and vb_flow_fit steps along
+int flow_evaluate(vb_ctx* ctx, vb_flow* f, const FlowCall& c, int64_t n_total, bool path, double* dout) {
+  const int64_t n = c.n;
   const FlowWork lw = flow_layout(*f, f->n_cap, (double*)f->work.ptr);
   hipStream_t st = ctx->stream;
-  const bool path = (flags & VB_FLAG_PATH_DERIV) != 0;
-  double* dout = (double*)f->out.ptr;
   VB_TRY(flow_forward(ctx, f, lw, c, path));
   // the model at x_K: log p into F, grad log p into C (the sweep's cotangent)
   double* XK = lw.X + f->k * lw.nb * lw.ldx;
@@ -652,8 +657,140 @@ int vb_flow_elbo_grad(vb_ctx* ctx, vb_flow* flow, int slot, int64_t n, int64_t n
   hipLaunchKernelGGL(flow_scale_kernel, dim3(blocks_for(1 + f->p)), dim3(256), 0, st, dout, 1 + f->p,
                      -1.0 / (double)n_total);
   VB_HIP(ctx, hipGetLastError());
+  return VB_OK;
+}
+
+}  // namespace
+}  // namespace vb
+
+int vb_flow_elbo_grad(vb_ctx* ctx, vb_flow* flow, int slot, int64_t n, int64_t n_total, int prior_family,
+                      double prior_df, const double* prior_param, const double* theta, unsigned flags, double* out) {
+  if (!ctx || !out) return fail(ctx, VB_ERR_INVALID, "NULL argument");
+  if (ctx->model.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model)");
+  if (flags & ~VB_FLAG_PATH_DERIV) return fail(ctx, VB_ERR_UNSUPPORTED, "NVPFlow: unknown flags %u", flags);
+  if (n_total < n) return fail(ctx, VB_ERR_INVALID, "n_total must be >= n");
+  FlowCall c;
+  VB_TRY(flow_call_setup(ctx, flow, slot, n, prior_family, prior_df, prior_param, theta, c));
+  if (ctx->model.dim != flow->d) return fail(ctx, VB_ERR_INVALID, "model dimension %d != flow dimension %lld",
+                                             ctx->model.dim, (long long)flow->d);
+  vb_flow* f = flow;
+  VB_TRY(flow_ensure_work(ctx, f, n));
+  hipStream_t st = ctx->stream;
+  double* dout = (double*)f->out.ptr;
+  VB_TRY(flow_evaluate(ctx, f, c, n_total, (flags & VB_FLAG_PATH_DERIV) != 0, dout));
   VB_HIP(ctx, hipMemcpyAsync(out, dout, (size_t)(1 + f->p) * sizeof(double), hipMemcpyDeviceToHost, st));
   VB_HIP(ctx, hipStreamSynchronize(st));
+  return comm_check(ctx);
+}
+
+int vb_flow_fit(vb_ctx* ctx, vb_flow* flow, int slot, int64_t n, int64_t n_total, int64_t row_offset, int prior_family,
+                double prior_df, const double* prior_param, unsigned flags, int noise_kind, double noise_df, uint64_t seed,
+                uint64_t first_stream, int opt_kind, const double hyper[4], int64_t n_iters, double* theta, double* state,
+                int has_state, double* values, double* history, int64_t hist_len, double* directions, double* gradients) {
+  if (!ctx || !hyper || !theta || !values || !prior_param) return fail(ctx, VB_ERR_INVALID, "NULL argument");
+  if (ctx->model.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model)");
+  if (!flow || !flow_known(ctx, flow)) return fail(ctx, VB_ERR_INVALID, "unknown NVPFlow handle for this context");
+  if (n <= 0 || n_iters <= 0) return fail(ctx, VB_ERR_INVALID, "n and n_iters must be positive");
+  if (n_total < n) return fail(ctx, VB_ERR_INVALID, "n_total must be >= n");
+  if (opt_kind < VB_OPT_SGD || opt_kind > VB_OPT_ADAGRAD)
+    return fail(ctx, VB_ERR_INVALID, "unknown optimiser kind %d", opt_kind);
+  if (hist_len < 0 || hist_len > n_iters || (hist_len > 0 && !history))
+    return fail(ctx, VB_ERR_INVALID, "hist_len must be in [0, n_iters] with a history buffer");
+  if (has_state && !state) return fail(ctx, VB_ERR_INVALID, "has_state set without a state buffer");
+  if (flags & ~VB_FLAG_PATH_DERIV)
+    return fail(ctx, VB_ERR_UNSUPPORTED, "NVPFlow: unknown flags %u", flags);
+  vb_flow* f = flow;
+  FlowCall c;
+  VB_TRY(flow_check_prior(ctx, prior_family, prior_df, c));
+  if (ctx->model.dim != f->d)
+    return fail(ctx, VB_ERR_INVALID, "model dimension %d != flow dimension %lld", ctx->model.dim, (long long)f->d);
+  VB_HIP(ctx, hipSetDevice(ctx->device));
+  VB_TRY(flow_order_main(ctx));
+  VB_TRY(noise_slot_alloc(ctx, slot, n, f->d));
+  NoiseSlot& ns = ctx->noise[slot];
+  c.eps = (const double*)ns.buf.ptr;
+  c.lde = ns.ld;
+  c.n = n;
+  const int64_t p = f->p;
+
+  // device state next to the flow's own theta: [out (1 + p) | s1 (p) | s2 (p) | values (n_iters) | iterates (hist_len x p)
+  // | directions | gradients] -- vb_fit's layout, so that vb_fit_history_mean serves both
+  int64_t off = 0;
+  auto carve = [&off](int64_t doubles) {
+    const int64_t o = off;
+    off += round_up(doubles, 16);
+    return o;
+  };
+  const int64_t o_out = carve(1 + p), o_s1 = carve(p), o_s2 = carve(p), o_val = carve(n_iters),
+                o_hist = carve(hist_len * p), o_dirs = carve(directions ? n_iters * p : 0),
+                o_grads = carve(gradients ? n_iters * p : 0);
+  ctx->fit_hist_len = 0;      // (the kept iterates of an earlier fit are about to be overwritten)
+  VB_TRY(ensure(ctx, ctx->fit_work, (size_t)off * sizeof(double)));
+  double* base = (double*)ctx->fit_work.ptr;
+  double* out_dev = base + o_out;
+  hipStream_t st = ctx->stream;
+  if (has_state) {
+    VB_HIP(ctx, hipMemcpyAsync(base + o_s1, state, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
+    VB_HIP(ctx, hipMemcpyAsync(base + o_s2, state + p, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
+  } else {   // the part of the state an optimiser does not use is returned as zeros, not as stale workspace
+    VB_HIP(ctx, hipMemsetAsync(base + o_s1, 0, (size_t)(o_val - o_s1) * sizeof(double), st));
+  }
+  VB_TRY(flow_upload(ctx, f, theta, prior_param));
+  VB_HIP(ctx, hipStreamSynchronize(st));   // the caller's buffers are pageable: copies above are staged
+  VB_TRY(flow_ensure_work(ctx, f, n));
+
+  FitStep step;
+  step.kind = opt_kind;
+  step.p = p;
+  step.lr = hyper[0];
+  step.beta1 = hyper[1];
+  step.one_minus_beta1 = 1.0 - hyper[1];
+  step.beta2 = hyper[2];
+  step.one_minus_beta2 = 1.0 - hyper[2];
+  step.jitter = hyper[3];
+  step.out = out_dev;
+  step.theta = (double*)f->theta.ptr;
+  step.s1 = base + o_s1;
+  step.s2 = base + o_s2;
+  step.values = base + o_val;
+  step.hist = hist_len > 0 ? base + o_hist : nullptr;
+  step.hist_first = n_iters - hist_len;
+  step.dirs = directions ? base + o_dirs : nullptr;
+  step.grads = gradients ? base + o_grads : nullptr;
+  FitRowStream rows;
+  rows.ctx = ctx, rows.p = p, rows.n_iters = n_iters, rows.hist_first = n_iters - hist_len;
+  rows.d_hist = step.hist, rows.d_dirs = step.dirs, rows.d_grads = step.grads;
+  rows.h_hist = hist_len > 0 ? history : nullptr, rows.h_dirs = directions, rows.h_grads = gradients;
+  VB_TRY(rows.begin());
+
+  const bool path = (flags & VB_FLAG_PATH_DERIV) != 0;
+  for (int64_t k = 0; k < n_iters; ++k) {
+    step.k = k;
+    step.first = (k == 0 && !has_state) ? 1 : 0;
+    VB_TRY(rng_fill(ctx, (double*)ns.buf.ptr, ns.ld, noise_kind, noise_df, seed, first_stream + (uint64_t)k, row_offset,
+                    n, f->d));
+    VB_TRY(flow_evaluate(ctx, f, c, n_total, path, out_dev));
+    VB_TRY(fit_step_enqueue(ctx, step));
+    if (k + 1 < n_iters) VB_TRY(flow_pack(ctx, f));      // the padded weight copies of the stepped parameter
+    VB_TRY(rows.after_step(k));
+  }
+  VB_HIP(ctx, hipMemcpyAsync(theta, f->theta.ptr, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st));
+  VB_HIP(ctx, hipMemcpyAsync(values, base + o_val, (size_t)n_iters * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (state) {
+    VB_HIP(ctx, hipMemcpyAsync(state, base + o_s1, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st));
+    VB_HIP(ctx, hipMemcpyAsync(state + p, base + o_s2, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  if (hist_len > 0 && !rows.on)
+    VB_HIP(ctx, hipMemcpyAsync(history, base + o_hist, (size_t)(hist_len * p) * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (directions && !rows.on)
+    VB_HIP(ctx, hipMemcpyAsync(directions, base + o_dirs, (size_t)(n_iters * p) * sizeof(double), hipMemcpyDeviceToHost,
+                               st));
+  if (gradients && !rows.on)
+    VB_HIP(ctx, hipMemcpyAsync(gradients, base + o_grads, (size_t)(n_iters * p) * sizeof(double), hipMemcpyDeviceToHost,
+                               st));
+  VB_TRY(rows.finish());
+  VB_HIP(ctx, hipStreamSynchronize(st));
+  ctx->fit_hist_off = o_hist, ctx->fit_hist_len = hist_len, ctx->fit_hist_p = p, ctx->fit_out_off = o_out;      // (vb_fit_history_mean)
   return comm_check(ctx);
 }
 

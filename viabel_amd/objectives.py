@@ -35,6 +35,12 @@ __all__ = [
 ]
 
 _NOISE_SLOT = 0
+# Device bytes one vb_flow_fit call may spend on the rows it logs (iterates, directions, gradients: p doubles each, 8.4 MB
+# at D = 256 with 256-wide nets); longer requests are split (ExclusiveKL._flow_device_fit).  hipMemGetInfo on an MI355X
+# reports 309.2 GB in all and 308.6 GB free to a fresh process; 16 GiB leaves the rest to the model, the other objectives
+# of a shared engine and the other ranks of a one-card job, and still holds the 600 iterates a 3 000-iteration fit
+# averages over (5 GB at that size).
+_FLOW_FIT_LOG_BYTES = 16 << 30
 _DIS_SLOT = 1      # DIS of the dense families keeps its state samples (as base noise) in a slot of its own
 _LR_SLOT = 3       # low-rank family: the n x k block of its noise (slot 2 belongs to the diagnostics)
 # ... and so does DIS of every other family kind (0 mean-field, 1 dense, 2 low-rank): the engine keeps one DIS state per
@@ -531,8 +537,11 @@ class ExclusiveKL(StochasticVariationalObjective):
     # ---- device-resident optimiser loop ---------------------------------------------------------------
     def supports_device_fit(self):
         """True when a whole stochastic-gradient fit can run on the device without host round trips: a
-        mean-field, full-rank or low-rank family drawing Philox noise (``rng='philox'``)."""
+        mean-field, full-rank or low-rank family drawing Philox noise (``rng='philox'``), or an NVPFlow whose prior
+        does (both estimator forms)."""
         approx = self.approx
+        if isinstance(approx, NVPFlow):
+            return approx.prior.rng == 'philox'
         if isinstance(approx, LRGaussian):
             return (approx.rng == 'philox' and 1 <= approx.k <= 16 and not self._use_path_deriv
                     and self.hessian_approx_method is None)     # the path-derivative correction is host algebra
@@ -549,7 +558,8 @@ class ExclusiveKL(StochasticVariationalObjective):
         Returns (theta, value_history, iterate_history[-hist_len:], optimiser state, directions or None,
         gradients or None)."""
         if not self.supports_device_fit():
-            raise NotImplementedError("device_fit needs a mean-field or full-rank family with rng='philox'")
+            raise NotImplementedError("device_fit needs rng='philox' noise: MFGaussian, MFStudentT, FullRankGaussian, "
+                                      "LRGaussian (k <= 16, entropy form) or an NVPFlow over such a prior")
         approx = self.approx
         init_param = np.asarray(init_param, dtype=np.float64)
         if init_param.shape != (approx.var_param_dim,):
@@ -558,6 +568,9 @@ class ExclusiveKL(StochasticVariationalObjective):
         eng.set_model(self.model.device_spec())
         N = self.num_mc_samples
         begin, end = shard_rows(N, eng.n_ranks, eng.rank)
+        if isinstance(approx, NVPFlow):
+            return self._flow_device_fit(eng, begin, end, n_iters, init_param, opt_kind, hyper, state, hist_len,
+                                         log_directions, log_gradients)
         family, df = approx._device_family()
         kind, noise_df = approx._philox_kind()
         first = approx._philox_calls
@@ -568,6 +581,57 @@ class ExclusiveKL(StochasticVariationalObjective):
                        row_offset=begin, noise_kind=kind, noise_df=noise_df, seed=approx._seed,
                        first_stream=first, state=state, hist_len=hist_len, log_directions=log_directions,
                        log_gradients=log_gradients, slot_aux=_LR_SLOT)
+
+    def _flow_device_fit(self, eng, begin, end, n_iters, theta, opt_kind, hyper, state, hist_len, log_directions,
+                         log_gradients):
+        """``device_fit`` of an NVPFlow (``vb_flow_fit``): the prior's Philox stream advances by ``n_iters`` exactly as
+        ``n_iters`` objective calls would advance it (``_stage_prior_noise``).  A flow's rows are long (p doubles each):
+        when the rows to be logged exceed ``_FLOW_FIT_LOG_BYTES`` of device memory the request runs as consecutive engine
+        calls that hand on the parameter, the optimiser state and the stream index -- the same trajectory, since the
+        optimiser state is all an iteration inherits.  (After a split the iterates are no longer resident as one block:
+        ``device_history_mean`` raises and the caller averages the returned rows.)"""
+        approx, prior = self.approx, self.approx.prior
+        handle = approx._device_handle(eng)
+        family, df, prior_param = approx._device_prior()
+        kind, noise_df = prior._philox_kind()
+        first = prior._philox_calls
+        prior._philox_calls += n_iters
+        flags = _lib.FLAG_PATH_DERIV if self._use_path_deriv else 0
+        p = approx.var_param_dim
+        hist_first = n_iters - hist_len
+        per_iter = int(log_directions) + int(log_gradients)
+
+        def log_bytes(k0, k1):      # device bytes of the rows iterations [k0, k1) log
+            return ((k1 - max(k0, hist_first) if k1 > hist_first else 0) + (k1 - k0) * per_iter) * p * 8
+
+        def call(k0, k1, theta, state):
+            return eng.flow_fit(handle, _NOISE_SLOT, end - begin, self.num_mc_samples, begin, family, df, prior_param,
+                                theta, k1 - k0, opt_kind, hyper, flags=flags, noise_kind=kind, noise_df=noise_df,
+                                seed=prior._seed, first_stream=first + k0, state=state,
+                                hist_len=max(0, k1 - max(k0, hist_first)), log_directions=log_directions,
+                                log_gradients=log_gradients)
+
+        if n_iters <= 0 or log_bytes(0, n_iters) <= _FLOW_FIT_LOG_BYTES:
+            return call(0, n_iters, theta, state)
+        values = np.empty(n_iters)
+        history = np.empty((hist_len, p))
+        directions = np.empty((n_iters, p)) if log_directions else None
+        gradients = np.empty((n_iters, p)) if log_gradients else None
+        k0 = 0
+        while k0 < n_iters:
+            k1 = k0 + 1           # the longest chunk within the budget; iterations that log nothing cost nothing
+            while k1 < n_iters and log_bytes(k0, k1 + 1) <= _FLOW_FIT_LOG_BYTES:
+                k1 += 1
+            theta, vals, hist, state, dirs, grads = call(k0, k1, theta, state)
+            values[k0:k1] = vals
+            if hist.shape[0]:
+                history[k1 - hist.shape[0] - hist_first:k1 - hist_first] = hist
+            if log_directions:
+                directions[k0:k1] = dirs
+            if log_gradients:
+                gradients[k0:k1] = grads
+            k0 = k1
+        return theta, values, history, state, directions, gradients
 
     def device_history_mean(self, rows):
         """``np.mean(history[-rows:], axis=0)`` of the iterates the last ``device_fit`` kept -- the iterate average

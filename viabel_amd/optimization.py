@@ -158,8 +158,14 @@ class StochasticGradientOptimizer(Optimizer):
         if tail is not None:
             window = max(1, int((n_iters - 1) * tail))
             # (the same mean from the rows still on the device: numpy's order of additions, no host pass over `window` iterates)
+            opt_param = None
             if window <= kept and window * p >= _DEVICE_MEAN_MIN:
-                log['opt_param'] = np.asarray(objective.device_history_mean(window))
+                try:
+                    opt_param = np.asarray(objective.device_history_mean(window))
+                except _lib.EngineError:      # a fit that ran as several engine calls keeps no resident block of iterates
+                    pass
+            if opt_param is not None:
+                log['opt_param'] = opt_param
             else:
                 log['opt_param'] = np.mean(history[-window:], axis=0)
         else:
