@@ -549,7 +549,8 @@ int vb_alpha_sums_mvt(vb_ctx* ctx, int slot, int64_t n, int64_t d, int64_t n_tot
  *   gradients   out: objective gradient of every iteration, row-major n_iters x p (FASO's grad_history,
  *               optimization.py:541); may be NULL
  * Sharded jobs (vb_comm_init): every rank passes its own n / row_offset and the same n_total; all ranks
- * apply the same step to the same all-reduced gradient. */
+ * apply the same step to the same all-reduced gradient; VB_ERR_COMM, as from every blocking entry point, once a
+ * device-side wait of the IPC transport has given up (vb_comm_check). */
 #define VB_OPT_SGD 0
 #define VB_OPT_RMSPROP 1
 #define VB_OPT_ADAM 2

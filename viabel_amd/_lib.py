@@ -961,22 +961,13 @@ class Engine:
         """``n_iters`` iterations of {Philox prior noise -> flow objective -> optimiser step} enqueued back to back
         (``vb_flow_fit``).  Returns (theta, values, history, state, directions or None, gradients or None) as ``fit``."""
         prior_param = _f64(prior_param)
-        theta = _f64(theta).copy()
-        p = theta.size
-        hyper = _f64(np.asarray(hyper, dtype=np.float64))
-        has_state = state is not None
-        state = _f64(state).copy() if has_state else np.zeros(2 * p, dtype=np.float64)
-        values = np.empty(max(int(n_iters), 0), dtype=np.float64)
-        history = np.empty((hist_len, p), dtype=np.float64)
-        directions = np.empty((n_iters, p), dtype=np.float64) if log_directions else None
-        gradients = np.empty((n_iters, p), dtype=np.float64) if log_gradients else None
-        self._check(self._lib.vb_flow_fit(
-            self._ctx, handle, slot, int(n), int(n_total), int(row_offset), int(prior_family), float(prior_df),
-            _dptr(prior_param), int(flags), int(noise_kind), float(noise_df), int(seed), int(first_stream), int(opt_kind),
-            _dptr(hyper), int(n_iters), _dptr(theta), _dptr(state), int(has_state), _dptr(values),
-            _dptr(history) if hist_len else None, int(hist_len),
-            _dptr(directions) if log_directions else None, _dptr(gradients) if log_gradients else None))
-        return theta, values, history, state, directions, gradients
+
+        def call(hyper_p, theta_p, p, tail):
+            return self._lib.vb_flow_fit(
+                self._ctx, handle, slot, int(n), int(n_total), int(row_offset), int(prior_family), float(prior_df),
+                _dptr(prior_param), int(flags), int(noise_kind), float(noise_df), int(seed), int(first_stream),
+                int(opt_kind), hyper_p, int(n_iters), theta_p, *tail)
+        return self._fit_call(call, theta, n_iters, hyper, state, hist_len, log_directions, log_gradients)
 
     # ------------------------------------------------------------------ ExclusiveKL, full rank
     def elbo_grad_fullrank(self, slot, n, d, theta, flags=0, n_total=None):
@@ -1099,21 +1090,28 @@ class Engine:
             state=None, hist_len=0, log_directions=False, log_gradients=False, slot_aux=-1):
         """``n_iters`` iterations of {Philox noise -> objective -> optimiser step} enqueued back to back
         (``vb_fit``).  Returns (theta, values, history, state, directions or None, gradients or None)."""
+        def call(hyper_p, theta_p, p, tail):
+            return self._lib.vb_fit(
+                self._ctx, slot, slot_aux, n, d, n if n_total is None else n_total, int(row_offset), family, float(df),
+                flags, cv_mode, noise_kind, float(noise_df), int(seed), int(first_stream), opt_kind, hyper_p,
+                int(n_iters), theta_p, p, *tail)
+        return self._fit_call(call, theta, n_iters, hyper, state, hist_len, log_directions, log_gradients)
+
+    def _fit_call(self, call, theta, n_iters, hyper, state, hist_len, log_directions, log_gradients):
+        """The buffers every device fit takes and returns.  ``call(hyper, theta, p, tail)`` invokes the C entry point, ``tail``
+        being its last seven arguments (state, has_state, values, history, hist_len, directions, gradients)."""
         theta = _f64(theta).copy()
         p = theta.size
         hyper = _f64(np.asarray(hyper, dtype=np.float64))
         has_state = state is not None
         state = _f64(state).copy() if has_state else np.zeros(2 * p, dtype=np.float64)
-        values = np.empty(n_iters, dtype=np.float64)
+        values = np.empty(max(int(n_iters), 0), dtype=np.float64)      # (a bad n_iters is the C check's to report)
         history = np.empty((hist_len, p), dtype=np.float64)
         directions = np.empty((n_iters, p), dtype=np.float64) if log_directions else None
         gradients = np.empty((n_iters, p), dtype=np.float64) if log_gradients else None
-        self._check(self._lib.vb_fit(
-            self._ctx, slot, slot_aux, n, d, n if n_total is None else n_total, int(row_offset), family, float(df), flags,
-            cv_mode, noise_kind, float(noise_df), int(seed), int(first_stream), opt_kind, _dptr(hyper), int(n_iters),
-            _dptr(theta), p, _dptr(state), int(has_state), _dptr(values),
-            _dptr(history) if hist_len else None, int(hist_len),
-            _dptr(directions) if log_directions else None, _dptr(gradients) if log_gradients else None))
+        self._check(call(_dptr(hyper), _dptr(theta), p, (
+            _dptr(state), int(has_state), _dptr(values), _dptr(history) if hist_len else None, int(hist_len),
+            _dptr(directions) if log_directions else None, _dptr(gradients) if log_gradients else None)))
         return theta, values, history, state, directions, gradients
 
     def mvt_route_stats(self):

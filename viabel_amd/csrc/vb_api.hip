@@ -1,7 +1,6 @@
 // C ABI of libviabel_hip.so: contexts, noise slots, model binding, synchronous / asynchronous
 // evaluators.  See include/viabel_hip.h for the contract and the reference seam it replaces.
 #include "vb_common.h"
-#include "vb_fit_rows.h"
 
 #include <mutex>
 
@@ -274,7 +273,7 @@ int sync_streams(vb_ctx* ctx) {
 
 // Main-stream work that writes buffers the pipeline may still be reading (noise, model parameters)
 // is ordered after everything the pipeline has in flight.
-static int main_stream_write(vb_ctx* ctx) {
+int main_stream_write(vb_ctx* ctx) {
   Pipeline& P = ctx->pipe;
   if (P.post_pending) {
     VB_HIP(ctx, hipStreamWaitEvent(ctx->stream, P.ev_fin[P.last_set], 0));
@@ -2199,235 +2198,11 @@ int vb_mvt_path_terms(vb_ctx* ctx, int slot, int64_t n, int64_t d, int64_t n_tot
   return mvt_path_terms(ctx, ctx->noise[slot], n, d, n_total, df, inv_s, m_w, e_w, log1p_sum);
 }
 
-// ---- device-resident fit (optimization.py:83-127) ----------------------------------------------------
-// (the logged rows leave through FitRowStream, vb_fit_rows.h)
-
-int vb_fit(vb_ctx* ctx, int slot, int slot_aux, int64_t n, int64_t d, int64_t n_total, int64_t row_offset, int family,
-           double df, unsigned flags, int cv_mode, int noise_kind, double noise_df, uint64_t seed,
-           uint64_t first_stream, int opt_kind, const double hyper[4], int64_t n_iters, double* theta, int64_t p,
-           double* state, int has_state, double* values, double* history, int64_t hist_len, double* directions,
-           double* gradients) {
-  if (!ctx || !hyper || !theta || !values) return fail(ctx, VB_ERR_INVALID, "NULL argument");
-  if (ctx->model.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model)");
-  if (n <= 0 || d <= 0 || n_iters <= 0) return fail(ctx, VB_ERR_INVALID, "n, d and n_iters must be positive");
-  if (n_total < n) return fail(ctx, VB_ERR_INVALID, "n_total must be >= n");
-  if (opt_kind < VB_OPT_SGD || opt_kind > VB_OPT_ADAGRAD)
-    return fail(ctx, VB_ERR_INVALID, "unknown optimiser kind %d", opt_kind);
-  if (hist_len < 0 || hist_len > n_iters || (hist_len > 0 && !history))
-    return fail(ctx, VB_ERR_INVALID, "hist_len must be in [0, n_iters] with a history buffer");
-  if (has_state && !state) return fail(ctx, VB_ERR_INVALID, "has_state set without a state buffer");
-  const bool meanfield = family == VB_FAMILY_MF_GAUSSIAN || family == VB_FAMILY_MF_STUDENT_T;
-  const bool fullrank = family == VB_FAMILY_FULLRANK_GAUSSIAN;
-  const bool lowrank = family == VB_FAMILY_LOWRANK_GAUSSIAN;
-  if (!meanfield && !fullrank && !lowrank)
-    return fail(ctx, VB_ERR_UNSUPPORTED, "device-resident fit: family %d is not supported", family);
-  const int64_t lr_k = lowrank ? (p - 2 * d) / d : 0;
-  if (lowrank) {
-    if (lr_k < 1 || lr_k > 16 || p != 2 * d + d * lr_k)
-      return fail(ctx, VB_ERR_INVALID, "low-rank family: parameter length %lld is not 2 d + d k with 1 <= k <= 16",
-                  (long long)p);
-    if (cv_mode != VB_CV_NONE || (flags & VB_FLAG_PATH_DERIV))
-      return fail(ctx, VB_ERR_UNSUPPORTED, "low-rank family: entropy-form estimator only");
-    if (slot_aux == slot) return fail(ctx, VB_ERR_INVALID, "the two noise blocks need different slots");
-  } else if (p != (meanfield ? 2 * d : d + d * (d + 1) / 2)) {
-    return fail(ctx, VB_ERR_INVALID, "parameter length %lld does not match the family", (long long)p);
-  }
-  if (fullrank && cv_mode != VB_CV_NONE)
-    return fail(ctx, VB_ERR_UNSUPPORTED, "full-rank family: the RGE control variates do not apply");
-  VB_HIP(ctx, hipSetDevice(ctx->device));
-  VB_TRY(main_stream_write(ctx));
-  VB_TRY(noise_alloc(ctx, slot, n, d));
-  NoiseSlot& ns = ctx->noise[slot];
-  if (lowrank) VB_TRY(noise_alloc(ctx, slot_aux, n, lr_k));
-
-  // device state: [theta (p) | out (1 + p) | s1 (p) | s2 (p) | values (n_iters) | iterates (hist_len x p)]
-  int64_t off = 0;
-  auto carve = [&off](int64_t doubles) {
-    const int64_t o = off;
-    off += round_up(doubles, 16);
-    return o;
-  };
-  const int64_t o_theta = carve(p), o_out = carve(1 + p), o_s1 = carve(p), o_s2 = carve(p),
-                o_val = carve(n_iters), o_hist = carve(hist_len * p), o_dirs = carve(directions ? n_iters * p : 0),
-                o_grads = carve(gradients ? n_iters * p : 0);
-  ctx->fit_hist_len = 0;      // (the kept iterates of an earlier fit are about to be overwritten)
-  VB_TRY(ensure(ctx, ctx->fit_work, (size_t)off * sizeof(double)));
-  double* base = (double*)ctx->fit_work.ptr;
-  double* theta_dev = base + o_theta;
-  double* out_dev = base + o_out;
-  hipStream_t st = ctx->stream;
-  VB_HIP(ctx, hipMemcpyAsync(theta_dev, theta, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
-  if (has_state) {
-    VB_HIP(ctx, hipMemcpyAsync(base + o_s1, state, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
-    VB_HIP(ctx, hipMemcpyAsync(base + o_s2, state + p, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
-  } else {   // the part of the state an optimiser does not use is returned as zeros, not as stale workspace
-    VB_HIP(ctx, hipMemsetAsync(base + o_s1, 0, (size_t)(o_val - o_s1) * sizeof(double), st));
-  }
-  VB_HIP(ctx, hipStreamSynchronize(st));   // the caller's buffers are pageable: copies above are staged
-
-  FitStep step;
-  step.kind = opt_kind;
-  step.p = p;
-  step.lr = hyper[0];
-  step.beta1 = hyper[1];
-  step.one_minus_beta1 = 1.0 - hyper[1];
-  step.beta2 = hyper[2];
-  step.one_minus_beta2 = 1.0 - hyper[2];
-  step.jitter = hyper[3];
-  step.out = out_dev;
-  step.theta = theta_dev;
-  step.s1 = base + o_s1;
-  step.s2 = base + o_s2;
-  step.values = base + o_val;
-  step.hist = hist_len > 0 ? base + o_hist : nullptr;
-  step.hist_first = n_iters - hist_len;
-  step.dirs = directions ? base + o_dirs : nullptr;
-  step.grads = gradients ? base + o_grads : nullptr;
-  FitRowStream rows;
-  rows.ctx = ctx, rows.p = p, rows.n_iters = n_iters, rows.hist_first = n_iters - hist_len;
-  rows.d_hist = step.hist, rows.d_dirs = step.dirs, rows.d_grads = step.grads;
-  rows.h_hist = hist_len > 0 ? history : nullptr, rows.h_dirs = directions, rows.h_grads = gradients;
-  VB_TRY(rows.begin());
-
-  MfCall c;
-  if (meanfield) {
-    c.count = 1;
-    c.noise[0] = &ns;
-    c.theta_src[0] = theta_dev;
-    c.theta_on_device = true;
-    c.out[0] = out_dev;
-    c.n = n;
-    c.d = d;
-    c.n_total = n_total;
-    c.family = family;
-    c.df = df;
-    c.flags = flags;
-    c.cv_mode = cv_mode;
-  }
-  const bool gen_in_kernel =
-      (ctx->model.id == VB_MODEL_GAUSS_DIAG || ctx->model.id == VB_MODEL_FUNNEL) &&
-      ((family == VB_FAMILY_MF_GAUSSIAN && noise_kind == VB_NOISE_NORMAL) ||
-       (family == VB_FAMILY_MF_STUDENT_T && noise_kind == VB_NOISE_STUDENT_T && noise_df == df));
-  bool step_done = false, prep_done = false;
-  // the dense family's fused step leaves mu / L' of the FIT's iterate in fr_lt (fr_step_unpack_enqueue): on every way out
-  // of this function -- error returns included -- the copy is declared stale for the resident parameter too, or a later
-  // set_theta-once / enqueue-many caller with the same d would be evaluated at the fit's parameter
-  struct LtReset {
-    vb_ctx* c;
-    bool on;
-    ~LtReset() {
-      if (on) {
-        c->fr_lt_owner = nullptr;
-        c->fr_lt_d = 0;
-      }
-    }
-  } lt_reset{ctx, fullrank};
-  if (meanfield) {
-    c.step = &step;
-    c.step_done = &step_done;
-    c.prep_done = &prep_done;
-  }
-  for (int64_t k = 0; k < n_iters; ++k) {
-    step.k = k;
-    step.first = (k == 0 && !has_state) ? 1 : 0;
-    step_done = false;
-    if (lowrank) {
-      NoiseSlot& nz = ctx->noise[slot_aux];
-      const uint64_t s2 = 2 * (first_stream + (uint64_t)k);
-      VB_TRY(rng_fill(ctx, (double*)ns.buf.ptr, ns.ld, VB_NOISE_NORMAL, 0.0, seed, s2, row_offset, n, d));
-      VB_TRY(rng_fill(ctx, (double*)nz.buf.ptr, nz.ld, VB_NOISE_NORMAL, 0.0, seed, s2 + 1, row_offset, n, lr_k));
-      VB_TRY(lr_elbo_grad_enqueue(ctx, ns, nz, n, d, lr_k, n_total, theta_dev, out_dev));
-    } else if (gen_in_kernel) {
-      // single-use Gaussian noise never touches HBM: the streaming kernel generates it in registers
-      c.skip_prep = prep_done;                 // done by the previous iteration's finalize kernel
-      c.prep_next = k + 1 < n_iters;
-      prep_done = false;
-      c.gen = 1;
-      c.gen_seed = seed;
-      c.gen_stream = first_stream + (uint64_t)k;
-      c.gen_row_offset = row_offset;
-      VB_TRY(mf_enqueue(ctx, c));
-    } else {
-      VB_TRY(rng_fill(ctx, (double*)ns.buf.ptr, ns.ld, noise_kind, noise_df, seed, first_stream + (uint64_t)k,
-                      row_offset, n, d));
-      if (meanfield)
-        VB_TRY(mf_enqueue(ctx, c));
-      else
-        VB_TRY(fr_elbo_grad_enqueue(ctx, ns, n, d, n_total, theta_dev, out_dev, flags));
-    }
-    if (fullrank && ctx->pipe.post_pending) {   // sharded full-rank evaluations finish on the communication stream
-      VB_HIP(ctx, hipStreamWaitEvent(st, ctx->pipe.ev_fin[ctx->pipe.last_set], 0));
-      ctx->pipe.post_pending = false;
-    }
-    if (fullrank && !ctx->comm) {
-      // dense family: the step writes mu and L' of the stepped parameter itself, the next evaluation skips its unpack
-      VB_TRY(fr_step_unpack_enqueue(ctx, step, d));
-      step_done = true;
-    }
-    if (!step_done) VB_TRY(fit_step_enqueue(ctx, step));
-    VB_TRY(rows.after_step(k));
-  }
-  VB_HIP(ctx, hipMemcpyAsync(theta, theta_dev, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st));
-  VB_HIP(ctx, hipMemcpyAsync(values, base + o_val, (size_t)n_iters * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (state) {
-    VB_HIP(ctx, hipMemcpyAsync(state, base + o_s1, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st));
-    VB_HIP(ctx, hipMemcpyAsync(state + p, base + o_s2, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st));
-  }
-  if (hist_len > 0 && !rows.on)
-    VB_HIP(ctx, hipMemcpyAsync(history, base + o_hist, (size_t)(hist_len * p) * sizeof(double),
-                               hipMemcpyDeviceToHost, st));
-  if (directions && !rows.on)
-    VB_HIP(ctx, hipMemcpyAsync(directions, base + o_dirs, (size_t)(n_iters * p) * sizeof(double),
-                               hipMemcpyDeviceToHost, st));
-  if (gradients && !rows.on)
-    VB_HIP(ctx, hipMemcpyAsync(gradients, base + o_grads, (size_t)(n_iters * p) * sizeof(double),
-                               hipMemcpyDeviceToHost, st));
-  VB_TRY(rows.finish());
-  VB_HIP(ctx, hipStreamSynchronize(st));
-  ctx->fit_hist_off = o_hist, ctx->fit_hist_len = hist_len, ctx->fit_hist_p = p, ctx->fit_out_off = o_out;      // (vb_fit_history_mean)
-  return VB_OK;
-}
-
-namespace {
-// out[j] = (h[0][j] + h[1][j] + ... in row order) / rows: numpy's add.reduce over the leading axis followed by true_divide
-__global__ void __launch_bounds__(256) fit_history_mean_kernel(const double* __restrict__ h, int64_t rows, int64_t p,
-                                                               double* __restrict__ out) {
-  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= p) return;
-  double s = h[j];
-  for (int64_t r0 = 1; r0 < rows; r0 += 8) {      // eight rows' loads in flight, added in row order
-    double v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = h[(r0 + u < rows ? r0 + u : rows - 1) * p + j];
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (r0 + u < rows) s += v[u];
-  }
-  out[j] = s / (double)rows;
-}
-}  // namespace
-
 int vb_mvt_route_stats(vb_ctx* ctx, uint64_t* epilogue_rows, uint64_t* chain_fetch) {
   if (!ctx || !epilogue_rows || !chain_fetch) return fail(ctx, VB_ERR_INVALID, "NULL argument");
   *epilogue_rows = ctx->mvt_epi_rows_calls;
   *chain_fetch = ctx->mvt_chain_fetch_calls;
   return VB_OK;
-}
-
-int vb_fit_history_mean(vb_ctx* ctx, int64_t rows, int64_t p, double* mean) {
-  if (!ctx || !mean || rows <= 0 || p <= 0) return fail(ctx, VB_ERR_INVALID, "bad argument");
-  if (!ctx->fit_work.ptr || ctx->fit_hist_len < rows || ctx->fit_hist_p != p)
-    return fail(ctx, VB_ERR_STATE, "no resident iterate history of %lld rows x %lld (the last fit kept %lld x %lld)", (long long)rows,
-                (long long)p, (long long)ctx->fit_hist_len, (long long)ctx->fit_hist_p);
-  VB_HIP(ctx, hipSetDevice(ctx->device));
-  VB_TRY(main_stream_write(ctx));
-  const double* h = (const double*)ctx->fit_work.ptr + ctx->fit_hist_off + (ctx->fit_hist_len - rows) * p;
-  double* out = (double*)ctx->fit_work.ptr + ctx->fit_out_off;      // (the fit's own [value | gradient] area: free once it has returned)
-  hipStream_t st = ctx->stream;
-  hipLaunchKernelGGL(fit_history_mean_kernel, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, st, h, rows, p, out);
-  VB_HIP(ctx, hipGetLastError());
-  const FetchSeg seg[1] = {{out, (size_t)p * sizeof(double), mean}};
-  return fetch_blocking(ctx, st, seg, 1);
 }
 
 // ---- measurement --------------------------------------------------------------------------------

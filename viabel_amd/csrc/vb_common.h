@@ -286,13 +286,13 @@ struct vb_ctx {
   double* pin_host = nullptr;           // pinned, device-mapped staging (vb_linalg.hip): host / device address
   double* pin_dev = nullptr;
   size_t pin_bytes = 0;
-  vb::DeviceBuffer fit_work;            // device-resident fit: [theta | out | state | value history | iterates]
+  vb::DeviceBuffer fit_work;            // device-resident fit: laid out by FitRun (vb_fit_run.h) alone
   int64_t fit_out_off = 0;
   uint64_t mvt_epi_rows_calls = 0, mvt_chain_fetch_calls = 0;      // vb_mvt_route_stats
   int ns_hint_m[2] = {0, 0}, ns_hint_steps[2] = {0, 0};      // steps the last Newton-Schulz root ([0]) / Frechet iteration ([1]) of size m ended with
   int64_t fit_hist_off = 0, fit_hist_len = 0, fit_hist_p = 0;      // where the last fit's kept iterates sit in fit_work (len 0: none)
-  // vb_fit's per-iteration rows (iterates, directions, gradients) leave while the next iterations run: a copy stream, a
-  // ring of pinned slots, one event pair per slot (vb_api.hip, FitRowStream)
+  // a device fit's per-iteration rows (iterates, directions, gradients) leave while the next iterations run: a copy stream,
+  // a ring of pinned slots, one event pair per slot (FitRun, vb_fit_run.h)
   static constexpr int kFitRing = 4;
   hipStream_t fit_copy_st = nullptr;
   double* fit_ring = nullptr;
@@ -615,6 +615,9 @@ int psis_tail_size(int64_t n, double reff);
 int alpha_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t n_total, int64_t d, int family, double df,
                   double alpha, const double* theta_src, double* out);
 int sync_streams(vb_ctx* ctx);   // main + pipeline streams
+// main-stream work that writes buffers the mean-field pipeline may still be reading (noise, model parameters) goes behind
+// everything the pipeline has in flight (vb_api.hip)
+int main_stream_write(vb_ctx* ctx);
 // blocking device -> host fetch of small results: one gathering kernel into mapped memory + a polled completion word
 // (vb_api.hip); plain copies + hipStreamSynchronize above 1 MB
 int fetch_blocking(vb_ctx* ctx, hipStream_t st, const FetchSeg* segs, int n_segs);

@@ -18,7 +18,7 @@
 // straight into the gradient at the layer's offset (the flat layout keeps W and b of a layer adjacent).  Weight-gradient
 // rows of masked-out inputs are exact zeros: those columns of y are 0.  No atomics: results are bit-reproducible.
 #include "vb_common.h"
-#include "vb_fit_rows.h"
+#include "vb_fit_run.h"
 #include "vb_gemm_f64.h"
 
 #include <cmath>
@@ -351,16 +351,6 @@ int flow_ensure_work(vb_ctx* ctx, vb_flow* f, int64_t n) {
   return VB_OK;
 }
 
-// the context's main stream may write buffers the mean-field pipeline still reads (as main_stream_write, vb_api.hip)
-int flow_order_main(vb_ctx* ctx) {
-  Pipeline& P = ctx->pipe;
-  if (P.post_pending) {
-    VB_HIP(ctx, hipStreamWaitEvent(ctx->stream, P.ev_fin[P.last_set], 0));
-    P.post_pending = false;
-  }
-  return VB_OK;
-}
-
 struct FlowCall {
   const double* eps;
   int64_t lde, n;
@@ -522,7 +512,7 @@ int flow_call_setup(vb_ctx* ctx, vb_flow* f, int slot, int64_t n, int prior_fami
   c.lde = ns.ld;
   c.n = n;
   VB_HIP(ctx, hipSetDevice(ctx->device));
-  VB_TRY(flow_order_main(ctx));
+  VB_TRY(main_stream_write(ctx));
   return flow_upload(ctx, f, theta, prior_param);
 }
 
@@ -688,15 +678,8 @@ int vb_flow_fit(vb_ctx* ctx, vb_flow* flow, int slot, int64_t n, int64_t n_total
                 uint64_t first_stream, int opt_kind, const double hyper[4], int64_t n_iters, double* theta, double* state,
                 int has_state, double* values, double* history, int64_t hist_len, double* directions, double* gradients) {
   if (!ctx || !hyper || !theta || !values || !prior_param) return fail(ctx, VB_ERR_INVALID, "NULL argument");
-  if (ctx->model.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model)");
+  VB_TRY(FitRun::check(ctx, "n", n > 0, n, n_total, n_iters, opt_kind, hist_len, history, has_state, state));
   if (!flow || !flow_known(ctx, flow)) return fail(ctx, VB_ERR_INVALID, "unknown NVPFlow handle for this context");
-  if (n <= 0 || n_iters <= 0) return fail(ctx, VB_ERR_INVALID, "n and n_iters must be positive");
-  if (n_total < n) return fail(ctx, VB_ERR_INVALID, "n_total must be >= n");
-  if (opt_kind < VB_OPT_SGD || opt_kind > VB_OPT_ADAGRAD)
-    return fail(ctx, VB_ERR_INVALID, "unknown optimiser kind %d", opt_kind);
-  if (hist_len < 0 || hist_len > n_iters || (hist_len > 0 && !history))
-    return fail(ctx, VB_ERR_INVALID, "hist_len must be in [0, n_iters] with a history buffer");
-  if (has_state && !state) return fail(ctx, VB_ERR_INVALID, "has_state set without a state buffer");
   if (flags & ~VB_FLAG_PATH_DERIV)
     return fail(ctx, VB_ERR_UNSUPPORTED, "NVPFlow: unknown flags %u", flags);
   vb_flow* f = flow;
@@ -705,93 +688,31 @@ int vb_flow_fit(vb_ctx* ctx, vb_flow* flow, int slot, int64_t n, int64_t n_total
   if (ctx->model.dim != f->d)
     return fail(ctx, VB_ERR_INVALID, "model dimension %d != flow dimension %lld", ctx->model.dim, (long long)f->d);
   VB_HIP(ctx, hipSetDevice(ctx->device));
-  VB_TRY(flow_order_main(ctx));
+  VB_TRY(main_stream_write(ctx));
   VB_TRY(noise_slot_alloc(ctx, slot, n, f->d));
   NoiseSlot& ns = ctx->noise[slot];
   c.eps = (const double*)ns.buf.ptr;
   c.lde = ns.ld;
   c.n = n;
-  const int64_t p = f->p;
 
-  // device state next to the flow's own theta: [out (1 + p) | s1 (p) | s2 (p) | values (n_iters) | iterates (hist_len x p)
-  // | directions | gradients] -- vb_fit's layout, so that vb_fit_history_mean serves both
-  int64_t off = 0;
-  auto carve = [&off](int64_t doubles) {
-    const int64_t o = off;
-    off += round_up(doubles, 16);
-    return o;
-  };
-  const int64_t o_out = carve(1 + p), o_s1 = carve(p), o_s2 = carve(p), o_val = carve(n_iters),
-                o_hist = carve(hist_len * p), o_dirs = carve(directions ? n_iters * p : 0),
-                o_grads = carve(gradients ? n_iters * p : 0);
-  ctx->fit_hist_len = 0;      // (the kept iterates of an earlier fit are about to be overwritten)
-  VB_TRY(ensure(ctx, ctx->fit_work, (size_t)off * sizeof(double)));
-  double* base = (double*)ctx->fit_work.ptr;
-  double* out_dev = base + o_out;
-  hipStream_t st = ctx->stream;
-  if (has_state) {
-    VB_HIP(ctx, hipMemcpyAsync(base + o_s1, state, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
-    VB_HIP(ctx, hipMemcpyAsync(base + o_s2, state + p, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
-  } else {   // the part of the state an optimiser does not use is returned as zeros, not as stale workspace
-    VB_HIP(ctx, hipMemsetAsync(base + o_s1, 0, (size_t)(o_val - o_s1) * sizeof(double), st));
-  }
+  FitRun run(ctx);      // (the parameter stays in the flow's own theta)
+  VB_TRY(run.begin(f->p, 0, n_iters, opt_kind, hyper, state, has_state, history, hist_len, directions, gradients));
+  run.step.theta = (double*)f->theta.ptr;
   VB_TRY(flow_upload(ctx, f, theta, prior_param));
-  VB_HIP(ctx, hipStreamSynchronize(st));   // the caller's buffers are pageable: copies above are staged
+  VB_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the caller's buffers are pageable: copies above are staged
   VB_TRY(flow_ensure_work(ctx, f, n));
-
-  FitStep step;
-  step.kind = opt_kind;
-  step.p = p;
-  step.lr = hyper[0];
-  step.beta1 = hyper[1];
-  step.one_minus_beta1 = 1.0 - hyper[1];
-  step.beta2 = hyper[2];
-  step.one_minus_beta2 = 1.0 - hyper[2];
-  step.jitter = hyper[3];
-  step.out = out_dev;
-  step.theta = (double*)f->theta.ptr;
-  step.s1 = base + o_s1;
-  step.s2 = base + o_s2;
-  step.values = base + o_val;
-  step.hist = hist_len > 0 ? base + o_hist : nullptr;
-  step.hist_first = n_iters - hist_len;
-  step.dirs = directions ? base + o_dirs : nullptr;
-  step.grads = gradients ? base + o_grads : nullptr;
-  FitRowStream rows;
-  rows.ctx = ctx, rows.p = p, rows.n_iters = n_iters, rows.hist_first = n_iters - hist_len;
-  rows.d_hist = step.hist, rows.d_dirs = step.dirs, rows.d_grads = step.grads;
-  rows.h_hist = hist_len > 0 ? history : nullptr, rows.h_dirs = directions, rows.h_grads = gradients;
-  VB_TRY(rows.begin());
 
   const bool path = (flags & VB_FLAG_PATH_DERIV) != 0;
   for (int64_t k = 0; k < n_iters; ++k) {
-    step.k = k;
-    step.first = (k == 0 && !has_state) ? 1 : 0;
+    run.iteration(k);
     VB_TRY(rng_fill(ctx, (double*)ns.buf.ptr, ns.ld, noise_kind, noise_df, seed, first_stream + (uint64_t)k, row_offset,
                     n, f->d));
-    VB_TRY(flow_evaluate(ctx, f, c, n_total, path, out_dev));
-    VB_TRY(fit_step_enqueue(ctx, step));
+    VB_TRY(flow_evaluate(ctx, f, c, n_total, path, run.out));
+    VB_TRY(fit_step_enqueue(ctx, run.step));
     if (k + 1 < n_iters) VB_TRY(flow_pack(ctx, f));      // the padded weight copies of the stepped parameter
-    VB_TRY(rows.after_step(k));
+    VB_TRY(run.after_step(k));
   }
-  VB_HIP(ctx, hipMemcpyAsync(theta, f->theta.ptr, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st));
-  VB_HIP(ctx, hipMemcpyAsync(values, base + o_val, (size_t)n_iters * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (state) {
-    VB_HIP(ctx, hipMemcpyAsync(state, base + o_s1, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st));
-    VB_HIP(ctx, hipMemcpyAsync(state + p, base + o_s2, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st));
-  }
-  if (hist_len > 0 && !rows.on)
-    VB_HIP(ctx, hipMemcpyAsync(history, base + o_hist, (size_t)(hist_len * p) * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (directions && !rows.on)
-    VB_HIP(ctx, hipMemcpyAsync(directions, base + o_dirs, (size_t)(n_iters * p) * sizeof(double), hipMemcpyDeviceToHost,
-                               st));
-  if (gradients && !rows.on)
-    VB_HIP(ctx, hipMemcpyAsync(gradients, base + o_grads, (size_t)(n_iters * p) * sizeof(double), hipMemcpyDeviceToHost,
-                               st));
-  VB_TRY(rows.finish());
-  VB_HIP(ctx, hipStreamSynchronize(st));
-  ctx->fit_hist_off = o_hist, ctx->fit_hist_len = hist_len, ctx->fit_hist_p = p, ctx->fit_out_off = o_out;      // (vb_fit_history_mean)
-  return comm_check(ctx);
+  return run.finish(theta, values, state);
 }
 
 int vb_flow_sample(vb_ctx* ctx, vb_flow* flow, int slot, int64_t n, int prior_family, double prior_df,
