@@ -438,6 +438,30 @@ int vb_log_weights_meanfield(vb_ctx* ctx, int slot, int64_t n, int64_t d, int fa
 int vb_psis_smooth(vb_ctx* ctx, const double* lw_in, int64_t n, double reff, double* lw_out,
                    double* khat);
 
+/* ---- Batched Pareto smoothing and PSIS leave-one-out (model comparison) -----------------
+ * vb_psis_smooth_batch: psislw of viabel/_psis.py:113-209 for m weight vectors of n values in one
+ * launch (one workgroup per vector).  Vector j starts at lw + j * ld (ld >= n doubles); the smoothed
+ * vector goes to out + j * ld, its tail index to khat[j].  Capacity: n <= 16 384 and a tail
+ * ceil(min(0.2 n, 3 sqrt(n / reff))) of at most 1024 values; VB_ERR_UNSUPPORTED beyond it (smooth
+ * such vectors one by one with vb_psis_smooth).
+ * vb_glm_pointwise: ll_out[s * n_data + i] = log p(y_i | x_i' theta_s) of the bound regression target
+ * (VB_MODEL_LOGISTIC with any VB_GLM_* likelihood) as a NORMALISED density -- the constants the
+ * model's log density keeps in its per-sample constant included, the prior not -- for the s host
+ * draws x (s x d, row-major): the `log_lik` argument of psisloo (viabel/_psis.py:69-110).
+ * VB_ERR_STATE without a bound model, VB_ERR_UNSUPPORTED for a model without observations.
+ * vb_glm_psis_loo: PSIS-LOO of that target from draws of an approximation q.  log_ratios[s] =
+ * log p(theta_s, y) - log q(theta_s) (NULL: draws from the exact posterior); observation i's
+ * weights are the smoothed, normalised log_ratios[s] - log p(y_i | theta_s).  Outputs, n_data
+ * doubles each: loo[i] = logsumexp_s(smoothed_s + log p(y_i | theta_s)), khat[i], and -- when the
+ * smoothed full-data log weights log_w[s] are given, otherwise lpd must be NULL too -- lpd[i] =
+ * logsumexp_s(log_w[s] + log p(y_i | theta_s)).  The n_data x s matrix stays on the device (in
+ * chunks of observations above 1 GiB).  Same capacity in s as vb_psis_smooth_batch in n.          */
+int vb_psis_smooth_batch(vb_ctx* ctx, const double* lw, int64_t n, int64_t m, int64_t ld, double reff,
+                         double* out, double* khat);
+int vb_glm_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out);
+int vb_glm_psis_loo(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const double* log_ratios,
+                    const double* log_w, double reff, double* loo, double* khat, double* lpd);
+
 /* ---- ExclusiveKL, multivariate t family ------------------------------------------------
  * ExclusiveKL closure (objectives.py:154-164, entropy form) for MultivariateT
  * (approximations.py:322-382): x_n = mu + (z_n Sigma^{1/2}) / s_n with the normals z (n x D) in

@@ -27,6 +27,8 @@ NOISE_NORMAL, NOISE_STUDENT_T = range(2)
 FLAG_PATH_DERIV = 1
 CV_MODES = {None: 0, 'full': 1, 'mean_only': 2, 'loo_diag_approx': 3, 'loo_direct_approx': 4}
 MAX_SLOTS = 64
+# capacity of the batched smoothing kernel (csrc/vb_psis_batch.hip: kPbMaxN, kPbTailCap)
+PSIS_BATCH_MAX_N, PSIS_BATCH_MAX_TAIL = 16384, 1024
 OPT_SGD, OPT_RMSPROP, OPT_ADAM, OPT_ADAGRAD = range(4)
 PRIOR_DIAG_GAUSSIAN, PRIOR_DIAG_STUDENT_T, PRIOR_DENSE = range(3)
 # int fn(void* user, const double* z, int64 n, int64 d, double* f, double* grad)   (include/viabel_hip.h: vb_model_callback)
@@ -124,6 +126,11 @@ SIGNATURES = {
                                                 ctypes.c_double, _c_double_p, _c_double_p]),
     'vb_psis_smooth': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_double, _c_double_p,
                                       _c_double_p]),
+    'vb_psis_smooth_batch': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_double, _c_double_p, _c_double_p]),
+    'vb_glm_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
+    'vb_glm_psis_loo': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p,
+                                       ctypes.c_double, _c_double_p, _c_double_p, _c_double_p]),
     'vb_alpha_grad_meanfield': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                ctypes.c_int, ctypes.c_double, _c_double_p, ctypes.c_double,
                                                _c_double_p, _c_double_p]),
@@ -679,6 +686,45 @@ class Engine:
             src = _dptr(log_weights)
         self._check(self._lib.vb_psis_smooth(self._ctx, src, n, float(reff), _dptr(out), ctypes.byref(khat)))
         return out, khat.value
+
+    def psis_smooth_batch(self, lw, reff=1.0, out=None):
+        """``lw``: ``(m, n)`` C-contiguous, one weight vector per ROW; all rows smoothed in one launch
+        (``vb_psis_smooth_batch``).  Returns ``(smoothed (m, n), khat (m,))``; ``out`` may be ``lw`` itself."""
+        lw = _f64(lw)
+        m, n = lw.shape
+        if out is None:
+            out = np.empty_like(lw)
+        khat = np.empty(m, dtype=np.float64)
+        self._check(self._lib.vb_psis_smooth_batch(self._ctx, _dptr(lw), n, m, n, float(reff), _dptr(out), _dptr(khat)))
+        return out, khat
+
+    def glm_pointwise(self, x, n_data):
+        """``(S, n_data)`` pointwise log-likelihoods of the bound regression target (``n_data`` observations) at the
+        draws ``x`` (S x D)."""
+        x = _f64(x)
+        s, d = x.shape
+        out = np.empty((s, int(n_data)), dtype=np.float64)
+        self._check(self._lib.vb_glm_pointwise(self._ctx, _dptr(x), s, d, _dptr(out)))
+        return out
+
+    def glm_psis_loo(self, x, n_data, log_ratios=None, log_w=None, reff=1.0):
+        """PSIS-LOO of the bound regression target (``n_data`` observations) from the draws ``x``
+        (``vb_glm_psis_loo``): ``(loo, khat, lpd)``, each ``(n_data,)``; ``lpd`` is None without ``log_w``."""
+        x = _f64(x)
+        s, d = x.shape
+        n_data = int(n_data)
+        loo, khat = np.empty(n_data, dtype=np.float64), np.empty(n_data, dtype=np.float64)
+        lpd = np.empty(n_data, dtype=np.float64) if log_w is not None else None
+        for name, v in (('log_ratios', log_ratios), ('log_w', log_w)):
+            if v is not None and np.shape(v) != (s,):
+                raise ValueError('{} must have shape ({},)'.format(name, s))
+        log_ratios = None if log_ratios is None else _f64(log_ratios)
+        log_w = None if log_w is None else _f64(log_w)
+        self._check(self._lib.vb_glm_psis_loo(self._ctx, _dptr(x), s, d,
+                                              None if log_ratios is None else _dptr(log_ratios),
+                                              None if log_w is None else _dptr(log_w), float(reff), _dptr(loo),
+                                              _dptr(khat), None if lpd is None else _dptr(lpd)))
+        return loo, khat, lpd
 
     # ------------------------------------------------------------------ AlphaDivergence, mean field
     def alpha_grad_meanfield(self, slot, n, d, theta, family, alpha, df=0.0, n_total=None):

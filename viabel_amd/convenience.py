@@ -9,14 +9,14 @@ host between the device's sampling and reduction kernels); ``fit`` (PyStan) is n
 import numpy as np
 
 from . import _lib
-from ._psis import psislw
+from ._psis import _tail_size, batch_capacity, psislw, psisloo
 from .approximations import MFGaussian, MFStudentT, NVPFlow
 from .diagnostics import all_diagnostics
-from .models import CallableModel, DeviceModel, SourceModel
+from .models import CallableModel, DeviceModel, LogisticRegressionModel, SourceModel
 from .objectives import ExclusiveKL, _stage_prior_noise
 from .optimization import FASO, RAABBVI, RMSProp
 
-__all__ = ['bbvi', 'vi_diagnostics', 'psis_correction', 'samples_and_log_weights']
+__all__ = ['bbvi', 'vi_diagnostics', 'psis_correction', 'samples_and_log_weights', 'loo', 'psisloo']
 
 
 def bbvi(dimension, *, n_iters=10000, num_mc_samples=10, log_density=None, approx=None, objective=None,
@@ -172,3 +172,55 @@ def samples_and_log_weights(var_param, model, approx, n_samples):
         return samples, log_p - log_q
     samples = approx.sample(var_param, n_samples)
     return samples, model(samples) - approx.log_density(var_param, samples)
+
+
+def loo(var_param, *, objective=None, model=None, approx=None, n_samples=4000, Reff=1.0):
+    """PSIS leave-one-out cross-validation of a fitted regression model, for comparing models by out-of-sample
+    predictive accuracy (``psisloo``, ``viabel/_psis.py:69-110``, made to work from a variational fit).
+
+    ``n_samples`` draws ``theta_s ~ q`` and their log ratios ``log p(theta_s, y) - log q(theta_s)``
+    (:func:`samples_and_log_weights`); observation ``i``'s leave-one-out weights are the Pareto-smoothed, normalised
+    ``log ratio_s - log p(y_i | theta_s)``.  The ``n_data x n_samples`` likelihood matrix is formed, smoothed and reduced
+    on the device (``vb_glm_psis_loo``); only three ``n_data``-vectors come back.  Returns a dict: ``elpd_loo`` (sum of
+    ``pointwise``), ``se_elpd_loo = sqrt(n_data var(pointwise))``, ``p_loo = sum(lpd - pointwise)``, ``pointwise``
+    (``log p(y_i | y_-i)``), ``lpd`` (``log p(y_i | y)`` under the smoothed full-data weights), ``khat`` (per
+    observation), ``khat_full`` (of the full-data ratios) and ``n_samples``.  Runs on the calling process's engine."""
+    if objective is None:
+        if model is None or approx is None:
+            raise ValueError('either objective or both model and approx must be specified')
+    elif model is not None or approx is not None:
+        raise ValueError('model and/or approx cannot be specified if objective is')
+    else:
+        model, approx = objective.model, objective.approx
+    if n_samples < 2:
+        raise ValueError('n_samples must be at least 2')
+    if not (Reff > 0):
+        raise ValueError('Reff must be positive')
+    if not isinstance(model, LogisticRegressionModel):
+        raise NotImplementedError(
+            'loo needs a target with per-observation structure (LogisticRegressionModel, PoissonRegressionModel, '
+            'LinearRegressionModel); {} has none. Build the (draws x observations) log-likelihood matrix yourself and '
+            'call psisloo(log_lik, log_ratios)'.format(type(model).__name__))
+    if not batch_capacity(n_samples, Reff):
+        raise NotImplementedError(
+            'loo keeps the likelihood matrix on the device and smooths it with the batched kernel, which takes at most '
+            '{} draws with a tail of at most {} values (n_samples = {}, Reff = {} has a tail of {}); use fewer draws, or '
+            'psisloo(log_lik, log_ratios) on a host matrix'.format(_lib.PSIS_BATCH_MAX_N, _lib.PSIS_BATCH_MAX_TAIL,
+                                                                  n_samples, Reff, _tail_size(n_samples, Reff)))
+    var_param = np.asarray(var_param, dtype=np.float64)
+    samples, log_ratios = samples_and_log_weights(var_param, model, approx, n_samples)
+    log_w, khat_full = psislw(log_ratios, Reff=Reff)
+    eng = _lib.default_engine()
+    eng.set_model(model.device_spec())
+    pointwise, khat, lpd = eng.glm_psis_loo(samples, model.n_data, log_ratios=log_ratios, log_w=log_w, reff=Reff)
+    n = pointwise.size
+    results = dict(elpd_loo=float(pointwise.sum()), se_elpd_loo=float(np.sqrt(n * np.var(pointwise))),
+                   p_loo=float(np.sum(lpd - pointwise)), pointwise=pointwise, lpd=lpd, khat=khat,
+                   khat_full=float(khat_full), n_samples=int(n_samples))
+    n_bad = int(np.sum(khat > 0.7))
+    print('elpd_loo = {:.2f} (SE {:.2f}), p_loo = {:.2f}'.format(results['elpd_loo'], results['se_elpd_loo'],
+                                                                 results['p_loo']))
+    print('{} of {} observations have Pareto khat > 0.7 (full-data ratios: khat = {:.2f})'.format(n_bad, n, khat_full))
+    if n_bad:
+        print('WARNING: khat > 0.7 means the leave-one-out terms of those observations are unreliable.')
+    return results

@@ -283,6 +283,7 @@ struct vb_ctx {
   int64_t psis_n = 0;                   // number of device-resident log weights (0: none)
   vb::DeviceBuffer psis_work;           // the multi-workgroup smoothing's exchange area (barrier counter, histograms, tail lists)
   unsigned long long psis_bar_base = 0; // value of that counter before the next launch
+  vb::DeviceBuffer loo_work;            // batched smoothing / PSIS-LOO (vb_psis_batch.hip): vectors, draws, per-vector results
   double* pin_host = nullptr;           // pinned, device-mapped staging (vb_linalg.hip): host / device address
   double* pin_dev = nullptr;
   size_t pin_bytes = 0;

@@ -10,6 +10,7 @@
 // fitted quantiles, truncation at 0 and log-sum-exp normalisation.  Integer atomics only (histogram, gather
 // counter); the sorted order is by (value, index), so the result does not depend on the gather order.
 #include "vb_common.h"
+#include "vb_psis_util.h"      // ps_wave_sum / ps_wave_max, ps_key / ps_unkey, ps_after
 
 #include <cfloat>
 #include <cmath>
@@ -20,17 +21,6 @@ namespace vb {
 constexpr int kPsisThreads = 1024;
 constexpr int kPsisTailCap = 4096;     // tail values sorted in LDS (M <= 4096  <=>  N <= 1.86e6 at Reff = 1)
 constexpr int kPsisQuadCap = 128;      // 30 + sqrt(4096) = 94 quadrature points at most
-
-__device__ __forceinline__ double ps_wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-  return x;
-}
-__device__ __forceinline__ double ps_wave_max(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x = fmax(x, __shfl_down(x, off, 64));
-  return x;
-}
 
 // block-wide sum / max over 1024 threads; every thread gets the result (sh: 16 doubles + 1)
 __device__ double ps_block_sum(double x, double* sh) {
@@ -52,20 +42,6 @@ __device__ double ps_block_max(double x, double* sh) {
 #pragma unroll
   for (int w = 1; w < kPsisThreads / 64; ++w) t = fmax(t, sh[w]);
   return t;
-}
-
-__device__ __forceinline__ unsigned long long ps_key(double v) {   // ascending order-preserving key
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double ps_unkey(unsigned long long k) {
-  const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double((long long)u);
-}
-
-// (value, index) lexicographic "a after b"
-__device__ __forceinline__ bool ps_after(double av, int ai, double bv, int bi) {
-  return (av > bv) | ((av == bv) & (ai > bi));      // no short circuit: a branch per comparison cost 25 us per call
 }
 
 // lw = f - b + sum(log sigma): the log importance weights log p(z_n) - log q(z_n) of the mean-field families

@@ -1,0 +1,690 @@
+// Batched Pareto smoothing and PSIS leave-one-out on the device.
+// Reference: viabel/_psis.py:69-110 (psisloo), :113-209 (psislw with a 2-D argument: one weight vector per column).
+//
+// psis_batch_kernel smooths m independent vectors of S log weights in ONE launch, one 256-thread workgroup per vector
+// (vb_psis.hip's kernels are sized for one long vector: 1024 threads, ~115 KB of LDS, one launch per vector).  Per vector
+// it does what psis_kernel does, in the same order: max shift, exact selection of the cut-off (the (M+1)-th largest,
+// M = ceil(min(0.2 S, 3 sqrt(S / Reff)))) by a byte-wise radix select on order-preserving keys, tail gathered and ordered
+// by (value, index), Zhang-Stephens fit with 30 + floor(sqrt(n_tail)) points, quantile replacement when k >= 1/3,
+// truncation at 0, log-sum-exp normalisation; k = inf when the tail has at most 4 values.
+//   * capacity: S <= 16 384 (VPT = 4, 16 or 64 values per thread, held in registers from the load to the end: the
+//     loads of a vector are contiguous and all issued before the first use) and a tail of at most 1024 values
+//     (384 at S = 16 384, Reff = 1; 62 quadrature points at most).  Longer vectors / tails keep the column loop.
+//   * the smoothed tail is NOT scattered back into the registers: it stays in LDS in sorted order with its element
+//     indices, and the closing sums take the untouched elements from registers and the tail from that list.
+//   * integer atomics on LDS only (histogram, gather counter); ties are ordered by index, every floating-point sum has a
+//     fixed order: results are bit-reproducible run to run and do not depend on the gather order.
+//   * mode "smooth": the vector is A[j], smoothed in place.  Mode "loo": the vector is log_ratios - A[j] (- A[j]
+//     without ratios), nothing is written back; loo[j] = logsumexp_s(smoothed_s + A[j][s]) and, with the full-data
+//     weights log_w, lpd[j] = logsumexp_s(log_w[s] + A[j][s]) leave instead: three doubles per vector.
+// Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; scratch 0 in all three variants;
+// LDS 14 920 B per workgroup: ten workgroups' worth in a CU's 160 KiB, so LDS never bounds the occupancy):
+//     VPT  4 (S <= 1024):    88 VGPRs -> 5 workgroups per CU
+//     VPT 16 (S <= 4096):   117 VGPRs -> 4 workgroups per CU
+//     VPT 64 (S <= 16 384): 256 VGPRs + 88 AGPRs -> 1 workgroup per CU (the vector alone is 128 registers; a fully
+//                           unrolled pass over it, its exponentials inlined, keeps the rest busy)
+//   Registers bound the occupancy everywhere.
+//
+// Pointwise log-likelihoods of the regression targets: LL[i][s] = log p(y_i | x_i' theta_s) as a normalised density is
+// one fp64 MFMA product X (n_data x D) times the TRANSPOSED draws (D x S) with a per-element epilogue (EpiPointwise).
+// That orientation -- not Z X' written transposed from the epilogue -- because the result must be observation-major
+// (n_data rows of S contiguous doubles: the smoothing kernel reads one observation's S values as a unit) and the GEMM's
+// result lanes hold adjacent COLUMNS: with draws as columns a lane pair stores 16 contiguous bytes and a quad 64,
+// whereas the transposed store would put every lane of a row on its own line, S doubles apart.  The transpose of the
+// draws is S x D doubles, negligible next to the n_data x S result.
+#include "vb_gemm_f64.h"
+#include "vb_psis_util.h"
+
+#include <cfloat>
+#include <cmath>
+#include <cstdlib>
+
+namespace vb {
+
+constexpr int kPbThreads = 256;
+constexpr int kPbWaves = kPbThreads / 64;
+constexpr int kPbTailCap = 1024;       // tail values sorted in LDS
+constexpr int kPbQuadCap = 64;         // 30 + sqrt(1024) = 62 quadrature points at most
+constexpr int kPbMaxVpt = 64;
+constexpr int64_t kPbMaxN = (int64_t)kPbMaxVpt * kPbThreads;      // 16 384
+constexpr int kPbBinCap = kPbThreads;  // the radix select ends by counting once the wanted rank's bin has one key per thread
+// device memory a call may hold for the n_data x S likelihood matrix (or the vectors of vb_psis_smooth_batch): larger
+// problems go through in chunks of observations
+constexpr size_t kLooBudgetBytes = (size_t)1 << 30;
+constexpr int64_t kLooBudgetDoubles = (int64_t)(kLooBudgetBytes / sizeof(double));
+
+struct PsisBatchArgs {
+  double* A;                  // m vectors of n doubles, vector j at A + j * ld
+  int64_t ld;
+  int n, m_tail;
+  int loo;                    // 0: smooth A[j] in place; 1: smooth log_ratios - A[j], write loo / lpd
+  const double* log_ratios;   // [n] or nullptr (loo)
+  const double* log_w;        // [n] or nullptr (loo): full-data smoothed log weights
+  double* khat;               // [m]
+  double* loo_out;            // [m] (loo)
+  double* lpd_out;            // [m] (loo, with log_w)
+};
+
+__device__ __forceinline__ double pb_block_sum(double x, double* sh) {
+  x = ps_wave_sum(x);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+__device__ __forceinline__ double pb_block_max(double x, double* sh) {
+  x = ps_wave_max(x);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
+  __syncthreads();
+  return fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
+}
+
+// running log-sum-exp of one thread: sum = s * exp(m)
+struct PbLse {
+  double m = -INFINITY, s = 0.0;
+  template <int C>
+  __device__ __forceinline__ void add(const double (&t)[C]) {      // C terms at the cost of C + 1 exponentials
+    double cm = t[0];
+#pragma unroll
+    for (int q = 1; q < C; ++q) cm = fmax(cm, t[q]);
+    const double mn = fmax(m, cm);
+    s *= (m == mn) ? 1.0 : exp(m - mn);
+#pragma unroll
+    for (int q = 0; q < C; ++q) s += (t[q] == -INFINITY) ? 0.0 : exp(t[q] - mn);      // (a term of -inf adds nothing)
+    m = mn;
+  }
+  __device__ __forceinline__ double total(double* sh) const {      // over the workgroup, in a fixed order
+    const double M = pb_block_max(m, sh);
+    const double part = (m == -INFINITY) ? 0.0 : s * exp(m - M);
+    return log(pb_block_sum(part, sh)) + M;
+  }
+};
+
+template <int VPT>
+__global__ void __launch_bounds__(kPbThreads) psis_batch_kernel(const PsisBatchArgs a) {
+  __shared__ double sh[kPbWaves];
+  __shared__ int hist[256];
+  __shared__ unsigned long long sel_prefix;
+  __shared__ long long sel_rank;
+  __shared__ int sel_bin_count;
+  __shared__ int tail_count;
+  __shared__ double tv[kPbTailCap];
+  __shared__ int ti[kPbTailCap];
+  __shared__ double q_bs[kPbQuadCap], q_L[kPbQuadCap], q_w[kPbQuadCap];
+  __shared__ double bc[2];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int n = a.n;
+  double* __restrict__ row = a.A + (int64_t)blockIdx.x * a.ld;
+
+  // the vector: element t + 256 u in r[u] (coalesced; up to sixteen loads per thread -- and as many of the ratios -- are
+  // issued before the first value is used).  The slots beyond n hold -inf: the smallest key, never above a cut-off, zero in
+  // every sum of exponentials -- the passes over the registers need no bounds predicate (64 of them held in scalar
+  // registers cost the VPT = 64 variant its second workgroup per CU); the wanted rank counts them in.
+  double r[VPT];
+  constexpr int LB = VPT < 16 ? VPT : 16;
+#pragma unroll
+  for (int u0 = 0; u0 < VPT; u0 += LB) {
+    double lr[LB];
+#pragma unroll
+    for (int q = 0; q < LB; ++q) {
+      const int i = t + (u0 + q) * kPbThreads;
+      r[u0 + q] = row[i < n ? i : n - 1];      // (clamped, not branched over: the slot is overwritten below)
+    }
+    if (a.loo) {
+#pragma unroll
+      for (int q = 0; q < LB; ++q) {
+        const int i = t + (u0 + q) * kPbThreads;
+        lr[q] = a.log_ratios ? a.log_ratios[i < n ? i : n - 1] : 0.0;
+      }
+#pragma unroll
+      for (int q = 0; q < LB; ++q) r[u0 + q] = a.log_ratios ? lr[q] - r[u0 + q] : -r[u0 + q];
+    }
+#pragma unroll
+    for (int q = 0; q < LB; ++q)
+      if (t + (u0 + q) * kPbThreads >= n) r[u0 + q] = -INFINITY;
+  }
+  // (every pass over the registers forms its element indices from an opaque copy of the thread index: left to itself the
+  // compiler keeps the VPT indices and byte offsets of the first pass alive to the last -- 150 registers at VPT = 64)
+  auto each = [&](auto&& f) __attribute__((always_inline)) {
+    int tt = t;
+    asm volatile("" : "+v"(tt));
+#pragma unroll
+    for (int u = 0; u < VPT; ++u) {
+      f(tt + u * kPbThreads, r[u]);
+    }
+  };
+
+  // 1. improve numerical accuracy: x -= max(x)   (_psis.py:166)
+  double mx = -INFINITY;
+  each([&](int, double v) { mx = fmax(mx, v); });
+  mx = pb_block_max(mx, sh);
+#pragma unroll
+  for (int u = 0; u < VPT; ++u) r[u] -= mx;
+
+  // 2. x_sorted[n - m_tail - 1] by radix select (8 bits per pass, most significant first)   (:170-173)
+  if (t == 0) {
+    sel_prefix = 0ull;
+    sel_rank = (long long)VPT * kPbThreads - a.m_tail - 1;     // 0-based ascending rank, the -inf pads included
+  }
+  int pass_done = -1;
+  for (int pass = 7; pass >= 0; --pass) {
+    hist[t] = 0;
+    __syncthreads();
+    const unsigned long long prefix = sel_prefix;
+    const unsigned long long mask = pass == 7 ? 0ull : (~0ull << (8 * (pass + 1)));
+    // the top bytes of log weights are sign and exponent: a wave's 64 keys fall into one or two bins (psis_kernel): two
+    // rounds of "the first lane's bin is counted by one add", the rest lane by lane
+#pragma unroll
+    for (int u = 0; u < VPT; ++u) {
+      const unsigned long long k = ps_key(r[u]);
+      const int bin = (int)((k >> (8 * pass)) & 255ull);
+      bool act = (k & mask) == prefix;
+#pragma unroll
+      for (int round = 0; round < 2; ++round) {
+        const unsigned long long todo = __ballot(act);
+        if (!todo) break;
+        const int leader = __builtin_ctzll(todo);
+        const int b = __shfl(bin, leader, 64);
+        const bool same = act && bin == b;
+        const unsigned long long mm = __ballot(same);
+        if (lane == leader) atomicAdd(&hist[b], __builtin_popcountll(mm));
+        act = act && !same;
+      }
+      if (act) atomicAdd(&hist[bin], 1);
+    }
+    __syncthreads();
+    if (wave == 0) {      // the bin that holds the wanted rank: four consecutive bins per lane
+      const long long want = sel_rank;
+      const int c0 = hist[4 * lane], c1 = hist[4 * lane + 1], c2 = hist[4 * lane + 2], c3 = hist[4 * lane + 3];
+      long long incl = (long long)c0 + c1 + c2 + c3;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const long long up = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += up;
+      }
+      const long long excl = incl - ((long long)c0 + c1 + c2 + c3);
+      const bool mine = (excl <= want && want < incl) || (lane == 63 && want >= incl);
+      if (mine) {
+        long long rr = want - excl;
+        int bin = 4 * lane, cb = c0;
+        if (rr >= c0 && bin < 255) { rr -= c0; ++bin; cb = c1;
+          if (rr >= c1 && bin < 255) { rr -= c1; ++bin; cb = c2;
+            if (rr >= c2 && bin < 255) { rr -= c2; ++bin; cb = c3; } } }
+        sel_rank = rr;
+        sel_prefix = prefix | ((unsigned long long)bin << (8 * pass));
+        sel_bin_count = cb;
+      }
+    }
+    __syncthreads();
+    pass_done = pass;
+    if (pass > 0 && sel_bin_count <= kPbBinCap) break;      // (uniform: a shared value read behind the barrier)
+  }
+  if (pass_done > 0) {
+    // the members of the selected bin, one per thread, counted against each other
+    unsigned long long* bk = reinterpret_cast<unsigned long long*>(tv);
+    if (t == 0) tail_count = 0;
+    __syncthreads();
+    const unsigned long long prefix = sel_prefix, mask = ~0ull << (8 * pass_done);
+    each([&](int, double v) {
+      const unsigned long long k = ps_key(v);
+      if ((k & mask) == prefix) {
+        const int p = atomicAdd(&tail_count, 1);
+        if (p < kPbBinCap) bk[p] = k;
+      }
+    });
+    __syncthreads();
+    const int nb = tail_count < kPbBinCap ? tail_count : kPbBinCap;
+    const long long want = sel_rank;
+    if (t < nb) {
+      const unsigned long long mk = bk[t];
+      int lt = 0, le = 0;
+      for (int j = 0; j < nb; ++j) {
+        const unsigned long long o = bk[j];
+        lt += o < mk ? 1 : 0;
+        le += o <= mk ? 1 : 0;
+      }
+      if (lt <= want && want < le) sel_prefix = mk;      // (every thread that holds this key writes the same value)
+    }
+    __syncthreads();
+  }
+  const double cutoffmin = log(DBL_MIN);                       // :159
+  const double xcutoff = fmax(ps_unkey(sel_prefix), cutoffmin);
+  const double expxc = exp(xcutoff);
+
+  // 3. right tail: x > xcutoff   (:175-177)
+  __syncthreads();
+  if (t == 0) tail_count = 0;
+  __syncthreads();
+  each([&](int i, double v) {
+    if (v > xcutoff) {
+      const int p = atomicAdd(&tail_count, 1);
+      if (p < kPbTailCap) {
+        tv[p] = v;
+        ti[p] = i;
+      }
+    }
+  });
+  __syncthreads();
+  const int n2 = tail_count < kPbTailCap ? tail_count : kPbTailCap;
+  double k = INFINITY, sigma = NAN;
+  bool replaced = false;
+  if (n2 > 4) {                                                 // :178-180
+    // 4. order of the tail by (value, index): every element counts the elements before it and moves to that position
+    constexpr int kPer = kPbTailCap / kPbThreads;
+    double my_v[kPer];
+    int my_i[kPer], my_r[kPer];
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) {
+      const int e = t + u * kPbThreads;
+      my_v[u] = e < n2 ? tv[e] : INFINITY;
+      my_i[u] = e < n2 ? ti[e] : 0x7fffffff;
+      my_r[u] = 0;
+    }
+    for (int j0 = 0; j0 < n2; j0 += 8) {      // eight comparands read before the first comparison; beyond n2 a sentinel
+      double v8[8];
+      int i8[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int jx = j0 + q;
+        const int jc = jx < n2 ? jx : n2 - 1;
+        const double vv = tv[jc];
+        const int ii = ti[jc];
+        v8[q] = jx < n2 ? vv : INFINITY;
+        i8[q] = jx < n2 ? ii : 0x7fffffff;
+      }
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+#pragma unroll
+        for (int u = 0; u < kPer; ++u)
+          if (u * kPbThreads < n2) my_r[u] += ps_after(my_v[u], my_i[u], v8[q], i8[q]) ? 1 : 0;     // (uniform condition)
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) {
+      if (t + u * kPbThreads < n2) {
+        tv[my_r[u]] = my_v[u];
+        ti[my_r[u]] = my_i[u];
+      }
+    }
+    __syncthreads();
+    // x2 = exp(x2) - exp(xcutoff)   (:185-186)
+    for (int i = t; i < n2; i += kPbThreads) tv[i] = exp(tv[i]) - expxc;
+    __syncthreads();
+
+    // 5. gpdfitnew (:266-325): PRIOR = 3, m = 30 + int(sqrt(n2))
+    const int m = 30 + (int)sqrt((double)n2);
+    const double xq = tv[(int)(n2 / 4.0 + 0.5) - 1], xl = tv[n2 - 1];
+    if (t < m) q_bs[t] = (1.0 - sqrt((double)m / ((double)(t + 1) - 0.5))) / (3.0 * xq) + 1.0 / xl;
+    __syncthreads();
+    // sixteen lanes per quadrature point, each a fixed stride of the tail, combined by a fixed butterfly: psis_kernel's
+    // order of additions (log(1 + y) for log1p(y): see there)
+    const int grp = t >> 4, gl = t & 15;
+    for (int j = grp; j < m; j += kPbThreads / 16) {          // ks_j = mean log1p(-bs_j x)
+      const double nb = -q_bs[j];
+      double s = 0.0;
+      int i = gl;
+      for (; i + 48 < n2; i += 64) {
+        const double l0 = log(fma(nb, tv[i], 1.0)), l1 = log(fma(nb, tv[i + 16], 1.0)), l2 = log(fma(nb, tv[i + 32], 1.0)),
+                     l3 = log(fma(nb, tv[i + 48], 1.0));
+        s += l0;
+        s += l1;
+        s += l2;
+        s += l3;
+      }
+      for (; i < n2; i += 16) s += log(fma(nb, tv[i], 1.0));
+#pragma unroll
+      for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+      if (gl == 0) {
+        const double ks = s / n2;
+        q_L[j] = n2 * (log(-(q_bs[j] / ks)) - ks - 1.0);
+      }
+    }
+    __syncthreads();
+    for (int j = grp; j < m; j += kPbThreads / 16) {
+      const double lj = q_L[j];
+      double s = 0.0;
+      for (int i = gl; i < m; i += 16) s += exp(q_L[i] - lj);
+#pragma unroll
+      for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+      if (gl == 0) {
+        const double w = 1.0 / s;
+        q_w[j] = w >= 10.0 * DBL_EPSILON ? w : 0.0;              // remove negligible weights
+      }
+    }
+    __syncthreads();
+    if (t == 0) {
+      double ws = 0.0, bsum = 0.0;
+      for (int i = 0; i < m; ++i) ws += q_w[i];
+      for (int i = 0; i < m; ++i) bsum += q_bs[i] * (q_w[i] / ws);
+      bc[0] = bsum;                                              // posterior mean of b
+    }
+    __syncthreads();
+    const double b = bc[0];
+    double s = 0.0;
+    for (int i = t; i < n2; i += kPbThreads) s += log1p(-b * tv[i]);
+    s = pb_block_sum(s, sh);
+    k = s / n2;
+    sigma = -k / b;
+    k = k * n2 / (n2 + 10.0) + 10.0 * 0.5 / (n2 + 10.0);        // weakly informative prior, a = 10
+
+    // 6. smoothed tail (:188-199): order statistics of the fitted GPD, truncated at the largest raw weight; left in
+    // tv (sorted order) beside the element indices ti
+    replaced = k >= 1.0 / 3.0 && !isinf(k);
+    if (replaced) {
+      __syncthreads();
+      for (int i = t; i < n2; i += kPbThreads) {
+        const double p = ((double)i + 0.5) / n2;
+        double qq = NAN;
+        if (sigma > 0.0) {
+          const double l = log1p(-p);
+          qq = (fabs(k) < DBL_EPSILON ? -l : expm1(-k * l) / k) * sigma;
+        }
+        double v = log(qq + expxc);
+        if (v > 0.0) v = 0.0;
+        tv[i] = v;
+      }
+    }
+  }
+  __syncthreads();
+
+  // 7. renormalise: x -= sumlogs(x)   (:201, :380-396); the replaced elements (x > xcutoff) come from the list
+  double m2 = -INFINITY;
+  each([&](int, double v) {
+    if (!(replaced && v > xcutoff)) m2 = fmax(m2, v);
+  });
+  if (replaced)
+    for (int i = t; i < n2; i += kPbThreads) m2 = fmax(m2, tv[i]);
+  m2 = pb_block_max(m2, sh);
+  double se = 0.0;
+  each([&](int, double v) {
+    if (!(replaced && v > xcutoff)) se += exp(v - m2);
+  });
+  if (replaced)
+    for (int i = t; i < n2; i += kPbThreads) se += exp(tv[i] - m2);
+  se = pb_block_sum(se, sh);
+  const double lse = log(se) + m2;
+  if (t == 0) a.khat[blockIdx.x] = k;
+
+  if (!a.loo) {
+    each([&](int i, double v) {
+      if (i < n && !(replaced && v > xcutoff)) row[i] = v - lse;
+    });
+    if (replaced)
+      for (int i = t; i < n2; i += kPbThreads) row[ti[i]] = tv[i] - lse;
+    return;
+  }
+
+  // 8. loo[j] = logsumexp_s(smoothed_s + A[j][s]), lpd[j] = logsumexp_s(log_w[s] + A[j][s]): the vector is read once
+  // more (a workgroup's own 8 S bytes, just read), a chunk of loads before its first use
+  constexpr int CH = 4;      // (eight: 12 more registers, and the VPT = 16 variant loses its fourth workgroup per CU)
+  int tq = t;
+  asm volatile("" : "+v"(tq));
+  PbLse acc_loo, acc_lpd;
+  const bool want_lpd = a.log_w != nullptr;
+#pragma unroll
+  for (int u0 = 0; u0 < VPT; u0 += CH) {
+    double av[CH], wv[CH];
+#pragma unroll
+    for (int q = 0; q < CH; ++q) {
+      const int i = tq + (u0 + q) * kPbThreads;
+      av[q] = i < n ? row[i] : -INFINITY;      // (beyond n: both terms -inf)
+      wv[q] = (want_lpd && i < n) ? a.log_w[i] : 0.0;
+    }
+    double tl[CH], tp[CH];
+#pragma unroll
+    for (int q = 0; q < CH; ++q) {
+      const double v = r[u0 + q];
+      tl[q] = !(replaced && v > xcutoff) ? (v - lse) + av[q] : -INFINITY;
+      tp[q] = wv[q] + av[q];
+    }
+    acc_loo.add(tl);
+    if (want_lpd) acc_lpd.add(tp);
+  }
+  if (replaced)
+    for (int i = t; i < n2; i += kPbThreads) {
+      const double tl[1] = {(tv[i] - lse) + row[ti[i]]};
+      acc_loo.add(tl);
+    }
+  const double loo = acc_loo.total(sh);
+  if (t == 0) a.loo_out[blockIdx.x] = loo;
+  if (want_lpd) {
+    const double lpd = acc_lpd.total(sh);
+    if (t == 0) a.lpd_out[blockIdx.x] = lpd;
+  }
+}
+
+static bool psis_batch_fits(int64_t n, double reff) {
+  return n >= 2 && n <= kPbMaxN && reff > 0.0 && psis_tail_size(n, reff) <= kPbTailCap;
+}
+
+static int psis_batch_enqueue(vb_ctx* ctx, hipStream_t st, PsisBatchArgs a, int64_t m) {
+  const dim3 grid((unsigned)m), block(kPbThreads);
+  if (a.n <= 4 * kPbThreads) hipLaunchKernelGGL(psis_batch_kernel<4>, grid, block, 0, st, a);
+  else if (a.n <= 16 * kPbThreads) hipLaunchKernelGGL(psis_batch_kernel<16>, grid, block, 0, st, a);
+  else hipLaunchKernelGGL(psis_batch_kernel<64>, grid, block, 0, st, a);
+  VB_HIP(ctx, hipGetLastError());
+  return VB_OK;
+}
+
+// ---- pointwise log-likelihoods of the regression targets -----------------------------------------------------------
+// what glm_term leaves out of log p(y_i | eta): Bernoulli-logit nothing, Poisson -log(y_i !), Gaussian -log(s) - log(2 pi) / 2
+__global__ void __launch_bounds__(256) glm_const_kernel(const double* __restrict__ y, int64_t n, int link, double aux,
+                                                        double* __restrict__ cst) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double c = 0.0;
+  if (link == VB_GLM_POISSON) c = -lgamma(y[i] + 1.0);
+  else if (link == VB_GLM_GAUSSIAN) c = -log(aux) - 0.91893853320467274178;
+  cst[i] = c;
+}
+
+struct EpiPointwise {        // LL[observation][draw] = log p(y_obs | eta): row = observation, col = draw
+  double* LL;
+  int64_t ld;
+  const double* y;
+  const double* cst;
+  int link;
+  double aux;
+  __device__ __forceinline__ double term(int row, double eta) const {
+    double dl;
+    return glm_term(link, aux, y[row], eta, &dl) + cst[row];
+  }
+  __device__ void operator()(int, int row, int col, double eta) const { LL[(int64_t)row * ld + col] = term(row, eta); }
+  __device__ d2v pair(int, int row, int col, double e0, double e1) const {
+    const d2v v = (d2v){term(row, e0), term(row, e1)};
+    *reinterpret_cast<d2v*>(LL + (int64_t)row * ld + col) = v;
+    return v;
+  }
+};
+
+// dst[c][r] = src[r][c] through a 32 x 33 LDS tile (both sides coalesced)
+__global__ void __launch_bounds__(256) pb_transpose_kernel(const double* __restrict__ src, int64_t lds, int64_t rows,
+                                                           int64_t cols, double* __restrict__ dst, int64_t ldd) {
+  __shared__ double tile[32][33];
+  const int64_t tiles_c = (cols + 31) / 32;
+  const int64_t c0 = (blockIdx.x % tiles_c) * 32, r0 = (blockIdx.x / tiles_c) * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int64_t rr = r0 + ty + 8 * q, cc = c0 + tx;
+    if (rr < rows && cc < cols) tile[ty + 8 * q][tx] = src[rr * lds + cc];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int64_t cc = c0 + ty + 8 * q, rr = r0 + tx;
+    if (rr < rows && cc < cols) dst[cc * ldd + rr] = tile[tx][ty + 8 * q];
+  }
+}
+
+static int pb_transpose(vb_ctx* ctx, hipStream_t st, const double* src, int64_t lds, int64_t rows, int64_t cols, double* dst,
+                        int64_t ldd) {
+  const int64_t tiles = ((cols + 31) / 32) * ((rows + 31) / 32);
+  if (tiles > 0x7fffffffll) return fail(ctx, VB_ERR_UNSUPPORTED, "matrix of %lld x %lld is too large to transpose in one launch",
+                                        (long long)rows, (long long)cols);
+  hipLaunchKernelGGL(pb_transpose_kernel, dim3((unsigned)tiles), dim3(256), 0, st, src, lds, rows, cols, dst, ldd);
+  VB_HIP(ctx, hipGetLastError());
+  return VB_OK;
+}
+
+static int glm_check(vb_ctx* ctx, int64_t s, int64_t d) {
+  if (ctx->model.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model)");
+  if (ctx->model.id != VB_MODEL_LOGISTIC)
+    return fail(ctx, VB_ERR_UNSUPPORTED, "pointwise log-likelihoods exist for the regression targets only (model id %d has no "
+                                         "per-observation structure)", ctx->model.id);
+  if (d != ctx->model.dim)
+    return fail(ctx, VB_ERR_INVALID, "x has %lld columns, model dimension is %d", (long long)d, ctx->model.dim);
+  if (s <= 0 || s > 0x7fffffffll) return fail(ctx, VB_ERR_INVALID, "the number of draws must be positive");
+  return VB_OK;
+}
+
+// Where the pieces of a pointwise / LOO call live in ctx->loo_work (doubles from the base)
+struct GlmLayout {
+  int64_t lds, ldx, ndp;                   // row strides: draws-as-columns (round_up(S, 16)), draws-as-rows, round_up(n_data, 16)
+  int64_t o_x, o_xt, o_c, o_vec, o_res, o_ll, o_t, total;
+  int64_t chunk;                           // observations per pass
+};
+static GlmLayout glm_layout(const ModelDev& m, int64_t s, int64_t d, bool with_transposed_out) {
+  GlmLayout L;
+  L.lds = round_up(s, 16), L.ldx = round_up(d, 16), L.ndp = round_up(m.n_data, 16);
+  const int64_t budget = kLooBudgetDoubles / (with_transposed_out ? 2 : 1);
+  int64_t chunk = budget / L.lds;
+  chunk = chunk < 1 ? 1 : (chunk > m.n_data ? m.n_data : chunk);
+  L.chunk = chunk;
+  int64_t off = 0;
+  auto carve = [&off](int64_t doubles) {
+    const int64_t o = off;
+    off += round_up(doubles, 16);
+    return o;
+  };
+  L.o_x = carve(s * L.ldx), L.o_xt = carve(d * L.lds), L.o_c = carve(L.ndp), L.o_vec = carve(2 * L.lds),
+  L.o_res = carve(3 * L.ndp), L.o_ll = carve(chunk * L.lds), L.o_t = carve(with_transposed_out ? s * chunk : 0);
+  L.total = off;
+  return L;
+}
+
+// draws up (S x D, host) and transposed (D x lds); the per-observation constants
+static int glm_stage(vb_ctx* ctx, hipStream_t st, const GlmLayout& L, const double* x_host, int64_t s, int64_t d) {
+  const ModelDev& m = ctx->model;
+  VB_TRY(ensure(ctx, ctx->loo_work, (size_t)L.total * sizeof(double)));
+  double* base = (double*)ctx->loo_work.ptr;
+  VB_HIP(ctx, hipMemsetAsync(base + L.o_xt, 0, (size_t)d * L.lds * sizeof(double), st));
+  VB_HIP(ctx, hipMemcpy2DAsync(base + L.o_x, (size_t)L.ldx * sizeof(double), x_host, (size_t)d * sizeof(double),
+                               (size_t)d * sizeof(double), (size_t)s, hipMemcpyHostToDevice, st));
+  VB_TRY(pb_transpose(ctx, st, base + L.o_x, L.ldx, s, d, base + L.o_xt, L.lds));
+  hipLaunchKernelGGL(glm_const_kernel, dim3((unsigned)((m.n_data + 255) / 256)), dim3(256), 0, st, m.p2, m.n_data, m.link, m.aux,
+                     base + L.o_c);
+  VB_HIP(ctx, hipGetLastError());
+  return VB_OK;
+}
+
+// LL[0 .. rows) = pointwise log-likelihoods of the observations [r0, r0 + rows) at the staged draws
+static int glm_pointwise_enqueue(vb_ctx* ctx, hipStream_t st, const GlmLayout& L, int64_t r0, int64_t rows, int64_t s, int64_t d) {
+  const ModelDev& m = ctx->model;
+  double* base = (double*)ctx->loo_work.ptr;
+  GemmArgs g;                        // LL = X theta'   [rows x S x D]
+  g.A = m.p0 + r0 * m.ldp, g.lda = m.ldp;
+  g.B = base + L.o_xt, g.ldb = L.lds;
+  g.M = (int)rows, g.N = (int)s, g.K = (int)d, g.tri_mode = 0;
+  gemm_f64_launch<true>(st, g, 1, ctx->prop.multiProcessorCount,
+                        EpiPointwise{base + L.o_ll, L.lds, m.p2 + r0, base + L.o_c + r0, m.link, m.aux});
+  VB_HIP(ctx, hipGetLastError());
+  return VB_OK;
+}
+
+}  // namespace vb
+
+using namespace vb;
+
+extern "C" {
+
+int vb_psis_smooth_batch(vb_ctx* ctx, const double* lw, int64_t n, int64_t m, int64_t ld, double reff, double* out,
+                         double* khat) {
+  if (!ctx || !lw || !out || !khat) return fail(ctx, VB_ERR_INVALID, "NULL argument");
+  if (n <= 1) return fail(ctx, VB_ERR_INVALID, "More than one log-weight needed.");
+  if (m <= 0 || m > 0x7fffffffll) return fail(ctx, VB_ERR_INVALID, "the number of weight vectors must be positive");
+  if (ld < n) return fail(ctx, VB_ERR_INVALID, "stride %lld is shorter than the vectors (%lld)", (long long)ld, (long long)n);
+  if (!(reff > 0.0)) return fail(ctx, VB_ERR_INVALID, "Reff must be positive");
+  if (!psis_batch_fits(n, reff))
+    return fail(ctx, VB_ERR_UNSUPPORTED, "batched PSIS takes vectors of at most %lld weights with a tail of at most %d values (got "
+                                         "%lld weights): smooth them one by one (vb_psis_smooth)",
+                (long long)kPbMaxN, kPbTailCap, (long long)n);
+  VB_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int64_t ldd = round_up(n, 16);
+  int64_t chunk = kLooBudgetDoubles / ldd;
+  chunk = chunk < 1 ? 1 : (chunk > m ? m : chunk);
+  VB_TRY(ensure(ctx, ctx->loo_work, (size_t)(chunk * ldd + round_up(chunk, 16)) * sizeof(double)));
+  double* A = (double*)ctx->loo_work.ptr;
+  double* kd = A + chunk * ldd;
+  for (int64_t j0 = 0; j0 < m; j0 += chunk) {
+    const int64_t rows = m - j0 < chunk ? m - j0 : chunk;
+    VB_HIP(ctx, hipMemcpy2DAsync(A, (size_t)ldd * sizeof(double), lw + j0 * ld, (size_t)ld * sizeof(double),
+                                 (size_t)n * sizeof(double), (size_t)rows, hipMemcpyHostToDevice, st));
+    PsisBatchArgs a{A, ldd, (int)n, psis_tail_size(n, reff), 0, nullptr, nullptr, kd, nullptr, nullptr};
+    VB_TRY(psis_batch_enqueue(ctx, st, a, rows));
+    VB_HIP(ctx, hipMemcpy2DAsync(out + j0 * ld, (size_t)ld * sizeof(double), A, (size_t)ldd * sizeof(double),
+                                 (size_t)n * sizeof(double), (size_t)rows, hipMemcpyDeviceToHost, st));
+    VB_HIP(ctx, hipMemcpyAsync(khat + j0, kd, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, st));
+    VB_HIP(ctx, hipStreamSynchronize(st));
+  }
+  return VB_OK;
+}
+
+int vb_glm_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out) {
+  if (!ctx || !x || !ll_out) return fail(ctx, VB_ERR_INVALID, "NULL argument");
+  VB_TRY(glm_check(ctx, s, d));
+  VB_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int64_t nd = ctx->model.n_data;
+  const GlmLayout L = glm_layout(ctx->model, s, d, true);
+  VB_TRY(glm_stage(ctx, st, L, x, s, d));
+  double* base = (double*)ctx->loo_work.ptr;
+  for (int64_t r0 = 0; r0 < nd; r0 += L.chunk) {      // chunk of observations -> (S x rows) -> columns [r0, r0 + rows) of the result
+    const int64_t rows = nd - r0 < L.chunk ? nd - r0 : L.chunk;
+    VB_TRY(glm_pointwise_enqueue(ctx, st, L, r0, rows, s, d));
+    VB_TRY(pb_transpose(ctx, st, base + L.o_ll, L.lds, rows, s, base + L.o_t, rows));
+    VB_HIP(ctx, hipMemcpy2DAsync(ll_out + r0, (size_t)nd * sizeof(double), base + L.o_t, (size_t)rows * sizeof(double),
+                                 (size_t)rows * sizeof(double), (size_t)s, hipMemcpyDeviceToHost, st));
+    VB_HIP(ctx, hipStreamSynchronize(st));
+  }
+  return VB_OK;
+}
+
+int vb_glm_psis_loo(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const double* log_ratios, const double* log_w,
+                    double reff, double* loo, double* khat, double* lpd) {
+  if (!ctx || !x || !loo || !khat) return fail(ctx, VB_ERR_INVALID, "NULL argument");
+  if ((log_w == nullptr) != (lpd == nullptr))
+    return fail(ctx, VB_ERR_INVALID, "log_w and lpd go together (both or neither)");
+  VB_TRY(glm_check(ctx, s, d));
+  if (s <= 1) return fail(ctx, VB_ERR_INVALID, "More than one draw needed.");
+  if (!(reff > 0.0)) return fail(ctx, VB_ERR_INVALID, "Reff must be positive");
+  if (!psis_batch_fits(s, reff))
+    return fail(ctx, VB_ERR_UNSUPPORTED, "PSIS-LOO on the device takes at most %lld draws with a tail of at most %d values (got %lld "
+                                         "draws, tail %d)",
+                (long long)kPbMaxN, kPbTailCap, (long long)s, psis_tail_size(s, reff));
+  VB_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int64_t nd = ctx->model.n_data;
+  const GlmLayout L = glm_layout(ctx->model, s, d, false);
+  VB_TRY(glm_stage(ctx, st, L, x, s, d));
+  double* base = (double*)ctx->loo_work.ptr;
+  double *lr_d = base + L.o_vec, *lw_d = lr_d + L.lds, *res = base + L.o_res;
+  if (log_ratios) VB_HIP(ctx, hipMemcpyAsync(lr_d, log_ratios, (size_t)s * sizeof(double), hipMemcpyHostToDevice, st));
+  if (log_w) VB_HIP(ctx, hipMemcpyAsync(lw_d, log_w, (size_t)s * sizeof(double), hipMemcpyHostToDevice, st));
+  for (int64_t r0 = 0; r0 < nd; r0 += L.chunk) {
+    const int64_t rows = nd - r0 < L.chunk ? nd - r0 : L.chunk;
+    VB_TRY(glm_pointwise_enqueue(ctx, st, L, r0, rows, s, d));
+    PsisBatchArgs a{base + L.o_ll, L.lds, (int)s, psis_tail_size(s, reff), 1, log_ratios ? lr_d : nullptr,
+                    log_w ? lw_d : nullptr, res + L.ndp + r0, res + r0, res + 2 * L.ndp + r0};
+    VB_TRY(psis_batch_enqueue(ctx, st, a, rows));
+  }
+  VB_HIP(ctx, hipMemcpyAsync(loo, res, (size_t)nd * sizeof(double), hipMemcpyDeviceToHost, st));
+  VB_HIP(ctx, hipMemcpyAsync(khat, res + L.ndp, (size_t)nd * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (lpd) VB_HIP(ctx, hipMemcpyAsync(lpd, res + 2 * L.ndp, (size_t)nd * sizeof(double), hipMemcpyDeviceToHost, st));
+  VB_HIP(ctx, hipStreamSynchronize(st));
+  return VB_OK;
+}
+
+}  // extern "C"

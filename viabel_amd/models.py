@@ -348,6 +348,20 @@ class LogisticRegressionModel(DeviceModel):
         return (_lib.MODEL_LOGISTIC, self._dim, np.concatenate([self.X.ravel(), self.y, [self.prior_sd]]),
                 np.array([self.X.shape[0]], dtype=np.int64))
 
+    @property
+    def n_data(self):
+        return self.X.shape[0]
+
+    def pointwise_log_likelihood(self, x):
+        """``log p(y_i | x_i' theta_s)`` for every draw (row of ``x``) and observation: ``(S, n_data)``, the ``log_lik``
+        argument of :func:`psisloo`.  Normalised densities (the Poisson ``- log y_i!``, the Gaussian
+        ``- log noise_sd - log(2 pi) / 2`` included), without the prior; one fp64 MFMA product with the likelihood in
+        its epilogue (``vb_glm_pointwise``).  ``x``: (S, D), or (D,) for one draw."""
+        x, _ = self._rows(x)
+        eng = _lib.default_engine()
+        eng.set_model(self.device_spec())
+        return eng.glm_pointwise(x, self.n_data)
+
 
 class PoissonRegressionModel(LogisticRegressionModel):
     """Bayesian Poisson regression ``y_i ~ Poisson(exp(x_i' b))`` with a ``N(0, prior_sd)`` prior: the same two-GEMM
