@@ -590,6 +590,40 @@ int vb_fit(vb_ctx* ctx, int slot, int slot_aux, int64_t n, int64_t d, int64_t n_
  * (60 rows of 4.2 MB at the headline shape: 7 ms of numpy on the host, 23 us per iteration of a 300-iteration fit).
  * VB_ERR_STATE: no such history (no fit yet, fewer rows kept, another p, or the work buffer has been reused).        */
 int vb_fit_history_mean(vb_ctx* ctx, int64_t rows, int64_t p, double* mean);
+
+/* ---- device-resident iterate chain and its convergence statistics (FASO / RAABBVI, optimization.py:479-633) ----
+ * A per-context store of iterates, row-major rows x p doubles, that every family's device fit appends to without a copy,
+ * and the statistics of _mc_diagnostics.py (split R-hat :124-184, ESS :40-99, MCSE :102-121) over its trailing rows, each
+ * parameter's column being one chain.
+ *
+ * vb_chain_open allocates (or reuses) room for capacity_rows rows of p doubles and starts with no rows; VB_ERR_HIP naming
+ *   the bytes asked for when the allocation does not fit, VB_ERR_INVALID when rows x p x 8 overflows, VB_ERR_STATE when a
+ *   chain is open already.  vb_chain_close detaches and frees it (no chain open: a no-op); vb_destroy does the same.
+ * While a chain is open, vb_fit / vb_flow_fit store iterate k into row rows + k (the store the optimiser step does for its
+ *   history) and add n_iters to rows when they return.  Such a call passes hist_len = 0; hist_len > 0, a parameter length
+ *   other than p or more iterations than rows left are VB_ERR_INVALID before anything is launched.  With no chain open the
+ *   two behave as they always did.
+ * vb_chain_rows reports the row count, vb_chain_append uploads n_rows rows behind the last one, vb_chain_fetch downloads
+ *   rows [first_row, first_row + n_rows).
+ * vb_chain_mean: np.mean(chain[-w:], axis=0), added in iteration order and divided by w -- vb_fit_history_mean's kernel.
+ *   (p = 1: the column is contiguous and numpy adds it pairwise in runs of 8192 values; a one-thread kernel restates that.)
+ * vb_chain_rhat: for each of n_windows (<= 16) trailing windows w >= 2 the maximum over the parameters of
+ *   compute_R_hat(chain[-w:], jitter): an odd window drops its last row, the halves are [T - w, T - w + half) and
+ *   [T - w + half, T - w + 2 half), within = M2 / (half - 1), W = mean of the two + jitter,
+ *   R = sqrt((half - 1) / half + between / (half W)); a NaN among the parameters gives NaN, as np.max does.  `rhat`, when
+ *   not NULL, receives the n_windows x p values themselves.  Moments are accumulated as Chan-merged (count, mean, M2).
+ * vb_chain_ess_mcse: ess() and MCSE() of the last w >= 2 rows, per parameter: direct centred lag products in blocks of 16
+ *   lags up to Geyer's stopping pair instead of the FFT; NaN for a constant column.
+ * All three block until the result is in the caller's array.  VB_ERR_STATE: no chain open; VB_ERR_INVALID: a window longer
+ * than the rows held.                                                                                                    */
+int vb_chain_open(vb_ctx* ctx, int64_t p, int64_t capacity_rows);
+int vb_chain_close(vb_ctx* ctx);
+int vb_chain_rows(vb_ctx* ctx, int64_t* rows);
+int vb_chain_append(vb_ctx* ctx, const double* rows_host, int64_t n_rows);
+int vb_chain_fetch(vb_ctx* ctx, int64_t first_row, int64_t n_rows, double* out);
+int vb_chain_mean(vb_ctx* ctx, int64_t w, double* mean);
+int vb_chain_rhat(vb_ctx* ctx, const int64_t* windows, int n_windows, double jitter, double* max_rhat, double* rhat);
+int vb_chain_ess_mcse(vb_ctx* ctx, int64_t w, double* ess, double* mcse);
 /* Observability (tests): how many DIS refreshes of the dense families took log p / log prior out of the sampling product's
  * epilogue (no pass over the samples: VB_MVT_EPI_ROWS), and how many steps had the chain-rule kernel store the gradient into the
  * mapped result buffer itself (VB_MVT_CHAIN_FETCH).                                                                         */

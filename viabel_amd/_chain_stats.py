@@ -6,13 +6,17 @@ Carlo standard error (``:102-121``), split R-hat of a single chain (``:124-160``
 search (``:163-184``).  O(window x var_param_dim) work, not on the gradient path.  Written vectorised
 (pair sums + running minimum) and pinned against the reference's functions by
 ``tests/golden/chainstats.npz``.
+
+``device_*``: the same statistics of the engine's device-resident iterate chain (``Engine.chain_open``,
+``csrc/vb_chain.hip``), for iterates that a device fit left there and that never come to the host.
 """
 import warnings
 
 import numpy as np
 from scipy.fft import next_fast_len
 
-__all__ = ['autocov', 'ess', 'MCSE', 'compute_R_hat', 'R_hat_convergence_check']
+__all__ = ['autocov', 'ess', 'MCSE', 'compute_R_hat', 'R_hat_convergence_check',
+           'device_MCSE', 'device_R_hat_convergence_check']
 
 
 def autocov(samples, axis=-1):
@@ -85,5 +89,17 @@ def compute_R_hat(chains, warmup=0, jitter=1e-8):
 def R_hat_convergence_check(samples, windows, Rhat_threshold=1.1):
     """Max R-hat over parameters for each trailing window; returns ``(converged, best_window)``."""
     worst = [np.max(compute_R_hat(np.array(samples[-w:]))) for w in windows]
+    best = int(np.argmin(worst))
+    return worst[best] <= Rhat_threshold, windows[best]
+
+
+def device_MCSE(eng, w):
+    """``MCSE(chain[-w:])`` of the engine's open iterate chain: ``(ess array, mcse array)``."""
+    return eng.chain_ess_mcse(w)
+
+
+def device_R_hat_convergence_check(eng, windows, Rhat_threshold=1.1):
+    """``R_hat_convergence_check(chain, windows)`` of the engine's open iterate chain."""
+    worst = eng.chain_rhat(windows)
     best = int(np.argmin(worst))
     return worst[best] <= Rhat_threshold, windows[best]

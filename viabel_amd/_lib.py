@@ -121,6 +121,14 @@ SIGNATURES = {
                               ctypes.c_int64, _c_double_p, ctypes.c_int64, _c_double_p, ctypes.c_int,
                               _c_double_p, _c_double_p, ctypes.c_int64, _c_double_p, _c_double_p]),
     'vb_fit_history_mean': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
+    'vb_chain_open': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_int64]),
+    'vb_chain_close': (ctypes.c_int, [_ctx_p]),
+    'vb_chain_rows': (ctypes.c_int, [_ctx_p, _c_int64_p]),
+    'vb_chain_append': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64]),
+    'vb_chain_fetch': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
+    'vb_chain_mean': (ctypes.c_int, [_ctx_p, ctypes.c_int64, _c_double_p]),
+    'vb_chain_rhat': (ctypes.c_int, [_ctx_p, _c_int64_p, ctypes.c_int, ctypes.c_double, _c_double_p, _c_double_p]),
+    'vb_chain_ess_mcse': (ctypes.c_int, [_ctx_p, ctypes.c_int64, _c_double_p, _c_double_p]),
     'vb_mvt_route_stats': (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     'vb_log_weights_meanfield': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                                 ctypes.c_double, _c_double_p, _c_double_p]),
@@ -1173,6 +1181,70 @@ class Engine:
         mean = pinned_array(p)
         self._check(self._lib.vb_fit_history_mean(self._ctx, int(rows), int(p), _dptr(mean)))
         return mean
+
+    # ------------------------------------------------------------------ device-resident iterate chain
+    def chain_open(self, p, capacity_rows):
+        """Open the engine's iterate chain: room for ``capacity_rows`` rows of ``p`` doubles on the device, none filled
+        (``vb_chain_open``).  While it is open, ``fit`` / ``flow_fit`` with ``hist_len=0`` append their iterates to it."""
+        self._check(self._lib.vb_chain_open(self._ctx, int(p), int(capacity_rows)))
+        self._chain_p = int(p)
+
+    def chain_close(self):
+        """Detach and free the chain (``vb_chain_close``); a no-op when none is open."""
+        self._chain_p = None
+        self._check(self._lib.vb_chain_close(self._ctx))
+
+    def _chain_dim(self):
+        p = getattr(self, '_chain_p', None)
+        if p is None:
+            raise EngineError('no iterate chain is open (chain_open)')
+        return p
+
+    def chain_rows(self):
+        """Rows the open chain holds."""
+        rows = ctypes.c_int64(0)
+        self._check(self._lib.vb_chain_rows(self._ctx, ctypes.byref(rows)))
+        return int(rows.value)
+
+    def chain_append(self, rows):
+        """Upload ``rows`` (``(n, p)``) behind the chain's last row (``vb_chain_append``)."""
+        p = self._chain_dim()
+        rows = _f64(np.atleast_2d(rows))
+        if rows.ndim != 2 or rows.shape[1] != p:
+            raise ValueError('rows must have shape (n, {}), the open chain\'s row length'.format(p))
+        self._check(self._lib.vb_chain_append(self._ctx, _dptr(rows), rows.shape[0]))
+
+    def chain_fetch(self, first_row, n_rows):
+        """Rows ``[first_row, first_row + n_rows)`` of the chain as an array (``vb_chain_fetch``)."""
+        p = self._chain_dim()
+        out = np.empty((max(int(n_rows), 0), p), dtype=np.float64)
+        self._check(self._lib.vb_chain_fetch(self._ctx, int(first_row), int(n_rows), _dptr(out) if out.size else None))
+        return out
+
+    def chain_mean(self, w):
+        """``np.mean(chain[-w:], axis=0)`` bit for bit, formed on the device (``vb_chain_mean``)."""
+        mean = pinned_array(self._chain_dim())
+        self._check(self._lib.vb_chain_mean(self._ctx, int(w), _dptr(mean)))
+        return mean
+
+    def chain_rhat(self, windows, jitter=1e-8, per_column=False):
+        """``np.max(compute_R_hat(chain[-w:], jitter=jitter))`` for every trailing window ``w`` (``vb_chain_rhat``);
+        with ``per_column`` also the ``(len(windows), p)`` values the maxima were taken of."""
+        p = self._chain_dim()
+        windows = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).ravel())
+        worst = np.empty(windows.size, dtype=np.float64)
+        rhat = np.empty((windows.size, p), dtype=np.float64) if per_column else None
+        self._check(self._lib.vb_chain_rhat(
+            self._ctx, windows.ctypes.data_as(_c_int64_p), int(windows.size), float(jitter), _dptr(worst),
+            _dptr(rhat) if per_column else None))
+        return (worst, rhat) if per_column else worst
+
+    def chain_ess_mcse(self, w):
+        """``(ess, mcse)`` arrays of ``_chain_stats.MCSE(chain[-w:])`` (``vb_chain_ess_mcse``)."""
+        p = self._chain_dim()
+        ess, mcse = np.empty(p, dtype=np.float64), np.empty(p, dtype=np.float64)
+        self._check(self._lib.vb_chain_ess_mcse(self._ctx, int(w), _dptr(ess), _dptr(mcse)))
+        return ess, mcse
 
     # ------------------------------------------------------------------ multi-GPU
     @staticmethod

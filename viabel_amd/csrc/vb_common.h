@@ -292,6 +292,12 @@ struct vb_ctx {
   uint64_t mvt_epi_rows_calls = 0, mvt_chain_fetch_calls = 0;      // vb_mvt_route_stats
   int ns_hint_m[2] = {0, 0}, ns_hint_steps[2] = {0, 0};      // steps the last Newton-Schulz root ([0]) / Frechet iteration ([1]) of size m ended with
   int64_t fit_hist_off = 0, fit_hist_len = 0, fit_hist_p = 0;      // where the last fit's kept iterates sit in fit_work (len 0: none)
+  // device-resident iterate chain (vb_chain.hip): chain_cap x chain_p doubles, row-major, the first chain_rows rows filled;
+  // while chain_open a device fit appends its iterates there (FitRun) instead of logging a history
+  vb::DeviceBuffer chain;
+  vb::DeviceBuffer chain_work;          // the chain statistics' partials and results
+  int64_t chain_p = 0, chain_cap = 0, chain_rows = 0;
+  bool chain_open = false;
   // a device fit's per-iteration rows (iterates, directions, gradients) leave while the next iterations run: a copy stream,
   // a ring of pinned slots, one event pair per slot (FitRun, vb_fit_run.h)
   static constexpr int kFitRing = 4;
@@ -759,6 +765,8 @@ struct FitStep {
   double* grads = nullptr;      // grads[k * p + i] = gradient (nullptr: not logged)
 };
 int fit_step_enqueue(vb_ctx* ctx, const FitStep& step);
+// out[j] = mean of h[0 .. rows)[j], added in row order: np.mean(h, axis=0) bit for bit (vb_fit.hip; vb_fit_history_mean, vb_chain_mean)
+int history_mean_enqueue(vb_ctx* ctx, const double* h, int64_t rows, int64_t p, double* out);
 
 // noise slot `slot` sized for an n x d matrix written by someone other than vb_noise_generate (vb_api.hip)
 int noise_slot_alloc(vb_ctx* ctx, int slot, int64_t n, int64_t d);

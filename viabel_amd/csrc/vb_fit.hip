@@ -180,6 +180,18 @@ __global__ void __launch_bounds__(256) fit_history_mean_kernel(const double* __r
 }
 }  // namespace
 
+}  // extern "C"
+
+namespace vb {
+int history_mean_enqueue(vb_ctx* ctx, const double* h, int64_t rows, int64_t p, double* out) {
+  hipLaunchKernelGGL(fit_history_mean_kernel, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, ctx->stream, h, rows, p, out);
+  VB_HIP(ctx, hipGetLastError());
+  return VB_OK;
+}
+}  // namespace vb
+
+extern "C" {
+
 int vb_fit_history_mean(vb_ctx* ctx, int64_t rows, int64_t p, double* mean) {
   if (!ctx || !mean || rows <= 0 || p <= 0) return fail(ctx, VB_ERR_INVALID, "bad argument");
   if (!ctx->fit_work.ptr || ctx->fit_hist_len < rows || ctx->fit_hist_p != p)
@@ -190,8 +202,7 @@ int vb_fit_history_mean(vb_ctx* ctx, int64_t rows, int64_t p, double* mean) {
   const double* h = (const double*)ctx->fit_work.ptr + ctx->fit_hist_off + (ctx->fit_hist_len - rows) * p;
   double* out = (double*)ctx->fit_work.ptr + ctx->fit_out_off;      // (the fit's own [value | gradient] area: free once it has returned)
   hipStream_t st = ctx->stream;
-  hipLaunchKernelGGL(fit_history_mean_kernel, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, st, h, rows, p, out);
-  VB_HIP(ctx, hipGetLastError());
+  VB_TRY(history_mean_enqueue(ctx, h, rows, p, out));
   const FetchSeg seg[1] = {{out, (size_t)p * sizeof(double), mean}};
   return fetch_blocking(ctx, st, seg, 1);
 }

@@ -4,6 +4,8 @@
 //    | iterates (hist_len x p) | directions (n_iters x p) | gradients (n_iters x p)]          (each rounded up to 16 doubles)
 // and moves the state in and the results out.  vb_fit (vb_fit.hip) and vb_flow_fit (vb_flow.hip) add their checks, their
 // parameter upload and the loop body; vb_fit_history_mean reads the kept iterates back through ctx->fit_hist_*.
+// While an iterate chain is open (vb_chain_open, vb_chain.hip) the step's history store points at the chain's tail instead:
+// iterate k lands in row chain_rows + k, nothing of length p is logged for the history, finish() adds n_iters to chain_rows.
 //
 // The rows a fit logs per iteration (iterate, descent direction, gradient: optimization.py:83-127 returns every iterate,
 // :541 FASO's gradient history) used to leave in one pageable copy after the last step: at p = 525 312 (D = 1024 dense)
@@ -28,6 +30,7 @@ struct FitRun {
   int has_state = 0;
   double *h_hist = nullptr, *h_dirs = nullptr, *h_grads = nullptr;      // caller's arrays
   bool streamed = false;        // the logged rows leave through the pinned ring
+  bool chained = false;         // the iterates go to the open chain's tail (no history of their own)
   int64_t drained = 0;          // iterations whose rows have reached the caller
 
   explicit FitRun(vb_ctx* c) : ctx(c) {}
@@ -51,6 +54,17 @@ struct FitRun {
   int begin(int64_t p, int64_t front_doubles, int64_t iters, int opt_kind, const double hyper[4], const double* state,
             int with_state, double* history, int64_t hist, double* directions, double* gradients) {
     n_iters = iters, hist_len = hist, has_state = with_state;
+    chained = ctx->chain_open;
+    if (chained) {      // (before anything is allocated or launched)
+      if (hist > 0)
+        return fail(ctx, VB_ERR_INVALID, "an iterate chain is open: the iterates stay on the device, pass hist_len = 0");
+      if (p != ctx->chain_p)
+        return fail(ctx, VB_ERR_INVALID, "the open iterate chain holds rows of %lld doubles, this fit's parameter has %lld",
+                    (long long)ctx->chain_p, (long long)p);
+      if (iters > ctx->chain_cap - ctx->chain_rows)
+        return fail(ctx, VB_ERR_INVALID, "the open iterate chain has room for %lld more rows, this fit appends %lld",
+                    (long long)(ctx->chain_cap - ctx->chain_rows), (long long)iters);
+    }
     int64_t off = 0;
     auto carve = [&off](int64_t doubles) {
       const int64_t o = off;
@@ -87,6 +101,10 @@ struct FitRun {
     step.values = base + o_val;
     step.hist = hist_len > 0 ? base + o_hist : nullptr;
     step.hist_first = n_iters - hist_len;
+    if (chained) {
+      step.hist = (double*)ctx->chain.ptr + ctx->chain_rows * p;
+      step.hist_first = 0;
+    }
     step.dirs = directions ? base + o_dirs : nullptr;
     step.grads = gradients ? base + o_grads : nullptr;
     h_hist = hist_len > 0 ? history : nullptr, h_dirs = directions, h_grads = gradients;
@@ -138,6 +156,7 @@ struct FitRun {
     }
     VB_HIP(ctx, hipStreamSynchronize(st));
     ctx->fit_hist_off = o_hist, ctx->fit_hist_len = hist_len, ctx->fit_hist_p = p, ctx->fit_out_off = o_out;
+    if (chained) ctx->chain_rows += n_iters;
     return comm_check(ctx);
   }
 

@@ -20,7 +20,7 @@ import numpy as np
 import tqdm
 
 from . import _lib
-from ._chain_stats import MCSE, R_hat_convergence_check
+from ._chain_stats import MCSE, R_hat_convergence_check, device_MCSE, device_R_hat_convergence_check
 from .approximations import MFGaussian
 
 __all__ = [
@@ -176,6 +176,14 @@ class StochasticGradientOptimizer(Optimizer):
 # iterate averages of at least this many numbers are formed on the device (vb_fit_history_mean); below, numpy's pass is cheaper
 # than a launch and a copy
 _DEVICE_MEAN_MIN = 1 << 20
+
+
+# Device bytes the iterate chain of one FASO(device_checks=True) run may take: n_iters rows of p doubles, allocated up front.
+# An MI355X reports 309 GB of HBM (see objectives._FLOW_FIT_LOG_BYTES, whose 16 GiB of logged rows this mode does not use);
+# 128 GiB holds bbvi's default 10 000 iterations at both sizes the project is measured at -- 42 GB at D = 1024 full rank
+# (4.2 MB a row), 84 GB for the NVP configuration (8.4 MB a row) -- and leaves more than half of the card to the model, the
+# noise and the fit's workspace.  A longer run at such a size has to use the host checks (or fewer iterations per FASO run).
+_DEVICE_CHAIN_BYTES = 128 << 30
 
 
 def _ema_update(state, decay, grad_sq):
@@ -375,7 +383,11 @@ class FASO(Optimizer):
     ``mcse_threshold`` with at least ``ESS_min`` effective samples.
     """
 
-    def __init__(self, sgo, *, mcse_threshold=0.1, W_min=200, ESS_min=None, k_check=None):
+    def __init__(self, sgo, *, mcse_threshold=0.1, W_min=200, ESS_min=None, k_check=None, device_checks=False):
+        """``device_checks``: keep the iterates on the device (the engine's iterate chain) and run the stationarity and
+        MCSE checks there (``csrc/vb_chain.hip``) instead of downloading every iterate and gradient.  The decisions, the
+        values and the iterate averages are those of the default mode; ``variational_param_history`` and
+        ``grad_history`` come back empty (shape ``(0, p)``).  Needs the device-resident loop."""
         if not isinstance(sgo, StochasticGradientOptimizer):
             raise ValueError('sgo must be a subclass of StochasticGradientOptimizer')
         self._sgo = sgo
@@ -383,6 +395,7 @@ class FASO(Optimizer):
         self._W_min = W_min
         self._ESS_min = W_min // 8 if ESS_min is None else ESS_min
         self._k_check = W_min if k_check is None else k_check
+        self._device_checks = bool(device_checks)
         if mcse_threshold <= 0:
             raise ValueError('"mcse_threshold" must be greater than zero')
         if W_min <= 0:
@@ -406,6 +419,19 @@ class FASO(Optimizer):
             return ess, mcse
         return MCSE(iterates)
 
+    def _device_iterate_mcse(self, objective, eng, W, dim_hint):
+        """``_iterate_mcse`` of the last ``W`` rows of the engine's iterate chain: the two P-vectors come from the device,
+        the mean-field Gaussian's special case is applied to them here."""
+        ess, mcse = device_MCSE(eng, W)
+        if isinstance(objective.approx, MFGaussian):
+            dim = int(dim_hint / 2)
+            last = eng.chain_fetch(eng.chain_rows() - 2, 2)
+            keep = (last[0] - last[1]) != 0          # constant coordinates carry no Monte Carlo error
+            ess, mcse = ess[keep], mcse[keep]
+            mean_log_sd = np.array(eng.chain_mean(W))[keep][-dim:]
+            mcse = np.concatenate((mcse[:dim] / np.exp(mean_log_sd), mcse[-dim:]))
+        return ess, mcse
+
     def _next_check(self, k, k_conv, W_check, n_iters):
         """First iteration >= k whose bookkeeping can do anything: the next stationarity check (multiples of
         k_check) before convergence, the next MCSE check (k_conv + W_check) after it."""
@@ -425,6 +451,25 @@ class FASO(Optimizer):
             on_device = sgo._device_fit_possible(objective, init_param)
         elif on_device and not sgo._device_fit_possible(objective, init_param):
             raise NotImplementedError('this optimiser / objective pair has no device-resident loop')
+        if not self._device_checks:
+            return self._optimize(n_iters, objective, init_param, on_device, None)
+        if not on_device:
+            raise NotImplementedError('device_checks: this optimiser / objective pair has no device-resident loop '
+                                      '(or on_device=False was asked for)')
+        chain_bytes = int(n_iters) * init_param.size * 8
+        if chain_bytes > _DEVICE_CHAIN_BYTES:
+            raise ValueError('device_checks: a chain of {} iterates x {} parameters takes {} bytes of device memory, '
+                             'the budget is {}'.format(n_iters, init_param.size, chain_bytes, _DEVICE_CHAIN_BYTES))
+        eng = objective._engine()
+        eng.chain_open(init_param.size, n_iters)
+        try:
+            return self._optimize(n_iters, objective, init_param, on_device, eng)
+        finally:
+            eng.chain_close()
+
+    def _optimize(self, n_iters, objective, init_param, on_device, chain):
+        """The loop.  ``chain``: the engine whose open iterate chain holds the iterates (``device_checks``), or None."""
+        sgo = self._sgo
         done_until = -1      # device mode: iterations up to here are already in `hist`
         diagnostics = self._sgo._diagnostics
         k_conv = k_stopped = k_Rhat = None
@@ -446,16 +491,24 @@ class FASO(Optimizer):
                             done_until = self._next_check(k, k_conv, W_check, n_iters)
                             count = done_until - k + 1
                             with _Stopwatch() as sw:
-                                param, values, iterates, state, dirs, grads = objective.device_fit(
-                                    count, param, sgo._device_kind, sgo._device_hyper(),
-                                    state=sgo._device_state(param.size), hist_len=count,
-                                    log_directions=diagnostics, log_gradients=True)
-                                sgo._set_device_state(state, param.size)
-                                hist['value_history'].extend(values)
-                                hist['grad_history'].extend(grads)
-                                hist['variational_param_history'].extend(iterates)
-                                if diagnostics:
-                                    hist['descent_dir_history'].extend(dirs)
+                                if chain is not None:      # the iterates stay in the chain, nothing of length p is logged
+                                    param, values, _, state, _, _ = objective.device_fit(
+                                        count, param, sgo._device_kind, sgo._device_hyper(),
+                                        state=sgo._device_state(param.size), hist_len=0,
+                                        log_directions=False, log_gradients=False)
+                                    sgo._set_device_state(state, param.size)
+                                    hist['value_history'].extend(values)
+                                else:
+                                    param, values, iterates, state, dirs, grads = objective.device_fit(
+                                        count, param, sgo._device_kind, sgo._device_hyper(),
+                                        state=sgo._device_state(param.size), hist_len=count,
+                                        log_directions=diagnostics, log_gradients=True)
+                                    sgo._set_device_state(state, param.size)
+                                    hist['value_history'].extend(values)
+                                    hist['grad_history'].extend(grads)
+                                    hist['variational_param_history'].extend(iterates)
+                                    if diagnostics:
+                                        hist['descent_dir_history'].extend(dirs)
                             opt_time += sw.interval
                         if k < done_until:
                             continue
@@ -475,8 +528,12 @@ class FASO(Optimizer):
                         W_upper = int(0.95 * k)
                         if W_upper > self._W_min:
                             windows = np.linspace(self._W_min, W_upper, num=5, dtype=int)
-                            ok, best_W = R_hat_convergence_check(hist['variational_param_history'], windows)
-                            iterate_average = np.mean(hist['variational_param_history'][-best_W:], axis=0)
+                            if chain is not None:
+                                ok, best_W = device_R_hat_convergence_check(chain, windows)
+                                iterate_average = np.array(chain.chain_mean(best_W))
+                            else:
+                                ok, best_W = R_hat_convergence_check(hist['variational_param_history'], windows)
+                                iterate_average = np.mean(hist['variational_param_history'][-best_W:], axis=0)
                             if diagnostics:
                                 hist['iterate_average_k_history'].append(k)
                                 hist['iterate_average_history'].append(iterate_average)
@@ -487,13 +544,19 @@ class FASO(Optimizer):
                     # after stationarity: Monte Carlo standard error of the iterate average
                     if k_conv is not None and k - k_conv == W_check:
                         W = W_check
-                        converged = np.array(hist['variational_param_history'][-W:])
-                        iterate_average = np.mean(converged, axis=0)
+                        if chain is not None:
+                            iterate_average = np.array(chain.chain_mean(W))
+                        else:
+                            converged = np.array(hist['variational_param_history'][-W:])
+                            iterate_average = np.mean(converged, axis=0)
                         if diagnostics and k not in hist['iterate_average_k_history']:
                             hist['iterate_average_k_history'].append(k)
                             hist['iterate_average_history'].append(iterate_average)
                         with _Stopwatch() as sw_mcse:
-                            ess, mcse = self._iterate_mcse(objective, converged, init_param.size)
+                            if chain is not None:
+                                ess, mcse = self._device_iterate_mcse(objective, chain, W, init_param.size)
+                            else:
+                                ess, mcse = self._iterate_mcse(objective, converged, init_param.size)
                         if diagnostics:
                             hist['ess_and_mcse_k_history'].append(k)
                             hist['ess_history'].append(ess)
@@ -524,6 +587,9 @@ class FASO(Optimizer):
         else:
             print('Convergence reached at iteration', k_stopped)
         results = {name: np.array(h) for name, h in hist.items()}
+        if chain is not None:      # the rows never came to the host: empty histories of the right width
+            for name in ('variational_param_history', 'grad_history') + (('descent_dir_history',) if diagnostics else ()):
+                results[name] = np.empty((0, init_param.size))
         results['k_conv'] = k_conv
         results['k_Rhat'] = k_Rhat
         results['k_stopped'] = k_stopped
@@ -657,7 +723,8 @@ class RAABBVI(FASO):
                 K_max -= (k_new + 1)
                 previous = average
                 if epoch == 0 and self._init_rmsprop:
-                    opt = FASO(sgo=RMSProp(learning_rate=sgo._learning_rate, diagnostics=diagnostics)) \
+                    opt = FASO(sgo=RMSProp(learning_rate=sgo._learning_rate, diagnostics=diagnostics),
+                               device_checks=self._device_checks) \
                         .optimize(K_max, objective, average, on_device=on_device)
                 else:
                     opt = super().optimize(K_max, objective, average, on_device=on_device)
@@ -739,6 +806,9 @@ class RAABBVI(FASO):
             print('WARNING: maximum number of iterations reached before '
                   'stopping rule was triggered')
         results = {name: np.array(h) for name, h in hist.items() if name not in ('k_Rhat', 'k_mcse', 'k_conv')}
+        if self._device_checks:      # the epochs' histories came back empty: keep their width
+            for name in ('variational_param_history', 'grad_history') + (('descent_dir_history',) if diagnostics else ()):
+                results[name] = np.reshape(results[name], (-1, init_param.size))
         results['opt_param'] = average
         results['k_stopped_final'] = k_stopped_final
         results['k_Rhat'] = hist['k_Rhat']
