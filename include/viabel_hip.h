@@ -759,6 +759,12 @@ uint64_t vb_legacy_rng_uid(const vb_legacy_rng* rng);
 #define VB_PROF_FR_MODEL_GEMM 2   /* correlated-Gaussian target: G = -(Z - m) P (dense)               */
 #define VB_PROF_FR_GRAD_GEMM 3    /* dense family: C = G' E (lower-triangular tiles, split over rows) */
 #define VB_PROF_NUM 4
+
+/* Dense Gaussian family on the correlated-Gaussian target: from this dimension and this many sample rows per dimension
+ * on, the evaluation folds L' into the precision matrix (G = -E (L' P) - 1 (P (mu - m))') instead of forming the
+ * samples Z = E L' + mu (csrc/vb_fullrank.hip, fr_pipeline_enqueue; DESIGN 4.4 has the measurements behind them). */
+#define VB_FR_FOLD_MIN_D 1024
+#define VB_FR_FOLD_MIN_ROWS_PER_D 3
 int vb_profile_enable(vb_ctx* ctx, int on);
 int vb_profile_read(vb_ctx* ctx, int64_t* launches, int64_t* evals, double* total_ms, int reset);
 int vb_profile_read_kernel(vb_ctx* ctx, int kernel_id, int64_t* launches, int64_t* evals, double* total_ms,

@@ -36,6 +36,8 @@ MODEL_CALLBACK_TYPE = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POI
                                        ctypes.c_int64, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double))
 COMM_ID_BYTES = 128
 PROF_MF_ACCUM, PROF_FR_SAMPLE_GEMM, PROF_FR_MODEL_GEMM, PROF_FR_GRAD_GEMM = range(4)
+# the folded full-rank evaluation's gate (include/viabel_hip.h: VB_FR_FOLD_MIN_D, VB_FR_FOLD_MIN_ROWS_PER_D); read-only mirrors
+FR_FOLD_MIN_D, FR_FOLD_MIN_ROWS_PER_D = 1024, 3
 
 # `const double*` / `double*` parameters are declared void*: ctypes then takes the array's address as a plain integer
 # (`_dptr`), half the cost of building a POINTER(c_double) per argument on calls that last tens of microseconds

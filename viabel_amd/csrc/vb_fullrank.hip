@@ -13,6 +13,8 @@
 //   GEMM 1 (MFMA)      Z = E L^T + mu      [N x D x D, triangular k-range]  fused model epilogue
 //   model              gauss_diag: G in the GEMM-1 epilogue; funnel: row kernel Z -> G;
 //                      gauss_full: GEMM 2 (MFMA)  G = -(Z - m) P
+//                      (from D = 1024 and 3 D samples on, folded: M = L' P, G = -E M - 1 (P (mu - m))', no GEMM 1 --
+//                      see fr_pipeline_enqueue)
 //   fr_colsum          column sums of G (-> d/dmu) and sum_n f(z_n), per 128-row block
 //   GEMM 3 (MFMA)      C = G^T E           [D x D x N, lower-triangular tiles, split-K]
 //   fr_reduce          fixed-order sum of the split-K slabs / row-block partials -> sum vector
@@ -185,6 +187,22 @@ struct EpiNegate {          // G = -acc   (gauss_full: G = -(Z - m) P)
   }
 };
 
+// G = -acc - b   (gauss_full, folded evaluation: acc = E M with M = L' P, b = P (mu - m); see fr_pipeline_enqueue)
+struct EpiNegateBias {
+  double* G;
+  int64_t ldz;
+  const double* b;
+  __device__ void operator()(int, int row, int col, double acc) const {
+    G[(int64_t)row * ldz + col] = -acc - b[col];
+  }
+  __device__ d2v pair(int, int row, int col, double a0, double a1) const {
+    const d2v bb = *reinterpret_cast<const d2v*>(b + col);
+    const d2v v = (d2v){-a0 - bb.x, -a1 - bb.y};
+    *reinterpret_cast<d2v*>(G + (int64_t)row * ldz + col) = v;
+    return v;
+  }
+};
+
 struct EpiAccumulate {      // G += acc   (path derivative: the rows of G take the score's L^-T eps)
   double* G;
   int64_t ldz;
@@ -231,6 +249,29 @@ struct EpiSplitSlabCs {
     const d2v v = (d2v){a0, a1};
     *reinterpret_cast<d2v*>(C + split * slab + (int64_t)row * ldc + col) = v;
     return v;
+  }
+};
+
+// ... and, per workgroup, the sum of L[row][col] * acc over the tile's entries on or below the diagonal (the folded
+// evaluation: sum (Z - m) o G = sum_{i >= j} L_ij C_ij + (mu - m) . colsum(G)).  L[row][col] is Lt[col][row]: a lane's
+// fragments a, a + 1 are adjacent rows, i.e. adjacent doubles of one row of Lt.
+struct EpiSplitSlabCsF {
+  double* C;
+  int64_t ldc, slab;
+  double* colsum;
+  int64_t colsum_ld;
+  const double* Lt;
+  int64_t ldl;
+  double* part;
+  __device__ double operator()(int split, int row, int col, double acc) const {
+    C[split * slab + (int64_t)row * ldc + col] = acc;
+    const double l = Lt[(int64_t)col * ldl + row];
+    return col <= row ? l * acc : 0.0;
+  }
+  __device__ d2v pair(int split, int row, int col, double a0, double a1) const {
+    *reinterpret_cast<d2v*>(C + split * slab + (int64_t)row * ldc + col) = (d2v){a0, a1};
+    const double l0 = Lt[(int64_t)col * ldl + row], l1 = Lt[(int64_t)(col + 1) * ldl + row];
+    return (d2v){col <= row ? l0 * a0 : 0.0, col + 1 <= row ? l1 * a1 : 0.0};
   }
 };
 
@@ -358,6 +399,81 @@ __global__ void __launch_bounds__(256) fr_colsum_kernel(const double* __restrict
   if (threadIdx.x == 0) fpart[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = f;
 }
 
+// ---- folded evaluation: M = sum of the split slabs of L' P, and b = P (mu - m) ------------------------------------------
+// The correlated-Gaussian target's G is linear in the noise: G = -(E L' + 1 c') P = -E M - 1 b', c = mu - m, M = L' P,
+// b = P c -- a D x D x D product that does not depend on the number of samples instead of the N x D x D sampling product.
+// Blocks [0, nb_b), 8 columns each (dispatched first: each is a chain of dependent passes): b[j] = sum_k P[k][j] c[k];
+// thread (pair p = t & 3, k group t >> 2) sums its 64th of the k range, sixteen rows per pass, the groups are
+// combined through LDS in fixed order.  The remaining blocks (none for an unsplit product): one thread per pair of
+// adjacent entries of M, the slabs of the split product added in slab order (a slab whose k range ends at or below the
+// first row of the entry's `bm_rows`-row block is not written by the product -- tri_mode 4 -- and not read).
+__global__ void __launch_bounds__(256) fr_fold_msum_kernel(const double* __restrict__ Mpart, int msplits, int64_t slab,
+                                                           int d, int64_t ldz, int k_split, int bm_rows,
+                                                           double* __restrict__ Mout, int nb_b,
+                                                           const double* __restrict__ P, int64_t ldp,
+                                                           const double* __restrict__ mu,
+                                                           const double* __restrict__ mean, double* __restrict__ b) {
+  if ((int)blockIdx.x >= nb_b) {
+    // (row and first slab from the block index: wave-uniform, no per-thread division -- with idx / ldz per thread the
+    // kernel was bound by that arithmetic: 20 us at D = 1024)
+    const int bpr = (int)((ldz / 2 + 255) / 256);                  // blocks per row of M
+    const int blk = (int)blockIdx.x - nb_b, r = blk / bpr;
+    const int cp = (blk - r * bpr) * 256 + (int)threadIdx.x;       // column pair
+    if (2 * cp >= ldz) return;
+    const int64_t idx = (int64_t)r * ldz + 2 * cp;
+    const int z0 = (r / bm_rows * bm_rows) / kGemmBK * kGemmBK / k_split;
+    fr_d2 s = (fr_d2){0.0, 0.0};
+    for (int zb = z0; zb < msplits; zb += 4) {      // four slabs in flight (clamped, not predicated), added in slab order
+      fr_d2 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        v[u] = *reinterpret_cast<const fr_d2*>(Mpart + (zb + u < msplits ? zb + u : msplits - 1) * slab + idx);
+      s = zb == z0 ? v[0] : s + v[0];
+#pragma unroll
+      for (int u = 1; u < 4; ++u)
+        if (zb + u < msplits) s += v[u];
+    }
+    *reinterpret_cast<fr_d2*>(Mout + idx) = s;
+    return;
+  }
+  __shared__ fr_d2 part[64][4];
+  const int p = threadIdx.x & 3, kg = threadIdx.x >> 2;
+  const int col = (int)blockIdx.x * 8 + 2 * p;
+  const int colc = col < d ? col : 0;                        // (rows of P are padded to an even stride >= d)
+  const int kper = (d + 63) / 64;
+  const int k0 = kg * kper, k1 = k0 + kper < d ? k0 + kper : d;
+  fr_d2 s = (fr_d2){0.0, 0.0};
+  for (int kb = k0; kb < k1; kb += 16) {
+    fr_d2 v[16];
+    double c[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int k = kb + u < k1 ? kb + u : k1 - 1;
+      v[u] = *reinterpret_cast<const fr_d2*>(P + (int64_t)k * ldp + colc);
+      c[u] = mu[k] - mean[k];
+    }
+#pragma unroll
+    for (int u = 0; u < 16; ++u)
+      if (kb + u < k1) s += v[u] * c[u];
+  }
+  part[kg][p] = s;
+  __syncthreads();
+  if (kg == 0) {
+    fr_d2 tot = part[0][p];
+#pragma unroll
+    for (int q = 1; q < 64; ++q) tot += part[q][p];
+    if (col < d) b[col] = tot.x;
+    if (col + 1 < d) b[col + 1] = tot.y;
+  }
+}
+
+// k splits of the M = L' P product (64 x 64 tiles): pieces of about sixteen slabs, so that no workgroup carries the
+// 64 slabs of row block 0 at D = 1024 alone (about 40 us on a CU by itself)
+static int fr_fold_splits(int d) {
+  const int s = d / (16 * kGemmBK);
+  return s < 1 ? 1 : (s > 8 ? 8 : s);
+}
+
 // ---- reduce: split-K slabs, row-block partials -> sum vector ------------------------------------------
 // sum vector layout: [F | colsum (ldz) | C (d x ldl)], F at index 0, colsum from 16, C from 16 + ldz
 
@@ -473,17 +589,20 @@ __global__ void __launch_bounds__(256) fr_reduce_packed_kernel(
     const double* __restrict__ Cpart, int splits, int64_t slab, int d, int64_t ldl,
     const double* __restrict__ colpart, int n_rb, int64_t ldz, const double* __restrict__ fpart, int n_fpart,
     FrSums S, const double* __restrict__ theta, double n_local_w, double n_total, double c0,
-    double* __restrict__ out, int pd, FrWeighted wm) {
+    double* __restrict__ out, int pd, FrWeighted wm, const double* __restrict__ fold_mu,
+    const double* __restrict__ fold_mean) {
   const double ent = pd ? 0.0 : 1.0;      // the entropy's -1 on the free diagonal (absent with the path derivative)
   // weighted mode (AlphaDivergence, objectives.py:458-460): the rows of G carried the weights s_n, the result is
   // scale * [sum s g | tril(sum s g eps') with the free diagonal x L_ii + sum s], the value comes from wm.value
   const bool weighted = wm.scale != 0.0;
   const double wsum = weighted ? wm.wsum[0] : 0.0;
-  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  // folded evaluation (fold_mu != nullptr): block 0 does the scalar tail only -- it walks the column sums once more --
+  // and the blocks behind it take the entries (one block more in the grid)
+  const int64_t tid = ((int64_t)blockIdx.x - (fold_mu ? 1 : 0)) * 256 + threadIdx.x;
   const int64_t idx = 2 * tid;
   const int64_t nC = (int64_t)d * ldl;
   const double invN = 1.0 / n_total;
-  if (idx < nC) {
+  if (tid >= 0 && idx < nC) {
     const int i = (int)(idx / ldl), j = (int)(idx % ldl);
     if (j <= i) {
       fr_d2 s = (fr_d2){0.0, 0.0};
@@ -520,7 +639,7 @@ __global__ void __launch_bounds__(256) fr_reduce_packed_kernel(
       }
     }
   }
-  if (tid < ldz) {
+  if (tid >= 0 && tid < ldz) {
     double s = 0.0;
     if (tid < d) {
       for (int rb0 = 0; rb0 < n_rb; rb0 += 32) {      // 32 loads in flight (16 until round 5), summed in row-block order
@@ -564,12 +683,43 @@ __global__ void __launch_bounds__(256) fr_reduce_packed_kernel(
       for (int u = 0; u < 4; ++u)
         if (c0 + u * 256 + tx < d) t += dg[u];
     }
-    __shared__ double sh3[8];
-    f = fr_wave_sum(f), t = fr_wave_sum(t);
-    if ((tx & 63) == 0) sh3[tx >> 6] = f, sh3[4 + (tx >> 6)] = t;
+    // folded evaluation (fold_mu != nullptr): the partials are sum L o tril(C) per tile and split of the gradient
+    // product, and sum f = 1/2 (their sum + (mu - m) . colsum(G)); the column sums are formed here once more, in the
+    // same row-block order as by the threads that write the gradient
+    double dot = 0.0;
+    if (fold_mu) {
+      for (int c0 = 0; c0 < d; c0 += 4 * 256) {      // four columns per thread and pass, every load requested first
+        double s[4] = {0.0, 0.0, 0.0, 0.0}, cc[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int c = c0 + q * 256 + tx, cl = c < d ? c : d - 1;
+          cc[q] = c < d ? fold_mu[cl] - fold_mean[cl] : 0.0;
+        }
+        for (int rb0 = 0; rb0 < n_rb; rb0 += 8) {
+          double v[4][8];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int c = c0 + q * 256 + tx, cl = c < d ? c : d - 1;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[q][u] = colpart[(int64_t)(rb0 + u < n_rb ? rb0 + u : n_rb - 1) * ldz + cl];
+          }
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+              if (rb0 + u < n_rb) s[q] += v[q][u];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) dot += cc[q] * s[q];
+      }
+    }
+    __shared__ double sh3[12];
+    f = fr_wave_sum(f), t = fr_wave_sum(t), dot = fr_wave_sum(dot);
+    if ((tx & 63) == 0) sh3[tx >> 6] = f, sh3[4 + (tx >> 6)] = t, sh3[8 + (tx >> 6)] = dot;
     __syncthreads();
     if (tx == 0) {
       f = (sh3[0] + sh3[1]) + (sh3[2] + sh3[3]);
+      if (fold_mu) f = 0.5 * (f + ((sh3[8] + sh3[9]) + (sh3[10] + sh3[11])));
       const double sum_logdiag = (sh3[4] + sh3[5]) + (sh3[6] + sh3[7]);
       if (FUSE) {
         const double F = f + n_local_w * c0;
@@ -1355,6 +1505,11 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
                 o_fpart = carve((int64_t)n_fpart + (int64_t)n_rb * cs_gx + gemm_max_blocks(n, D) + (n * ldz) / 512 + 1),
                 o_r = carve(glm ? n * ldr : 0);
   // path derivative: (L')^-1 (Xa), a product buffer T (then L^-1), partial sums of squares of the noise
+  // folded evaluation of the correlated-Gaussian target (below): the split slabs of M = L' P, M itself, b = P (mu - m)
+  const bool fold_shape = !mvt && m.id == VB_MODEL_GAUSS_FULL && !pd && d >= VB_FR_FOLD_MIN_D &&
+                          n >= (int64_t)VB_FR_FOLD_MIN_ROWS_PER_D * d;
+  const int msplits = fr_fold_splits(D);
+  const int64_t o_mpart = fold_shape ? carve((int64_t)(msplits + 1) * slab) : 0, o_bvec = fold_shape ? carve(ldz) : 0;
   const int64_t o_xa = pd ? carve(slab) : 0, o_t = pd ? carve(slab) : 0, o_m2 = pd ? carve(256) : 0;
   // sum vector: the t family takes the full D x ldl matrix; the Gaussian family packs the lower triangle in
   // theta's own order, twice over when the all-reduce of one evaluation overlaps the kernels of the next
@@ -1453,7 +1608,6 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
   g1.N = D;
   g1.K = D;
   g1.tri_mode = mvt ? 0 : 1;
-  prof_events(ctx, &g1.ev0, &g1.ev1, 1, VB_PROF_FR_SAMPLE_GEMM);
   int fmode = 0;
   // correlated-Gaussian target under the dense Gaussian family: no pass over G and Z between the GEMMs -- sum f comes
   // out of the model GEMM's epilogue (EpiNegateF) and the column sums of G out of the gradient GEMM (EpiSplitSlabCs)
@@ -1474,7 +1628,18 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
     while (kparts > 1 && (D % (kGemmBK * kparts) != 0 || D / kparts < 16 * kGemmBK)) --kparts;
     if ((int64_t)kparts * pslab > (int64_t)(splits + 1) * slab) kparts = 1;
   }
+  // The folded evaluation.  G is linear in the noise for this target, G = -(E L' + 1 c') P = -E M - 1 b' with c = mu - m,
+  // M = L' P and b = P c, and the only other use of Z - m, sum f = 1/2 sum (Z - m) o G, follows from what the gradient
+  // product forms anyway:  sum (Z - m) o G = tr((E L' + 1 c')' G) = sum_{i >= j} L_ij C_ij + c . colsum(G),  C = G' E.
+  // So the N x D x D sampling product, the store of Z and its re-read become a D x D x D product (triangular k ranges,
+  // tri_mode 4) that is formed anew in EVERY evaluation -- M follows the parameter, and an optimiser steps it every time.
+  // Not with the path derivative (it changes G between the products), not with the caller's own Z or G, not for short
+  // shards (kparts), and only from the shapes at which it measures faster (the gate's table).  Ranks of one
+  // job may fall on different sides of the gate: both routes hand the same sums to the all-reduce.
+  const bool fold = fold_shape && fused_sums && kparts == 1 && !wm.z_ready && !wm.g_ready;
+  if (!fold) prof_events(ctx, &g1.ev0, &g1.ev1, 1, VB_PROF_FR_SAMPLE_GEMM);      // (folded: no such launch to time)
   // the fused evaluation: 2 = Z and G in one persistent launch, 3 = the gradient product's split slabs as well
+  // (its phase 1 is the product the fold removes: where the fold applies it takes precedence)
   int fz_mode = ctx->fr_fused_mode;
   if (fz_mode < 0) {
     const char* e = getenv("VB_FR_FUSED");
@@ -1483,7 +1648,7 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
   if (!(fused_sums && kparts == 1 && n % 128 == 0 && D % 64 == 0 &&
         (int64_t)n * ldz * 8 < ((int64_t)1 << 31)))
     fz_mode = 0;
-  if ((fz_mode != 2 && fz_mode != 3) || pd) fz_mode = 0;      // (the path derivative changes G between the products)
+  if ((fz_mode != 2 && fz_mode != 3) || pd || fold) fz_mode = 0;      // (the path derivative changes G between the products)
   const unsigned sum_blocks = (unsigned)((pslab / 2 + 255) / 256);
   // Z = E L' + mu - shift into `Z` (the samples, or z - m for the correlated Gaussian target)
   auto sample_gemm = [&](const double* shift) {
@@ -1574,7 +1739,34 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
     g2.N = D;
     g2.K = D;
     g2.tri_mode = 0;
-    if (wm.g_ready) {
+    if (fold) {
+      // (a pipelined upload's chunked sampling launch has nothing to feed here: wait for the whole parameter)
+      VB_TRY(up_wait_all());
+      double *Mpart = base + o_mpart, *bvec = base + o_bvec;
+      double* Mres = msplits > 1 ? Mpart + (int64_t)msplits * slab : Mpart;
+      GemmArgs gm;                                 // M[r][j] = sum_{k >= r} Lt[r][k] P[k][j]
+      gm.A = Lt;
+      gm.lda = ldl;
+      gm.B = m.p1;
+      gm.ldb = m.ldp;
+      gm.M = D;
+      gm.N = D;
+      gm.K = D;
+      gm.tri_mode = 4;
+      gemm_f64_launch<true>(st, gm, msplits, n_cu, EpiSplitSlab{Mpart, ldz, slab}, 4);      // 64 x 64 tiles, two stages
+      const int ks = (int)round_up((D + msplits - 1) / msplits, kGemmBK);                   // (the launcher's k_split)
+      const int nb_sum = msplits > 1 ? D * (int)((ldz / 2 + 255) / 256) : 0, nb_b = (D + 7) / 8;
+      hipLaunchKernelGGL(fr_fold_msum_kernel, dim3((unsigned)(nb_sum + nb_b)), dim3(256), 0, st,
+                         (const double*)Mpart, msplits, slab, D, ldz, ks, 64, Mres, nb_b, m.p1, (int64_t)m.ldp,
+                         (const double*)mu, m.p0, bvec);
+      VB_HIP(ctx, hipGetLastError());
+      g2.A = (const double*)ns.buf.ptr;            // G = -E M - 1 b'
+      g2.lda = ns.ld;
+      g2.B = Mres;
+      g2.ldb = ldz;
+      prof_events(ctx, &g2.ev0, &g2.ev1, 1, VB_PROF_FR_MODEL_GEMM);
+      gemm_f64_launch<true>(st, g2, 1, n_cu, EpiNegateBias{G, ldz, bvec});
+    } else if (wm.g_ready) {
       G = const_cast<double*>(wm.g_ready);      // (the caller's G of these very samples: see FrWeighted)
     } else if (fz_mode >= 2) {
       // one persistent launch for Z - m and G (and, fz_mode 3, the split slabs of C): vb_fullrank_fused.h
@@ -1589,7 +1781,7 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
       sample_gemm(m.p0);                         // Z - m
       VB_HIP(ctx, hipGetLastError());
     }
-    if (fz_mode >= 2 || wm.g_ready) {
+    if (fz_mode >= 2 || wm.g_ready || fold) {
     } else if (kparts > 1 && fused_sums) {
       gemm_f64_launch<true>(st, g2, kparts, n_cu, EpiSplitSlab{Cpart, ldz, pslab});
       hipLaunchKernelGGL(fr_gsum_kernel, dim3(sum_blocks), dim3(256), 0, st, (const double*)Cpart, kparts, pslab, n, D, ldz,
@@ -1674,16 +1866,22 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
       cfg3 = 2;     // the launcher's own choice for this shape (128 x 64 tiles), made here so that the list fits it
       VB_TRY(tri2_tile_map(ctx, D, 128, 64, &g3.tile_map, &g3.tile_blocks));
     }
-    gemm_f64_launch<false>(st, g3, splits, n_cu, EpiSplitSlabCs{Cpart, ldl, slab, colpart, ldz}, cfg3);
+    if (fold) {      // one partial of sum L o tril(C) per tile and split
+      const unsigned tiles3 = gemm_f64_launch<false>(st, g3, splits, n_cu,
+                                                     EpiSplitSlabCsF{Cpart, ldl, slab, colpart, ldz, Lt, ldl, fpart}, cfg3);
+      n_fpart_red = (int)tiles3 * splits;
+    } else {
+      gemm_f64_launch<false>(st, g3, splits, n_cu, EpiSplitSlabCs{Cpart, ldl, slab, colpart, ldz}, cfg3);
+      if (fused_sums || diag_f) n_fpart_red = (int)tiles2;          // one partial of sum f per tile of the model GEMM
+    }
     n_rb_red = splits;                  // one row of column sums per split
-    if (fused_sums || diag_f) n_fpart_red = (int)tiles2;          // one partial of sum f per tile of the model GEMM
   } else {
     gemm_f64_launch<false>(st, g3, splits, n_cu, EpiSplitSlab{Cpart, ldl, slab});
   }
   VB_HIP(ctx, hipGetLastError());
 
   const int64_t red_items = slab / 2 > ldz ? slab / 2 : ldz;
-  const dim3 red_grid((unsigned)((red_items + 255) / 256));
+  const dim3 red_grid((unsigned)((red_items + 255) / 256) + (fold ? 1u : 0u));
   VB_TRY(up_wait_all());      // (the epilogue reads the flat parameter's diagonal)
   if (mvt) {
     fr_reduce_launch(ctx, st, (const double*)Cpart, splits, slab, D, ldl, (const double*)colpart, n_rb, ldz, (const double*)fpart,
@@ -1697,14 +1895,14 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
     hipLaunchKernelGGL(fr_reduce_packed_kernel<true>, red_grid, dim3(256), 0, st, (const double*)Cpart,
                        splits, slab, D, ldl, (const double*)colpart, n_rb_red, ldz,
                        (const double*)fpart, n_fpart_red, S, theta_dev, (double)n_total, (double)n_total, m.c0, out_dev,
-                       pd ? 1 : 0, wm);
+                       pd ? 1 : 0, wm, fold ? (const double*)mu : nullptr, fold ? m.p0 : nullptr);
     VB_HIP(ctx, hipGetLastError());
     return VB_OK;
   }
   hipLaunchKernelGGL(fr_reduce_packed_kernel<false>, red_grid, dim3(256), 0, st, (const double*)Cpart,
                      splits, slab, D, ldl, (const double*)colpart, n_rb_red, ldz,
                      (const double*)fpart, n_fpart_red, S, theta_dev, (double)n_total, (double)n_total, m.c0, out_dev,
-                     pd ? 1 : 0, wm);
+                     pd ? 1 : 0, wm, fold ? (const double*)mu : nullptr, fold ? m.p0 : nullptr);
   VB_HIP(ctx, hipGetLastError());
   hipStream_t st_post = st;
   if (overlap) {

@@ -51,6 +51,12 @@ struct GemmArgs {
   int tri_mode;     // 0: dense; 1: B[k][j] == 0 for k > j (k-range cut per column block);
                     // 2: only output tiles with bm >= bn (lower triangle of a square C);
                     // 3: B[k][j] == 0 for k < j (the mirror image of 1; LDS-DMA kernel, otherwise computed densely)
+                    // 4: A[m][k] == 0 for k < m, A given as A[m][k] (an upper-triangular left factor: M = L' P of the
+                    //    folded full-rank evaluation): the k range of row block bm starts at its first row rounded down
+                    //    to a slab, row block 0 -- the longest range -- is dispatched first.  May be split over k: the
+                    //    launcher then lists on the grid's x axis only the (row block, split) pairs with a k range
+                    //    (tri4_splits; gridDim.z = 1), so slab z of C is NOT written for the row blocks that start at
+                    //    or beyond the end of split z (LDS-DMA kernel, otherwise computed densely)
   int k_split;      // K range per blockIdx.z (multiple of kGemmBK); splits = gridDim.z
   // batch mode (batch != 0): blockIdx.z selects one of gridDim.z independent products of the same shape -- operand
   // z starts batch_a / batch_b doubles after operand z - 1, every product runs over the whole K range and the
@@ -67,6 +73,7 @@ struct GemmArgs {
   // global indices.  (The blocking full-rank call starts the sampling product of the heaviest column blocks while the rest
   // of the parameter is still crossing PCIe: vb_fullrank.hip, FrUpload.)
   int bn_begin = 0, bn_count = 0;
+  int tri4_splits = 0;      // tri_mode 4 with a split k range: the number of splits (set by the launcher)
   // split products, optional (LDS-DMA kernel; the launcher clears it unless gridDim.z % 8 == 0): the workgroups of ONE split
   // -- which read the same k range of both operands -- are dispatched to ONE XCD.  Workgroups go to the XCDs round robin
   // in linear order (x fastest), so the gridDim.x tiles of a split land on all eight L2s and every L2 streams every
@@ -420,6 +427,7 @@ inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu
   // operands straight into LDS (vb_gemm_f64_dma.h) when every k range is a whole number of slabs
   const bool dma = gemm_uses_dma(g) && !(flags & 1);
   if (g.tri_mode == 3 && (!dma || splits != 1 || g.batch)) g.tri_mode = 0;      // the zeros are multiplied instead of skipped
+  if (g.tri_mode == 4 && (!dma || !A_KCONTIG || g.batch)) g.tri_mode = 0;
   if (cfg == 0) {
     if (dma && (g.tri_mode == 1 || g.tri_mode == 3) && splits == 1 && gemm_count_blocks(g, 128, 64) < 4L * n_cu) {
       // k ranges grow with the column block: with only a couple of tiles per CU the long ones finish alone.  The
@@ -460,12 +468,18 @@ inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu
   g.tiles_n = gemm_tiles(g.N, bn_cols);
   if (g.bn_count && (g.tri_mode != 1 || g.bn_begin + g.bn_count > g.tiles_n)) g.bn_begin = g.bn_count = 0;
   if (splits % 8 != 0 || g.batch) g.xcd_group = 0;
-  const dim3 grid(g.tile_map ? (unsigned)g.tile_blocks
+  dim3 grid(g.tile_map ? (unsigned)g.tile_blocks
                              : g.bn_count ? (unsigned)(g.tiles_m * g.bn_count) : (unsigned)gemm_count_blocks(g, bm_rows, bn_cols), 1,
                   (unsigned)splits);
+  if (g.tri_mode == 4 && splits > 1) {      // only the (row block, split) pairs that have a k range, heaviest row block first
+    g.tri4_splits = splits;
+    long items = 0;
+    for (int bm = 0; bm < g.tiles_m; ++bm) items += (long)(splits - (bm * bm_rows / kGemmBK * kGemmBK) / g.k_split) * g.tiles_n;
+    grid = dim3((unsigned)items, 1, 1);
+  }
   // (triangular k ranges: the tiles of a CU differ in length anyway, and the alternation costs 1 - 3 us there --
   // 4096 x 768 x 768: 55.5 -> 52.7 us, 512: 30.1 -> 29.1 us, 1024: unchanged, tools/gemm_bench.hip with it switched off)
-  g.prio_div = (g.tri_mode != 1 && g.tri_mode != 3) ? n_cu : 0;
+  g.prio_div = (g.tri_mode != 1 && g.tri_mode != 3 && g.tri_mode != 4) ? n_cu : 0;
   if (dma) {
     if (cfg == 1) gemm_f64_dma_launch<A_KCONTIG, 4, 16, 3, Epi>(st, g, grid, epi);
     else if (cfg == 2) gemm_f64_dma_launch<A_KCONTIG, 4, 8, 3, Epi>(st, g, grid, epi);

@@ -42,7 +42,8 @@ struct GemmNoDep {
 // One output tile of the product: block x of a launch with gx blocks per split, split (or batch index) bz.
 template <bool A_KCONTIG, int AF, int NB, int STAGES, class Epi, class Dep>
 __device__ __forceinline__ void gemm_f64_dma_tile(const GemmArgs& g, const Epi& epi, const Dep& dep, const int bx,
-                                                  const int bz, const int gx) {
+                                                  const int bz_in, const int gx) {
+  int bz = bz_in;
   constexpr int BM = 32 * AF, BN = 8 * NB;
   constexpr int kStages = STAGES;
   static_assert(STAGES == 2 || STAGES == 3, "two or three LDS stages");
@@ -93,6 +94,24 @@ __device__ __forceinline__ void gemm_f64_dma_tile(const GemmArgs& g, const Epi& 
 #ifdef VB_GEMM_CLOCK
     if (bn < g.dbg_bn_min || bn > g.dbg_bn_max) return;
 #endif
+  } else if (g.tri_mode == 4 && g.tri4_splits > 1) {
+    // split triangular left factor: the grid's x axis lists only the (row block, split) pairs whose k range is not
+    // empty (GemmArgs::tri4_splits) -- equal pieces of work, so the workgroups a CU ends up with add up evenly
+    int idx = bx;
+    bm = 0;
+    int z0 = 0;
+    for (;;) {
+      z0 = (bm * BM / kGemmBK * kGemmBK) / g.k_split;
+      const int cnt = (g.tri4_splits - z0) * g.tiles_n;
+      if (idx < cnt || bm == g.tiles_m - 1) break;
+      idx -= cnt;
+      ++bm;
+    }
+    bz = z0 + idx / g.tiles_n;
+    bn = idx % g.tiles_n;
+  } else if (g.tri_mode == 4) {      // row block 0 has the longest k range: row blocks in ascending order
+    bm = bx / g.tiles_n;
+    bn = bx % g.tiles_n;
   } else {
     bn = bx / g.tiles_m;
     bm = bx % g.tiles_m;
@@ -102,6 +121,10 @@ __device__ __forceinline__ void gemm_f64_dma_tile(const GemmArgs& g, const Epi& 
   int k_end = (g.batch || k_begin + g.k_split >= g.K) ? g.K : k_begin + g.k_split;
   if (g.tri_mode == 3) {         // B[k][j] == 0 for k < j: the k range of column block bn starts at its first column
     const int kmin = n0 / kGemmBK * kGemmBK;
+    if (k_begin < kmin) k_begin = kmin < k_end ? kmin : k_end;
+  }
+  if (g.tri_mode == 4) {         // A[m][k] == 0 for k < m: the k range of row block bm starts at its first row
+    const int kmin = m0 / kGemmBK * kGemmBK;
     if (k_begin < kmin) k_begin = kmin < k_end ? kmin : k_end;
   }
   const double* __restrict__ gA = g.A + (g.batch ? (int64_t)bz * g.batch_a : 0);
