@@ -483,11 +483,7 @@ int vb_elbo_sums_mvt(vb_ctx* ctx, int slot, int64_t n, int64_t d, int64_t n_tota
  * the device).  Targets: gauss_diag, funnel, gauss_full and the regression models.  fp64 MFMA GEMMs.
  * vb_elbo_grad_fullrank = set_theta + enqueue + get; the three-step form keeps theta and the
  * result resident on the device (P = D + D(D+1)/2 doubles is 4.2 MB at D = 1024).  Hand the blocking call a
- * gradient array from vb_host_alloc and the download is a direct DMA.  VB_FR_UPLOAD_PIPE=1 (round 6: bit-identical,
- * measured slower, off): the flat parameter crosses PCIe in three row chunks of L, last rows first, and the sampling
- * product of a chunk's column blocks starts behind its copy.          */
-/* how many vb_elbo_grad_fullrank calls of this context took the pipelined upload (observability: tests) */
-int vb_fullrank_upload_stats(vb_ctx* ctx, uint64_t* pipelined_calls);
+ * gradient array from vb_host_alloc and the download is a direct DMA.          */
 int vb_elbo_grad_fullrank(vb_ctx* ctx, int slot, int64_t n, int64_t d, int64_t n_total,
                           const double* theta, unsigned flags, double* value, double* grad);
 int vb_fullrank_set_theta(vb_ctx* ctx, const double* theta, int64_t d);

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # switches that tests set to compare two routes
 TESTED = {
     'VB_DIS_BISECT', 'VB_DIS_RESIDENT', 'VB_DIS_ROUNDS', 'VB_FETCH_FLAGSYNC', 'VB_FIT_STREAM_MIN_BYTES',
-    'VB_FIT_STREAM_ROWS', 'VB_FR_FUSED', 'VB_FR_UPLOAD_PIPE', 'VB_GRAM_XCD', 'VB_LEGACY_AHEAD', 'VB_LEGACY_BUDGET_SCALE',
+    'VB_FIT_STREAM_ROWS', 'VB_FR_FUSED', 'VB_GRAM_XCD', 'VB_LEGACY_AHEAD', 'VB_LEGACY_BUDGET_SCALE',
     'VB_MF_ONE', 'VB_MVT_CHAIN', 'VB_MVT_CHAIN_FETCH', 'VB_MVT_DIRECT', 'VB_MVT_EPI_ROWS', 'VB_MVT_FLAGSYNC',
     'VB_MVT_FUSED_ROWS', 'VB_MVT_SIDE_INVERSE', 'VB_MVT_UNPACK', 'VB_NOISE_AHEAD', 'VB_NS_HINT', 'VB_PSIS_FUSED_IO',
     'VB_PSIS_GRID',
@@ -48,8 +48,8 @@ def read_names():
     return names
 
 
-def test_kept_set_is_38_distinct_names():
-    assert len(TESTED) + len(CONFIG) + len(DIAGNOSTICS) == len(KEPT) == 38
+def test_kept_set_is_37_distinct_names():
+    assert len(TESTED) + len(CONFIG) + len(DIAGNOSTICS) == len(KEPT) == 37
 
 
 def test_library_reads_exactly_the_kept_switches():

@@ -106,30 +106,14 @@ def test_psis_and_dis_and_t_family(env):
     _same(*_both(mvt))
 
 
-# ---- round 6: the blocking full-rank call with its parameter upload pipelined against the sampling product -----------
-def _pipe_both(call):
-    old = os.environ.get('VB_FR_UPLOAD_PIPE')
-    try:
-        os.environ['VB_FR_UPLOAD_PIPE'] = '0'
-        plain = call()
-        os.environ['VB_FR_UPLOAD_PIPE'] = '1'
-        piped = call()
-    finally:
-        if old is None:
-            os.environ.pop('VB_FR_UPLOAD_PIPE', None)
-        else:
-            os.environ['VB_FR_UPLOAD_PIPE'] = old
-    return plain, piped
-
-
+# ---- the blocking full-rank call above 1 MB of parameter (plain copies instead of the mapped staging) ------------------
 @pytest.mark.parametrize('d,n', [(1024, 4096), (512, 4096), (1008, 1000), (576, 257), (2048, 512)])
 @pytest.mark.parametrize('target', ['gauss_full', 'funnel', 'gauss_diag'])
-def test_fullrank_pipelined_upload_is_the_same_evaluation(env, d, n, target):
-    """vb_elbo_grad_fullrank above 1 MB of parameter with VB_FR_UPLOAD_PIPE=1 (built in round 6, measured slower, off by
-    default): three row chunks of L, heaviest first, the sampling product of each chunk's column blocks behind its copy.  Every element of Z is the same k loop
-    in the same order whichever launch computes it, so value and gradient are bit-identical -- back to back with changing
-    parameters, targets whose first product has a reducing epilogue (gauss_diag: not chunked, but behind the upload) and
-    shards too short for the plain product (k-split) included."""
+def test_fullrank_blocking_large_parameter_is_the_resident_evaluation(env, d, n, target):
+    """vb_elbo_grad_fullrank above 1 MB of parameter against the resident route (vb_fullrank_set_theta + enqueue + get) on
+    the same noise: the same evaluation, so value and gradient are bit-identical -- back to back with changing
+    parameters, targets whose first product has a reducing epilogue (gauss_diag) and shards too short for the plain
+    product (k-split) included."""
     vb, eng, _lib = env
     rng = np.random.RandomState(d + n)
     if target == 'gauss_full':
@@ -142,22 +126,29 @@ def test_fullrank_pipelined_upload_is_the_same_evaluation(env, d, n, target):
     fam = vb.FullRankGaussian(d)
     thetas = [fam.pack(0.1 * rng.randn(d), np.exp(-1.0) * np.eye(d) + 0.01 * np.tril(rng.randn(d, d))) for _ in range(3)]
 
-    def call():
+    def blocking():
         eng.set_model(model.device_spec())
         out = []
         for k, theta in enumerate(thetas):
             eng.noise_generate(5, n, d, seed=3, stream=k)
             out.append(eng.elbo_grad_fullrank(5, n, d, theta))
         return out
-    before = eng.fullrank_upload_stats()
-    plain, piped = _pipe_both(call)
-    assert eng.fullrank_upload_stats() == before + len(thetas)      # the second pass really took the pipelined route
-    _same(plain, piped)
+
+    def resident():
+        eng.set_model(model.device_spec())
+        out = []
+        for k, theta in enumerate(thetas):
+            eng.noise_generate(5, n, d, seed=3, stream=k)
+            eng.fullrank_set_theta(theta, d)
+            eng.elbo_grad_fullrank_enqueue(5, n, d)
+            out.append(eng.fullrank_get(d))
+        return out
+    _same(blocking(), resident())
 
 
-def test_fullrank_pipelined_upload_after_asynchronous_evaluations(env):
-    """The upload must stay behind evaluations still reading the PREVIOUS parameter (vb_elbo_grad_fullrank_enqueue leaves work
-    in flight) and in front of everything that reads the new one."""
+def test_fullrank_new_parameter_stays_behind_asynchronous_evaluations(env):
+    """A new parameter (the blocking call's, or vb_fullrank_set_theta's) must stay behind evaluations still reading the
+    PREVIOUS one (vb_elbo_grad_fullrank_enqueue leaves work in flight) and in front of everything that reads the new one."""
     vb, eng, _lib = env
     d, n = 1024, 4096
     rng = np.random.RandomState(9)

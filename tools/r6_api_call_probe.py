@@ -1,4 +1,4 @@
-"""Round 6: the blocking full-rank call, pipelined upload on / off, pinned gradient array on / off."""
+"""The blocking full-rank call: pageable / pinned parameter, pinned gradient array on / off."""
 import os
 import sys
 import time
@@ -37,9 +37,6 @@ theta_pinned = real_pinned(theta.size)
 theta_pinned[:] = theta
 for src in ('pageable', 'pinned'):
     theta = theta_pinned if src == 'pinned' else theta_pageable
-    for pipe in ('0', '1'):
-        for pinned in (False, True):
-            os.environ['VB_FR_UPLOAD_PIPE'] = pipe
-            _lib.pinned_array = real_pinned if pinned else (lambda k: np.empty(k, dtype=np.float64))
-            print('theta %-8s pipe %s pinned grad %-5s: %.1f us per blocking call'
-                  % (src, pipe, pinned, run()), flush=True)
+    for pinned in (False, True):
+        _lib.pinned_array = real_pinned if pinned else (lambda k: np.empty(k, dtype=np.float64))
+        print('theta %-8s pinned grad %-5s: %.1f us per blocking call' % (src, pinned, run()), flush=True)

@@ -224,7 +224,6 @@ SIGNATURES = {
     'vb_dis_state_park': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     'vb_dis_state_unpark': (ctypes.c_int, [_ctx_p, ctypes.c_void_p]),
     'vb_dis_state_drop': (ctypes.c_int, [ctypes.c_void_p]),
-    'vb_fullrank_upload_stats': (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_uint64)]),
     'vb_host_alloc': (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]),
     'vb_host_free': (ctypes.c_int, [ctypes.c_void_p]),
     'vb_comm_allreduce_time': (ctypes.c_int, [_ctx_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
@@ -1035,12 +1034,6 @@ class Engine:
             self._ctx, slot, n, d, n if n_total is None else n_total, _dptr(theta), flags,
             ctypes.byref(value), _dptr(grad)))
         return value.value, grad
-
-    def fullrank_upload_stats(self):
-        """How many blocking full-rank calls took the pipelined parameter upload (``vb_fullrank_upload_stats``)."""
-        n = ctypes.c_uint64(0)
-        self._check(self._lib.vb_fullrank_upload_stats(self._ctx, ctypes.byref(n)))
-        return n.value
 
     def fullrank_set_theta(self, theta, d):
         theta = _f64(theta)

@@ -260,13 +260,7 @@ int sync_streams(vb_ctx* ctx) {
   if (ctx->pipe.post) VB_HIP(ctx, hipStreamSynchronize(ctx->pipe.post));
   if (ctx->mvt_side) VB_HIP(ctx, hipStreamSynchronize(ctx->mvt_side));
   if (ctx->fit_copy_st) VB_HIP(ctx, hipStreamSynchronize(ctx->fit_copy_st));
-  if (ctx->up_stream) {
-    VB_HIP(ctx, hipStreamSynchronize(ctx->up_stream));
-    VB_HIP(ctx, hipStreamSynchronize(ctx->up_side[0]));
-    VB_HIP(ctx, hipStreamSynchronize(ctx->up_side[1]));
-  }
   if (ctx->legacy_spec && ctx->legacy_spec->stream) VB_HIP(ctx, hipStreamSynchronize(ctx->legacy_spec->stream));
-  ctx->fr_busy = false;
   ctx->pipe.post_pending = false;
   return comm_check(ctx);
 }
@@ -576,18 +570,6 @@ int vb_destroy(vb_ctx* ctx) {
     if (S->clone) vb_legacy_rng_destroy(S->clone);
     delete S;
     ctx->legacy_spec = nullptr;
-  }
-  if (ctx->up_stream) {
-    (void)hipStreamSynchronize(ctx->up_stream);
-    (void)hipStreamDestroy(ctx->up_stream);
-    for (int i = 0; i < 2; ++i) {
-      (void)hipStreamSynchronize(ctx->up_side[i]);
-      (void)hipStreamDestroy(ctx->up_side[i]);
-      (void)hipEventDestroy(ctx->up_ev_join[i]);
-    }
-    (void)hipEventDestroy(ctx->up_ev_main);
-    for (hipEvent_t e : ctx->fr_up.ev)
-      if (e) (void)hipEventDestroy(e);
   }
   if (ctx->fit_copy_st) {
     (void)hipStreamSynchronize(ctx->fit_copy_st);
@@ -1800,12 +1782,6 @@ int vb_elbo_grad_mvt_symroot_path(vb_ctx* ctx, int slot, int64_t n, int64_t d, i
   return elbo_grad_mvt_symroot(ctx, slot, n, d, n_total, df, theta, value, grad, info, true);
 }
 
-int vb_fullrank_upload_stats(vb_ctx* ctx, uint64_t* pipelined_calls) {
-  if (!ctx || !pipelined_calls) return fail(ctx, VB_ERR_INVALID, "NULL argument");
-  *pipelined_calls = ctx->fr_up_calls;
-  return VB_OK;
-}
-
 // Page-locked host memory for result arrays (round 6): a 4.2-MB gradient copied into pageable memory is staged by the runtime
 // (118 us at D = 1024: 36 GB/s); into a pinned block the DMA engine writes it directly.  The Python binding hands such
 // blocks out as the numpy arrays it returns and takes them back when the arrays die (viabel_amd/_lib.py: PinnedPool).
@@ -2061,7 +2037,6 @@ int vb_elbo_grad_fullrank_enqueue(vb_ctx* ctx, int slot, int64_t n, int64_t d, i
                 (long long)d);
   if (n_total < n) return fail(ctx, VB_ERR_INVALID, "n_total must be >= n");
   VB_HIP(ctx, hipSetDevice(ctx->device));
-  ctx->fr_busy = true;      // (asynchronous: the next parameter upload must stay behind this evaluation's reads)
   return fr_elbo_grad_enqueue(ctx, ctx->noise[slot], n, d, n_total, (const double*)ctx->fr_theta.ptr,
                               (double*)ctx->fr_out.ptr, flags);
 }
@@ -2086,42 +2061,8 @@ int vb_fullrank_get(vb_ctx* ctx, double* value, double* grad, int64_t p) {
 
 int vb_elbo_grad_fullrank(vb_ctx* ctx, int slot, int64_t n, int64_t d, int64_t n_total,
                           const double* theta, unsigned flags, double* value, double* grad) {
-  if (!ctx || !theta || d <= 0) return fail(ctx, VB_ERR_INVALID, "bad argument");
-  const int64_t p = d + d * (d + 1) / 2;
-  // Round 6, built and MEASURED SLOWER -- off unless VB_FR_UPLOAD_PIPE=1: a parameter too large for the
-  // staged small-copy path (4.2 MB at D = 1024) crosses PCIe in row chunks, heaviest rows of L first, and the sampling
-  // product of a chunk's column blocks starts behind its copy while the rest is in flight (fr_upload_begin); the noise
-  // generated for this call (already queued on the main stream) runs beside the first chunk.  Results are bit-identical
-  // (tests/test_gpu_fetch_routes.py).  tools/r6_api_call_probe.py, D = 1024 / N = 4096, blocking call with a pinned
-  // gradient array: one copy + synchronisation in front 539 us; this route with 1 / 2 / 3 / 4 chunks 561 / 612 / 636 /
-  // 708 us from a pageable parameter and 556 / 572 / 586 / 605 us from a pinned one.  Every hipMemcpyAsync costs 15-35 us
-  // whatever its size (a pageable source is pinned and unpinned per call), every cross-stream event wait ~10 us: the ~70 us
-  // of overlap the chunks buy are spent twice over.  What did pay: the gradient lands in page-locked memory (vb_host_alloc,
-  // PinnedPool in the Python binding): 549 -> 539 us.
-  const char* pe = getenv("VB_FR_UPLOAD_PIPE");      // (read per call: the tests switch it)
-  const bool pipe_env = pe && atoi(pe) != 0;
-  const bool pipelined = pipe_env && !ctx->comm && (size_t)p * sizeof(double) > kFetchMaxBytes && d % 16 == 0 &&
-                         !(flags & VB_FLAG_PATH_DERIV);
-  if (pipelined) {
-    VB_HIP(ctx, hipSetDevice(ctx->device));
-    VB_TRY(ensure(ctx, ctx->fr_theta, (size_t)p * sizeof(double)));
-    VB_TRY(ensure(ctx, ctx->fr_out, (size_t)(1 + p) * sizeof(double)));
-    VB_TRY(main_stream_write(ctx));
-    ctx->fr_p = p;
-    VB_TRY(fr_upload_begin(ctx, theta, d));
-    ++ctx->fr_up_calls;
-    const int rc = vb_elbo_grad_fullrank_enqueue(ctx, slot, n, d, n_total, flags);
-    ctx->fr_busy = false;
-    if (rc != VB_OK) {
-      ctx->fr_up_active = false;
-      (void)hipStreamSynchronize(ctx->up_stream);      // the caller's array must not be read after we return
-      return rc;
-    }
-    return vb_fullrank_get(ctx, value, grad, p);
-  }
   VB_TRY(vb_fullrank_set_theta(ctx, theta, d));
   VB_TRY(vb_elbo_grad_fullrank_enqueue(ctx, slot, n, d, n_total, flags));
-  ctx->fr_busy = false;
   return vb_fullrank_get(ctx, value, grad, d + d * (d + 1) / 2);
 }
 

@@ -314,22 +314,6 @@ struct vb_ctx {
   vb::DeviceBuffer fr_theta;            // full-rank: resident flat parameter
   vb::DeviceBuffer fr_out;              // full-rank: [value | grad] on the device
   int64_t fr_p = 0;                     // length of the resident full-rank parameter
-  // the blocking call's pipelined parameter upload (vb_elbo_grad_fullrank, round 6): the flat parameter crosses PCIe in
-  // row chunks of L, HEAVIEST rows first, on `up_stream`; behind each chunk its columns of L' are unpacked and an event is
-  // recorded; the sampling product of a chunk's column blocks starts behind its event (column block b of Z = E L' + mu needs
-  // rows [64 b, 64 b + 64) of L only) while the lighter rows are still in flight.
-  struct FrUpload {
-    int n_chunks = 0;
-    int bn_begin[4] = {0, 0, 0, 0}, bn_count[4] = {0, 0, 0, 0};      // column blocks of 64 per chunk, chunk 0 = the last rows
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};           // behind chunk c's copy + unpack
-    bool consumed = false;               // the pipeline started the sampling product chunk by chunk (else it waits for ev[last])
-  } fr_up;
-  bool fr_up_active = false;            // fr_up describes THIS evaluation's parameter
-  bool fr_busy = false;                 // an asynchronous evaluation (vb_elbo_grad_fullrank_enqueue) may still read fr_theta / fr_lt
-  hipStream_t up_stream = nullptr;      // copies + unpacks of the chunks
-  hipStream_t up_side[2] = {nullptr, nullptr};   // sampling products of chunks 1, 2 (chunk 0's runs on the main stream)
-  hipEvent_t up_ev_main = nullptr, up_ev_join[2] = {nullptr, nullptr};
-  uint64_t fr_up_calls = 0;             // evaluations that took the pipelined route (observability: tests)
   // numpy's legacy normal stream on the device (vb_legacy_dev.hip): scratch; where the jump polynomials were uploaded
   vb::DeviceBuffer alpha_g;             // AlphaDivergence, correlated-Gaussian target: G of the samples (see FrWeighted::g_ready)
   vb::DeviceBuffer legacy_work;
@@ -694,7 +678,6 @@ struct FitStep;
 // optimiser step of the dense family fused with the unpack of the stepped parameter (vb_fit): theta <- step(theta, grad)
 // and mu, L' of the NEW theta into fr_lt in one kernel; the next evaluation of `theta_dev` skips its unpack
 int fr_step_unpack_enqueue(vb_ctx* ctx, const FitStep& a, int64_t d);
-int fr_upload_begin(vb_ctx* ctx, const double* theta_host, int64_t d);
 int fr_unpack_enqueue(vb_ctx* ctx, hipStream_t st, const double* theta_dev, int D, int64_t ldl, double* Lt, double* mu,
                       double* theta_copy = nullptr);
 int fr_tri_inverse_enqueue(vb_ctx* ctx, hipStream_t st, const double* theta_dev, const double* Lt, int D, int64_t ldl,

@@ -14,7 +14,7 @@
 //   model              gauss_diag: G in the GEMM-1 epilogue; funnel: row kernel Z -> G;
 //                      gauss_full: GEMM 2 (MFMA)  G = -(Z - m) P
 //                      (from D = 1024 and 3 D samples on, folded: M = L' P, G = -E M - 1 (P (mu - m))', no GEMM 1 --
-//                      see fr_pipeline_enqueue)
+//                      see fr_route)
 //   fr_colsum          column sums of G (-> d/dmu) and sum_n f(z_n), per 128-row block
 //   GEMM 3 (MFMA)      C = G^T E           [D x D x N, lower-triangular tiles, split-K]
 //   fr_reduce          fixed-order sum of the split-K slabs / row-block partials -> sum vector
@@ -187,7 +187,7 @@ struct EpiNegate {          // G = -acc   (gauss_full: G = -(Z - m) P)
   }
 };
 
-// G = -acc - b   (gauss_full, folded evaluation: acc = E M with M = L' P, b = P (mu - m); see fr_pipeline_enqueue)
+// G = -acc - b   (gauss_full, folded evaluation: acc = E M with M = L' P, b = P (mu - m); see fr_route)
 struct EpiNegateBias {
   double* G;
   int64_t ldz;
@@ -784,7 +784,7 @@ __global__ void __launch_bounds__(256) fr_rowscale_kernel(double* __restrict__ G
 
 // ---- path derivative ("sticking the landing", objectives.py:156-159) for the dense Gaussian ----------------
 // value = -mean(f(z) - log q(z; stop(theta))): the score -dlog q/dz = L^-T eps is added to the model gradient row by
-// row, G~ = G + E L^-1 (one N x D x D / 2 product, fr_pipeline_enqueue), and the sums of G~ are the entropy form's sums
+// row, G~ = G + E L^-1 (one N x D x D / 2 product, fr_score), and the sums of G~ are the entropy form's sums
 // without the entropy term; value: 1/2 sum ||eps_n||^2 / N replaces D / 2.  L^-1 = ((L')^-1)' is formed explicitly
 // (blocked recursive inversion, see fr_triinv_leaf_kernel and the host loop, then a transposition).  Rounds 2-3 went
 // through the noise Gram matrix (C' = C + L^-T sum eps eps'): the same N x D^2 flops for the Gram product plus a
@@ -934,107 +934,6 @@ int fr_unpack_enqueue(vb_ctx* ctx, hipStream_t st, const double* theta_dev, int 
   return VB_OK;
 }
 
-// ---- the blocking call's pipelined parameter upload (FrUpload, vb_common.h) -------------------------------------------
-// L' columns [32 jt0, 32 (jt0 + gridDim.y)) from the flat parameter: fr_unpack_kernel's tiles with the column tile index
-// offset by jt0; mu is written by the launch that has with_mu set.
-__global__ void __launch_bounds__(256) fr_unpack_cols_kernel(const double* __restrict__ theta, int d, int64_t ldl,
-                                                             double* __restrict__ Lt, double* __restrict__ mu, int jt0,
-                                                             int with_mu) {
-  __shared__ double tile[32][33];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int k0 = blockIdx.x * 32, j0 = (jt0 + (int)blockIdx.y) * 32;
-  if (with_mu && blockIdx.y == 0) {
-    const int i = k0 + (int)threadIdx.x;
-    if (threadIdx.x < 32 && i < d) mu[i] = theta[i];
-  }
-  if (k0 > j0 + 31) {            // below the diagonal of L' (k > j): zeros
-#pragma unroll
-    for (int r = ty; r < 32; r += 8) {
-      const int k = k0 + r, j = j0 + tx;
-      if (k < d && j < d) Lt[(int64_t)k * ldl + j] = 0.0;
-    }
-    return;
-  }
-#pragma unroll
-  for (int r = ty; r < 32; r += 8) {       // read L[j0 + r][k0 + tx]
-    const int j = j0 + r, k = k0 + tx;
-    double v = 0.0;
-    if (j < d && k <= j) {
-      v = theta[d + (int64_t)j * (j + 1) / 2 + k];
-      if (k == j) v = exp(v);
-    }
-    tile[r][tx] = v;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = ty; r < 32; r += 8) {
-    const int k = k0 + r, j = j0 + tx;
-    if (k < d && j < d) Lt[(int64_t)k * ldl + j] = tile[tx][r];
-  }
-}
-
-// Start the upload of `theta_host` (caller's pageable array) into ctx->fr_theta and its unpacked copy (ctx->fr_lt): mu and
-// the LAST rows of L first.  The sampling product Z = E L' + mu cuts its k range per column block (tri_mode 1), so column
-// block b needs rows [64 b, 64 b + 64) of L -- contiguous in the flat parameter -- and the heaviest blocks need the last
-// rows: they go first, their product starts behind the first chunk's event, and the light blocks' rows arrive while the
-// heavy tiles run.  Three chunks of about equal bytes (boundaries at multiples of 64 rows).  Everything else that reads the
-// parameter is ordered behind the last chunk's event by fr_pipeline_enqueue.
-int fr_upload_begin(vb_ctx* ctx, const double* theta_host, int64_t d) {
-  vb_ctx::FrUpload& U = ctx->fr_up;
-  const int D = (int)d;
-  const int64_t ldl = round_up(d, 16);
-  const int tn = gemm_tiles(D, 64);
-  if (!ctx->up_stream) {
-    VB_HIP(ctx, hipStreamCreateWithFlags(&ctx->up_stream, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) {
-      VB_HIP(ctx, hipStreamCreateWithFlags(&ctx->up_side[i], hipStreamNonBlocking));
-      VB_HIP(ctx, hipEventCreateWithFlags(&ctx->up_ev_join[i], hipEventDisableTiming));
-    }
-    VB_HIP(ctx, hipEventCreateWithFlags(&ctx->up_ev_main, hipEventDisableTiming));
-    for (int c = 0; c < 4; ++c) VB_HIP(ctx, hipEventCreateWithFlags(&U.ev[c], hipEventDisableTiming));
-  }
-  VB_TRY(ensure(ctx, ctx->fr_lt, (size_t)(ldl + d * ldl) * sizeof(double)));
-  double* mu = (double*)ctx->fr_lt.ptr;
-  double* Lt = mu + ldl;
-  double* dev = (double*)ctx->fr_theta.ptr;
-  // chunk boundaries in column blocks of 64: equal areas of the triangle, from the bottom (three chunks)
-  const int nc = tn < 3 ? tn : 3;
-  int edge[5];
-  edge[0] = tn;
-  for (int c = 1; c < nc; ++c) {
-    int e = (int)(tn * sqrt((double)(nc - c) / nc) + 0.5);
-    if (e >= edge[c - 1]) e = edge[c - 1] - 1;
-    if (e < nc - c) e = nc - c;
-    edge[c] = e;
-  }
-  edge[nc] = 0;
-  U.n_chunks = nc;
-  U.consumed = false;
-  hipStream_t us = ctx->up_stream;
-  // what is in flight on the main stream may still read the previous parameter
-  VB_HIP(ctx, hipEventRecord(ctx->up_ev_main, ctx->stream));
-  if (ctx->fr_busy) VB_HIP(ctx, hipStreamWaitEvent(us, ctx->up_ev_main, 0));
-  ctx->fr_busy = false;
-  VB_HIP(ctx, hipMemcpyAsync(dev, theta_host, (size_t)d * sizeof(double), hipMemcpyHostToDevice, us));      // mu
-  for (int c = 0; c < nc; ++c) {
-    const int b0 = edge[c + 1], b1 = edge[c];
-    const int64_t r0 = (int64_t)b0 * 64, r1 = (int64_t)b1 * 64 < d ? (int64_t)b1 * 64 : d;
-    const int64_t o0 = d + r0 * (r0 + 1) / 2, o1 = d + r1 * (r1 + 1) / 2;
-    U.bn_begin[c] = b0;
-    U.bn_count[c] = b1 - b0;
-    VB_HIP(ctx, hipMemcpyAsync(dev + o0, theta_host + o0, (size_t)(o1 - o0) * sizeof(double), hipMemcpyHostToDevice, us));
-    const int jt0 = (int)(r0 / 32), jt1 = (int)((r1 + 31) / 32);
-    hipLaunchKernelGGL(fr_unpack_cols_kernel, dim3((unsigned)((D + 31) / 32), (unsigned)(jt1 - jt0)), dim3(256), 0, us,
-                       (const double*)dev, D, ldl, Lt, mu, jt0, c == 0 ? 1 : 0);
-    VB_HIP(ctx, hipGetLastError());
-    VB_HIP(ctx, hipEventRecord(U.ev[c], us));
-  }
-  ctx->fr_up_active = true;
-  ctx->fr_lt_d = d;                 // the unpacked copy is (being made) current: the pipeline must not unpack again
-  ctx->fr_lt_owner = nullptr;
-  return VB_OK;
-}
-
 // ---- optimiser step + unpack in one kernel (vb_fit, dense family) --------------------------------------------------------
 // The loop used to run fit_step_kernel (5.9 us at D = 1024) and, at the top of the next evaluation, fr_unpack_kernel
 // (6.6 us) on the parameter it had just written.  Same tiling as the unpack: a 32 x 32 tile of the packed triangle is
@@ -1167,15 +1066,7 @@ int fr_reduce_enqueue(vb_ctx* ctx, const double* Cpart, int splits, int64_t slab
 
 int gram_lower_enqueue(vb_ctx* ctx, const double* A, const double* B, int64_t ld, int d, int64_t n, int splits,
                        double* Cpart, int64_t ldc, int64_t slab) {
-  GemmArgs g3;
-  g3.A = A;
-  g3.lda = ld;
-  g3.B = B;
-  g3.ldb = ld;
-  g3.M = d;
-  g3.N = d;
-  g3.K = (int)n;
-  g3.tri_mode = 2;
+  GemmArgs g3 = gemm_product(A, ld, B, ld, d, d, (int)n, 2);
   const char* xcd_env = getenv("VB_GRAM_XCD");
   g3.xcd_group = xcd_env ? atoi(xcd_env) : 1;
   gemm_f64_launch<false>(ctx->stream, g3, splits, ctx->prop.multiProcessorCount, EpiSplitSlab{Cpart, ldc, slab});
@@ -1190,15 +1081,7 @@ int gram_lower_enqueue(vb_ctx* ctx, const double* A, const double* B, int64_t ld
 int gram_lower_colsum_enqueue(vb_ctx* ctx, const double* A, const double* B, int64_t ld, int d, int64_t n, int splits,
                               double* Cpart, int64_t ldc, int64_t slab, double* colsum, int64_t colsum_ld,
                               int colsum_rows, bool* fused) {
-  GemmArgs g3;
-  g3.A = A;
-  g3.lda = ld;
-  g3.B = B;
-  g3.ldb = ld;
-  g3.M = d;
-  g3.N = d;
-  g3.K = (int)n;
-  g3.tri_mode = 2;
+  const GemmArgs g3 = gemm_product(A, ld, B, ld, d, d, (int)n, 2);
   *fused = n % kGemmBK == 0 && gemm_uses_dma(g3) && splits <= colsum_rows;
   if (*fused)
     gemm_f64_launch<false>(ctx->stream, g3, splits, ctx->prop.multiProcessorCount,
@@ -1444,6 +1327,505 @@ static int fr_fused_enqueue(vb_ctx* ctx, hipStream_t st, int phases, GemmArgs g1
 }
 
 // ---- host orchestration ------------------------------------------------------------------------------
+// One evaluation is decided once, before its first launch (FrRoute, fr_route), laid out once (FrBufs, fr_carve) and
+// then enqueued stage by stage in pipeline order; the stages only read the route.
+
+// correlated-Gaussian target: who forms G
+enum FrDense {
+  kDenseFolded,          // G = -E M - 1 b' with M = L' P: no sampling product (the folded evaluation, below)
+  kDenseCallerG,         // the caller's G of these very samples (FrWeighted::g_ready)
+  kDensePersistent,      // one persistent launch for Z - m and G (fz_mode 3: the gradient product as well)
+  kDenseChain            // sampling product, then model product
+};
+
+struct FrRoute {
+  // the call
+  bool mvt = false, pd = false, glm = false, source = false, overlap = false;
+  int n_cu = 0;
+  // shapes
+  int64_t n = 0, d = 0, ldl = 0, ldz = 0, ldr = 0, slab = 0, pslab = 0, np = 0, glm_part = 0;
+  int D = 0, n_rb = 0, cs_gx = 0, n_fpart = 0;
+  int tri1 = 0, tri3 = 0;       // tri_mode of the sampling and of the gradient product
+  // the decisions
+  int splits = 1;               // gradient product: pieces of the sample axis
+  int kparts = 1;               // short shards: pieces of the k range of the N x D x D products (1: not split)
+  unsigned sum_blocks = 0;      // grid of the kernels that add those pieces
+  bool fold_shape = false;      // the folded evaluation's buffers are carved
+  int msplits = 1;              // its M = L' P product: pieces of the k range
+  bool fold = false;
+  int fz_mode = 0;              // 2 / 3: the persistent launch (kDensePersistent)
+  FrDense dense = kDenseChain;
+  bool model_ksplit = false;    // kDenseChain: the model product is cut like the sampling product
+  bool caller_z = false;        // the target reads the caller's samples: no sampling product
+  bool fused_sums = false;      // correlated Gaussian: sum f from the model product, column sums from the gradient product
+  bool diag_f = false;          // diagonal Gaussian: sum f from the sampling product's epilogue
+  bool cs_only = false;         // sum f is there already, the column sums come from the gradient product
+  bool g_prescaled = false;     // the target's own kernel writes G already scaled by the row weights
+  bool scale_rows_w = false;    // weighted sums: a pass over G scales its rows
+  bool two_passes = false;      // path derivative: a column pass for f before the score is added
+  bool colpass = false;         // the column pass between the products
+  bool colpass_keeps_f = false; // ... and its f partials are the evaluation's (otherwise they go to an unused tail)
+  int fmode = 0;                // how the column pass forms f (fr_colsum_kernel)
+  bool grad_colsums = false;    // the gradient product forms the column sums of G (one row per split)
+  bool grad_launch = true;      // (false: the persistent launch wrote the split slabs already)
+  int cfg3 = 0;                 // its tile configuration (0: the launcher's choice; 2: 128 x 64 with the XCD tile map)
+  bool f_per_tile = false;      // sum f: one partial per tile of the launch that formed it (tiles2), not n_fpart
+};
+
+// Decides the whole evaluation from what is known up front.  No HIP call, no state: of `ctx` it reads the CU count, whether
+// a communicator is attached and the fused mode.
+static FrRoute fr_route(const vb_ctx* ctx, const ModelDev& m, int64_t n, int64_t d, bool mvt, bool pd, bool row_scaled,
+                        const FrWeighted& wm) {
+  FrRoute r;
+  const bool gauss_diag = m.id == VB_MODEL_GAUSS_DIAG, gauss_full = m.id == VB_MODEL_GAUSS_FULL,
+             funnel = m.id == VB_MODEL_FUNNEL;
+  r.mvt = mvt;
+  r.pd = pd;
+  r.glm = m.id == VB_MODEL_LOGISTIC;
+  r.source = m.id == VB_MODEL_SOURCE;
+  r.overlap = !mvt && ctx->comm != nullptr;
+  r.n_cu = ctx->prop.multiProcessorCount;
+  r.n = n;
+  r.d = d;
+  r.D = (int)d;
+  r.ldl = r.ldz = round_up(d, 16);
+  r.slab = d * r.ldl;
+  r.pslab = n * r.ldz;
+  r.np = d * (d + 1) / 2;
+  r.tri1 = mvt ? 0 : 1;
+  r.tri3 = mvt ? 0 : 2;
+  const int D = r.D, n_cu = r.n_cu;
+  // the shapes of the sampling and of the gradient product (what the launcher's own decisions read)
+  const GemmArgs s1 = gemm_product(nullptr, 0, nullptr, 0, (int)n, D, D, r.tri1);
+  const GemmArgs s3 = gemm_product(nullptr, 0, nullptr, 0, D, D, (int)n, r.tri3);
+
+  const int tiles = gemm_tiles(D, 128);
+  const int lower_tiles = mvt ? tiles * tiles : tiles * (tiles + 1) / 2;
+  r.splits = n_cu / lower_tiles;   // one wave of workgroups: no second, mostly empty round
+  // at least this many sample rows per split: 192 lets D = 512 take 21 splits of its 36 lower 64 x 64 tiles (756
+  // workgroups on the 768 resident slots: gradient GEMM 38.9 -> 33.7 us, split reduction 8.5 -> 10.4 us; 256 rows
+  // stopped it at 16 splits); D = 1024 takes 7 either way
+  const int max_splits = (int)(n / 192) > 0 ? (int)(n / 192) : 1;
+  if (r.splits > max_splits) r.splits = max_splits;
+  if (r.splits < 1) r.splits = 1;
+  r.n_rb = (int)((n + 127) / 128);
+  r.cs_gx = (D + 127) / 128;
+  // regression targets: the log-likelihood partials of the eta GEMM follow the column-sum kernel's f partials
+  r.glm_part = r.glm ? gemm_max_blocks(n, m.n_data) : 0;
+  r.ldr = r.glm ? round_up(m.n_data, 16) : 0;
+  r.n_fpart = funnel ? (int)((n + 3) / 4) : r.source ? (int)n : r.n_rb * r.cs_gx + (int)r.glm_part;
+
+  // correlated-Gaussian target under the dense Gaussian family: no pass over G and Z between the GEMMs -- sum f comes
+  // out of the model GEMM's epilogue (EpiNegateF) and the column sums of G out of the gradient GEMM (EpiSplitSlabCs)
+  const bool sums_in_gemms = !mvt && !wm.roww && !row_scaled && n % kGemmBK == 0 && gemm_uses_dma(s1) &&
+                             (int64_t)r.splits <= r.n_rb;
+  r.fused_sums = gauss_full && sums_in_gemms;
+  // diagonal Gaussian target under the dense Gaussian family: sum f out of the sampling product's epilogue
+  r.diag_f = gauss_diag && sums_in_gemms;
+
+  // short shards (fewer than two 64 x 64 tiles per CU): the N x D x D products with their k range cut into `kparts`
+  // pieces (see fr_zsum_kernel); the slabs of partial products live in the split area of the gradient product, which
+  // is not in use yet
+  if (!row_scaled && !pd && !gauss_diag) {      // (pd keeps a slab of its own there)
+    // measured (tools/fr_bench.py, D = 1024): 512 rows 126 -> 85 us per evaluation, 256 rows 118 -> 61 us, 1 024 rows
+    // 133 -> 128 us, 2 048 rows unchanged (not split).  At D = 512 a tile's 32 slabs are no longer than a piece plus
+    // the extra kernel: not split (pieces of at least 16 slabs out of at least 48).
+    const long tiles64 = gemm_count_blocks(s1, 64, 64);
+    if (tiles64 < 2L * n_cu && D >= 48 * kGemmBK) r.kparts = (int)((2L * n_cu + tiles64 - 1) / tiles64);
+    if (r.kparts > 4) r.kparts = 4;
+    while (r.kparts > 1 && (D % (kGemmBK * r.kparts) != 0 || D / r.kparts < 16 * kGemmBK)) --r.kparts;
+    if ((int64_t)r.kparts * r.pslab > (int64_t)(r.splits + 1) * r.slab) r.kparts = 1;
+  }
+  r.sum_blocks = (unsigned)((r.pslab / 2 + 255) / 256);
+
+  // The folded evaluation.  G is linear in the noise for this target, G = -(E L' + 1 c') P = -E M - 1 b' with c = mu - m,
+  // M = L' P and b = P c, and the only other use of Z - m, sum f = 1/2 sum (Z - m) o G, follows from what the gradient
+  // product forms anyway:  sum (Z - m) o G = tr((E L' + 1 c')' G) = sum_{i >= j} L_ij C_ij + c . colsum(G),  C = G' E.
+  // So the N x D x D sampling product, the store of Z and its re-read become a D x D x D product (triangular k ranges,
+  // tri_mode 4) that is formed anew in EVERY evaluation -- M follows the parameter, and an optimiser steps it every time.
+  // Not with the path derivative (it changes G between the products), not with the caller's own Z or G, not for short
+  // shards (kparts), and only from the shapes at which it measures faster (DESIGN 4.4: the gate's table).  Ranks of one
+  // job may fall on different sides of the gate: both routes hand the same sums to the all-reduce.
+  r.fold_shape = !mvt && gauss_full && !pd && d >= VB_FR_FOLD_MIN_D && n >= (int64_t)VB_FR_FOLD_MIN_ROWS_PER_D * d;
+  r.msplits = fr_fold_splits(D);
+  r.fold = r.fold_shape && r.fused_sums && r.kparts == 1 && !wm.z_ready && !wm.g_ready;
+
+  // the fused evaluation: 2 = Z and G in one persistent launch, 3 = the gradient product's split slabs as well
+  // (its phase 1 is the product the fold removes: where the fold applies it takes precedence; the path derivative changes G
+  // between the products; the caller's G leaves nothing to fuse)
+  r.fz_mode = ctx->fr_fused_mode;
+  if (r.fz_mode < 0) {
+    const char* e = getenv("VB_FR_FUSED");
+    r.fz_mode = e ? atoi(e) : 0;
+  }
+  if (!(r.fused_sums && r.kparts == 1 && n % 128 == 0 && D % 64 == 0 && (int64_t)n * r.ldz * 8 < ((int64_t)1 << 31)))
+    r.fz_mode = 0;
+  if ((r.fz_mode != 2 && r.fz_mode != 3) || pd || r.fold || wm.g_ready) r.fz_mode = 0;
+  r.dense = r.fold ? kDenseFolded : wm.g_ready ? kDenseCallerG : r.fz_mode >= 2 ? kDensePersistent : kDenseChain;
+  r.model_ksplit = r.kparts > 1 && r.fused_sums;
+  // (the caller's samples: see FrWeighted; the correlated Gaussian wants Z - m and forms its own)
+  r.caller_z = wm.z_ready != nullptr && (funnel || r.source || r.glm);
+
+  r.g_prescaled = funnel && wm.roww != nullptr;
+  r.scale_rows_w = wm.roww != nullptr && !r.g_prescaled;
+  // targets whose row kernel leaves sum f behind already (funnel, source models): the column sums of G are all the pass
+  // between the products would add, and they come out of the gradient product's LDS tiles as for the correlated Gaussian
+  // (weighted sums: the same, once G is scaled -- the column sums of the gradient product's operand tiles ARE sum w g)
+  r.cs_only = r.diag_f || (!r.fused_sums && !mvt && (funnel || r.source) && (!wm.roww || r.g_prescaled) && !row_scaled &&
+                           n % kGemmBK == 0 && gemm_uses_dma(s3) && (int64_t)r.splits <= r.n_rb);
+  // path derivative: sum f belongs to the model's G, the column sums and the gradient product to G~ = G + E L^-1.  Where
+  // the column pass forms f from G (every target but the funnel and source models, whose own kernels left it behind) it
+  // runs once before the score is added -- for f -- and once after, for the column sums only
+  const bool f_from_pass = !(funnel || r.source);
+  r.colpass = !r.fused_sums && !r.cs_only;
+  r.two_passes = pd && r.colpass && f_from_pass;
+  r.colpass_keeps_f = f_from_pass && !r.two_passes;
+  // (weighted sums over the caller's G take their value from the weights: no f there)
+  r.fmode = gauss_diag ? 1 : r.glm ? 3 : (gauss_full && !wm.g_ready) ? 2 : 0;
+
+  r.grad_launch = r.fz_mode != 3;
+  r.grad_colsums = r.fused_sums || r.cs_only;
+  // 128 x 64 tiles are the launcher's own choice for this shape, made here so that the XCD tile list fits it
+  if (r.grad_launch && r.grad_colsums && gemm_count_blocks(s3, 128, 64) * r.splits * 100 >= 190L * n_cu) r.cfg3 = 2;
+  r.f_per_tile = r.fused_sums || r.diag_f;
+  return r;
+}
+
+// device buffers of one evaluation
+struct FrBufs {
+  const double* E = nullptr;      // the noise, row stride lde
+  int64_t lde = 0;
+  double *mu = nullptr, *Lt = nullptr;      // (the dense family's live in ctx->fr_lt: fr_prepare_dense)
+  double *Z = nullptr, *G = nullptr, *Cpart = nullptr, *colpart = nullptr, *fpart = nullptr;
+  double* Rm = nullptr;                                             // regression targets: the residuals
+  double *Mpart = nullptr, *bvec = nullptr;                         // folded evaluation: slabs of M = L' P, then M; b = P (mu - m)
+  double *Xa = nullptr, *T = nullptr, *sq = nullptr;                // path derivative: (L')^-1, a product buffer (then L^-1),
+                                                                    // partial sums of squares of the noise
+  FrSums S;
+};
+
+// one allocation (ctx->fr_work), carved; `set`: which of the two sum vectors of an overlapped evaluation
+static int fr_carve(vb_ctx* ctx, const FrRoute& r, const NoiseSlot& ns, int set, FrBufs* out) {
+  const int64_t n = r.n, ldz = r.ldz, slab = r.slab;
+  int64_t off = 0;
+  auto carve = [&off](int64_t doubles) {
+    const int64_t o = off;
+    off += round_up(doubles, 16);
+    return o;
+  };
+  const int64_t o_mu = carve(ldz), o_lt = carve(slab), o_z = carve(n * ldz), o_g = carve(n * ldz),
+                o_cpart = carve((int64_t)(r.splits + 1) * slab), o_col = carve((int64_t)(r.n_rb + 1) * ldz),
+                o_fpart = carve((int64_t)r.n_fpart + (int64_t)r.n_rb * r.cs_gx + gemm_max_blocks(n, r.D) + (n * ldz) / 512 + 1),
+                o_r = carve(r.glm ? n * r.ldr : 0);
+  const int64_t o_mpart = r.fold_shape ? carve((int64_t)(r.msplits + 1) * slab) : 0, o_bvec = r.fold_shape ? carve(ldz) : 0;
+  const int64_t o_xa = r.pd ? carve(slab) : 0, o_t = r.pd ? carve(slab) : 0, o_m2 = r.pd ? carve(256) : 0;
+  // sum vector: the t family takes the full D x ldl matrix; the Gaussian family packs the lower triangle in
+  // theta's own order, twice over when the all-reduce of one evaluation overlaps the kernels of the next
+  FrBufs b;
+  b.S.off_col = 16;
+  b.S.off_c = 16 + ldz;
+  b.S.len = 16 + ldz + (r.mvt ? slab : round_up(r.np, 16));
+  const int64_t o_sums = carve(b.S.len * (r.overlap ? 2 : 1));
+  VB_TRY(ensure(ctx, ctx->fr_work, (size_t)off * sizeof(double)));
+  double* base = (double*)ctx->fr_work.ptr;
+  b.E = (const double*)ns.buf.ptr;
+  b.lde = ns.ld;
+  b.mu = base + o_mu, b.Lt = base + o_lt, b.Z = base + o_z, b.G = base + o_g, b.Cpart = base + o_cpart;
+  b.colpart = base + o_col, b.fpart = base + o_fpart, b.Rm = base + o_r;
+  b.Mpart = base + o_mpart, b.bvec = base + o_bvec;
+  b.Xa = base + o_xa, b.T = base + o_t, b.sq = base + o_m2;
+  b.S.sums = base + o_sums + (int64_t)set * b.S.len;
+  *out = b;
+  return VB_OK;
+}
+
+// stream plan (as mf_enqueue's `overlap`): everything up to the split reduction stays in order on the main
+// stream; the all-reduce and the epilogue go to `post` behind one event, into sum set `seq & 1`, and the main
+// stream only waits for them when that set comes round again two evaluations later.  Returns the set.
+static int fr_stream_plan(vb_ctx* ctx, const FrRoute& r, int* set) {
+  Pipeline& P = ctx->pipe;
+  hipStream_t st = ctx->stream;
+  *set = 0;
+  if (r.overlap) {
+    VB_TRY(pipe_init(ctx));
+    *set = (int)(ctx->fr_seq++ & 1);
+    if (P.fin_valid[*set]) VB_HIP(ctx, hipStreamWaitEvent(st, P.ev_fin[*set], 0));
+  } else if (P.post_pending) {   // order this in-order evaluation after everything `post` has in flight
+    VB_HIP(ctx, hipStreamWaitEvent(st, P.ev_fin[P.last_set], 0));
+    P.post_pending = false;
+  }
+  return VB_OK;
+}
+
+// Prepare, t family: mu and the dense root into the work buffer
+static int fr_prepare_mvt(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const double* mu_dev, const double* root_dev) {
+  hipStream_t st = ctx->stream;
+  VB_HIP(ctx, hipMemcpyAsync(b.mu, mu_dev, (size_t)r.d * sizeof(double), hipMemcpyDeviceToDevice, st));
+  VB_HIP(ctx, hipMemcpy2DAsync(b.Lt, (size_t)r.ldl * sizeof(double), root_dev, (size_t)r.ldl * sizeof(double),
+                               (size_t)r.d * sizeof(double), (size_t)r.d, hipMemcpyDeviceToDevice, st));
+  return VB_OK;
+}
+
+// Prepare, dense family: mu and L' in a buffer of their own (ctx->fr_lt) -- when the parameter is the resident one
+// (vb_fullrank_set_theta) it is unpacked once per upload, not once per evaluation
+static int fr_prepare_dense(vb_ctx* ctx, const FrRoute& r, FrBufs* b, const double* theta_dev) {
+  const int64_t d = r.d;
+  VB_TRY(ensure(ctx, ctx->fr_lt, (size_t)(r.ldz + r.slab) * sizeof(double)));
+  b->mu = (double*)ctx->fr_lt.ptr;
+  b->Lt = b->mu + r.ldz;
+  const bool resident = theta_dev == (const double*)ctx->fr_theta.ptr;
+  // ... or vb_fit's parameter, whose step kernel wrote mu and L' of the stepped value itself (fr_step_unpack_enqueue)
+  const bool stepped = ctx->fr_lt_owner != nullptr && ctx->fr_lt_owner == theta_dev;
+  const bool lt_cached = (resident || stepped) && ctx->fr_lt_d == d;
+  if (!stepped) ctx->fr_lt_owner = nullptr;
+  ctx->fr_lt_d = (resident || stepped) ? d : 0;     // (a foreign parameter leaves the copy stale for the resident one)
+  if (!lt_cached) {
+    hipLaunchKernelGGL(fr_unpack_kernel, dim3((unsigned)((d + 31) / 32), (unsigned)((d + 31) / 32)), dim3(256), 0, ctx->stream,
+                       theta_dev, r.D, r.ldl, b->Lt, b->mu);
+    VB_HIP(ctx, hipGetLastError());
+  }
+  return VB_OK;
+}
+
+// Path derivative (objectives.py:166-168: the score's own parameter dependence is stopped): with z = mu + L eps the
+// gradient of -log q along the path is L^-T eps, so every row of G takes that term -- G~ = G + E L^-1, one more
+// N x D x D / 2 product (fr_score) -- and the usual sums of G~ finish the job: no entropy term, no noise Gram matrix, no
+// D x D x D product (round 4; rounds 2-3 formed L^-T (E'E / N): 620 -> ~500 us at D = 1024, N = 4096).
+// The prologue: (L')^-1 = U^-1 by recursive doubling (fr_tri_inverse_enqueue), L^-1 for the product, sum ||eps||^2.
+static int fr_score_prologue(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const double* theta_dev) {
+  hipStream_t st = ctx->stream;
+  const int D = r.D;
+  VB_TRY(fr_tri_inverse_enqueue(ctx, st, theta_dev, b.Lt, D, r.ldl, b.Xa, b.T));
+  VB_HIP(ctx, hipGetLastError());
+  // L^-1 = (U^-1)' with its rows k-major for the product (T is free again)
+  hipLaunchKernelGGL(fr_transpose_kernel, dim3((unsigned)((D + 31) / 32), (unsigned)((D + 31) / 32)), dim3(256), 0, st,
+                     (const double*)b.Xa, b.T, D, r.ldl);
+  // sum ||eps_n||^2 -> sums[1]: the value's mean log q of the samples (:167)
+  const int sq_blocks = (int)(r.n < 256 ? r.n : 256);
+  hipLaunchKernelGGL(fr_sumsq_kernel, dim3((unsigned)sq_blocks), dim3(256), 0, st, b.E, b.lde, r.n, D, b.sq);
+  hipLaunchKernelGGL(fr_sumsq_final_kernel, dim3(1), dim3(256), 0, st, (const double*)b.sq, sq_blocks, b.S.sums + 1);
+  VB_HIP(ctx, hipGetLastError());
+  return VB_OK;
+}
+
+// GEMM 1: Z[n][j] = sum_k E[n][k] Lt[k][j]   (Lt[k][j] = 0 for k > j), timed as VB_PROF_FR_SAMPLE_GEMM
+static GemmArgs fr_sample_product(vb_ctx* ctx, const FrRoute& r, const FrBufs& b) {
+  GemmArgs g1 = gemm_product(b.E, b.lde, b.Lt, r.ldl, (int)r.n, r.D, r.D, r.tri1);
+  prof_events(ctx, &g1.ev0, &g1.ev1, 1, VB_PROF_FR_SAMPLE_GEMM);
+  return g1;
+}
+
+// Sample: Z = E L' + mu - shift (the samples, or z - m for the correlated Gaussian target), plain or with the k range
+// split; returns the Z the target reads -- the caller's where it brought them
+static const double* fr_sample(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const double* shift, const double* row_scale,
+                               const double* z_ready) {
+  if (r.caller_z) return z_ready;
+  hipStream_t st = ctx->stream;
+  const GemmArgs g1 = fr_sample_product(ctx, r, b);
+  if (r.kparts > 1) {
+    gemm_f64_launch<true>(st, g1, r.kparts, r.n_cu, EpiSplitSlab{b.Cpart, r.ldz, r.pslab});
+    hipLaunchKernelGGL(fr_zsum_kernel, dim3(r.sum_blocks), dim3(256), 0, st, (const double*)b.Cpart, r.kparts, r.pslab, r.n,
+                       r.D, r.ldz, (const double*)b.mu, shift, b.Z);
+  } else {
+    gemm_f64_launch<true>(st, g1, 1, r.n_cu, EpiStoreZ{b.Z, r.ldz, b.mu, shift, row_scale});
+  }
+  return b.Z;
+}
+
+// Model, diagonal Gaussian: G out of the sampling product's epilogue, sum f as well where the route says so (a reducing
+// epilogue: returns its number of partials)
+static unsigned fr_model_gauss_diag(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelDev& m,
+                                    const double* row_scale) {
+  const GemmArgs g1 = fr_sample_product(ctx, r, b);
+  if (r.diag_f)
+    return gemm_f64_launch<true>(ctx->stream, g1, 1, r.n_cu, EpiGaussDiagF{b.G, r.ldz, b.mu, m.p0, m.p1, b.fpart});
+  gemm_f64_launch<true>(ctx->stream, g1, 1, r.n_cu, EpiGaussDiag{b.G, r.ldz, b.mu, m.p0, m.p1, row_scale});
+  return 0;
+}
+
+static int fr_model_funnel(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelDev& m, const double* Z,
+                           const double* roww) {
+  hipLaunchKernelGGL(fr_funnel_kernel, dim3((unsigned)((r.n + 3) / 4)), dim3(256), 0, ctx->stream, Z, b.G, r.ldz, r.n, r.D, m,
+                     b.fpart, roww);
+  return VB_OK;
+}
+
+// the user's row kernel: G and one f per sample (summed with the other f partials)
+static int fr_model_source(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const double* Z) {
+  return user_rows_enqueue(ctx, ctx->stream, Z, r.ldz, r.n, r.D, b.G, r.ldz, b.fpart);
+}
+
+static int fr_model_glm(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelDev& m, const double* Z) {
+  hipStream_t st = ctx->stream;
+  double* part = b.fpart + (int64_t)r.n_rb * r.cs_gx;
+  VB_HIP(ctx, hipMemsetAsync(part, 0, (size_t)r.glm_part * sizeof(double), st));
+  // eta = Z X'   [n x n_data x d]
+  const GemmArgs gh = gemm_product(Z, r.ldz, m.p1, m.ldq, (int)r.n, (int)m.n_data, r.D, 0);
+  gemm_f64_launch<true>(st, gh, 1, r.n_cu, EpiGlm{b.Rm, r.ldr, m.p2, part, m.link, m.aux});
+  VB_HIP(ctx, hipGetLastError());
+  return glm_grad_enqueue(ctx, st, m, b.Rm, r.ldr, Z, b.G, r.ldz, r.n, r.D);   // G = R X - Z / sd^2
+}
+
+// the folded evaluation (fr_route): M = L' P and b = P (mu - m), then G = -E M - 1 b'
+static int fr_model_folded(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelDev& m) {
+  hipStream_t st = ctx->stream;
+  const int D = r.D, msplits = r.msplits;
+  double* Mres = msplits > 1 ? b.Mpart + (int64_t)msplits * r.slab : b.Mpart;
+  // M[r][j] = sum_{k >= r} Lt[r][k] P[k][j]
+  const GemmArgs gm = gemm_product(b.Lt, r.ldl, m.p1, m.ldp, D, D, D, 4);
+  gemm_f64_launch<true>(st, gm, msplits, r.n_cu, EpiSplitSlab{b.Mpart, r.ldz, r.slab}, 4);      // 64 x 64 tiles, two stages
+  const int ks = (int)round_up((D + msplits - 1) / msplits, kGemmBK);                          // (the launcher's k_split)
+  const int nb_sum = msplits > 1 ? D * (int)((r.ldz / 2 + 255) / 256) : 0, nb_b = (D + 7) / 8;
+  hipLaunchKernelGGL(fr_fold_msum_kernel, dim3((unsigned)(nb_sum + nb_b)), dim3(256), 0, st, (const double*)b.Mpart, msplits,
+                     r.slab, D, r.ldz, ks, 64, Mres, nb_b, m.p1, (int64_t)m.ldp, (const double*)b.mu, m.p0, b.bvec);
+  VB_HIP(ctx, hipGetLastError());
+  GemmArgs g2 = gemm_product(b.E, b.lde, Mres, r.ldz, (int)r.n, D, D, 0);
+  prof_events(ctx, &g2.ev0, &g2.ev1, 1, VB_PROF_FR_MODEL_GEMM);
+  gemm_f64_launch<true>(st, g2, 1, r.n_cu, EpiNegateBias{b.G, r.ldz, b.bvec});
+  return VB_OK;
+}
+
+// Model, correlated Gaussian: G = -(Z - m) P,  P symmetric: B[k][j] = P[k][j].  Returns the G the later stages read (the
+// caller's where it brought it) and, in *tiles2, the number of sum-f partials where the route forms f here.
+static int fr_model_gauss_full(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelDev& m, const double* row_scale,
+                               const double* g_ready, double** G, unsigned* tiles2) {
+  hipStream_t st = ctx->stream;
+  const int D = r.D;
+  *G = b.G;
+  GemmArgs g2 = gemm_product(b.Z, r.ldz, m.p1, m.ldp, (int)r.n, D, D, 0);
+  switch (r.dense) {
+    case kDenseFolded:
+      return fr_model_folded(ctx, r, b, m);
+    case kDenseCallerG:
+      *G = const_cast<double*>(g_ready);
+      return VB_OK;
+    case kDensePersistent: {      // (and, fz_mode 3, the split slabs of C): vb_fullrank_fused.h
+      const GemmArgs g1 = gemm_product(b.E, b.lde, b.Lt, r.ldl, (int)r.n, D, D, r.tri1);
+      GemmArgs g3f = gemm_product(b.G, r.ldz, b.E, b.lde, D, D, (int)r.n, 2);
+      if (r.fz_mode == 3) VB_TRY(tri2_tile_map(ctx, D, 128, 64, &g3f.tile_map, &g3f.tile_blocks));
+      return fr_fused_enqueue(ctx, st, r.fz_mode, g1, g2, g3f, r.splits, b.Z, b.G, r.ldz, b.mu, m.p0, b.fpart,
+                              EpiSplitSlabCs{b.Cpart, r.ldl, r.slab, b.colpart, r.ldz}, tiles2);
+    }
+    case kDenseChain:
+      break;
+  }
+  fr_sample(ctx, r, b, m.p0, row_scale, nullptr);      // Z - m
+  VB_HIP(ctx, hipGetLastError());
+  if (r.model_ksplit) {
+    gemm_f64_launch<true>(st, g2, r.kparts, r.n_cu, EpiSplitSlab{b.Cpart, r.ldz, r.pslab});
+    hipLaunchKernelGGL(fr_gsum_kernel, dim3(r.sum_blocks), dim3(256), 0, st, (const double*)b.Cpart, r.kparts, r.pslab, r.n, D,
+                       r.ldz, (const double*)b.Z, b.G, b.fpart);
+    *tiles2 = r.sum_blocks;
+    return VB_OK;
+  }
+  prof_events(ctx, &g2.ev0, &g2.ev1, 1, VB_PROF_FR_MODEL_GEMM);
+  if (r.fused_sums) *tiles2 = gemm_f64_launch<true>(st, g2, 1, r.n_cu, EpiNegateF{b.G, r.ldz, b.Z, b.fpart});
+  else gemm_f64_launch<true>(st, g2, 1, r.n_cu, EpiNegate{b.G, r.ldz});
+  return VB_OK;
+}
+
+// the pass over G (and Z) between the products: column sums of G and, per fmode, the f partials
+static int fr_colpass(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelDev& m, double* G, const double* Z, int fmode,
+                      double* fpart, const double* row_scale) {
+  hipLaunchKernelGGL(fr_colsum_kernel, dim3((unsigned)r.cs_gx, (unsigned)r.n_rb), dim3(256), 0, ctx->stream, (const double*)G, Z,
+                     r.ldz, r.n, r.D, fmode, m.p1, b.colpart, fpart, r.glm ? 1.0 / (m.tau * m.tau) : 0.0,
+                     (const double*)nullptr, 0, row_scale ? G : (double*)nullptr, row_scale);
+  VB_HIP(ctx, hipGetLastError());
+  return VB_OK;
+}
+
+static int fr_rowscale(vb_ctx* ctx, const FrRoute& r, double* G, const double* w) {
+  hipLaunchKernelGGL(fr_rowscale_kernel, dim3((unsigned)r.n, (unsigned)((r.D + 255) / 256)), dim3(256), 0, ctx->stream, G, r.ldz,
+                     r.n, r.D, w);
+  VB_HIP(ctx, hipGetLastError());
+  return VB_OK;
+}
+
+// Score (path derivative): the column pass for f first where the route wants two, then G~ = G + E L^-1
+// (L^-1[k][j] = 0 for k < j: tri_mode 3)
+static int fr_score(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelDev& m, double* G, const double* Z) {
+  if (r.two_passes) VB_TRY(fr_colpass(ctx, r, b, m, G, Z, r.fmode, b.fpart, nullptr));
+  const GemmArgs gy = gemm_product(b.E, b.lde, b.T, r.ldl, (int)r.n, r.D, r.D, 3);
+  gemm_f64_launch<true>(ctx->stream, gy, 1, r.n_cu, EpiAccumulate{G, r.ldz});
+  VB_HIP(ctx, hipGetLastError());
+  return VB_OK;
+}
+
+// GEMM 3: C[i][j] = sum_n G[n][i] E[n][j]: lower-triangular tiles (all tiles for the t family), split over the sample
+// axis.  Returns in *tiles3 the number of output tiles of the launch.
+static int fr_grad_product(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const double* G, unsigned* tiles3) {
+  hipStream_t st = ctx->stream;
+  *tiles3 = 0;
+  if (!r.grad_launch) return VB_OK;
+  GemmArgs g3 = gemm_product(G, r.ldz, b.E, b.lde, r.D, r.D, (int)r.n, r.tri3);
+  prof_events(ctx, &g3.ev0, &g3.ev1, 1, VB_PROF_FR_GRAD_GEMM);
+  if (r.cfg3 == 2) VB_TRY(tri2_tile_map(ctx, r.D, 128, 64, &g3.tile_map, &g3.tile_blocks));
+  if (r.fold)      // one partial of sum L o tril(C) per tile and split
+    *tiles3 = gemm_f64_launch<false>(st, g3, r.splits, r.n_cu,
+                                     EpiSplitSlabCsF{b.Cpart, r.ldl, r.slab, b.colpart, r.ldz, b.Lt, r.ldl, b.fpart}, r.cfg3);
+  else if (r.grad_colsums)
+    *tiles3 = gemm_f64_launch<false>(st, g3, r.splits, r.n_cu, EpiSplitSlabCs{b.Cpart, r.ldl, r.slab, b.colpart, r.ldz}, r.cfg3);
+  else
+    *tiles3 = gemm_f64_launch<false>(st, g3, r.splits, r.n_cu, EpiSplitSlab{b.Cpart, r.ldl, r.slab});
+  VB_HIP(ctx, hipGetLastError());
+  return VB_OK;
+}
+
+// Finish, t family: the raw sums [F | sum g | sum_n g_n (e_n / s_n)' (full D x D)], all-reduced
+static int fr_finish_mvt(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, FrSums* sums_out) {
+  fr_reduce_launch(ctx, ctx->stream, (const double*)b.Cpart, r.splits, r.slab, r.D, r.ldl, (const double*)b.colpart, r.n_rb, r.ldz,
+                   (const double*)b.fpart, r.n_fpart, b.S, 1, nullptr);
+  VB_HIP(ctx, hipGetLastError());
+  if (ctx->comm) VB_TRY(comm_allreduce_sum(ctx, ctx->stream, b.S.sums, (size_t)b.S.len));
+  *sums_out = b.S;
+  return VB_OK;
+}
+
+// Finish, dense family: the split reduction (rows of column sums and f partials as the route left them); on a single GPU
+// it writes (value, grad) itself, in a job its sums are all-reduced and the epilogue follows -- on `post` behind one
+// event when the evaluation overlaps the next (fr_stream_plan)
+static int fr_finish_dense(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelDev& m, int set, int n_fpart_red,
+                           const double* theta_dev, double* out_dev, int64_t n_total, const FrWeighted& wm) {
+  hipStream_t st = ctx->stream;
+  const int D = r.D, n_rb_red = (r.grad_colsums || !r.grad_launch) ? r.splits : r.n_rb;      // one row of column sums per split
+  const int64_t red_items = r.slab / 2 > r.ldz ? r.slab / 2 : r.ldz;
+  const dim3 red_grid((unsigned)((red_items + 255) / 256) + (r.fold ? 1u : 0u));
+  const double *fold_mu = r.fold ? (const double*)b.mu : nullptr, *fold_m = r.fold ? m.p0 : nullptr;
+  if (!ctx->comm) {   // single GPU
+    hipLaunchKernelGGL(fr_reduce_packed_kernel<true>, red_grid, dim3(256), 0, st, (const double*)b.Cpart, r.splits, r.slab, D,
+                       r.ldl, (const double*)b.colpart, n_rb_red, r.ldz, (const double*)b.fpart, n_fpart_red, b.S, theta_dev,
+                       (double)n_total, (double)n_total, m.c0, out_dev, r.pd ? 1 : 0, wm, fold_mu, fold_m);
+    VB_HIP(ctx, hipGetLastError());
+    return VB_OK;
+  }
+  hipLaunchKernelGGL(fr_reduce_packed_kernel<false>, red_grid, dim3(256), 0, st, (const double*)b.Cpart, r.splits, r.slab, D,
+                     r.ldl, (const double*)b.colpart, n_rb_red, r.ldz, (const double*)b.fpart, n_fpart_red, b.S, theta_dev,
+                     (double)n_total, (double)n_total, m.c0, out_dev, r.pd ? 1 : 0, wm, fold_mu, fold_m);
+  VB_HIP(ctx, hipGetLastError());
+  Pipeline& P = ctx->pipe;
+  hipStream_t st_post = st;
+  if (r.overlap) {
+    VB_HIP(ctx, hipEventRecord(P.ev_k1[set], st));
+    st_post = P.post;
+    VB_HIP(ctx, hipStreamWaitEvent(st_post, P.ev_k1[set], 0));
+  }
+  VB_TRY(comm_allreduce_sum(ctx, st_post, b.S.sums, (size_t)b.S.len));
+  // one workgroup per CU: 328 -> 310 us per evaluation with a one-rank communicator (64: 312, 16: 350 -- the epilogue
+  // then is what the evaluation after next waits for; unlimited = 2 050 workgroups: 328)
+  const int64_t epi_full = (r.np + 255) / 256;
+  const unsigned epi_grid = (unsigned)((r.overlap && epi_full > r.n_cu) ? r.n_cu : epi_full);
+  hipLaunchKernelGGL(fr_epilogue_packed_kernel, dim3(epi_grid), dim3(256), 0, st_post, b.S, theta_dev, D, (double)n_total,
+                     (double)n_total, m.c0, out_dev, r.pd ? 1 : 0, wm);
+  VB_HIP(ctx, hipGetLastError());
+  if (r.overlap) {
+    VB_HIP(ctx, hipEventRecord(P.ev_fin[set], st_post));
+    P.fin_valid[set] = true;
+    P.post_pending = true;
+    P.last_set = set;
+  }
+  return VB_OK;
+}
+
 // theta_dev != nullptr: full-rank Gaussian (Z = E L' + mu, lower-triangular gradient, epilogue into the flat layout).
 // theta_dev == nullptr: multivariate t (X = (E R) / s + mu with the dense symmetric root R and the per-row scale
 // `row_scale`; the caller gets the raw sums [F | sum g | sum_n g_n (e_n / s_n)' (full D x D)] in `sums_out`).
@@ -1463,468 +1845,52 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
   }
   const bool pd = (flags & VB_FLAG_PATH_DERIV) != 0;
   if (pd && mvt) return fail(ctx, VB_ERR_UNSUPPORTED, "path derivative: dense Gaussian family only");
-  const bool glm = m.id == VB_MODEL_LOGISTIC;
-  const bool source = m.id == VB_MODEL_SOURCE;
-  if (m.id != VB_MODEL_GAUSS_DIAG && m.id != VB_MODEL_FUNNEL && m.id != VB_MODEL_GAUSS_FULL && !glm && !source)
+  if (m.id != VB_MODEL_GAUSS_DIAG && m.id != VB_MODEL_FUNNEL && m.id != VB_MODEL_GAUSS_FULL && m.id != VB_MODEL_LOGISTIC &&
+      m.id != VB_MODEL_SOURCE)
     return fail(ctx, VB_ERR_UNSUPPORTED, "full-rank path: unsupported model id %d", m.id);
   if (m.dim != d)
     return fail(ctx, VB_ERR_INVALID, "model dimension %d != family dimension %lld", m.dim, (long long)d);
   if (n <= 0 || d <= 0 || n > ns.n || d != ns.d)
     return fail(ctx, VB_ERR_INVALID, "noise slot holds %lld x %lld, evaluation asks %lld x %lld",
                 (long long)ns.n, (long long)ns.d, (long long)n, (long long)d);
-  hipStream_t st = ctx->stream;
-  const int D = (int)d;
-  const int64_t ldl = round_up(d, 16), ldz = round_up(d, 16);
-  const int n_cu = ctx->prop.multiProcessorCount;
-  const int tiles = gemm_tiles(D, 128);
-  const int lower_tiles = mvt ? tiles * tiles : tiles * (tiles + 1) / 2;
-  int splits = n_cu / lower_tiles;   // one wave of workgroups: no second, mostly empty round
-  // at least this many sample rows per split: 192 lets D = 512 take 21 splits of its 36 lower 64 x 64 tiles (756
-  // workgroups on the 768 resident slots: gradient GEMM 38.9 -> 33.7 us, split reduction 8.5 -> 10.4 us; 256 rows
-  // stopped it at 16 splits); D = 1024 takes 7 either way
-  const int max_splits = (int)(n / 192) > 0 ? (int)(n / 192) : 1;
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  const int n_rb = (int)((n + 127) / 128);
-  const int cs_gx = (D + 127) / 128;
-  // regression targets: the log-likelihood partials of the eta GEMM follow the column-sum kernel's f partials
-  const int64_t glm_part = glm ? gemm_max_blocks(n, m.n_data) : 0;
-  const int64_t ldr = glm ? round_up(m.n_data, 16) : 0;
-  const int n_fpart = m.id == VB_MODEL_FUNNEL ? (int)((n + 3) / 4) : source ? (int)n : n_rb * cs_gx + (int)glm_part;
-  const int64_t slab = d * ldl;
 
-  // device buffers (one allocation, carved)
-  int64_t off = 0;
-  auto carve = [&off](int64_t doubles) {
-    const int64_t o = off;
-    off += round_up(doubles, 16);
-    return o;
-  };
-  const int64_t o_mu = carve(ldz), o_lt = carve(slab), o_z = carve(n * ldz), o_g = carve(n * ldz),
-                o_cpart = carve((int64_t)(splits + 1) * slab), o_col = carve((int64_t)(n_rb + 1) * ldz),
-                o_fpart = carve((int64_t)n_fpart + (int64_t)n_rb * cs_gx + gemm_max_blocks(n, D) + (n * ldz) / 512 + 1),
-                o_r = carve(glm ? n * ldr : 0);
-  // path derivative: (L')^-1 (Xa), a product buffer T (then L^-1), partial sums of squares of the noise
-  // folded evaluation of the correlated-Gaussian target (below): the split slabs of M = L' P, M itself, b = P (mu - m)
-  const bool fold_shape = !mvt && m.id == VB_MODEL_GAUSS_FULL && !pd && d >= VB_FR_FOLD_MIN_D &&
-                          n >= (int64_t)VB_FR_FOLD_MIN_ROWS_PER_D * d;
-  const int msplits = fr_fold_splits(D);
-  const int64_t o_mpart = fold_shape ? carve((int64_t)(msplits + 1) * slab) : 0, o_bvec = fold_shape ? carve(ldz) : 0;
-  const int64_t o_xa = pd ? carve(slab) : 0, o_t = pd ? carve(slab) : 0, o_m2 = pd ? carve(256) : 0;
-  // sum vector: the t family takes the full D x ldl matrix; the Gaussian family packs the lower triangle in
-  // theta's own order, twice over when the all-reduce of one evaluation overlaps the kernels of the next
-  const int64_t np = d * (d + 1) / 2;
-  FrSums S;
-  S.off_col = 16;
-  S.off_c = 16 + ldz;
-  S.len = 16 + ldz + (mvt ? slab : round_up(np, 16));
-  const bool overlap = !mvt && ctx->comm != nullptr;
-  const int64_t o_sums = carve(S.len * (overlap ? 2 : 1));
-  VB_TRY(ensure(ctx, ctx->fr_work, (size_t)off * sizeof(double)));
-  double* base = (double*)ctx->fr_work.ptr;
-  double *mu = base + o_mu, *Lt = base + o_lt, *Z = base + o_z, *G = base + o_g, *Cpart = base + o_cpart,
-         *colpart = base + o_col, *fpart = base + o_fpart;
-  // the dense family keeps mu and L' in a buffer of their own: when the parameter is the resident one
-  // (vb_fullrank_set_theta) it is unpacked once per upload, not once per evaluation
-  bool lt_cached = false;
-  if (!mvt) {
-    VB_TRY(ensure(ctx, ctx->fr_lt, (size_t)(ldz + slab) * sizeof(double)));
-    mu = (double*)ctx->fr_lt.ptr;
-    Lt = mu + ldz;
-    const bool resident = theta_dev == (const double*)ctx->fr_theta.ptr;
-    // ... or vb_fit's parameter, whose step kernel wrote mu and L' of the stepped value itself (fr_step_unpack_enqueue)
-    const bool stepped = ctx->fr_lt_owner != nullptr && ctx->fr_lt_owner == theta_dev;
-    lt_cached = (resident || stepped) && ctx->fr_lt_d == d;
-    if (!stepped) ctx->fr_lt_owner = nullptr;
-    ctx->fr_lt_d = (resident || stepped) ? d : 0;     // (a foreign parameter leaves the copy stale for the resident one)
-  }
-  // stream plan (as mf_enqueue's `overlap`): everything up to the split reduction stays in order on the main
-  // stream; the all-reduce and the epilogue go to `post` behind one event, into sum set `seq & 1`, and the main
-  // stream only waits for them when that set comes round again two evaluations later
-  Pipeline& P = ctx->pipe;
+  const FrRoute r = fr_route(ctx, m, n, d, mvt, pd, row_scale != nullptr, wm);
   int set = 0;
-  if (overlap) {
-    VB_TRY(pipe_init(ctx));
-    set = (int)(ctx->fr_seq++ & 1);
-    if (P.fin_valid[set]) VB_HIP(ctx, hipStreamWaitEvent(st, P.ev_fin[set], 0));
-  } else if (P.post_pending) {   // order this in-order evaluation after everything `post` has in flight
-    VB_HIP(ctx, hipStreamWaitEvent(st, P.ev_fin[P.last_set], 0));
-    P.post_pending = false;
-  }
-  S.sums = base + o_sums + (int64_t)set * S.len;
+  FrBufs b;
+  VB_TRY(fr_stream_plan(ctx, r, &set));
+  VB_TRY(fr_carve(ctx, r, ns, set, &b));
 
-  // a pipelined upload of this evaluation's parameter is in flight (vb_elbo_grad_fullrank): the sampling product below may
-  // consume it chunk by chunk; whoever else reads the parameter or its unpacked copy first waits for the last chunk
-  vb_ctx::FrUpload* up = (ctx->fr_up_active && !mvt && lt_cached) ? &ctx->fr_up : nullptr;
-  ctx->fr_up_active = false;
-  bool up_waited = false;
-  auto up_wait_all = [&]() -> int {
-    if (up && !up_waited) {
-      VB_HIP(ctx, hipStreamWaitEvent(st, up->ev[up->n_chunks - 1], 0));
-      up_waited = true;
-    }
-    return VB_OK;
-  };
-  if (up && pd) VB_TRY(up_wait_all());      // (the triangular inverse reads the whole parameter at once)
+  if (mvt) VB_TRY(fr_prepare_mvt(ctx, r, b, mu_dev, root_dev));
+  else VB_TRY(fr_prepare_dense(ctx, r, &b, theta_dev));
+  if (pd) VB_TRY(fr_score_prologue(ctx, r, b, theta_dev));
 
-  if (mvt) {
-    VB_HIP(ctx, hipMemcpyAsync(mu, mu_dev, (size_t)d * sizeof(double), hipMemcpyDeviceToDevice, st));
-    VB_HIP(ctx, hipMemcpy2DAsync(Lt, (size_t)ldl * sizeof(double), root_dev, (size_t)ldl * sizeof(double),
-                                 (size_t)d * sizeof(double), (size_t)d, hipMemcpyDeviceToDevice, st));
-  } else if (!lt_cached) {
-    hipLaunchKernelGGL(fr_unpack_kernel, dim3((unsigned)((d + 31) / 32), (unsigned)((d + 31) / 32)), dim3(256), 0, st, theta_dev,
-                       D, ldl, Lt, mu);
-    VB_HIP(ctx, hipGetLastError());
-  }
-
-  if (pd) {
-    // Path derivative (objectives.py:166-168: the score's own parameter dependence is stopped): with z = mu + L eps the
-    // gradient of -log q along the path is L^-T eps, so every row of G takes that term -- G~ = G + E L^-1, one more
-    // N x D x D / 2 product -- and the usual sums of G~ finish the job: no entropy term, no noise Gram matrix, no
-    // D x D x D product (round 4; rounds 2-3 formed L^-T (E'E / N): 620 -> ~500 us at D = 1024, N = 4096).
-    // (L')^-1 = U^-1 by recursive doubling: diagonal blocks of kTriLeaf rows are inverted by back substitution
-    // (one wave per column), then [[A, B], [0, C]]^-1 = [[A^-1, -A^-1 B C^-1], [0, C^-1]] level by level --
-    // two GEMMs per pair of blocks, D^3 / 3 flops in all instead of a triangular solve
-    double *Xa = base + o_xa, *T = base + o_t, *sq = base + o_m2;
-    VB_TRY(fr_tri_inverse_enqueue(ctx, st, theta_dev, Lt, D, ldl, Xa, T));
-    VB_HIP(ctx, hipGetLastError());
-    // L^-1 = (U^-1)' with its rows k-major for the product below (T is free again)
-    hipLaunchKernelGGL(fr_transpose_kernel, dim3((unsigned)((D + 31) / 32), (unsigned)((D + 31) / 32)), dim3(256), 0, st,
-                       (const double*)Xa, T, D, ldl);
-    // sum ||eps_n||^2 -> sums[1]: the value's mean log q of the samples (:167)
-    const int sq_blocks = (int)(n < 256 ? n : 256);
-    hipLaunchKernelGGL(fr_sumsq_kernel, dim3((unsigned)sq_blocks), dim3(256), 0, st, (const double*)ns.buf.ptr, ns.ld, n, D, sq);
-    hipLaunchKernelGGL(fr_sumsq_final_kernel, dim3(1), dim3(256), 0, st, (const double*)sq, sq_blocks, S.sums + 1);
-    VB_HIP(ctx, hipGetLastError());
-  }
-
-  // GEMM 1: Z[n][j] = sum_k E[n][k] Lt[k][j]   (Lt[k][j] = 0 for k > j)
-  GemmArgs g1;
-  g1.A = (const double*)ns.buf.ptr;
-  g1.lda = ns.ld;
-  g1.B = Lt;
-  g1.ldb = ldl;
-  g1.M = (int)n;
-  g1.N = D;
-  g1.K = D;
-  g1.tri_mode = mvt ? 0 : 1;
-  int fmode = 0;
-  // correlated-Gaussian target under the dense Gaussian family: no pass over G and Z between the GEMMs -- sum f comes
-  // out of the model GEMM's epilogue (EpiNegateF) and the column sums of G out of the gradient GEMM (EpiSplitSlabCs)
-  const bool fused_sums = !mvt && m.id == VB_MODEL_GAUSS_FULL && !wm.roww && !row_scale &&
-                          n % kGemmBK == 0 && gemm_uses_dma(g1) && (int64_t)splits <= n_rb;
-  // short shards (fewer than two 64 x 64 tiles per CU): the N x D x D products with their k range cut into `kparts`
-  // pieces (see fr_zsum_kernel); the slabs of partial products live in the split area of the gradient product, which
-  // is not in use yet
-  int kparts = 1;
-  const int64_t pslab = n * ldz;
-  if (!row_scale && !pd && m.id != VB_MODEL_GAUSS_DIAG) {      // (pd keeps a slab of its own there)
-    // measured (tools/fr_bench.py, D = 1024): 512 rows 126 -> 85 us per evaluation, 256 rows 118 -> 61 us, 1 024 rows
-    // 133 -> 128 us, 2 048 rows unchanged (not split).  At D = 512 a tile's 32 slabs are no longer than a piece plus
-    // the extra kernel: not split (pieces of at least 16 slabs out of at least 48).
-    const long tiles64 = gemm_count_blocks(g1, 64, 64);
-    if (tiles64 < 2L * n_cu && D >= 48 * kGemmBK) kparts = (int)((2L * n_cu + tiles64 - 1) / tiles64);
-    if (kparts > 4) kparts = 4;
-    while (kparts > 1 && (D % (kGemmBK * kparts) != 0 || D / kparts < 16 * kGemmBK)) --kparts;
-    if ((int64_t)kparts * pslab > (int64_t)(splits + 1) * slab) kparts = 1;
-  }
-  // The folded evaluation.  G is linear in the noise for this target, G = -(E L' + 1 c') P = -E M - 1 b' with c = mu - m,
-  // M = L' P and b = P c, and the only other use of Z - m, sum f = 1/2 sum (Z - m) o G, follows from what the gradient
-  // product forms anyway:  sum (Z - m) o G = tr((E L' + 1 c')' G) = sum_{i >= j} L_ij C_ij + c . colsum(G),  C = G' E.
-  // So the N x D x D sampling product, the store of Z and its re-read become a D x D x D product (triangular k ranges,
-  // tri_mode 4) that is formed anew in EVERY evaluation -- M follows the parameter, and an optimiser steps it every time.
-  // Not with the path derivative (it changes G between the products), not with the caller's own Z or G, not for short
-  // shards (kparts), and only from the shapes at which it measures faster (DESIGN 4.4: the gate's table).  Ranks of one
-  // job may fall on different sides of the gate: both routes hand the same sums to the all-reduce.
-  const bool fold = fold_shape && fused_sums && kparts == 1 && !wm.z_ready && !wm.g_ready;
-  if (!fold) prof_events(ctx, &g1.ev0, &g1.ev1, 1, VB_PROF_FR_SAMPLE_GEMM);      // (folded: no such launch to time)
-  // the fused evaluation: 2 = Z and G in one persistent launch, 3 = the gradient product's split slabs as well
-  // (its phase 1 is the product the fold removes: where the fold applies it takes precedence)
-  int fz_mode = ctx->fr_fused_mode;
-  if (fz_mode < 0) {
-    const char* e = getenv("VB_FR_FUSED");
-    fz_mode = e ? atoi(e) : 0;
-  }
-  if (!(fused_sums && kparts == 1 && n % 128 == 0 && D % 64 == 0 &&
-        (int64_t)n * ldz * 8 < ((int64_t)1 << 31)))
-    fz_mode = 0;
-  if ((fz_mode != 2 && fz_mode != 3) || pd || fold) fz_mode = 0;      // (the path derivative changes G between the products)
-  const unsigned sum_blocks = (unsigned)((pslab / 2 + 255) / 256);
-  // Z = E L' + mu - shift into `Z` (the samples, or z - m for the correlated Gaussian target)
-  auto sample_gemm = [&](const double* shift) {
-    if (wm.z_ready && !shift) {      // (the caller's samples: see FrWeighted)
-      Z = const_cast<double*>(wm.z_ready);
-      return;
-    }
-    if (up && !up_waited && kparts == 1 && !row_scale && gemm_uses_dma(g1) && up->n_chunks > 1 &&
-        gemm_count_blocks(g1, 128, 64) < 4L * n_cu) {
-      // chunk 0 (the heaviest column blocks) on the main stream behind its event; the lighter chunks on side streams
-      // behind theirs (and behind everything the main stream had queued before: the noise), joined below
-      up->consumed = true;
-      (void)hipEventRecord(ctx->up_ev_main, st);
-      for (int c = 0; c < up->n_chunks; ++c) {
-        hipStream_t sc = c == 0 ? st : ctx->up_side[(c - 1) & 1];
-        if (c > 0) (void)hipStreamWaitEvent(sc, ctx->up_ev_main, 0);
-        (void)hipStreamWaitEvent(sc, up->ev[c], 0);
-        GemmArgs gc = g1;
-        gc.ev0 = gc.ev1 = nullptr;
-        gc.bn_begin = up->bn_begin[c];
-        gc.bn_count = up->bn_count[c];
-        gemm_f64_launch<true>(sc, gc, 1, n_cu, EpiStoreZ{Z, ldz, mu, shift, row_scale}, 4);
-      }
-      for (int i = 0; i < 2 && i < up->n_chunks - 1; ++i) {
-        (void)hipEventRecord(ctx->up_ev_join[i], ctx->up_side[i]);
-        (void)hipStreamWaitEvent(st, ctx->up_ev_join[i], 0);
-      }
-      up_waited = true;      // (the main stream is now behind the last chunk's event as well)
-      return;
-    }
-    (void)up_wait_all();
-    if (kparts > 1) {
-      gemm_f64_launch<true>(st, g1, kparts, n_cu, EpiSplitSlab{Cpart, ldz, pslab});
-      hipLaunchKernelGGL(fr_zsum_kernel, dim3(sum_blocks), dim3(256), 0, st, (const double*)Cpart, kparts, pslab, n, D, ldz,
-                         (const double*)mu, shift, Z);
-    } else {
-      gemm_f64_launch<true>(st, g1, 1, n_cu, EpiStoreZ{Z, ldz, mu, shift, row_scale});
-    }
-  };
-  unsigned tiles2 = 0;
-  bool g_prescaled = false;      // the target's own kernel wrote G already scaled by the row weights
-  // diagonal Gaussian target under the dense Gaussian family: sum f out of the sampling product's epilogue
-  const bool diag_f = !mvt && m.id == VB_MODEL_GAUSS_DIAG && !wm.roww && !row_scale &&
-                      n % kGemmBK == 0 && gemm_uses_dma(g1) && (int64_t)splits <= n_rb;
-  if (m.id == VB_MODEL_GAUSS_DIAG) VB_TRY(up_wait_all());      // (a reducing epilogue: one launch)
-  if (m.id == VB_MODEL_GAUSS_DIAG && diag_f) {
-    tiles2 = gemm_f64_launch<true>(st, g1, 1, n_cu, EpiGaussDiagF{G, ldz, mu, m.p0, m.p1, fpart});
-    fmode = 1;
-  } else if (m.id == VB_MODEL_GAUSS_DIAG) {
-    gemm_f64_launch<true>(st, g1, 1, n_cu, EpiGaussDiag{G, ldz, mu, m.p0, m.p1, row_scale});
-    fmode = 1;
-  } else if (m.id == VB_MODEL_FUNNEL) {
-    sample_gemm(nullptr);
-    VB_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(fr_funnel_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const double*)Z,
-                       G, ldz, n, D, m, fpart, wm.roww);
-    g_prescaled = wm.roww != nullptr;
-  } else if (source) {        // the user's row kernel: G and one f per sample (summed with the other f partials)
-    sample_gemm(nullptr);
-    VB_HIP(ctx, hipGetLastError());
-    VB_TRY(user_rows_enqueue(ctx, st, Z, ldz, n, D, G, ldz, fpart));
-  } else if (glm) {
-    sample_gemm(nullptr);
-    VB_HIP(ctx, hipGetLastError());
-    double* Rm = base + o_r;
-    double* part = fpart + (int64_t)n_rb * cs_gx;
-    VB_HIP(ctx, hipMemsetAsync(part, 0, (size_t)glm_part * sizeof(double), st));
-    GemmArgs gh;                                   // eta = Z X'   [n x n_data x d]
-    gh.A = Z;
-    gh.lda = ldz;
-    gh.B = m.p1;
-    gh.ldb = m.ldq;
-    gh.M = (int)n;
-    gh.N = (int)m.n_data;
-    gh.K = D;
-    gh.tri_mode = 0;
-    gemm_f64_launch<true>(st, gh, 1, n_cu, EpiGlm{Rm, ldr, m.p2, part, m.link, m.aux});
-    VB_HIP(ctx, hipGetLastError());
-    VB_TRY(glm_grad_enqueue(ctx, st, m, Rm, ldr, Z, G, ldz, n, D));   // G = R X - Z / sd^2
-    fmode = 3;
+  const double* Z = b.Z;
+  double* G = b.G;
+  unsigned tiles2 = 0, tiles3 = 0;      // partials of sum f that a reducing launch left behind
+  if (m.id == VB_MODEL_GAUSS_DIAG) {
+    tiles2 = fr_model_gauss_diag(ctx, r, b, m, row_scale);
+  } else if (m.id == VB_MODEL_GAUSS_FULL) {
+    VB_TRY(fr_model_gauss_full(ctx, r, b, m, row_scale, wm.g_ready, &G, &tiles2));
   } else {
-    GemmArgs g2;                                   // G = -(Z - m) P,  P symmetric: B[k][j] = P[k][j]
-    g2.A = Z;
-    g2.lda = ldz;
-    g2.B = m.p1;
-    g2.ldb = m.ldp;
-    g2.M = (int)n;
-    g2.N = D;
-    g2.K = D;
-    g2.tri_mode = 0;
-    if (fold) {
-      // (a pipelined upload's chunked sampling launch has nothing to feed here: wait for the whole parameter)
-      VB_TRY(up_wait_all());
-      double *Mpart = base + o_mpart, *bvec = base + o_bvec;
-      double* Mres = msplits > 1 ? Mpart + (int64_t)msplits * slab : Mpart;
-      GemmArgs gm;                                 // M[r][j] = sum_{k >= r} Lt[r][k] P[k][j]
-      gm.A = Lt;
-      gm.lda = ldl;
-      gm.B = m.p1;
-      gm.ldb = m.ldp;
-      gm.M = D;
-      gm.N = D;
-      gm.K = D;
-      gm.tri_mode = 4;
-      gemm_f64_launch<true>(st, gm, msplits, n_cu, EpiSplitSlab{Mpart, ldz, slab}, 4);      // 64 x 64 tiles, two stages
-      const int ks = (int)round_up((D + msplits - 1) / msplits, kGemmBK);                   // (the launcher's k_split)
-      const int nb_sum = msplits > 1 ? D * (int)((ldz / 2 + 255) / 256) : 0, nb_b = (D + 7) / 8;
-      hipLaunchKernelGGL(fr_fold_msum_kernel, dim3((unsigned)(nb_sum + nb_b)), dim3(256), 0, st,
-                         (const double*)Mpart, msplits, slab, D, ldz, ks, 64, Mres, nb_b, m.p1, (int64_t)m.ldp,
-                         (const double*)mu, m.p0, bvec);
-      VB_HIP(ctx, hipGetLastError());
-      g2.A = (const double*)ns.buf.ptr;            // G = -E M - 1 b'
-      g2.lda = ns.ld;
-      g2.B = Mres;
-      g2.ldb = ldz;
-      prof_events(ctx, &g2.ev0, &g2.ev1, 1, VB_PROF_FR_MODEL_GEMM);
-      gemm_f64_launch<true>(st, g2, 1, n_cu, EpiNegateBias{G, ldz, bvec});
-    } else if (wm.g_ready) {
-      G = const_cast<double*>(wm.g_ready);      // (the caller's G of these very samples: see FrWeighted)
-    } else if (fz_mode >= 2) {
-      // one persistent launch for Z - m and G (and, fz_mode 3, the split slabs of C): vb_fullrank_fused.h
-      EpiSplitSlabCs e3{Cpart, ldl, slab, colpart, ldz};
-      GemmArgs g3f;
-      g3f.A = G, g3f.lda = ldz, g3f.B = (const double*)ns.buf.ptr, g3f.ldb = ns.ld;
-      g3f.M = D, g3f.N = D, g3f.K = (int)n, g3f.tri_mode = 2;
-      if (fz_mode == 3) VB_TRY(tri2_tile_map(ctx, D, 128, 64, &g3f.tile_map, &g3f.tile_blocks));
-      VB_TRY(up_wait_all());
-      VB_TRY(fr_fused_enqueue(ctx, st, fz_mode, g1, g2, g3f, splits, Z, G, ldz, mu, m.p0, fpart, e3, &tiles2));
-    } else {
-      sample_gemm(m.p0);                         // Z - m
-      VB_HIP(ctx, hipGetLastError());
-    }
-    if (fz_mode >= 2 || wm.g_ready || fold) {
-    } else if (kparts > 1 && fused_sums) {
-      gemm_f64_launch<true>(st, g2, kparts, n_cu, EpiSplitSlab{Cpart, ldz, pslab});
-      hipLaunchKernelGGL(fr_gsum_kernel, dim3(sum_blocks), dim3(256), 0, st, (const double*)Cpart, kparts, pslab, n, D, ldz,
-                         (const double*)Z, G, fpart);
-      tiles2 = sum_blocks;
-    } else {
-      prof_events(ctx, &g2.ev0, &g2.ev1, 1, VB_PROF_FR_MODEL_GEMM);
-      if (fused_sums) tiles2 = gemm_f64_launch<true>(st, g2, 1, n_cu, EpiNegateF{G, ldz, Z, fpart});
-      else gemm_f64_launch<true>(st, g2, 1, n_cu, EpiNegate{G, ldz});
-    }
-    fmode = wm.g_ready ? 0 : 2;      // (weighted sums take their value from the weights: no f here)
+    Z = fr_sample(ctx, r, b, nullptr, row_scale, wm.z_ready);
+    VB_HIP(ctx, hipGetLastError());
+    if (m.id == VB_MODEL_FUNNEL) VB_TRY(fr_model_funnel(ctx, r, b, m, Z, wm.roww));
+    else if (r.source) VB_TRY(fr_model_source(ctx, r, b, Z));
+    else VB_TRY(fr_model_glm(ctx, r, b, m, Z));
   }
   VB_HIP(ctx, hipGetLastError());
 
-  if (wm.roww && !g_prescaled) {   // weighted sums: scale the rows of G before anything is summed
-    hipLaunchKernelGGL(fr_rowscale_kernel, dim3((unsigned)n, (unsigned)((D + 255) / 256)), dim3(256), 0, st, G, ldz, n,
-                       D, wm.roww);
-    VB_HIP(ctx, hipGetLastError());
-  }
-  // C = G' E: lower-triangular tiles (all tiles for the t family), split over the sample axis
-  GemmArgs g3;
-  g3.A = G;
-  g3.lda = ldz;
-  g3.B = (const double*)ns.buf.ptr;
-  g3.ldb = ns.ld;
-  g3.M = D;
-  g3.N = D;
-  g3.K = (int)n;
-  g3.tri_mode = mvt ? 0 : 2;
-  // targets whose row kernel leaves sum f behind already (funnel, source models): the column sums of G are all the pass
-  // below would add, and they come out of the gradient product's LDS tiles as for the correlated Gaussian
-  // (weighted sums: the same, once G is scaled -- the column sums of the gradient product's operand tiles ARE sum w g)
-  const bool cs_only = diag_f || (!fused_sums && !mvt && (m.id == VB_MODEL_FUNNEL || source) &&
-                                 (!wm.roww || g_prescaled) &&
-                                 !row_scale && n % kGemmBK == 0 && gemm_uses_dma(g3) && (int64_t)splits <= n_rb);
-  // path derivative: sum f belongs to the model's G, the column sums and the gradient product to G~ = G + E L^-1.  Where
-  // the pass below forms f from G (every target but the funnel and source models, whose own kernels left it behind) it
-  // runs once before the score is added -- for f -- and once after, for the column sums only
-  const bool f_from_pass = !(m.id == VB_MODEL_FUNNEL || source);
-  const bool two_passes = pd && !fused_sums && !cs_only && f_from_pass;
-  if (two_passes) {
-    hipLaunchKernelGGL(fr_colsum_kernel, dim3((unsigned)cs_gx, (unsigned)n_rb), dim3(256), 0, st,
-                       (const double*)G, (const double*)Z, ldz, n, D, fmode, m.p1, colpart, fpart,
-                       glm ? 1.0 / (m.tau * m.tau) : 0.0, (const double*)nullptr, 0, (double*)nullptr,
-                       (const double*)nullptr);
-    VB_HIP(ctx, hipGetLastError());
-  }
-  if (pd) {       // G~ = G + E L^-1   (L^-1[k][j] = 0 for k < j: tri_mode 3)
-    GemmArgs gy;
-    gy.A = (const double*)ns.buf.ptr;
-    gy.lda = ns.ld;
-    gy.B = base + o_t;
-    gy.ldb = ldl;
-    gy.M = (int)n;
-    gy.N = D;
-    gy.K = D;
-    gy.tri_mode = 3;
-    gemm_f64_launch<true>(st, gy, 1, n_cu, EpiAccumulate{G, ldz});
-    VB_HIP(ctx, hipGetLastError());
-  }
-  if (!fused_sums && !cs_only) {
-    hipLaunchKernelGGL(fr_colsum_kernel, dim3((unsigned)cs_gx, (unsigned)n_rb), dim3(256), 0, st,
-                       (const double*)G, (const double*)Z, ldz, n, D, two_passes ? 0 : fmode, m.p1, colpart,
-                       (!f_from_pass || two_passes) ? fpart + n_fpart /*unused tail*/ : fpart,
-                       glm ? 1.0 / (m.tau * m.tau) : 0.0, (const double*)nullptr, 0, row_scale ? G : (double*)nullptr,
-                       row_scale);
-    VB_HIP(ctx, hipGetLastError());
-  } else if (row_scale) {
-    hipLaunchKernelGGL(fr_rowscale_kernel, dim3((unsigned)n, (unsigned)((D + 255) / 256)), dim3(256), 0, st, G, ldz, n,
-                       D, row_scale);
-    VB_HIP(ctx, hipGetLastError());
-  }
-  // GEMM 3: C[i][j] = sum_n G[n][i] E[n][j]
-  prof_events(ctx, &g3.ev0, &g3.ev1, 1, VB_PROF_FR_GRAD_GEMM);
-  int n_rb_red = n_rb, n_fpart_red = n_fpart;
-  if (fz_mode == 3) {          // the fused launch has written the split slabs and their column sums
-    n_rb_red = splits;
-    n_fpart_red = (int)tiles2;
-  } else if (fused_sums || cs_only) {
-    int cfg3 = 0;
-    if (gemm_count_blocks(g3, 128, 64) * splits * 100 >= 190L * n_cu) {
-      cfg3 = 2;     // the launcher's own choice for this shape (128 x 64 tiles), made here so that the list fits it
-      VB_TRY(tri2_tile_map(ctx, D, 128, 64, &g3.tile_map, &g3.tile_blocks));
-    }
-    if (fold) {      // one partial of sum L o tril(C) per tile and split
-      const unsigned tiles3 = gemm_f64_launch<false>(st, g3, splits, n_cu,
-                                                     EpiSplitSlabCsF{Cpart, ldl, slab, colpart, ldz, Lt, ldl, fpart}, cfg3);
-      n_fpart_red = (int)tiles3 * splits;
-    } else {
-      gemm_f64_launch<false>(st, g3, splits, n_cu, EpiSplitSlabCs{Cpart, ldl, slab, colpart, ldz}, cfg3);
-      if (fused_sums || diag_f) n_fpart_red = (int)tiles2;          // one partial of sum f per tile of the model GEMM
-    }
-    n_rb_red = splits;                  // one row of column sums per split
-  } else {
-    gemm_f64_launch<false>(st, g3, splits, n_cu, EpiSplitSlab{Cpart, ldl, slab});
-  }
-  VB_HIP(ctx, hipGetLastError());
+  if (r.scale_rows_w) VB_TRY(fr_rowscale(ctx, r, G, wm.roww));   // weighted sums: before anything is summed
+  if (pd) VB_TRY(fr_score(ctx, r, b, m, G, Z));
+  if (r.colpass)
+    VB_TRY(fr_colpass(ctx, r, b, m, G, Z, r.two_passes ? 0 : r.fmode, r.colpass_keeps_f ? b.fpart : b.fpart + r.n_fpart,
+                      row_scale));
+  else if (row_scale) VB_TRY(fr_rowscale(ctx, r, G, row_scale));
+  VB_TRY(fr_grad_product(ctx, r, b, G, &tiles3));
 
-  const int64_t red_items = slab / 2 > ldz ? slab / 2 : ldz;
-  const dim3 red_grid((unsigned)((red_items + 255) / 256) + (fold ? 1u : 0u));
-  VB_TRY(up_wait_all());      // (the epilogue reads the flat parameter's diagonal)
-  if (mvt) {
-    fr_reduce_launch(ctx, st, (const double*)Cpart, splits, slab, D, ldl, (const double*)colpart, n_rb, ldz, (const double*)fpart,
-                     n_fpart, S, 1, nullptr);
-    VB_HIP(ctx, hipGetLastError());
-    if (ctx->comm) VB_TRY(comm_allreduce_sum(ctx, st, S.sums, (size_t)S.len));
-    *sums_out = S;
-    return VB_OK;
-  }
-  if (!ctx->comm) {   // single GPU: the split reduction writes (value, grad) itself
-    hipLaunchKernelGGL(fr_reduce_packed_kernel<true>, red_grid, dim3(256), 0, st, (const double*)Cpart,
-                       splits, slab, D, ldl, (const double*)colpart, n_rb_red, ldz,
-                       (const double*)fpart, n_fpart_red, S, theta_dev, (double)n_total, (double)n_total, m.c0, out_dev,
-                       pd ? 1 : 0, wm, fold ? (const double*)mu : nullptr, fold ? m.p0 : nullptr);
-    VB_HIP(ctx, hipGetLastError());
-    return VB_OK;
-  }
-  hipLaunchKernelGGL(fr_reduce_packed_kernel<false>, red_grid, dim3(256), 0, st, (const double*)Cpart,
-                     splits, slab, D, ldl, (const double*)colpart, n_rb_red, ldz,
-                     (const double*)fpart, n_fpart_red, S, theta_dev, (double)n_total, (double)n_total, m.c0, out_dev,
-                     pd ? 1 : 0, wm, fold ? (const double*)mu : nullptr, fold ? m.p0 : nullptr);
-  VB_HIP(ctx, hipGetLastError());
-  hipStream_t st_post = st;
-  if (overlap) {
-    VB_HIP(ctx, hipEventRecord(P.ev_k1[set], st));
-    st_post = P.post;
-    VB_HIP(ctx, hipStreamWaitEvent(st_post, P.ev_k1[set], 0));
-  }
-  VB_TRY(comm_allreduce_sum(ctx, st_post, S.sums, (size_t)S.len));
-  // one workgroup per CU: 328 -> 310 us per evaluation with a one-rank communicator (64: 312, 16: 350 -- the epilogue
-  // then is what the evaluation after next waits for; unlimited = 2 050 workgroups: 328)
-  const int64_t epi_full = (np + 255) / 256;
-  const unsigned epi_grid = (unsigned)((overlap && epi_full > n_cu) ? n_cu : epi_full);
-  hipLaunchKernelGGL(fr_epilogue_packed_kernel, dim3(epi_grid), dim3(256), 0, st_post, S,
-                     theta_dev, D, (double)n_total, (double)n_total, m.c0, out_dev, pd ? 1 : 0, wm);
-  VB_HIP(ctx, hipGetLastError());
-  if (overlap) {
-    VB_HIP(ctx, hipEventRecord(P.ev_fin[set], st_post));
-    P.fin_valid[set] = true;
-    P.post_pending = true;
-    P.last_set = set;
-  }
-  return VB_OK;
+  if (mvt) return fr_finish_mvt(ctx, r, b, sums_out);
+  const int n_fpart_red = r.fold ? (int)tiles3 * r.splits : r.f_per_tile ? (int)tiles2 : r.n_fpart;
+  return fr_finish_dense(ctx, r, b, m, set, n_fpart_red, theta_dev, out_dev, n_total, wm);
 }
 
 // Z = E L' + mu into `Z` (n x ldz, ldz = round_up(d, 16)): the samples themselves, for per-row evaluations.
@@ -1935,26 +1901,18 @@ int fr_sample_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, co
   const int D = (int)d;
   const int64_t ldl = round_up(d, 16), ldz = ldl;
   hipStream_t st = ctx->stream;
-  GemmArgs g1;
-  g1.A = (const double*)ns.buf.ptr;
-  g1.lda = ns.ld;
-  g1.ldb = ldl;
-  g1.M = (int)n;
-  g1.N = D;
-  g1.K = D;
+  const double* E = (const double*)ns.buf.ptr;
+  const int n_cu = ctx->prop.multiProcessorCount;
   if (theta_dev) {
     VB_TRY(ensure(ctx, ctx->fr_work, (size_t)(ldz + d * ldl) * sizeof(double)));
     double* mu = (double*)ctx->fr_work.ptr;
     double* Lt = mu + ldz;
     hipLaunchKernelGGL(fr_unpack_kernel, dim3((unsigned)((d + 31) / 32), (unsigned)((d + 31) / 32)), dim3(256), 0, st, theta_dev, D, ldl,
                        Lt, mu);
-    g1.B = Lt;
-    g1.tri_mode = 1;
-    gemm_f64_launch<true>(st, g1, 1, ctx->prop.multiProcessorCount, EpiStoreZ{Z, ldz, mu, nullptr, row_scale});
+    gemm_f64_launch<true>(st, gemm_product(E, ns.ld, Lt, ldl, (int)n, D, D, 1), 1, n_cu, EpiStoreZ{Z, ldz, mu, nullptr, row_scale});
   } else {
-    g1.B = root_dev;
-    g1.tri_mode = 0;
-    gemm_f64_launch<true>(st, g1, 1, ctx->prop.multiProcessorCount, EpiStoreZ{Z, ldz, mu_dev, nullptr, row_scale});
+    gemm_f64_launch<true>(st, gemm_product(E, ns.ld, root_dev, ldl, (int)n, D, D, 0), 1, n_cu,
+                          EpiStoreZ{Z, ldz, mu_dev, nullptr, row_scale});
   }
   VB_HIP(ctx, hipGetLastError());
   return VB_OK;

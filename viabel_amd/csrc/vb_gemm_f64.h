@@ -43,12 +43,12 @@ __device__ long long vb_gemm_dbg[8 * 4096];
 #endif
 
 struct GemmArgs {
-  const double* A;
-  const double* B;
-  int64_t lda, ldb;
-  int M, N, K;
-  int tiles_m, tiles_n;
-  int tri_mode;     // 0: dense; 1: B[k][j] == 0 for k > j (k-range cut per column block);
+  const double* A = nullptr;
+  const double* B = nullptr;
+  int64_t lda = 0, ldb = 0;
+  int M = 0, N = 0, K = 0;
+  int tiles_m = 0, tiles_n = 0;      // (set by the launcher)
+  int tri_mode = 0; // 0: dense; 1: B[k][j] == 0 for k > j (k-range cut per column block);
                     // 2: only output tiles with bm >= bn (lower triangle of a square C);
                     // 3: B[k][j] == 0 for k < j (the mirror image of 1; LDS-DMA kernel, otherwise computed densely)
                     // 4: A[m][k] == 0 for k < m, A given as A[m][k] (an upper-triangular left factor: M = L' P of the
@@ -57,7 +57,7 @@ struct GemmArgs {
                     //    launcher then lists on the grid's x axis only the (row block, split) pairs with a k range
                     //    (tri4_splits; gridDim.z = 1), so slab z of C is NOT written for the row blocks that start at
                     //    or beyond the end of split z (LDS-DMA kernel, otherwise computed densely)
-  int k_split;      // K range per blockIdx.z (multiple of kGemmBK); splits = gridDim.z
+  int k_split = 0;  // K range per blockIdx.z (multiple of kGemmBK); splits = gridDim.z
   // batch mode (batch != 0): blockIdx.z selects one of gridDim.z independent products of the same shape -- operand
   // z starts batch_a / batch_b doubles after operand z - 1, every product runs over the whole K range and the
   // epilogue receives z as its `split` argument
@@ -68,11 +68,6 @@ struct GemmArgs {
   // same XCD (block x runs on XCD x % 8 and each XCD has its own L2)
   const int* tile_map = nullptr;
   int tile_blocks = 0;
-  // tri_mode 1, optional: only the column blocks [bn_begin, bn_begin + bn_count) of the product (bn_count == 0: all) --
-  // the launch covers tiles_m x bn_count tiles in the usual heavy-first order; rows, columns and k ranges keep their
-  // global indices.  (The blocking full-rank call starts the sampling product of the heaviest column blocks while the rest
-  // of the parameter is still crossing PCIe: vb_fullrank.hip, FrUpload.)
-  int bn_begin = 0, bn_count = 0;
   int tri4_splits = 0;      // tri_mode 4 with a split k range: the number of splits (set by the launcher)
   // split products, optional (LDS-DMA kernel; the launcher clears it unless gridDim.z % 8 == 0): the workgroups of ONE split
   // -- which read the same k range of both operands -- are dispatched to ONE XCD.  Workgroups go to the XCDs round robin
@@ -91,6 +86,14 @@ struct GemmArgs {
   int dbg_prio_slabs = 0;      // > 0: tiles of at most that many k slabs run at wave priority 3; < 0: tiles of more than -that many
 #endif
 };
+
+// the product of A (row stride lda) and B (row stride ldb), everything optional off
+inline GemmArgs gemm_product(const double* A, int64_t lda, const double* B, int64_t ldb, int M, int N, int K, int tri_mode) {
+  GemmArgs g;
+  g.A = A, g.lda = lda, g.B = B, g.ldb = ldb;
+  g.M = M, g.N = N, g.K = K, g.tri_mode = tri_mode;
+  return g;
+}
 
 // Epilogue functor interface:  void operator()(int split, int row, int col, double acc) const;
 // called for every in-range element of the block tile.  A functor that defines `double* part` and
@@ -169,9 +172,9 @@ __global__ void __launch_bounds__(256, AF * NB > 32 ? 1 : 2) gemm_f64_kernel(con
   } else if (g.tri_mode == 1) {
     // first half of the grid: heaviest column blocks (largest k range) in descending order; second half:
     // the light ones ascending, so the two workgroups a CU ends up with sum to the same k range
-    const int tn = g.bn_count ? g.bn_count : g.tiles_n;
+    const int tn = g.tiles_n;
     const int idx = blockIdx.x / g.tiles_m, half = (tn + 1) / 2;
-    bn = g.bn_begin + (idx < half ? tn - 1 - idx : idx - half);
+    bn = idx < half ? tn - 1 - idx : idx - half;
     bm = blockIdx.x % g.tiles_m;
   } else {
     bn = blockIdx.x / g.tiles_m;
@@ -466,11 +469,8 @@ inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu
   const int bm_rows = (cfg == 3 || cfg == 4 || cfg >= 7) ? 64 : 128, bn_cols = cfg >= 7 ? 32 : (cfg == 1 || cfg == 6) ? 128 : 64;
   g.tiles_m = gemm_tiles(g.M, bm_rows);
   g.tiles_n = gemm_tiles(g.N, bn_cols);
-  if (g.bn_count && (g.tri_mode != 1 || g.bn_begin + g.bn_count > g.tiles_n)) g.bn_begin = g.bn_count = 0;
   if (splits % 8 != 0 || g.batch) g.xcd_group = 0;
-  dim3 grid(g.tile_map ? (unsigned)g.tile_blocks
-                             : g.bn_count ? (unsigned)(g.tiles_m * g.bn_count) : (unsigned)gemm_count_blocks(g, bm_rows, bn_cols), 1,
-                  (unsigned)splits);
+  dim3 grid(g.tile_map ? (unsigned)g.tile_blocks : (unsigned)gemm_count_blocks(g, bm_rows, bn_cols), 1, (unsigned)splits);
   if (g.tri_mode == 4 && splits > 1) {      // only the (row block, split) pairs that have a k range, heaviest row block first
     g.tri4_splits = splits;
     long items = 0;
