@@ -13,8 +13,8 @@
 //   GEMM 1 (MFMA)      Z = E L^T + mu      [N x D x D, triangular k-range]  fused model epilogue
 //   model              gauss_diag: G in the GEMM-1 epilogue; funnel: row kernel Z -> G;
 //                      gauss_full: GEMM 2 (MFMA)  G = -(Z - m) P
-//                      (from D = 1024 and 3 D samples on, folded: M = L' P, G = -E M - 1 (P (mu - m))', no GEMM 1 --
-//                      see fr_route)
+//                      (from D = 1024 and 3 D samples on, folded: G is linear in the noise and is not formed at all --
+//                      M = L' P, S = E' E, C = -tril(M' S) - b s', colsum(G) = -s' M - n b'; see fr_route)
 //   fr_colsum          column sums of G (-> d/dmu) and sum_n f(z_n), per 128-row block
 //   GEMM 3 (MFMA)      C = G^T E           [D x D x N, lower-triangular tiles, split-K]
 //   fr_reduce          fixed-order sum of the split-K slabs / row-block partials -> sum vector
@@ -187,22 +187,6 @@ struct EpiNegate {          // G = -acc   (gauss_full: G = -(Z - m) P)
   }
 };
 
-// G = -acc - b   (gauss_full, folded evaluation: acc = E M with M = L' P, b = P (mu - m); see fr_route)
-struct EpiNegateBias {
-  double* G;
-  int64_t ldz;
-  const double* b;
-  __device__ void operator()(int, int row, int col, double acc) const {
-    G[(int64_t)row * ldz + col] = -acc - b[col];
-  }
-  __device__ d2v pair(int, int row, int col, double a0, double a1) const {
-    const d2v bb = *reinterpret_cast<const d2v*>(b + col);
-    const d2v v = (d2v){-a0 - bb.x, -a1 - bb.y};
-    *reinterpret_cast<d2v*>(G + (int64_t)row * ldz + col) = v;
-    return v;
-  }
-};
-
 struct EpiAccumulate {      // G += acc   (path derivative: the rows of G take the score's L^-T eps)
   double* G;
   int64_t ldz;
@@ -252,26 +236,38 @@ struct EpiSplitSlabCs {
   }
 };
 
-// ... and, per workgroup, the sum of L[row][col] * acc over the tile's entries on or below the diagonal (the folded
-// evaluation: sum (Z - m) o G = sum_{i >= j} L_ij C_ij + (mu - m) . colsum(G)).  L[row][col] is Lt[col][row]: a lane's
-// fragments a, a + 1 are adjacent rows, i.e. adjacent doubles of one row of Lt.
-struct EpiSplitSlabCsF {
+// The folded evaluation's gradient product (fr_route): acc = sum_k M[k][row] S[k][col] over the split's k range, and
+// C_split[row][col] = -acc - (split 0: b[row] s[col]) -- the slabs add up to C = G' E = -M' S - b s' itself.  Per
+// workgroup, the sum of L[row][col] * C_split[row][col] over the tile's entries on or below the diagonal
+// (sum (Z - m) o G = sum_{i >= j} L_ij C_ij + (mu - m) . colsum(G)).  L[row][col] is Lt[col][row]: a lane's fragments
+// a, a + 1 are adjacent rows, i.e. adjacent doubles of one row of Lt.  No `colsum` member: no column-sum hook runs.
+// The waves of the diagonal tiles also store the entries ABOVE the diagonal that their sub-tiles cover: in slab 0 those are
+// -b[row] s[col] (plus a partial product), not zeros -- nobody reads them (fr_reduce_packed_kernel takes j <= i only), but
+// the slabs of this route must not be read in full.
+struct EpiFoldSlabF {
   double* C;
   int64_t ldc, slab;
-  double* colsum;
-  int64_t colsum_ld;
+  const double* b;          // P (mu - m)
+  const double* s;          // colsum(E)
   const double* Lt;
   int64_t ldl;
   double* part;
   __device__ double operator()(int split, int row, int col, double acc) const {
-    C[split * slab + (int64_t)row * ldc + col] = acc;
+    const double v = split == 0 ? -acc - b[row] * s[col] : -acc;
+    C[split * slab + (int64_t)row * ldc + col] = v;
     const double l = Lt[(int64_t)col * ldl + row];
-    return col <= row ? l * acc : 0.0;
+    return col <= row ? l * v : 0.0;
   }
   __device__ d2v pair(int split, int row, int col, double a0, double a1) const {
-    *reinterpret_cast<d2v*>(C + split * slab + (int64_t)row * ldc + col) = (d2v){a0, a1};
+    d2v v = (d2v){-a0, -a1};
+    if (split == 0) {
+      const double br = b[row];
+      const d2v ss = *reinterpret_cast<const d2v*>(s + col);
+      v.x -= br * ss.x, v.y -= br * ss.y;
+    }
+    *reinterpret_cast<d2v*>(C + split * slab + (int64_t)row * ldc + col) = v;
     const double l0 = Lt[(int64_t)col * ldl + row], l1 = Lt[(int64_t)(col + 1) * ldl + row];
-    return (d2v){col <= row ? l0 * a0 : 0.0, col + 1 <= row ? l1 * a1 : 0.0};
+    return (d2v){col <= row ? l0 * v.x : 0.0, col + 1 <= row ? l1 * v.y : 0.0};
   }
 };
 
@@ -401,7 +397,8 @@ __global__ void __launch_bounds__(256) fr_colsum_kernel(const double* __restrict
 
 // ---- folded evaluation: M = sum of the split slabs of L' P, and b = P (mu - m) ------------------------------------------
 // The correlated-Gaussian target's G is linear in the noise: G = -(E L' + 1 c') P = -E M - 1 b', c = mu - m, M = L' P,
-// b = P c -- a D x D x D product that does not depend on the number of samples instead of the N x D x D sampling product.
+// b = P c -- a D x D x D product that does not depend on the number of samples instead of the N x D x D sampling product
+// (and G itself is never formed: fr_route).
 // Blocks [0, nb_b), 8 columns each (dispatched first: each is a chain of dependent passes): b[j] = sum_k P[k][j] c[k];
 // thread (pair p = t & 3, k group t >> 2) sums its 64th of the k range, sixteen rows per pass, the groups are
 // combined through LDS in fixed order.  The remaining blocks (none for an unsplit product): one thread per pair of
@@ -472,6 +469,133 @@ __global__ void __launch_bounds__(256) fr_fold_msum_kernel(const double* __restr
 static int fr_fold_splits(int d) {
   const int s = d / (16 * kGemmBK);
   return s < 1 ? 1 : (s > 8 ? 8 : s);
+}
+
+// ---- folded evaluation: S = E' E, s = colsum(E) and colsum(G) = -s' M - n b' -----------------------------------------
+// The Gram product of the noise leaves the lower tiles of E' E in `gsplits` slabs (pieces of the sample axis) and one row
+// of column sums of E per slab.  One launch, three kinds of workgroups:
+//   [0, nb_cs), 8 columns each, dispatched first (each is a chain of dependent passes), as the b blocks of
+//     fr_fold_msum_kernel: colsum(G)[j] = -sum_k s[k] M[k][j] - n b[j], with s[k] added up from the rows of `colpart` in
+//     row order by the thread that needs it (M is complete: this launch follows fr_fold_msum_kernel);
+//   the next nb_s: s itself, one thread per column (the gradient product's epilogue reads it);
+//   the rest, one per 32 x 32 tile (bi, bj <= bi) of S: the slabs added in slab order,
+//     the sum written to S[i][j] and, through LDS, to S[j][i] -- both halves from the same sum, so S is exactly
+//     symmetric, and both stores are contiguous runs.  Of a diagonal tile only the entries j <= i are read (the product's
+//     waves that lie above the diagonal store zeros there).  Only the lower tiles are dispatched; the tile comes from the
+//     block index by arithmetic that is uniform over the block, and no thread divides.
+// Everything is added in a fixed order: the same inputs give the same bits.
+__global__ void __launch_bounds__(256) fr_fold_ssum_kernel(const double* __restrict__ Spart, int gsplits, int64_t slab, int d,
+                                                           int64_t ldl, const double* __restrict__ colpart, int64_t ldz,
+                                                           const double* __restrict__ M, const double* __restrict__ b,
+                                                           double n_rows, int nb_cs, int nb_s,
+                                                           double* __restrict__ S, double* __restrict__ svec,
+                                                           double* __restrict__ csg) {
+  if ((int)blockIdx.x < nb_cs) {
+    __shared__ fr_d2 part[64][4];
+    const int p = threadIdx.x & 3, kg = threadIdx.x >> 2;
+    const int col = (int)blockIdx.x * 8 + 2 * p;
+    const int colc = col < d ? col : 0;                        // (rows of M have an even stride >= d)
+    const int kper = (d + 63) / 64;
+    const int k0 = kg * kper, k1 = k0 + kper < d ? k0 + kper : d;
+    fr_d2 acc = (fr_d2){0.0, 0.0};
+    for (int kb = k0; kb < k1; kb += 16) {
+      fr_d2 v[16];
+      double c[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int k = kb + u < k1 ? kb + u : k1 - 1;
+        v[u] = *reinterpret_cast<const fr_d2*>(M + (int64_t)k * ldz + colc);
+        c[u] = colpart[k];
+      }
+      for (int z = 1; z < gsplits; ++z)
+#pragma unroll
+        for (int u = 0; u < 16; ++u) c[u] += colpart[(int64_t)z * ldz + (kb + u < k1 ? kb + u : k1 - 1)];
+#pragma unroll
+      for (int u = 0; u < 16; ++u)
+        if (kb + u < k1) acc += v[u] * c[u];
+    }
+    part[kg][p] = acc;
+    __syncthreads();
+    if (kg == 0) {
+      fr_d2 tot = part[0][p];
+#pragma unroll
+      for (int q = 1; q < 64; ++q) tot += part[q][p];
+      if (col < d) csg[col] = -tot.x - n_rows * b[col];
+      if (col + 1 < d) csg[col + 1] = -tot.y - n_rows * b[col + 1];
+    }
+    return;
+  }
+  if ((int)blockIdx.x < nb_cs + nb_s) {
+    const int k = ((int)blockIdx.x - nb_cs) * 256 + (int)threadIdx.x;
+    if (k >= ldz) return;
+    double s = 0.0;
+    if (k < d) {
+      s = colpart[k];
+      for (int z = 1; z < gsplits; ++z) s += colpart[(int64_t)z * ldz + k];
+    }
+    svec[k] = s;
+    return;
+  }
+  int bi = 0, bj = (int)blockIdx.x - nb_cs - nb_s;      // lower tiles only, row by row: tile row bi has bi + 1 of them
+  while (bj > bi) bj -= ++bi;                            // (uniform over the block: scalar arithmetic)
+  __shared__ double tile[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int i0 = bi * 32, j0 = bj * 32;
+  double v[4];
+  int64_t idx[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int i = i0 + ty + 8 * q, j = j0 + tx;
+    idx[q] = (i < d && j <= i) ? (int64_t)i * ldl + j : 0;      // (not read by the sum: clamped, not predicated)
+    v[q] = 0.0;
+  }
+  for (int zb = 0; zb < gsplits; zb += 8) {      // eight slabs in flight, added in slab order
+    double w[8][4];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) w[u][q] = Spart[(zb + u < gsplits ? zb + u : gsplits - 1) * slab + idx[q]];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (zb + u < gsplits) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = (zb + u == 0) ? w[u][q] : v[q] + w[u][q];
+      }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) tile[ty + 8 * q][tx] = v[q];
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int r = ty + 8 * q;
+    if (bi == bj) {                // the tile on the diagonal: its upper half is the mirror image of its lower half
+      const int i = i0 + r, j = j0 + tx;
+      if (i < d && j < d) S[(int64_t)i * ldl + j] = tx <= r ? v[q] : tile[tx][r];
+    } else {
+      const int i = i0 + r, j = j0 + tx;
+      if (i < d && j < d) S[(int64_t)i * ldl + j] = v[q];
+      const int it = j0 + r, jt = i0 + tx;      // row of the mirrored tile, its column
+      if (it < d && jt < d) S[(int64_t)it * ldl + jt] = tile[tx][r];
+    }
+  }
+}
+
+// k splits of the folded gradient product C = -tril(M' S) - b s' (K = D, lower 64 x 64 tiles): pieces of about sixteen
+// slabs, as the M product's, and no more of them than fill the chip's four workgroups per CU once -- no second round
+// (D = 1024: 4 pieces, 544 workgroups).  The rule is MEASURED AT THE HEADLINE SHAPE ONLY (D = 1024): 128 x 64
+// tiles in 7 pieces of ten slabs 35.3 us for the product and 9.7 us for the reduction of its slabs, this 34.4 and 8.0; 2
+// or 4 pieces of 128 x 64 tiles and 8 pieces of either tile were 6 to 12 us slower per evaluation.  For larger D it is an
+// extrapolation nobody has timed: D = 2048 gets one piece (528 workgroups of 128 slabs on 1 024 slots), D >= ~2 900 the
+// unsplit 128 x 64 or three-stage 64 x 64 tiles of fr_route.  `max_splits` does not bind at the shapes inside the gate (D = 1024: 4 of
+// 8 slabs, D = 2048: 1 of 2 -- both counts follow the CUs per lower tile): it is there for a gate that moves.
+static int fr_fold_csplits(int d, int n_cu, int max_splits) {
+  const GemmArgs sc = gemm_product(nullptr, 0, nullptr, 0, d, d, d, 2);
+  const long tiles = gemm_count_blocks(sc, 64, 64);
+  int s = d / (16 * kGemmBK);
+  if ((long)s * tiles > 4L * n_cu) s = (int)(4L * n_cu / tiles);
+  if (s > max_splits) s = max_splits;      // (the slabs of C take the place of the Gram product's)
+  if (s > 16) s = 16;                      // (the reduction keeps sixteen slabs in flight)
+  return s < 1 ? 1 : s;
 }
 
 // ---- reduce: split-K slabs, row-block partials -> sum vector ------------------------------------------
@@ -1332,7 +1456,8 @@ static int fr_fused_enqueue(vb_ctx* ctx, hipStream_t st, int phases, GemmArgs g1
 
 // correlated-Gaussian target: who forms G
 enum FrDense {
-  kDenseFolded,          // G = -E M - 1 b' with M = L' P: no sampling product (the folded evaluation, below)
+  kDenseNoG,             // nobody: the sums of G = -E M - 1 b' from M = L' P and the noise's Gram matrix (the folded
+                         // evaluation, below) -- no sampling product, no model product
   kDenseCallerG,         // the caller's G of these very samples (FrWeighted::g_ready)
   kDensePersistent,      // one persistent launch for Z - m and G (fz_mode 3: the gradient product as well)
   kDenseChain            // sampling product, then model product
@@ -1353,6 +1478,8 @@ struct FrRoute {
   bool fold_shape = false;      // the folded evaluation's buffers are carved
   int msplits = 1;              // its M = L' P product: pieces of the k range
   bool fold = false;
+  int csplits = 1;              // its gradient product C = -tril(M' S) - b s': pieces of the k range
+  int cfgc = 0;                 // ... and its tile configuration (gemm_f64_launch's cfg)
   int fz_mode = 0;              // 2 / 3: the persistent launch (kDensePersistent)
   FrDense dense = kDenseChain;
   bool model_ksplit = false;    // kDenseChain: the model product is cut like the sampling product
@@ -1441,14 +1568,27 @@ static FrRoute fr_route(const vb_ctx* ctx, const ModelDev& m, int64_t n, int64_t
   // The folded evaluation.  G is linear in the noise for this target, G = -(E L' + 1 c') P = -E M - 1 b' with c = mu - m,
   // M = L' P and b = P c, and the only other use of Z - m, sum f = 1/2 sum (Z - m) o G, follows from what the gradient
   // product forms anyway:  sum (Z - m) o G = tr((E L' + 1 c')' G) = sum_{i >= j} L_ij C_ij + c . colsum(G),  C = G' E.
-  // So the N x D x D sampling product, the store of Z and its re-read become a D x D x D product (triangular k ranges,
-  // tri_mode 4) that is formed anew in EVERY evaluation -- M follows the parameter, and an optimiser steps it every time.
+  // Nothing the evaluation returns needs G itself: with S = E' E, s = colsum(E) and n the rows of this rank,
+  //   C = G' E = -M' S - b s'        colsum(G) = -s' M - n b'
+  // so neither N x D x D product is formed and neither Z nor G is stored.  The chain:
+  //   M slabs = L' P (tri_mode 4, msplits)  ->  fr_fold_msum_kernel: M, b
+  //   Gram product of the noise: the gradient product's own shape, kernel and tile map with A = B = E, `splits` slabs of
+  //     the lower tiles of S, one row of column sums of E per slab out of its LDS tiles (EpiSplitSlabCs)
+  //   fr_fold_ssum_kernel: S in full (mirrored), s, colsum(G)
+  //   C slabs = -(M' S) - b s' (lower tiles, K = D in csplits pieces, EpiFoldSlabF: sum L o tril(C) per tile and split)
+  //   fr_reduce_packed_kernel, as for every route: the slabs of C, ONE row of column sums, the f partials.
+  // M and S are formed anew in EVERY evaluation: M follows the parameter, which an optimiser steps every time, and S the
+  // noise, which every iteration of a fit draws afresh -- nothing is kept per slot, per parameter or per engine.
+  // The K axis of the C product: the LDS-DMA kernel reads whole kGemmBK-row slabs of M and S, so a D that is no multiple
+  // of kGemmBK is kept OUT of the route -- fused_sums below already asks gemm_uses_dma of a product with K = D -- and the
+  // rows of M and S have no pad (ldz = ldl = D).
   // Not with the path derivative (it changes G between the products), not with the caller's own Z or G, not for short
   // shards (kparts), and only from the shapes at which it measures faster (the gate's table).  Ranks of one
-  // job may fall on different sides of the gate: both routes hand the same sums to the all-reduce.
+  // job may fall on different sides of the gate: both routes hand the same sums [F | colsum | C] of the rank's own rows
+  // to the all-reduce.
   r.fold_shape = !mvt && gauss_full && !pd && d >= VB_FR_FOLD_MIN_D && n >= (int64_t)VB_FR_FOLD_MIN_ROWS_PER_D * d;
   r.msplits = fr_fold_splits(D);
-  r.fold = r.fold_shape && r.fused_sums && r.kparts == 1 && !wm.z_ready && !wm.g_ready;
+  r.fold = r.fold_shape && r.fused_sums && r.kparts == 1 && !wm.z_ready && !wm.g_ready && n >= d + 2;      // (fr_carve; cannot bind while the gate asks n >= 3 d)
 
   // the fused evaluation: 2 = Z and G in one persistent launch, 3 = the gradient product's split slabs as well
   // (its phase 1 is the product the fold removes: where the fold applies it takes precedence; the path derivative changes G
@@ -1461,7 +1601,7 @@ static FrRoute fr_route(const vb_ctx* ctx, const ModelDev& m, int64_t n, int64_t
   if (!(r.fused_sums && r.kparts == 1 && n % 128 == 0 && D % 64 == 0 && (int64_t)n * r.ldz * 8 < ((int64_t)1 << 31)))
     r.fz_mode = 0;
   if ((r.fz_mode != 2 && r.fz_mode != 3) || pd || r.fold || wm.g_ready) r.fz_mode = 0;
-  r.dense = r.fold ? kDenseFolded : wm.g_ready ? kDenseCallerG : r.fz_mode >= 2 ? kDensePersistent : kDenseChain;
+  r.dense = r.fold ? kDenseNoG : wm.g_ready ? kDenseCallerG : r.fz_mode >= 2 ? kDensePersistent : kDenseChain;
   r.model_ksplit = r.kparts > 1 && r.fused_sums;
   // (the caller's samples: see FrWeighted; the correlated Gaussian wants Z - m and forms its own)
   r.caller_z = wm.z_ready != nullptr && (funnel || r.source || r.glm);
@@ -1488,6 +1628,12 @@ static FrRoute fr_route(const vb_ctx* ctx, const ModelDev& m, int64_t n, int64_t
   // 128 x 64 tiles are the launcher's own choice for this shape, made here so that the XCD tile list fits it
   if (r.grad_launch && r.grad_colsums && gemm_count_blocks(s3, 128, 64) * r.splits * 100 >= 190L * n_cu) r.cfg3 = 2;
   r.f_per_tile = r.fused_sums || r.diag_f;
+  if (r.fold) {     // its gradient product: 64 x 64 tiles, two LDS stages, while they fit the chip at once (fr_fold_csplits)
+    r.csplits = fr_fold_csplits(D, n_cu, r.splits + 1);
+    const GemmArgs sc = gemm_product(nullptr, 0, nullptr, 0, D, D, D, 2);
+    if (gemm_count_blocks(sc, 64, 64) * r.csplits <= 4L * n_cu) r.cfgc = 4;
+    else r.cfgc = gemm_count_blocks(sc, 128, 64) * r.csplits * 100 >= 190L * n_cu ? 2 : 3;
+  }
   return r;
 }
 
@@ -1499,6 +1645,7 @@ struct FrBufs {
   double *Z = nullptr, *G = nullptr, *Cpart = nullptr, *colpart = nullptr, *fpart = nullptr;
   double* Rm = nullptr;                                             // regression targets: the residuals
   double *Mpart = nullptr, *bvec = nullptr;                         // folded evaluation: slabs of M = L' P, then M; b = P (mu - m)
+  double *Sg = nullptr, *svec = nullptr, *csg = nullptr;            // ... S = E' E (D x ldl), s = colsum(E), colsum(G)
   double *Xa = nullptr, *T = nullptr, *sq = nullptr;                // path derivative: (L')^-1, a product buffer (then L^-1),
                                                                     // partial sums of squares of the noise
   FrSums S;
@@ -1533,6 +1680,9 @@ static int fr_carve(vb_ctx* ctx, const FrRoute& r, const NoiseSlot& ns, int set,
   b.mu = base + o_mu, b.Lt = base + o_lt, b.Z = base + o_z, b.G = base + o_g, b.Cpart = base + o_cpart;
   b.colpart = base + o_col, b.fpart = base + o_fpart, b.Rm = base + o_r;
   b.Mpart = base + o_mpart, b.bvec = base + o_bvec;
+  // the folded evaluation writes neither Z nor G: S, s and colsum(G) live where G would (n rows of ldz, n >= d + 2); the
+  // slabs of the Gram product and then the slabs of C are the split area's (csplits <= splits + 1)
+  if (r.fold) b.Sg = b.G, b.svec = b.G + slab, b.csg = b.G + slab + ldz;
   b.Xa = base + o_xa, b.T = base + o_t, b.sq = base + o_m2;
   b.S.sums = base + o_sums + (int64_t)set * b.S.len;
   *out = b;
@@ -1666,7 +1816,7 @@ static int fr_model_glm(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const Mo
   return glm_grad_enqueue(ctx, st, m, b.Rm, r.ldr, Z, b.G, r.ldz, r.n, r.D);   // G = R X - Z / sd^2
 }
 
-// the folded evaluation (fr_route): M = L' P and b = P (mu - m), then G = -E M - 1 b'
+// the folded evaluation (fr_route), its part that follows the parameter: M = L' P and b = P (mu - m)
 static int fr_model_folded(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelDev& m) {
   hipStream_t st = ctx->stream;
   const int D = r.D, msplits = r.msplits;
@@ -1679,9 +1829,32 @@ static int fr_model_folded(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const
   hipLaunchKernelGGL(fr_fold_msum_kernel, dim3((unsigned)(nb_sum + nb_b)), dim3(256), 0, st, (const double*)b.Mpart, msplits,
                      r.slab, D, r.ldz, ks, 64, Mres, nb_b, m.p1, (int64_t)m.ldp, (const double*)b.mu, m.p0, b.bvec);
   VB_HIP(ctx, hipGetLastError());
-  GemmArgs g2 = gemm_product(b.E, b.lde, Mres, r.ldz, (int)r.n, D, D, 0);
-  prof_events(ctx, &g2.ev0, &g2.ev1, 1, VB_PROF_FR_MODEL_GEMM);
-  gemm_f64_launch<true>(st, g2, 1, r.n_cu, EpiNegateBias{b.G, r.ldz, b.bvec});
+  return VB_OK;
+}
+
+// ... and its part that follows the noise: S = E' E and s = colsum(E) (the Gram product, timed as VB_PROF_FR_GRAD_GEMM:
+// the gradient product's shape), colsum(G) = -s' M - n b', then the slabs of C = -tril(M' S) - b s' with one partial of
+// sum L o tril(C) per tile and split.  Returns in *tiles3 the number of output tiles of the C product.
+static int fr_grad_folded(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, unsigned* tiles3) {
+  hipStream_t st = ctx->stream;
+  const int D = r.D;
+  const double* M = r.msplits > 1 ? b.Mpart + (int64_t)r.msplits * r.slab : b.Mpart;
+  GemmArgs gs = gemm_product(b.E, b.lde, b.E, b.lde, D, D, (int)r.n, 2);
+  prof_events(ctx, &gs.ev0, &gs.ev1, 1, VB_PROF_FR_GRAD_GEMM);
+  if (r.cfg3 == 2) VB_TRY(tri2_tile_map(ctx, D, 128, 64, &gs.tile_map, &gs.tile_blocks));
+  gemm_f64_launch<false>(st, gs, r.splits, r.n_cu, EpiSplitSlabCs{b.Cpart, r.ldl, r.slab, b.colpart, r.ldz}, r.cfg3);
+  VB_HIP(ctx, hipGetLastError());
+  const int nb_cs = (D + 7) / 8, nb_s = (int)((r.ldz + 255) / 256), tiles = (D + 31) / 32;
+  hipLaunchKernelGGL(fr_fold_ssum_kernel, dim3((unsigned)(nb_cs + nb_s + tiles * (tiles + 1) / 2)), dim3(256), 0, st,
+                     (const double*)b.Cpart, r.splits, r.slab, D, r.ldl, (const double*)b.colpart, r.ldz, M,
+                     (const double*)b.bvec, (double)r.n, nb_cs, nb_s, b.Sg, b.svec, b.csg);
+  VB_HIP(ctx, hipGetLastError());
+  // C[i][j] = sum_k M[k][i] S[k][j]: the gradient product's form, lower tiles, split over k
+  GemmArgs gc = gemm_product(M, r.ldz, b.Sg, r.ldl, D, D, D, 2);
+  if (r.cfgc == 2) VB_TRY(tri2_tile_map(ctx, D, 128, 64, &gc.tile_map, &gc.tile_blocks));
+  *tiles3 = gemm_f64_launch<false>(st, gc, r.csplits, r.n_cu,
+                                   EpiFoldSlabF{b.Cpart, r.ldl, r.slab, b.bvec, b.svec, b.Lt, r.ldl, b.fpart}, r.cfgc);
+  VB_HIP(ctx, hipGetLastError());
   return VB_OK;
 }
 
@@ -1694,7 +1867,7 @@ static int fr_model_gauss_full(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, c
   *G = b.G;
   GemmArgs g2 = gemm_product(b.Z, r.ldz, m.p1, m.ldp, (int)r.n, D, D, 0);
   switch (r.dense) {
-    case kDenseFolded:
+    case kDenseNoG:
       return fr_model_folded(ctx, r, b, m);
     case kDenseCallerG:
       *G = const_cast<double*>(g_ready);
@@ -1756,14 +1929,12 @@ static int fr_score(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelD
 static int fr_grad_product(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const double* G, unsigned* tiles3) {
   hipStream_t st = ctx->stream;
   *tiles3 = 0;
+  if (r.fold) return fr_grad_folded(ctx, r, b, tiles3);      // (no G: from the noise's Gram matrix)
   if (!r.grad_launch) return VB_OK;
   GemmArgs g3 = gemm_product(G, r.ldz, b.E, b.lde, r.D, r.D, (int)r.n, r.tri3);
   prof_events(ctx, &g3.ev0, &g3.ev1, 1, VB_PROF_FR_GRAD_GEMM);
   if (r.cfg3 == 2) VB_TRY(tri2_tile_map(ctx, r.D, 128, 64, &g3.tile_map, &g3.tile_blocks));
-  if (r.fold)      // one partial of sum L o tril(C) per tile and split
-    *tiles3 = gemm_f64_launch<false>(st, g3, r.splits, r.n_cu,
-                                     EpiSplitSlabCsF{b.Cpart, r.ldl, r.slab, b.colpart, r.ldz, b.Lt, r.ldl, b.fpart}, r.cfg3);
-  else if (r.grad_colsums)
+  if (r.grad_colsums)
     *tiles3 = gemm_f64_launch<false>(st, g3, r.splits, r.n_cu, EpiSplitSlabCs{b.Cpart, r.ldl, r.slab, b.colpart, r.ldz}, r.cfg3);
   else
     *tiles3 = gemm_f64_launch<false>(st, g3, r.splits, r.n_cu, EpiSplitSlab{b.Cpart, r.ldl, r.slab});
@@ -1787,19 +1958,22 @@ static int fr_finish_mvt(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, FrSums*
 static int fr_finish_dense(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelDev& m, int set, int n_fpart_red,
                            const double* theta_dev, double* out_dev, int64_t n_total, const FrWeighted& wm) {
   hipStream_t st = ctx->stream;
-  const int D = r.D, n_rb_red = (r.grad_colsums || !r.grad_launch) ? r.splits : r.n_rb;      // one row of column sums per split
+  // one row of column sums per split; the folded evaluation: its slabs of C, the one row colsum(G)
+  const int D = r.D, n_rb_red = r.fold ? 1 : (r.grad_colsums || !r.grad_launch) ? r.splits : r.n_rb;
+  const int splits = r.fold ? r.csplits : r.splits;
+  const double* colpart = r.fold ? b.csg : b.colpart;
   const int64_t red_items = r.slab / 2 > r.ldz ? r.slab / 2 : r.ldz;
   const dim3 red_grid((unsigned)((red_items + 255) / 256) + (r.fold ? 1u : 0u));
   const double *fold_mu = r.fold ? (const double*)b.mu : nullptr, *fold_m = r.fold ? m.p0 : nullptr;
   if (!ctx->comm) {   // single GPU
-    hipLaunchKernelGGL(fr_reduce_packed_kernel<true>, red_grid, dim3(256), 0, st, (const double*)b.Cpart, r.splits, r.slab, D,
-                       r.ldl, (const double*)b.colpart, n_rb_red, r.ldz, (const double*)b.fpart, n_fpart_red, b.S, theta_dev,
+    hipLaunchKernelGGL(fr_reduce_packed_kernel<true>, red_grid, dim3(256), 0, st, (const double*)b.Cpart, splits, r.slab, D,
+                       r.ldl, colpart, n_rb_red, r.ldz, (const double*)b.fpart, n_fpart_red, b.S, theta_dev,
                        (double)n_total, (double)n_total, m.c0, out_dev, r.pd ? 1 : 0, wm, fold_mu, fold_m);
     VB_HIP(ctx, hipGetLastError());
     return VB_OK;
   }
-  hipLaunchKernelGGL(fr_reduce_packed_kernel<false>, red_grid, dim3(256), 0, st, (const double*)b.Cpart, r.splits, r.slab, D,
-                     r.ldl, (const double*)b.colpart, n_rb_red, r.ldz, (const double*)b.fpart, n_fpart_red, b.S, theta_dev,
+  hipLaunchKernelGGL(fr_reduce_packed_kernel<false>, red_grid, dim3(256), 0, st, (const double*)b.Cpart, splits, r.slab, D,
+                     r.ldl, colpart, n_rb_red, r.ldz, (const double*)b.fpart, n_fpart_red, b.S, theta_dev,
                      (double)n_total, (double)n_total, m.c0, out_dev, r.pd ? 1 : 0, wm, fold_mu, fold_m);
   VB_HIP(ctx, hipGetLastError());
   Pipeline& P = ctx->pipe;
@@ -1889,7 +2063,7 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
   VB_TRY(fr_grad_product(ctx, r, b, G, &tiles3));
 
   if (mvt) return fr_finish_mvt(ctx, r, b, sums_out);
-  const int n_fpart_red = r.fold ? (int)tiles3 * r.splits : r.f_per_tile ? (int)tiles2 : r.n_fpart;
+  const int n_fpart_red = r.fold ? (int)tiles3 * r.csplits : r.f_per_tile ? (int)tiles2 : r.n_fpart;
   return fr_finish_dense(ctx, r, b, m, set, n_fpart_red, theta_dev, out_dev, n_total, wm);
 }
 
