@@ -55,6 +55,11 @@ typedef struct vb_ctx vb_ctx;
                                   dparams=[X(n_data x D)|y(n_data)|prior_sd], iparams=[n_data]             */
 
 #define VB_MODEL_SOURCE 4      /* a log density given as HIP source (vb_set_model_source): the adaptor for user models */
+#define VB_MODEL_SOFTMAX 5     /* multinomial logistic (softmax) regression, N(0, sd) prior on every coefficient:
+                                  D = n_classes * p, theta = [b_0 | ... | b_{C-1}] (class-major, b_c of length p)
+                                  dparams=[X(n_data x p)|y(n_data)|prior_sd], iparams=[n_data, n_classes];
+                                  y holds integer labels in [0, n_classes).  Taken by every route that takes a
+                                  VB_MODEL_SOURCE target (per-row f and gradient formed before the streaming pass) */
 
 /* noise kinds for vb_noise_generate */
 /* likelihoods of the regression target VB_MODEL_LOGISTIC (iparams = [n_data, link]; default Bernoulli-logit):
@@ -459,6 +464,10 @@ int vb_psis_smooth(vb_ctx* ctx, const double* lw_in, int64_t n, double reff, dou
 int vb_psis_smooth_batch(vb_ctx* ctx, const double* lw, int64_t n, int64_t m, int64_t ld, double reff,
                          double* out, double* khat);
 int vb_glm_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out);
+/* The same for the bound VB_MODEL_SOFTMAX target: ll_out[s * n_data + i] = eta_{i, y_i} - logsumexp_c eta_ic at
+ * eta_ic = x_i' b_c of draw s (s x d row-major, d = n_classes * p); the prior not included.  VB_ERR_STATE without a
+ * bound model, VB_ERR_UNSUPPORTED for any other model.                                                          */
+int vb_softmax_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out);
 int vb_glm_psis_loo(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const double* log_ratios,
                     const double* log_w, double reff, double* loo, double* khat, double* lpd);
 

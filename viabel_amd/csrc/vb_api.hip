@@ -539,7 +539,7 @@ int vb_destroy(vb_ctx* ctx) {
   for (DeviceBuffer* b : {&ctx->model_params, &ctx->theta, &ctx->workspace, &ctx->sums, &ctx->out,
                           &ctx->scratch, &ctx->scratch2, &ctx->rowvec, &ctx->fr_work, &ctx->fr_theta,
                           &ctx->fr_out, &ctx->dis_state, &ctx->mvt_state, &ctx->mvt_ekl_state, &ctx->lg_work, &ctx->user_params, &ctx->psis_lw, &ctx->psis_work, &ctx->rows_work,
-                          &ctx->lr_work, &ctx->mvt_elbo, &ctx->fit_work, &ctx->glm_work, &ctx->fr_lt, &ctx->bisect_work, &ctx->chi_dev, &ctx->lr_obj, &ctx->gen_geom.buf, &ctx->tri_map, &ctx->mvt_invs, &ctx->temper.buf, &ctx->temper.work, &ctx->fz_words, &ctx->fz_items, &ctx->legacy_work, &ctx->alpha_g, &ctx->mf_one, &ctx->fetch_ticket, &ctx->loo_work, &ctx->chain, &ctx->chain_work})
+                          &ctx->lr_work, &ctx->mvt_elbo, &ctx->fit_work, &ctx->glm_work, &ctx->sm_work,&ctx->fr_lt, &ctx->bisect_work, &ctx->chi_dev, &ctx->lr_obj, &ctx->gen_geom.buf, &ctx->tri_map, &ctx->mvt_invs, &ctx->temper.buf, &ctx->temper.work, &ctx->fz_words, &ctx->fz_items, &ctx->legacy_work, &ctx->alpha_g, &ctx->mf_one, &ctx->fetch_ticket, &ctx->loo_work, &ctx->chain, &ctx->chain_work})
     if (b->ptr) (void)hipFree(b->ptr);
   if (ctx->mvt_pin) (void)hipHostFree(ctx->mvt_pin);
   if (ctx->fetch_host) (void)hipHostFree(ctx->fetch_host);
@@ -825,6 +825,38 @@ int vb_set_model(vb_ctx* ctx, int model_id, int64_t dim, const double* dparams, 
         dev[(size_t)nd * m.ldp + (size_t)j * m.ldq + i] = v;
       }
     for (int64_t i = 0; i < nd; ++i) dev[(size_t)nd * m.ldp + (size_t)dim * m.ldq + i] = dparams[nd * dim + i];
+  } else if (model_id == VB_MODEL_SOFTMAX) {
+    if (n_iparams != 2 || !iparams || !dparams || iparams[0] <= 0 || iparams[1] < 2 || dim % iparams[1] != 0 ||
+        iparams[0] > 0x7fffffffll || dim > 0x7fffffffll ||
+        n_dparams != (size_t)(iparams[0] * (dim / iparams[1]) + iparams[0]) + 1)
+      return fail(ctx, VB_ERR_INVALID,
+                  "softmax regression expects dparams = [X(n_data x p) | y(n_data) | prior_sd], iparams = [n_data, n_classes] "
+                  "and a dimension of n_classes * p");
+    const int64_t nd = iparams[0], nc = iparams[1], p = dim / nc;
+    const double sd = dparams[nd * p + nd];
+    if (!(sd > 0.0)) return fail(ctx, VB_ERR_INVALID, "softmax prior_sd must be positive");
+    for (int64_t i = 0; i < nd; ++i) {
+      const double yi = dparams[nd * p + i];
+      if (!(yi >= 0.0 && yi < (double)nc) || yi != floor(yi))
+        return fail(ctx, VB_ERR_INVALID, "softmax labels must be integers in [0, n_classes) (y[%lld] = %g)", (long long)i, yi);
+    }
+    m.n_data = nd;
+    m.n_classes = (int)nc;
+    m.n_feat = (int)p;
+    m.ldp = round_up(p, 16);
+    m.ldq = round_up(nd, 16);
+    m.tau = sd;
+    m.c0 = 0.0;      // (the rows carry prior and constant themselves, like a source model's: see ModelDev::f0)
+    m.f0 = -(double)dim * (log(sd) + 0.5 * kLog2Pi);
+    // [X (nd x ldp) | X' (p x ldq) | y (ldq)]: the logistic target's layout with p in place of dim
+    dev.assign((size_t)nd * m.ldp + (size_t)p * m.ldq + (size_t)m.ldq, 0.0);
+    for (int64_t i = 0; i < nd; ++i)
+      for (int64_t j = 0; j < p; ++j) {
+        const double v = dparams[i * p + j];
+        dev[(size_t)i * m.ldp + j] = v;
+        dev[(size_t)nd * m.ldp + (size_t)j * m.ldq + i] = v;
+      }
+    for (int64_t i = 0; i < nd; ++i) dev[(size_t)nd * m.ldp + (size_t)p * m.ldq + i] = dparams[nd * p + i];
   } else {
     return fail(ctx, VB_ERR_INVALID, "unknown model id %d", model_id);
   }
@@ -838,6 +870,10 @@ int vb_set_model(vb_ctx* ctx, int model_id, int64_t dim, const double* dparams, 
     if (model_id == VB_MODEL_LOGISTIC) {
       m.p1 = m.p0 + (size_t)m.n_data * m.ldp;
       m.p2 = m.p1 + (size_t)dim * m.ldq;
+    }
+    if (model_id == VB_MODEL_SOFTMAX) {
+      m.p1 = m.p0 + (size_t)m.n_data * m.ldp;
+      m.p2 = m.p1 + (size_t)m.n_feat * m.ldq;
     }
   }
   ctx->model = m;

@@ -72,7 +72,17 @@ struct ModelDev {
   int64_t n_data = 0;           // logistic: observations
   int link = 0;                 // regression target: VB_GLM_* likelihood
   double aux = 1.0;             // VB_GLM_GAUSSIAN: observation noise stdev
+  // VB_MODEL_SOFTMAX (vb_softmax.hip): p0 = X [n_data x ldp], p1 = X' [n_feat x ldq], p2 = y, laid out as for the
+  // logistic target with n_feat in place of dim; tau = prior_sd.  Like a source model it hands every pipeline finished
+  // rows (f, G) with the prior and the constant inside, so c0 -- which the pipelines' epilogues add per sample -- stays 0
+  // and the normalising constant lives in f0.
+  int n_classes = 0;            // softmax: C
+  int n_feat = 0;               // softmax: p (dim = C p)
+  double f0 = 0.0;              // softmax: -C p (log sd + log(2 pi) / 2), added to every row's f
 };
+
+// targets whose rows (f, grad f) are formed before a pipeline's streaming pass and loaded by it (model_rows_enqueue)
+__host__ __device__ __forceinline__ bool model_has_rows(int id) { return id == VB_MODEL_SOURCE || id == VB_MODEL_SOFTMAX; }
 
 // per-observation log-likelihood term (without constants) and its derivative with respect to eta = x' b
 __device__ __forceinline__ double glm_term(int link, double aux, double y, double eta, double* dl) {
@@ -212,6 +222,7 @@ struct vb_ctx {
   std::vector<UserModule> user_modules;
   vb::DeviceBuffer user_params;
   vb::DeviceBuffer glm_work;            // regression targets: split-K slabs of the gradient GEMM
+  vb::DeviceBuffer sm_work;             // softmax target: packed samples, predictors / residuals, packed gradient, partials
   vb::DeviceBuffer mvt_state;           // multivariate-t DIS: state samples X, scratch
   int64_t mvt_n = 0, mvt_d = 0, mvt_n_total = 0;
   int64_t mvt_lq_off = 0;               // where this rank's log q of the residual pass start inside o_lq (the refresh writes them
@@ -434,6 +445,15 @@ int user_model_set(vb_ctx* ctx, int64_t dim, const char* source, const double* p
 int user_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
                       int64_t ldg, double* f);
 void user_model_release(vb_ctx* ctx);
+// softmax regression target (vb_softmax.hip), the contract of user_rows_enqueue: f[row] = f(Z[row]) and, unless G is
+// NULL, G[row] = grad f(Z[row]) (row stride ldg; columns >= d are not written)
+int softmax_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
+                         int64_t ldg, double* f);
+// rows of the bound target by whichever of the two forms them: a source model's kernel or the softmax pipeline
+int model_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
+                       int64_t ldg, double* f);
+// doubles of predictor matrix H one row chunk of the softmax pipeline may hold (mirrored by _lib.SOFTMAX_CHUNK_DOUBLES)
+constexpr int64_t kSoftmaxChunkDoubles = (int64_t)16 << 20;
 struct LegacyFinish;
 // (defer != nullptr: the kernels are enqueued, the state is left untouched and *defer describes the finish -- exact path only,
 // VB_ERR_UNSUPPORTED otherwise)

@@ -1509,7 +1509,7 @@ static FrRoute fr_route(const vb_ctx* ctx, const ModelDev& m, int64_t n, int64_t
   r.mvt = mvt;
   r.pd = pd;
   r.glm = m.id == VB_MODEL_LOGISTIC;
-  r.source = m.id == VB_MODEL_SOURCE;
+  r.source = model_has_rows(m.id);
   r.overlap = !mvt && ctx->comm != nullptr;
   r.n_cu = ctx->prop.multiProcessorCount;
   r.n = n;
@@ -1802,7 +1802,7 @@ static int fr_model_funnel(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const
 
 // the user's row kernel: G and one f per sample (summed with the other f partials)
 static int fr_model_source(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const double* Z) {
-  return user_rows_enqueue(ctx, ctx->stream, Z, r.ldz, r.n, r.D, b.G, r.ldz, b.fpart);
+  return model_rows_enqueue(ctx, ctx->stream, Z, r.ldz, r.n, r.D, b.G, r.ldz, b.fpart);
 }
 
 static int fr_model_glm(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelDev& m, const double* Z) {
@@ -2020,7 +2020,7 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
   const bool pd = (flags & VB_FLAG_PATH_DERIV) != 0;
   if (pd && mvt) return fail(ctx, VB_ERR_UNSUPPORTED, "path derivative: dense Gaussian family only");
   if (m.id != VB_MODEL_GAUSS_DIAG && m.id != VB_MODEL_FUNNEL && m.id != VB_MODEL_GAUSS_FULL && m.id != VB_MODEL_LOGISTIC &&
-      m.id != VB_MODEL_SOURCE)
+      !model_has_rows(m.id))
     return fail(ctx, VB_ERR_UNSUPPORTED, "full-rank path: unsupported model id %d", m.id);
   if (m.dim != d)
     return fail(ctx, VB_ERR_INVALID, "model dimension %d != family dimension %lld", m.dim, (long long)d);

@@ -241,7 +241,9 @@ __global__ void __launch_bounds__(256) lr_sample_kernel(const LrArgs a, double* 
 // ---- the streaming pass --------------------------------------------------------------------------------
 template <int MODEL, int KP>
 __global__ void __launch_bounds__(256) lr_accum_kernel(const LrArgs a) {
-  constexpr bool SRC = MODEL == VB_MODEL_SOURCE;           // g is loaded (the user's kernel made it), not computed
+  // g is loaded, not computed: the user's kernel or the softmax pipeline made it (model_rows_enqueue; both targets are
+  // launched as MODEL = VB_MODEL_SOURCE)
+  constexpr bool SRC = MODEL == VB_MODEL_SOURCE;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int rb = blockIdx.x / a.n_cb, cb = blockIdx.x % a.n_cb;
@@ -565,7 +567,7 @@ static int lr_run(vb_ctx* ctx, const NoiseSlot& ns, const NoiseSlot& nz, int64_t
   hipLaunchKernelGGL((lr_capacitance_kernel<KP>), dim3(1), dim3(KP * KP), 0, st, a);
   VB_HIP(ctx, hipGetLastError());
   const dim3 grid((unsigned)(a.n_rb * a.n_cb));
-  if (m.id == VB_MODEL_SOURCE) {
+  if (model_has_rows(m.id)) {
     // samples as a matrix -> the user's row kernel -> (f, G); the streaming pass then loads G beside the noise
     const int64_t o_x = 0, o_g = round_up(n * a.ld, 16), o_f = o_g + round_up(n * a.ld, 16);
     VB_TRY(ensure(ctx, ctx->lg_work, (size_t)(o_f + round_up(n, 16)) * sizeof(double)));
@@ -574,7 +576,7 @@ static int lr_run(vb_ctx* ctx, const NoiseSlot& ns, const NoiseSlot& nz, int64_t
     VB_HIP(ctx, hipMemsetAsync(G, 0, (size_t)n * a.ld * sizeof(double), st));     // pad columns are streamed too
     hipLaunchKernelGGL((lr_sample_kernel<KP>), dim3((unsigned)n, (unsigned)((d + 255) / 256)), dim3(256), 0, st, a, X);
     VB_HIP(ctx, hipGetLastError());
-    VB_TRY(user_rows_enqueue(ctx, st, X, a.ld, n, (int)d, G, a.ld, frow));
+    VB_TRY(model_rows_enqueue(ctx, st, X, a.ld, n, (int)d, G, a.ld, frow));
     a.G = G, a.frow = frow;
     hipLaunchKernelGGL((lr_accum_kernel<VB_MODEL_SOURCE, KP>), grid, dim3(256), 0, st, a);
   } else if (funnel)
@@ -596,7 +598,7 @@ static int lr_run(vb_ctx* ctx, const NoiseSlot& ns, const NoiseSlot& nz, int64_t
 int lr_elbo_grad_enqueue(vb_ctx* ctx, const NoiseSlot& ns, const NoiseSlot& nz, int64_t n, int64_t d, int64_t k,
                          int64_t n_total, const double* theta_src, double* out) {
   const ModelDev& m = ctx->model;
-  if (m.id != VB_MODEL_GAUSS_DIAG && m.id != VB_MODEL_FUNNEL && m.id != VB_MODEL_SOURCE)
+  if (m.id != VB_MODEL_GAUSS_DIAG && m.id != VB_MODEL_FUNNEL && !model_has_rows(m.id))
     return fail(ctx, VB_ERR_UNSUPPORTED, "low-rank path supports the gauss_diag, funnel and source models (model id %d "
                 "bound)", m.id);
   if (m.dim != d) return fail(ctx, VB_ERR_INVALID, "model dimension %d != family dimension %lld", m.dim, (long long)d);

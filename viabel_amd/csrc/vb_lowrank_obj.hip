@@ -439,7 +439,7 @@ int lro_check(vb_ctx* ctx, const NoiseSlot& ns, const NoiseSlot& nz, int64_t n, 
   if (n <= 0 || n > ns.n || d != ns.d || n > nz.n || k != nz.d || k < 1 || k > kMaxRank)
     return fail(ctx, VB_ERR_INVALID, "noise slots must hold n x d and n x k (1 <= k <= 64) matrices");
   if (ctx->model.id != VB_MODEL_GAUSS_DIAG && ctx->model.id != VB_MODEL_FUNNEL &&
-      ctx->model.id != VB_MODEL_SOURCE)
+      !model_has_rows(ctx->model.id))
     return fail(ctx, VB_ERR_UNSUPPORTED, "low-rank DIS / alpha objectives implement the gauss_diag, funnel and source "
                 "models");
   if (ctx->model.dim != d) return fail(ctx, VB_ERR_INVALID, "model dimension != family dimension");
@@ -559,10 +559,10 @@ int lr_alpha_sums(vb_ctx* ctx, const NoiseSlot& ns, const NoiseSlot& nz, int64_t
                      (const double*)(base + L.o_sig), (const double*)(base + L.o_b), base + L.o_x, L.ld, base + L.o_zp, L.ldk, L.ldt);
   VB_HIP(ctx, hipGetLastError());
   VB_TRY(lro_rows(ctx, L, base, n, d, k, cq, 1, base + L.o_lq));          // T = [t | 1 | log q], t = z - tau
-  const bool source = ctx->model.id == VB_MODEL_SOURCE;
+  const bool source = model_has_rows(ctx->model.id);
   if (source) {      // the user's row kernel gives f and G in one pass (pad columns of G stay zero)
     VB_HIP(ctx, hipMemsetAsync(base + L.o_g, 0, (size_t)n * L.ld * sizeof(double), st));
-    VB_TRY(user_rows_enqueue(ctx, st, base + L.o_x, L.ld, n, (int)d, base + L.o_g, L.ld, base + L.o_f));
+    VB_TRY(model_rows_enqueue(ctx, st, base + L.o_x, L.ld, n, (int)d, base + L.o_g, L.ld, base + L.o_f));
   } else {
     VB_TRY(model_logp_rows(ctx, base + L.o_x, L.ld, n, d, base + L.o_f));
   }

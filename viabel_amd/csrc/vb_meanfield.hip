@@ -1600,7 +1600,7 @@ static int source_accumulate(vb_ctx* ctx, hipStream_t st, const NoiseSlot& ns, c
                      bp.theta_src[0], wsb + ws.off_theta, wsb + ws.off_colp, g.Dp, (const double*)ns.buf.ptr, ns.ld,
                      Z, ldz, n, (int)d);
   VB_HIP(ctx, hipGetLastError());
-  VB_TRY(user_rows_enqueue(ctx, st, Z, ldz, n, (int)d, G, ldz, frow));
+  VB_TRY(model_rows_enqueue(ctx, st, Z, ldz, n, (int)d, G, ldz, frow));
   if (roww) {      // weighted gradient (AlphaDivergence): sum_n w_n g_n = the plain sums of the row-scaled matrix
     hipLaunchKernelGGL(lg_rowscale_kernel, dim3((unsigned)n, (unsigned)((d + 255) / 256)), dim3(256), 0, st, G, ldz, n,
                        (int)d, roww);
@@ -1635,7 +1635,7 @@ int mf_enqueue(vb_ctx* ctx, const MfCall& c) {
     return fail(ctx, VB_ERR_INVALID, "batch size %d outside [1, %d]", c.count, kMaxBatch);
   // `logistic` = "the model's gradient matrix is produced before the streaming pass and loaded by it": the regression
   // targets (two GEMMs) and the source model (the user's row kernel)
-  const bool source = model.id == VB_MODEL_SOURCE;
+  const bool source = model_has_rows(model.id);      // (a source model or the softmax target)
   const bool logistic = model.id == VB_MODEL_LOGISTIC || source;
   // (a source model also takes the weighted-gradient mode of AlphaDivergence: its G is scaled row by row)
   const bool source_weighted = source && c.count == 1 && c.mode == 1 && c.cv_mode == VB_CV_NONE && c.roww[0] != nullptr;

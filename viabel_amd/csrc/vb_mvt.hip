@@ -1133,7 +1133,7 @@ int mvt_dis_refresh(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t n_total
                     double* root_info) {
   int64_t mine = 0;   // this rank's block inside the gathered per-sample vectors (shard_rows)
   VB_TRY(comm_shard_begin(ctx, n, n_total, &mine));
-  if (ctx->model.id != VB_MODEL_GAUSS_DIAG && ctx->model.id != VB_MODEL_FUNNEL && ctx->model.id != VB_MODEL_SOURCE)
+  if (ctx->model.id != VB_MODEL_GAUSS_DIAG && ctx->model.id != VB_MODEL_FUNNEL && !model_has_rows(ctx->model.id))
     return fail(ctx, VB_ERR_UNSUPPORTED, "row log-density implements gauss_diag, funnel and source models");
   if (ctx->model.dim != d) return fail(ctx, VB_ERR_INVALID, "model dimension != family dimension");
   if (n <= 0 || n > ns.n || d != ns.d) return fail(ctx, VB_ERR_INVALID, "noise slot shape mismatch");

@@ -385,7 +385,7 @@ int model_grad_rows(vb_ctx* ctx, const double* x_dev, int64_t ld, int64_t n, int
   hipStream_t st = ctx->stream;
   const int n_cu = ctx->prop.multiProcessorCount;
   VB_HIP(ctx, hipMemsetAsync(g_dev, 0, (size_t)n * ld * sizeof(double), st));
-  if (m.id == VB_MODEL_SOURCE) return user_rows_enqueue(ctx, st, x_dev, ld, n, (int)d, g_dev, ld, f_dev);
+  if (model_has_rows(m.id)) return model_rows_enqueue(ctx, st, x_dev, ld, n, (int)d, g_dev, ld, f_dev);
   if (m.id == VB_MODEL_GAUSS_DIAG || m.id == VB_MODEL_FUNNEL) {
     VB_TRY(model_logp_rows(ctx, x_dev, ld, n, d, f_dev));
     hipLaunchKernelGGL(model_grad_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, x_dev, ld, n, (int)d, m,
@@ -438,7 +438,7 @@ int model_logp_rows(vb_ctx* ctx, const double* x_dev, int64_t ld, int64_t n, int
                     double* out_dev) {
   if (ctx->model.id == VB_MODEL_GAUSS_FULL) return gauss_full_rows(ctx, x_dev, ld, n, d, out_dev);
   if (ctx->model.id == VB_MODEL_LOGISTIC) return logistic_rows(ctx, x_dev, ld, n, d, out_dev);
-  if (ctx->model.id == VB_MODEL_SOURCE) return user_rows_enqueue(ctx, ctx->stream, x_dev, ld, n, (int)d, nullptr, 0, out_dev);
+  if (model_has_rows(ctx->model.id)) return model_rows_enqueue(ctx, ctx->stream, x_dev, ld, n, (int)d, nullptr, 0, out_dev);
   if (ctx->model.id != VB_MODEL_GAUSS_DIAG && ctx->model.id != VB_MODEL_FUNNEL)
     return fail(ctx, VB_ERR_UNSUPPORTED, "row log-density: unknown model id %d", ctx->model.id);
   const unsigned grid = (unsigned)((n + 4 * kRowsPerWave - 1) / (4 * kRowsPerWave));

@@ -187,7 +187,7 @@ int rowstats_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, con
                      double* out_f, double* out_b, const ModelDev* prior, double* out_prior) {
   hipLaunchKernelGGL(rs_cols_kernel, dim3(1), dim3(256), 0, ctx->stream, theta_src, (int)d, ns.ld, cols, scal);
   VB_HIP(ctx, hipGetLastError());
-  if (model.id == VB_MODEL_SOURCE) {
+  if (model_has_rows(model.id)) {
     // the row kernel forms the base log density b_n as for any target (its own f is thrown away: a diagonal
     // Gaussian over memory that exists); f_n comes from the user's kernel on the materialised samples
     ModelDev stand_in;
@@ -205,7 +205,7 @@ int rowstats_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, con
     hipLaunchKernelGGL(rs_sample_kernel, dim3((unsigned)n, (unsigned)((d + 255) / 256)), dim3(256), 0, ctx->stream,
                        theta_src, (const double*)ns.buf.ptr, ns.ld, Z, ldz, n, (int)d);
     VB_HIP(ctx, hipGetLastError());
-    return user_rows_enqueue(ctx, ctx->stream, Z, ldz, n, (int)d, nullptr, 0, out_f);
+    return model_rows_enqueue(ctx, ctx->stream, Z, ldz, n, (int)d, nullptr, 0, out_f);
   }
   hipLaunchKernelGGL(rs_rowstats_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream,
                      (const double*)ns.buf.ptr, ns.ld, n, (int)d, (const double*)cols, model, student, df,
@@ -220,7 +220,7 @@ int rowstats_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, con
 int alpha_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t n_total, int64_t d, int family, double df,
                   double alpha, const double* theta_src, double* out) {
   if (!(alpha != 0.0)) return fail(ctx, VB_ERR_INVALID, "alpha must be non-zero");
-  if (ctx->model.id != VB_MODEL_GAUSS_DIAG && ctx->model.id != VB_MODEL_FUNNEL && ctx->model.id != VB_MODEL_SOURCE)
+  if (ctx->model.id != VB_MODEL_GAUSS_DIAG && ctx->model.id != VB_MODEL_FUNNEL && !model_has_rows(ctx->model.id))
     return fail(ctx, VB_ERR_UNSUPPORTED, "mean-field alpha-divergence supports the gauss_diag, funnel and source models");
   if (ctx->model.dim != d) return fail(ctx, VB_ERR_INVALID, "model dimension != family dimension");
   if (n <= 0 || n > ns.n || d != ns.d || n_total < n) return fail(ctx, VB_ERR_INVALID, "noise slot shape mismatch");
@@ -676,7 +676,7 @@ int dis_refresh_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t n_t
                         double* logp_host, double* logq_host) {
   int64_t mine = 0;   // this rank's block inside the gathered per-sample vectors (shard_rows)
   VB_TRY(comm_shard_begin(ctx, n, n_total, &mine));
-  if (ctx->model.id != VB_MODEL_GAUSS_DIAG && ctx->model.id != VB_MODEL_FUNNEL && ctx->model.id != VB_MODEL_SOURCE)
+  if (ctx->model.id != VB_MODEL_GAUSS_DIAG && ctx->model.id != VB_MODEL_FUNNEL && !model_has_rows(ctx->model.id))
     return fail(ctx, VB_ERR_UNSUPPORTED, "mean-field DIS supports the gauss_diag, funnel and source models");
   if (ctx->model.dim != d) return fail(ctx, VB_ERR_INVALID, "model dimension != family dimension");
   if (n <= 0 || n > ns.n || d != ns.d) return fail(ctx, VB_ERR_INVALID, "noise slot shape mismatch");
@@ -706,7 +706,7 @@ int dis_refresh_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t n_t
   prior.p1 = base + L.o_prior + ld;
 
   // (built-in targets: the tempering prior's log density comes out of the same pass; a source model's pass is its own)
-  const bool fused_prior = ctx->model.id != VB_MODEL_SOURCE;
+  const bool fused_prior = !model_has_rows(ctx->model.id);
   VB_TRY(rowstats_enqueue(ctx, ns, n, d, theta_src, ctx->model, student, df, base + L.o_cols, base + L.o_scal,
                           base + L.o_lp + mine, base + L.o_b + mine, fused_prior ? &prior : nullptr,
                           base + L.o_lprior + mine));

@@ -13,8 +13,8 @@ import numpy as np
 from . import _lib
 
 __all__ = ['Model', 'DeviceModel', 'GaussianModel', 'FunnelModel', 'CorrelatedGaussianModel',
-           'LogisticRegressionModel', 'PoissonRegressionModel', 'LinearRegressionModel', 'SourceModel',
-           'CallableModel']
+           'LogisticRegressionModel', 'PoissonRegressionModel', 'LinearRegressionModel', 'SoftmaxRegressionModel',
+           'SourceModel', 'CallableModel']
 
 
 class Model(object):
@@ -391,3 +391,70 @@ class LinearRegressionModel(LogisticRegressionModel):
         return (_lib.MODEL_LOGISTIC, self._dim,
                 np.concatenate([self.X.ravel(), self.y, [self.prior_sd, self.noise_sd]]),
                 np.array([self.X.shape[0], _lib.GLM_GAUSSIAN], dtype=np.int64))
+
+
+class SoftmaxRegressionModel(DeviceModel):
+    """Bayesian multinomial logistic (softmax) regression ``y_i ~ Categorical(softmax(x_i' b_0, ..., x_i' b_{C-1}))``.
+
+    ``X`` is ``(n_data, p)``, ``y`` holds integer labels in ``[0, n_classes)`` (an integer array, or a float array
+    with integral values).  ``dim = n_classes * p`` and the parameter is **class-major**:
+    ``theta = [b_0 | b_1 | ... | b_{C-1}]``, each ``b_c`` of length ``p``.  All ``C p`` coordinates are free and carry
+    the ``N(0, prior_sd)`` prior -- no reference class is pinned: the likelihood is invariant under adding one vector
+    to every ``b_c`` and the prior alone fixes that direction, so compare fits through the differences
+    ``b_c - b_0``.  For ``C = 2`` the likelihood equals the logistic one at ``beta = b_1 - b_0``.  There is no
+    intercept: add a column of ones to ``X``.  Log density, normalised in ``theta``::
+
+        eta_ic   = x_i' b_c
+        f(theta) = sum_i [eta_{i, y_i} - logsumexp_c eta_ic] - |theta|^2 / (2 sd^2) - C p (log sd + log(2 pi) / 2)
+        df/db_c  = sum_i ([y_i = c] - softmax_c(eta_i)) x_i - b_c / sd^2
+
+    The classes of an observation are coupled, so this is not an epilogue of one GEMM: the engine packs the class
+    blocks of every sample as rows, forms all predictors with one fp64 MFMA product, runs a coupling kernel
+    (max-subtracted logsumexp, residuals in place) and takes the gradient with the regression targets' second product
+    (``csrc/vb_softmax.hip``, ``DESIGN.md``).  To every objective it looks like a :class:`SourceModel` -- per-sample
+    ``f`` and gradient formed before the streaming pass -- and is accepted wherever one is: ``ExclusiveKL`` (both
+    estimator forms, the RGE control variates, ``NVPFlow``), ``AlphaDivergence`` and ``DISInclusiveKL`` with every
+    family, ``bbvi``, ``vi_diagnostics`` and the device-resident fit.  Not in the reference."""
+
+    def __init__(self, X, y, n_classes, prior_sd=10.0):
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y_in = np.asarray(y)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1 or y_in.shape != (X.shape[0],):
+            raise ValueError('X must be (n_data, p) and y (n_data,)')
+        if isinstance(n_classes, bool) or int(n_classes) != n_classes or int(n_classes) < 2:
+            raise ValueError('n_classes must be an integer >= 2')
+        n_classes = int(n_classes)
+        if y_in.dtype.kind not in 'iuf':
+            raise ValueError('y must hold integer labels (an integer array, or floats with integral values)')
+        y = y_in.astype(np.float64)
+        if not np.all(np.isfinite(y)) or np.any(y != np.floor(y)):
+            raise ValueError('y must hold integral labels')
+        if np.any(y < 0) or np.any(y >= n_classes):
+            raise ValueError('labels must lie in [0, n_classes)')
+        if not prior_sd > 0:
+            raise ValueError('prior_sd must be positive')
+        self.X, self.y, self.prior_sd = X, y, float(prior_sd)
+        self._n_classes = n_classes
+        super().__init__(n_classes * X.shape[1])
+
+    def _build_spec(self):
+        return (_lib.MODEL_SOFTMAX, self._dim, np.concatenate([self.X.ravel(), self.y, [self.prior_sd]]),
+                np.array([self.X.shape[0], self._n_classes], dtype=np.int64))
+
+    @property
+    def n_data(self):
+        return self.X.shape[0]
+
+    @property
+    def n_classes(self):
+        return self._n_classes
+
+    def pointwise_log_likelihood(self, x):
+        """``log p(y_i | theta_s) = eta_{i, y_i} - logsumexp_c eta_ic`` for every draw (row of ``x``) and observation:
+        ``(S, n_data)``, the ``log_lik`` argument of :func:`psisloo` (``psisloo(log_lik, log_ratios)`` is this model's
+        route to LOO; ``loo()`` takes the one-predictor regression targets only).  Without the prior
+        (``vb_softmax_pointwise``).  ``x``: (S, D), or (D,) for one draw."""
+        x, _ = self._rows(x)
+        eng = _lib.default_engine()
+        eng.set_model(self.device_spec())
+        return eng.softmax_pointwise(x, self.n_data)

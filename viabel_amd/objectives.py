@@ -363,7 +363,7 @@ class ExclusiveKL(StochasticVariationalObjective):
                         _NOISE_SLOT, end - begin, approx.dim, var_param, family, approx._seed,
                         approx._next_philox_stream(), df=df, flags=flags, cv_mode=cv_mode, n_total=N, row_offset=begin)
                 n_local, n_total = self._stage_noise(eng, self.num_mc_samples)
-                if cv_mode != 0 and spec[0] == _lib.MODEL_SOURCE:
+                if cv_mode != 0 and spec[0] in _lib.MODELS_WITH_ROWS:
                     # a user model's Hessian is not one of the device epilogue's closed forms: plain sums on the
                     # device, the model's derivatives at the mean from its own device gradient (_source_model_cv)
                     value, grad = eng.elbo_grad_meanfield(_NOISE_SLOT, n_local, approx.dim, var_param, family,
@@ -545,7 +545,7 @@ class ExclusiveKL(StochasticVariationalObjective):
         if isinstance(approx, LRGaussian):
             return (approx.rng == 'philox' and 1 <= approx.k <= 16 and not self._use_path_deriv
                     and self.hessian_approx_method is None)     # the path-derivative correction is host algebra
-        if self.hessian_approx_method is not None and self.model.device_spec()[0] == _lib.MODEL_SOURCE:
+        if self.hessian_approx_method is not None and self.model.device_spec()[0] in _lib.MODELS_WITH_ROWS:
             return False                 # control variates of a source model combine host-side (_source_model_cv)
         return (isinstance(approx, (MFGaussian, MFStudentT, FullRankGaussian)) and approx.rng == 'philox'
                 and not (isinstance(approx, FullRankGaussian) and self.hessian_approx_method is not None))
