@@ -86,6 +86,10 @@ typedef struct vb_ctx vb_ctx;
 const char* vb_version(void);
 int vb_device_count(int* count);
 int vb_create(int device_id, vb_ctx** out);
+/* Waits for the context's streams, then releases everything the context holds: every device buffer, page-locked
+ * block, event and stream of the engine is owned by a member of the context (or of an NVPFlow handle it lists) and is
+ * released with it -- there is no list to keep.  A parked DIS state (vb_dis_state_park) owns its buffers itself and
+ * outlives the context.  NULL: a no-op.                                                                              */
 int vb_destroy(vb_ctx* ctx);
 /* text of the last failure on `ctx` (ctx == NULL: last failure of vb_create / vb_device_count) */
 const char* vb_last_error(vb_ctx* ctx);
@@ -350,6 +354,12 @@ int vb_dis_scalars_get(vb_ctx* ctx, double out[4]);
  * viabel_amd/_lib.py, PinnedPool -- the reference returns freshly allocated numpy arrays, objectives.py:32-44).        */
 int vb_host_alloc(size_t bytes, void** ptr);
 int vb_host_free(void* ptr);      /* NULL: a no-op, as free(NULL) */
+/* GPU resources the engine holds in this process right now, over all contexts, NVPFlow handles and parked DIS states:
+ * out = [device buffers, page-locked blocks, events, streams].  After the last of them is destroyed every count is back
+ * where it stood before the first was created -- the way to observe a release on a device shared with other work (free
+ * memory as the runtime reports it is device-wide).  Blocks from vb_host_alloc belong to the caller and are not counted;
+ * nor are the windows of the IPC transport.  Any thread, no context.                                                   */
+int vb_resource_counts(uint64_t out[4]);
 /* The DIS state samples live in the context, one set per family kind (0: mean-field, 1: MultivariateT / dense
  * Gaussian, 2: low-rank Gaussian); every refresh of a kind overwrites its set and bumps its generation counter.  A
  * caller that keeps weights for a later vb_dis_grad_* call compares the counter with the one it saw after its own

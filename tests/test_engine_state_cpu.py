@@ -1,6 +1,7 @@
 """CPU: bookkeeping of the engine's state that no GPU test would notice going wrong.
 
-- ``vb_destroy`` frees every device buffer of the context (a buffer it does not name leaks with every destroyed engine);
+- every GPU resource is held by an owning type, so ``vb_destroy`` has no list from which a buffer could be missing
+  (``tests/test_gpu_engine_resources.py`` counts the live resources on the GPU);
 - the noise slots the objectives keep state in between calls are distinct, so that objectives of different kinds taking
   turns on one engine never read each other's draws (``tests/test_gpu_shared_engine.py`` runs the interleavings)."""
 import os
@@ -29,42 +30,46 @@ def _block(src, opener):
     raise AssertionError('unbalanced braces after ' + opener)
 
 
-def ctx_device_buffers():
-    """Every ``DeviceBuffer`` member of ``struct vb_ctx``, nested structs' members qualified (``temper.buf``)."""
-    with open(os.path.join(CSRC, 'vb_common.h')) as f:
-        body = _block(_strip_comments(f.read()), 'struct vb_ctx {')
-    levels = [[]]           # DeviceBuffer members of the struct being read, innermost last
-    text, inner = '', None
-    for tok in re.split(r'([{};])', body):
-        if tok == '{':      # a nested struct, or a braced initializer
-            levels.append([])
-            text, inner = '', None
-        elif tok == '}':
-            inner = levels.pop()
-            text = ''
-        elif tok == ';':
-            if inner is not None:       # `} member;` ends a nested struct: its buffers are the member's
-                member = re.fullmatch(r'\s*(\w+)(?:\[\w*\])?\s*', text)
-                if member:
-                    levels[-1].extend(member.group(1) + '.' + n for n in inner)
-            else:
-                m = re.match(r'\s*(?:vb::)?DeviceBuffer\s+(.+)$', text, flags=re.S)
-                if m:
-                    levels[-1].extend(re.match(r'\s*(\w+)', decl).group(1) for decl in m.group(1).split(','))
-            text, inner = '', None
-        else:
-            text += tok
-    assert len(levels) == 1
-    return levels[0]
+# the runtime calls that make or release a device buffer, a page-locked block, an event or a stream
+RESOURCE_API = [r'\bhipMalloc\(', r'\bhipFree\(', r'\bhipHostMalloc\(', r'\bhipHostFree\(', r'\bhipEventCreate',
+                r'\bhipEventDestroy\(', r'\bhipStreamCreate', r'\bhipStreamDestroy\(']
+RESOURCE_HEADER = 'vb_resource.h'
+# ... and the only functions outside the resource header that may use them
+ALLOWED = [('vb_comm.hip', 'int vb_comm_ipc_window('),         # IPC set-up: a protocol with the peers,
+           ('vb_comm.hip', 'int vb_comm_destroy('),            # ... and its teardown
+           ('vb_comm.hip', 'int vb_comm_allreduce_time('),     # two local timing events
+           ('vb_api.hip', 'int vb_host_alloc('),               # blocks that belong to the caller
+           ('vb_api.hip', 'int vb_host_free(')]
+CTX_ALIASES = {'mvt_ev_fork', 'result_stream'}                 # non-owning handles of vb_ctx
 
 
-def test_destroy_frees_every_device_buffer_of_the_context():
-    buffers = ctx_device_buffers()
-    assert {'dis_state', 'mvt_state', 'lr_obj', 'temper.buf', 'temper.work', 'fz_words', 'fz_items'} <= set(buffers), buffers
-    with open(os.path.join(CSRC, 'vb_api.hip')) as f:
-        destroy = _block(_strip_comments(f.read()), 'int vb_destroy(vb_ctx* ctx)')
-    missing = [b for b in buffers if not re.search(r'ctx->' + re.escape(b) + r'\b', destroy)]
-    assert not missing, 'vb_destroy does not free: ' + ', '.join(missing)
+def _uses(text):
+    return [pat for pat in RESOURCE_API if re.search(pat, text)]
+
+
+def test_resources_are_owned_by_the_resource_types():
+    """Ownership is in the types of vb_resource.h, so that ``delete ctx`` releases everything and a new buffer cannot be
+    forgotten: nothing else in the engine allocates, creates, frees or destroys, ``vb_destroy`` least of all, and the
+    context keeps no raw event or stream of its own."""
+    sources = {}
+    for name in sorted(os.listdir(CSRC)):
+        if name.endswith(('.hip', '.h', '.cpp')):
+            with open(os.path.join(CSRC, name)) as f:
+                sources[name] = _strip_comments(f.read())
+    assert _uses(sources[RESOURCE_HEADER])
+    destroy = _block(sources['vb_api.hip'], 'int vb_destroy(vb_ctx* ctx)')
+    assert not _uses(destroy), _uses(destroy)
+    assert 'delete ctx' in destroy
+    for name, opener in ALLOWED:
+        body = _block(sources[name], opener)
+        assert _uses(body), 'stale allow-list entry: %s %s' % (name, opener)
+        sources[name] = sources[name].replace(body, '')
+    stray = {name: _uses(text) for name, text in sources.items() if name != RESOURCE_HEADER and _uses(text)}
+    assert not stray, stray
+    ctx = _block(sources['vb_common.h'], 'struct vb_ctx {')
+    raw = [re.match(r'\W*(\w+)', decl).group(1)
+           for m in re.finditer(r'\bhip(?:Event|Stream)_t\b([^;(]*);', ctx) for decl in m.group(1).split(',')]
+    assert set(raw) == CTX_ALIASES, raw
 
 
 def test_objective_state_slots_are_distinct():

@@ -9,25 +9,18 @@ kinds): each objective's values and gradients must be EXACTLY what it computes a
 fixed order -- or, where an interleaving cannot be served, the call raises an ``EngineError`` that names the remedy.  Never
 another number.  The anchor at the end compares interleaved runs with the oracle, so the numbers are the reference's and not
 merely repeatable ones."""
-import contextlib
 import itertools
 
 import numpy as np
 import pytest
 
 import _golden as G
+from _engine_subjects import CALLS, D, N, SUBJECTS, Runner, _fresh_engine, _problem
 from oracle import families as ofam
 from oracle import models as omod
 from oracle import objectives as oobj
 
 pytestmark = pytest.mark.gpu
-
-D, N = 48, 4200         # one shape for every subject: each cross-kind overwrite fits the shape checks
-CALLS = 6
-
-# DIS subjects keep weights between refreshes (num_resampling_batches > 1): kind 0 (mean-field), 1 (dense), 2 (low-rank)
-SUBJECTS = ['dis_mf_np', 'dis_mft_px', 'dis_fr_px', 'dis_mvt_np', 'dis_lr',
-            'ekl_mf_px', 'ekl_mvt_np', 'ekl_lr', 'ekl_nvp', 'alpha_fr_px']
 
 
 @pytest.fixture(scope='module')
@@ -38,92 +31,10 @@ def vb():
     return viabel_amd
 
 
-@contextlib.contextmanager
-def _fresh_engine():
-    """A new engine as the process's default for the objectives made inside: every case (and every solo run) starts from
-    an empty engine, so one case's leftovers cannot decide another's outcome."""
-    from viabel_amd import _lib
-    old, eng = _lib.default_engine(), _lib.Engine(0)
-    _lib.set_default_engine(eng)
-    try:
-        yield eng
-    finally:
-        _lib.set_default_engine(old)
-        eng.close()
-
-
 @pytest.fixture
 def engine(vb):
     with _fresh_engine() as eng:
         yield eng
-
-
-def _problem(d):
-    rng = np.random.RandomState(3 + d)
-    model_mean, model_sd = 0.2 * rng.randn(d), np.exp(0.1 * rng.randn(d))
-    A = rng.randn(d, d)
-    th_ch = np.concatenate([0.1 * rng.randn(d), ofam.psd_to_free(0.7 * (A @ A.T / d + np.eye(d)))])
-    th_mf = np.concatenate([0.1 * rng.randn(d), -0.5 + 0.1 * rng.randn(d)])
-    prior = np.concatenate([np.zeros(d), 0.3 * np.ones(d)])
-    return model_mean, model_sd, th_ch, th_mf, prior
-
-
-def make(vb, sid, variant=0, d=D, n=N):
-    """A fresh objective of subject `sid` and its starting parameter.  `variant` 1 is a second objective of the same
-    subject (other family seed); `d`, `n` another shape."""
-    model_mean, model_sd, th_ch, th_mf, prior = _problem(d)
-    model = vb.GaussianModel(model_mean, model_sd)
-    seed = 1 + 10 * variant
-    dis = dict(ess_target=n // 6, temper_prior=vb.MFGaussian(d), temper_prior_params=prior, use_resampling=True)
-    if sid == 'dis_mf_np':
-        return vb.DISInclusiveKL(vb.MFGaussian(d, seed=seed), model, n, num_resampling_batches=3, **dis), th_mf
-    if sid == 'dis_mft_px':
-        return vb.DISInclusiveKL(vb.MFStudentT(d, 7.0, seed=seed, rng='philox'), model, n, num_resampling_batches=3,
-                                 **dis), th_mf
-    if sid == 'dis_fr_px':
-        return vb.DISInclusiveKL(vb.FullRankGaussian(d, seed=seed, rng='philox'), model, n, num_resampling_batches=2,
-                                 **dis), th_ch
-    if sid == 'dis_mvt_np':
-        return vb.DISInclusiveKL(vb.MultivariateT(d, 9.0, seed=seed), model, n, num_resampling_batches=2, **dis), th_ch
-    if sid == 'dis_lr':
-        fam = vb.LRGaussian(d, seed=seed, k=3)
-        return (vb.DISInclusiveKL(fam, model, n, num_resampling_batches=2, **dis),
-                fam.pack(np.zeros(d), -0.5 * np.ones(d), 0.1 * np.ones((d, 3))))
-    if sid == 'ekl_mf_px':
-        return vb.ExclusiveKL(vb.MFGaussian(d, seed=seed, rng='philox'), model, n), th_mf
-    if sid == 'ekl_mvt_np':
-        return vb.ExclusiveKL(vb.MultivariateT(d, 9.0, seed=seed), model, n, use_path_deriv=True), th_ch
-    if sid == 'ekl_lr':
-        fam = vb.LRGaussian(d, seed=seed, k=3)
-        return vb.ExclusiveKL(fam, model, n), fam.pack(np.zeros(d), -0.5 * np.ones(d), 0.1 * np.ones((d, 3)))
-    if sid == 'ekl_nvp':
-        masks = np.array([[(j + i) % 2 for j in range(d)] for i in range(2)], dtype=float)
-        flow = vb.NVPFlow([[d, 32], [32, d]], [[d, 32], [32, d]], masks, vb.MFStudentT(d, 5.0, seed=seed),
-                          np.zeros(2 * d), d)
-        return vb.ExclusiveKL(flow, model, n), 0.05 * np.random.RandomState(7).randn(flow.var_param_dim)
-    if sid == 'alpha_fr_px':
-        return vb.AlphaDivergence(vb.FullRankGaussian(d, seed=seed, rng='philox'), model, n, 0.5), th_ch
-    raise ValueError(sid)
-
-
-def _np_seed(sid, variant=0, d=D):
-    return 1000 + 37 * SUBJECTS.index(sid) + 7 * variant + d
-
-
-class Runner:
-    """One objective's turns: it gets back the global numpy generator it would see alone before each call."""
-
-    def __init__(self, vb, sid, variant=0, d=D, n=N):
-        self.obj, self.th = make(vb, sid, variant, d, n)
-        self.state = np.random.RandomState(_np_seed(sid, variant, d)).get_state()
-        self.out = []
-
-    def step(self):
-        np.random.set_state(self.state)
-        v, g = self.obj(self.th)
-        self.state = np.random.get_state()
-        self.out.append((v, g.copy()))
-        self.th = self.th - 0.01 * g / (1.0 + np.abs(g))
 
 
 _SOLO = {}

@@ -232,6 +232,7 @@ SIGNATURES = {
     'vb_dis_state_drop': (ctypes.c_int, [ctypes.c_void_p]),
     'vb_host_alloc': (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]),
     'vb_host_free': (ctypes.c_int, [ctypes.c_void_p]),
+    'vb_resource_counts': (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
     'vb_comm_allreduce_time': (ctypes.c_int, [_ctx_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     'vb_comm_unique_id': (ctypes.c_int, [ctypes.c_char_p]),
     'vb_comm_init': (ctypes.c_int, [_ctx_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]),
@@ -327,6 +328,15 @@ def device_count():
     """GPUs visible to HIP (0 without one)."""
     n = ctypes.c_int(0)
     return n.value if load().vb_device_count(ctypes.byref(n)) == VB_OK else 0
+
+
+def resource_counts():
+    """``(device buffers, pinned blocks, events, streams)`` the engine holds in this process (``vb_resource_counts``):
+    back at their earlier values once every engine, flow and parked DIS state created since has been released."""
+    out = (ctypes.c_uint64 * 4)()
+    if load().vb_resource_counts(out) != VB_OK:
+        raise EngineError('vb_resource_counts failed')
+    return tuple(int(v) for v in out)
 
 
 class PinnedPool:

@@ -31,9 +31,7 @@ int ensure(vb_ctx* ctx, DeviceBuffer& b, size_t bytes) {
   if (b.ptr) {
     // buffers may still be referenced by work in flight on any of the context's streams
     VB_TRY(sync_streams(ctx));
-    VB_HIP(ctx, hipFree(b.ptr));
-    b.ptr = nullptr;
-    b.bytes = 0;
+    VB_HIP(ctx, b.release());
     if (&b == &ctx->mvt_state) {      // caches keyed on the state buffer: a new allocation may return the old address
       ctx->mvt_prior.clear();
       ctx->mvt_inv_key[0] = 0;
@@ -44,24 +42,21 @@ int ensure(vb_ctx* ctx, DeviceBuffer& b, size_t bytes) {
     }
   }
   size_t cap = bytes < 256 ? 256 : bytes;
-  VB_HIP(ctx, hipMalloc(&b.ptr, cap));
+  VB_HIP(ctx, b.alloc(cap));
   VB_HIP(ctx, hipMemsetAsync(b.ptr, 0, cap, ctx->stream));
-  b.bytes = cap;
+  return VB_OK;
+}
+
+int ensure_pinned(vb_ctx* ctx, PinnedBuffer& b, size_t bytes, bool mapped) {
+  VB_HIP(ctx, b.release());
+  VB_HIP(ctx, b.alloc(bytes, mapped));
   return VB_OK;
 }
 
 int ensure_pinned(vb_ctx* ctx, size_t bytes) {
-  if (ctx->pin_host && ctx->pin_bytes >= bytes) return VB_OK;
-  if (ctx->pin_host) {
-    VB_TRY(sync_streams(ctx));
-    VB_HIP(ctx, hipHostFree(ctx->pin_host));
-    ctx->pin_host = nullptr;
-    ctx->pin_bytes = 0;
-  }
-  VB_HIP(ctx, hipHostMalloc((void**)&ctx->pin_host, bytes, hipHostMallocMapped));
-  VB_HIP(ctx, hipHostGetDevicePointer((void**)&ctx->pin_dev, ctx->pin_host, 0));
-  ctx->pin_bytes = bytes;
-  return VB_OK;
+  if (ctx->pin.bytes >= bytes) return VB_OK;
+  if (ctx->pin.host) VB_TRY(sync_streams(ctx));
+  return ensure_pinned(ctx, ctx->pin, bytes, true);
 }
 
 // ---- small results to the host without a copy engine and without a wake-up ------------------------------------------------
@@ -119,18 +114,11 @@ int fetch_plan(vb_ctx* ctx, const FetchSeg* segs, int n_segs, FetchPlan* plan) {
   const char* e = getenv("VB_FETCH_FLAGSYNC");
   if (!ok || total > kFetchMaxBytes || (e && atoi(e) == 0)) return VB_OK;
   const size_t need = total + 64;      // ... | completion word (a line of its own)
-  if (ctx->fetch_bytes < need) {
-    if (ctx->fetch_host) {
-      VB_TRY(sync_streams(ctx));
-      VB_HIP(ctx, hipHostFree(ctx->fetch_host));
-      ctx->fetch_host = nullptr;
-      ctx->fetch_bytes = 0;
-    }
+  if (ctx->fetch_pin.bytes < need) {
+    if (ctx->fetch_pin.host) VB_TRY(sync_streams(ctx));
     const size_t cap = need < (size_t)1 << 16 ? (size_t)1 << 16 : need;
-    VB_HIP(ctx, hipHostMalloc((void**)&ctx->fetch_host, cap, hipHostMallocMapped));
-    memset(ctx->fetch_host, 0, cap);
-    VB_HIP(ctx, hipHostGetDevicePointer((void**)&ctx->fetch_dev, ctx->fetch_host, 0));
-    ctx->fetch_bytes = cap;
+    VB_TRY(ensure_pinned(ctx, ctx->fetch_pin, cap, true));
+    memset(ctx->fetch_pin.host, 0, cap);
   }
   VB_TRY(ensure(ctx, ctx->fetch_ticket, 64));      // (zero-filled when new; the kernels leave it zero)
   long long at = 0;
@@ -140,9 +128,9 @@ int fetch_plan(vb_ctx* ctx, const FetchSeg* segs, int n_segs, FetchPlan* plan) {
   }
   plan->first[n_segs] = at;
   plan->n = n_segs;
-  plan->host = (unsigned long long*)ctx->fetch_host;
-  plan->dev = (unsigned long long*)ctx->fetch_dev;
-  plan->o_done = ctx->fetch_bytes / 8 - 8;
+  plan->host = ctx->fetch_pin.host_as<unsigned long long>();
+  plan->dev = ctx->fetch_pin.dev_as<unsigned long long>();
+  plan->o_done = ctx->fetch_pin.bytes / 8 - 8;
   plan->done_dev = plan->dev + plan->o_done;
   plan->ticket = (unsigned*)ctx->fetch_ticket.ptr;
   plan->seq = ++ctx->fetch_seq;
@@ -226,29 +214,24 @@ int push_small(vb_ctx* ctx, hipStream_t st, const void* host_src, size_t bytes, 
     return VB_OK;
   }
   if (ctx->push_bytes < bytes) {
-    if (ctx->push_host) {
-      VB_TRY(sync_streams(ctx));
-      VB_HIP(ctx, hipHostFree(ctx->push_host));
-      ctx->push_host = nullptr;
-      ctx->push_bytes = 0;
-    }
+    if (ctx->push_pin.host) VB_TRY(sync_streams(ctx));
+    ctx->push_bytes = 0;
     const size_t cap = bytes < (size_t)1 << 16 ? (size_t)1 << 16 : (bytes + 63) / 64 * 64;
-    VB_HIP(ctx, hipHostMalloc((void**)&ctx->push_host, 2 * cap, hipHostMallocMapped));
-    VB_HIP(ctx, hipHostGetDevicePointer((void**)&ctx->push_dev, ctx->push_host, 0));
+    VB_TRY(ensure_pinned(ctx, ctx->push_pin, 2 * cap, true));
     ctx->push_bytes = cap;
   }
   ctx->push_slot ^= 1;
-  hipEvent_t& ev = ctx->push_ev[ctx->push_slot];
-  if (!ev) VB_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  Event& ev = ctx->push_ev[ctx->push_slot];
+  if (!ev) VB_HIP(ctx, ev.create(hipEventDisableTiming));
   else VB_HIP(ctx, hipEventSynchronize(ev));
-  char* slot = (char*)ctx->push_host + (size_t)ctx->push_slot * ctx->push_bytes;
+  char* slot = ctx->push_pin.host_as<char>() + (size_t)ctx->push_slot * ctx->push_bytes;
   memcpy(slot, host_src, bytes);
   const long long words = (long long)(bytes / 8);
   long long blocks = (words + 1023) / 1024;
   if (blocks < 1) blocks = 1;
   if (blocks > 256) blocks = 256;
   hipLaunchKernelGGL(push_copy_kernel, dim3((unsigned)blocks), dim3(256), 0, st,
-                     (const unsigned long long*)((char*)ctx->push_dev + (size_t)ctx->push_slot * ctx->push_bytes),
+                     (const unsigned long long*)(ctx->push_pin.dev_as<char>() + (size_t)ctx->push_slot * ctx->push_bytes),
                      (unsigned long long*)dev_dst, words, (long long)(row_bytes / 8), (long long)(dst_stride_bytes / 8));
   VB_HIP(ctx, hipGetLastError());
   VB_HIP(ctx, hipEventRecord(ev, st));
@@ -366,7 +349,7 @@ void noise_prefetch(vb_ctx* ctx) {
 // A blocking call whose results reach mapped host memory from its last kernel: the event marks that kernel, the next
 // call's noise (NoiseAhead) is enqueued behind it, and the host waits for the event only.
 int wait_then_prefetch(vb_ctx* ctx) {
-  if (!ctx->done_ev) VB_HIP(ctx, hipEventCreateWithFlags(&ctx->done_ev, hipEventDisableTiming));
+  VB_HIP(ctx, ctx->done_ev.create(hipEventDisableTiming));
   VB_HIP(ctx, hipEventRecord(ctx->done_ev, ctx->stream));
   noise_prefetch(ctx);
   VB_HIP(ctx, hipEventSynchronize(ctx->done_ev));
@@ -378,10 +361,9 @@ void prof_events(vb_ctx* ctx, hipEvent_t* ev0, hipEvent_t* ev1, int evals, int k
   if (!ctx->profile || kernel_id < 0 || kernel_id >= VB_PROF_NUM) return;
   vb_ctx::ProfLog& log = ctx->prof[kernel_id];
   if (log.used == log.events.size()) {
-    hipEvent_t a, b;
-    (void)hipEventCreate(&a);
-    (void)hipEventCreate(&b);
-    log.events.push_back({a, b});
+    log.events.emplace_back();
+    (void)log.events.back().first.create(hipEventDefault);
+    (void)log.events.back().second.create(hipEventDefault);
   }
   *ev0 = log.events[log.used].first;
   *ev1 = log.events[log.used].second;
@@ -439,18 +421,13 @@ static int wait_ticket(vb_ctx* ctx, uint64_t id) {
 // evaluation needs no separate copy commands on the stream.
 static int stage_theta(vb_ctx* ctx, ResultSlot& rs, const double* theta, int64_t p) {
   const size_t need = (size_t)(1 + 2 * p) * sizeof(double);   // [theta staging | value | grad]
-  if (rs.p < p || !rs.host) {
-    if (rs.host) {
-      VB_TRY(sync_streams(ctx));
-      VB_HIP(ctx, hipHostFree(rs.host));
-      rs.host = nullptr;
-    }
-    VB_HIP(ctx, hipHostMalloc((void**)&rs.host, need, hipHostMallocMapped));
-    VB_HIP(ctx, hipHostGetDevicePointer((void**)&rs.dev, rs.host, 0));
+  if (rs.p < p || !rs.pin.host) {
+    if (rs.pin.host) VB_TRY(sync_streams(ctx));
+    VB_TRY(ensure_pinned(ctx, rs.pin, need, true));
     rs.p = p;
   }
   VB_TRY(wait_ticket(ctx, rs.batch_id));   // the evaluation that last used this slot may still be running
-  memcpy(rs.host, theta, (size_t)p * sizeof(double));
+  memcpy(rs.pin.host, theta, (size_t)p * sizeof(double));
   rs.pending = true;
   return VB_OK;
 }
@@ -459,7 +436,7 @@ static int stage_theta(vb_ctx* ctx, ResultSlot& rs, const double* theta, int64_t
 static int ticket(vb_ctx* ctx, ResultSlot** rs, int count) {
   if (ctx->batch_events.empty()) {
     ctx->batch_events.resize(32);
-    for (auto& e : ctx->batch_events) VB_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto& e : ctx->batch_events) VB_HIP(ctx, e.create(hipEventDisableTiming));
   }
   const uint64_t id = ++ctx->batch_id;
   VB_HIP(ctx, hipEventRecord(ctx->batch_events[id % ctx->batch_events.size()],
@@ -500,7 +477,7 @@ int vb_create(int device_id, vb_ctx** out) {
   ctx->device = device_id;
   e = hipSetDevice(device_id);
   if (e == hipSuccess) e = hipGetDeviceProperties(&ctx->prop, device_id);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = ctx->stream.create(hipStreamNonBlocking);
   if (e != hipSuccess) {
     fail(nullptr, VB_ERR_HIP, "context creation failed: %s", hipGetErrorString(e));
     delete ctx;
@@ -517,76 +494,6 @@ int vb_destroy(vb_ctx* ctx) {
   user_model_release(ctx);
   flow_release_all(ctx);
   vb_comm_destroy(ctx);
-  if (ctx->pipe.post) {
-    (void)hipStreamDestroy(ctx->pipe.post);
-    for (int i = 0; i < kPipeSets; ++i) {
-      (void)hipEventDestroy(ctx->pipe.ev_k1[i]);
-      (void)hipEventDestroy(ctx->pipe.ev_fin[i]);
-    }
-  }
-  for (auto& s : ctx->noise) {
-    if (s.buf.ptr) (void)hipFree(s.buf.ptr);
-    if (s.ahead.shadow.ptr) (void)hipFree(s.ahead.shadow.ptr);
-    if (s.norms.ptr) (void)hipFree(s.norms.ptr);
-    if (s.ahead.shadow_norms.ptr) (void)hipFree(s.ahead.shadow_norms.ptr);
-  }
-  if (ctx->chi_ahead.shadow.ptr) (void)hipFree(ctx->chi_ahead.shadow.ptr);
-  for (auto& r : ctx->results)
-    if (r.host) (void)hipHostFree(r.host);
-  if (ctx->sync_result.host) (void)hipHostFree(ctx->sync_result.host);
-  if (ctx->done_host) (void)hipHostFree(ctx->done_host);
-  if (ctx->pin_host) (void)hipHostFree(ctx->pin_host);
-  for (DeviceBuffer* b : {&ctx->model_params, &ctx->theta, &ctx->workspace, &ctx->sums, &ctx->out,
-                          &ctx->scratch, &ctx->scratch2, &ctx->rowvec, &ctx->fr_work, &ctx->fr_theta,
-                          &ctx->fr_out, &ctx->dis_state, &ctx->mvt_state, &ctx->mvt_ekl_state, &ctx->lg_work, &ctx->user_params, &ctx->psis_lw, &ctx->psis_work, &ctx->rows_work,
-                          &ctx->lr_work, &ctx->mvt_elbo, &ctx->fit_work, &ctx->glm_work, &ctx->sm_work,&ctx->fr_lt, &ctx->bisect_work, &ctx->chi_dev, &ctx->lr_obj, &ctx->gen_geom.buf, &ctx->tri_map, &ctx->mvt_invs, &ctx->temper.buf, &ctx->temper.work, &ctx->fz_words, &ctx->fz_items, &ctx->legacy_work, &ctx->alpha_g, &ctx->mf_one, &ctx->fetch_ticket, &ctx->loo_work, &ctx->chain, &ctx->chain_work})
-    if (b->ptr) (void)hipFree(b->ptr);
-  if (ctx->mvt_pin) (void)hipHostFree(ctx->mvt_pin);
-  if (ctx->fetch_host) (void)hipHostFree(ctx->fetch_host);
-  if (ctx->push_host) (void)hipHostFree(ctx->push_host);
-  for (hipEvent_t e : ctx->push_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (ctx->user_host_pin) (void)hipHostFree(ctx->user_host_pin);
-  if (ctx->legacy_pin) (void)hipHostFree(ctx->legacy_pin);
-  for (hipEvent_t e : ctx->mvt_pin_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (ctx->mvt_side) {
-    (void)hipStreamSynchronize(ctx->mvt_side);
-    (void)hipStreamDestroy(ctx->mvt_side);
-    (void)hipEventDestroy(ctx->mvt_ev_join);
-  }
-  if (ctx->done_ev) (void)hipEventDestroy(ctx->done_ev);
-  if (ctx->legacy_spec) {
-    LegacySpec* S = ctx->legacy_spec;
-    if (S->stream) {
-      (void)hipStreamSynchronize(S->stream);
-      (void)hipStreamDestroy(S->stream);
-    }
-    if (S->ev_main) (void)hipEventDestroy(S->ev_main);
-    if (S->land_host) (void)hipHostFree(S->land_host);
-    for (DeviceBuffer& b : S->shadow)
-      if (b.ptr) (void)hipFree(b.ptr);
-    if (S->work.ptr) (void)hipFree(S->work.ptr);
-    if (S->clone) vb_legacy_rng_destroy(S->clone);
-    delete S;
-    ctx->legacy_spec = nullptr;
-  }
-  if (ctx->fit_copy_st) {
-    (void)hipStreamSynchronize(ctx->fit_copy_st);
-    (void)hipStreamDestroy(ctx->fit_copy_st);
-  }
-  if (ctx->fit_ring) (void)hipHostFree(ctx->fit_ring);
-  for (int i = 0; i < vb_ctx::kFitRing; ++i) {
-    if (ctx->fit_ev_step[i]) (void)hipEventDestroy(ctx->fit_ev_step[i]);
-    if (ctx->fit_ev_copy[i]) (void)hipEventDestroy(ctx->fit_ev_copy[i]);
-  }
-  for (auto& e : ctx->batch_events) (void)hipEventDestroy(e);
-  for (auto& log : ctx->prof)
-    for (auto& ev : log.events) {
-      (void)hipEventDestroy(ev.first);
-      (void)hipEventDestroy(ev.second);
-    }
-  (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return VB_OK;
 }
@@ -936,18 +843,19 @@ static int legacy_spec_create(vb_ctx* ctx) {
   if (ctx->legacy_spec) return VB_OK;
   LegacySpec* S = new (std::nothrow) LegacySpec;
   if (!S) return fail(ctx, VB_ERR_HIP, "out of host memory");
-  ctx->legacy_spec = S;
-  VB_HIP(ctx, hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking));
-  VB_HIP(ctx, hipEventCreateWithFlags(&S->ev_main, hipEventDisableTiming));
-  VB_HIP(ctx, hipHostMalloc((void**)&S->land_host, kLegacyFinishWords * sizeof(unsigned long long), hipHostMallocMapped));
-  memset(S->land_host, 0, kLegacyFinishWords * sizeof(unsigned long long));
-  VB_HIP(ctx, hipHostGetDevicePointer((void**)&S->land_dev, S->land_host, 0));
-  VB_TRY(vb_legacy_rng_create(0, &S->clone));
+  ctx->legacy_spec.reset(S);
+  VB_HIP(ctx, S->stream.create(hipStreamNonBlocking));
+  VB_HIP(ctx, S->ev_main.create(hipEventDisableTiming));
+  VB_TRY(ensure_pinned(ctx, S->land, kLegacyFinishWords * sizeof(unsigned long long), true));
+  memset(S->land.host, 0, kLegacyFinishWords * sizeof(unsigned long long));
+  ::vb_legacy_rng* clone = nullptr;
+  VB_TRY(vb_legacy_rng_create(0, &clone));
+  S->clone.reset(clone);
   return VB_OK;
 }
 
 static void legacy_spec_cancel(vb_ctx* ctx) {
-  LegacySpec* S = ctx->legacy_spec;
+  LegacySpec* S = ctx->legacy_spec.get();
   if (!S || !S->active) return;
   (void)hipStreamSynchronize(S->stream);      // its kernels write the shadows and its scratch: quiescent before anything reuses them
   S->active = false;
@@ -963,7 +871,7 @@ static void legacy_spec_enqueue_next(vb_ctx* ctx) {
   const int i = S.n_finished;
   const LegacyReq& r = S.reqs[i];
   const LegacyGenState& g = S.state[i];
-  if (vb_legacy_rng_set_state(S.clone, g.key, g.pos, g.has_gauss, g.gauss) != VB_OK) {
+  if (vb_legacy_rng_set_state(S.clone.get(), g.key, g.pos, g.has_gauss, g.gauss) != VB_OK) {
     S.failed = true;
     return;
   }
@@ -979,16 +887,14 @@ static void legacy_spec_enqueue_next(vb_ctx* ctx) {
       S.shadow_d[i] = r.d, S.shadow_ld[i] = ld;
     }
     if (rc == VB_OK && r.prog == -1) {
-      NoiseSlot view;
-      view.buf = S.shadow[i], view.n = r.rows, view.d = r.d, view.ld = ld;
       LegacyGenState h = g;
-      rc = legacy_dev_randn(ctx, h.key, &h.pos, &h.has_gauss, &h.gauss, view, r.n_total, r.d, r.row_begin, r.rows, &S.fin);
+      rc = legacy_dev_randn(ctx, h.key, &h.pos, &h.has_gauss, &h.gauss, (double*)S.shadow[i].ptr, ld, r.n_total, r.d, r.row_begin, r.rows, &S.fin);
       S.head_state = g;      // (no host-drawn head: the finish starts from the request's own start state)
     } else if (rc == VB_OK) {
-      rc = legacy_gamma_device(ctx, S.clone, r.prog, r.df, (double*)S.shadow[i].ptr, ld, r.n_total, r.d, r.row_begin, r.rows, &S.fin);
-      if (rc == VB_OK) gen_state_get(S.clone, &S.head_state);
+      rc = legacy_gamma_device(ctx, S.clone.get(), r.prog, r.df, (double*)S.shadow[i].ptr, ld, r.n_total, r.d, r.row_begin, r.rows, &S.fin);
+      if (rc == VB_OK) gen_state_get(S.clone.get(), &S.head_state);
     }
-    if (rc == VB_OK) rc = legacy_finish_launch(ctx, ctx->stream, S.fin, S.land_dev, ++S.seq);
+    if (rc == VB_OK) rc = legacy_finish_launch(ctx, ctx->stream, S.fin, S.land.dev_as<unsigned long long>(), ++S.seq);
   }
   S.enqueuing = false;
   if (rc != VB_OK) {
@@ -1001,7 +907,7 @@ static void legacy_spec_enqueue_next(vb_ctx* ctx) {
 // has the request in flight landed?  Then complete it on the host and start the next one.  Cheap when nothing is pending;
 // called from the draw entry points and from fetch_blocking's wait.
 static void legacy_spec_poll(vb_ctx* ctx) {
-  LegacySpec* Sp = ctx->legacy_spec;
+  LegacySpec* Sp = ctx->legacy_spec.get();
   if (Sp && Sp->enqueuing) return;      // (a wait inside the job's own draw: see LegacySpec::enqueuing)
   if (Sp && Sp->active && !Sp->failed && Sp->in_flight < 0 && Sp->n_finished < Sp->n_reqs) {
     legacy_spec_enqueue_next(ctx);      // (a job whose start was deferred to the caller's first wait: vb_legacy_round_end)
@@ -1009,10 +915,11 @@ static void legacy_spec_poll(vb_ctx* ctx) {
   }
   if (!Sp || !Sp->active || Sp->in_flight < 0) return;
   LegacySpec& S = *Sp;
-  if (*(volatile unsigned long long*)(S.land_host + 344) != S.seq) return;
+  const unsigned long long* landing = S.land.host_as<unsigned long long>();
+  if (*(volatile const unsigned long long*)(landing + 344) != S.seq) return;
   __atomic_thread_fence(__ATOMIC_ACQUIRE);
   LegacyGenState e = S.head_state;
-  const int rc = legacy_finish_complete(ctx, S.fin, S.land_host, e.key, &e.pos, &e.has_gauss, &e.gauss);
+  const int rc = legacy_finish_complete(ctx, S.fin, landing, e.key, &e.pos, &e.has_gauss, &e.gauss);
   const int i = S.in_flight;
   S.in_flight = -1;
   if (rc != VB_OK) {
@@ -1028,7 +935,7 @@ static void legacy_spec_poll(vb_ctx* ctx) {
 // for it (it has usually landed), and report the shadow to adopt and the generator's end state.  false: not ours (the job, if
 // any, is discarded) -- the caller draws.
 static bool legacy_spec_take(vb_ctx* ctx, vb_legacy_rng* rng, const LegacyReq& r, int* index) {
-  LegacySpec* Sp = ctx->legacy_spec;
+  LegacySpec* Sp = ctx->legacy_spec.get();
   if (!Sp || !Sp->active) return false;
   LegacySpec& S = *Sp;
   const int i = S.n_adopted;
@@ -1112,7 +1019,7 @@ int vb_legacy_rng_randn_device(vb_ctx* ctx, vb_legacy_rng* rng, int slot, int64_
   int pos = 0, has_gauss = 0;
   double gauss = 0.0;
   VB_TRY(vb_legacy_rng_get_state(rng, key, &pos, &has_gauss, &gauss));
-  const int rc = legacy_dev_randn(ctx, key, &pos, &has_gauss, &gauss, ctx->noise[slot], n_total, d, row_begin, rows);
+  const int rc = legacy_dev_randn(ctx, key, &pos, &has_gauss, &gauss, (double*)ctx->noise[slot].buf.ptr, ctx->noise[slot].ld, n_total, d, row_begin, rows);
   if (rc == VB_ERR_UNSUPPORTED) return fail(ctx, VB_ERR_UNSUPPORTED, "device draw not available for this request: draw on the host");
   VB_TRY(rc);
   legacy_round_note(ctx, rng, req);
@@ -1247,7 +1154,7 @@ int vb_legacy_rng_chisquare_device(vb_ctx* ctx, vb_legacy_rng* rng, double df, i
 
 int vb_legacy_round_end(vb_ctx* ctx, vb_legacy_rng* rng) {
   if (!ctx || !rng) return fail(ctx, VB_ERR_INVALID, "NULL argument");
-  LegacySpec* Sp = ctx->legacy_spec;
+  LegacySpec* Sp = ctx->legacy_spec.get();
   if (!Sp || Sp->round_rng != rng || Sp->round_uid != vb_legacy_rng_uid(rng))
     return VB_OK;      // no device draw of this generator since the last round end
   LegacySpec& S = *Sp;
@@ -1295,7 +1202,7 @@ int vb_legacy_round_end(vb_ctx* ctx, vb_legacy_rng* rng) {
 
 int vb_legacy_ahead_stats(vb_ctx* ctx, uint64_t* launched, uint64_t* adopted, uint64_t* discarded) {
   if (!ctx || !launched || !adopted || !discarded) return fail(ctx, VB_ERR_INVALID, "NULL argument");
-  const LegacySpec* S = ctx->legacy_spec;
+  const LegacySpec* S = ctx->legacy_spec.get();
   *launched = S ? S->launched : 0;
   *adopted = S ? S->adopted : 0;
   *discarded = S ? S->discarded : 0;
@@ -1396,8 +1303,8 @@ static int mf_call(vb_ctx* ctx, int count, const int* slots, int64_t n, int64_t 
       ResultSlot& r = *rs[b0 + b];
       VB_TRY(stage_theta(ctx, r, thetas + (size_t)(b0 + b) * 2 * d, 2 * d));
       c.noise[b] = gen ? &ctx->gen_geom : &ctx->noise[slot];
-      c.theta_src[b] = r.dev;
-      c.out[b] = r.dev + r.p;
+      c.theta_src[b] = r.dev();
+      c.out[b] = r.dev() + r.p;
     }
     c.n = n;
     c.d = d;
@@ -1415,12 +1322,11 @@ static int mf_call(vb_ctx* ctx, int count, const int* slots, int64_t n, int64_t 
     }
     ctx->done_groups = 0;
     if (blocking && count == 1) {
-      if (!ctx->done_host) {
-        VB_HIP(ctx, hipHostMalloc((void**)&ctx->done_host, 64 * 8 * sizeof(unsigned long long), hipHostMallocMapped));
-        memset(ctx->done_host, 0, 64 * 8 * sizeof(unsigned long long));
-        VB_HIP(ctx, hipHostGetDevicePointer((void**)&ctx->done_dev, ctx->done_host, 0));
+      if (!ctx->done_pin.host) {
+        VB_TRY(ensure_pinned(ctx, ctx->done_pin, 64 * 8 * sizeof(unsigned long long), true));
+        memset(ctx->done_pin.host, 0, ctx->done_pin.bytes);
       }
-      c.done_dev = ctx->done_dev;
+      c.done_dev = ctx->done_pin.dev_as<unsigned long long>();
       c.done_seq = ++ctx->done_seq;
       c.done_groups = &ctx->done_groups;
     }
@@ -1436,7 +1342,7 @@ static int mf_wait_blocking(vb_ctx* ctx) {
   const int groups = ctx->done_groups;
   if (groups > 0) {
     const unsigned long long seq = ctx->done_seq;
-    volatile unsigned long long* w = ctx->done_host;
+    volatile unsigned long long* w = ctx->done_pin.host_as<unsigned long long>();
     for (unsigned spins = 0; spins < 400000u; ++spins) {
       int g = 0;
       while (g < groups && w[8 * g] == seq) ++g;
@@ -1459,8 +1365,8 @@ int vb_elbo_grad_meanfield(vb_ctx* ctx, int slot, int64_t n, int64_t d, int64_t 
   VB_TRY(mf_call(ctx, 1, &slot, n, d, n_total, family, df, theta, flags, cv_mode, &rs, false, nullptr, true));
   VB_TRY(mf_wait_blocking(ctx));
   rs->pending = false;
-  *value = rs->host[rs->p];
-  memcpy(grad, rs->host + rs->p + 1, (size_t)(2 * d) * sizeof(double));
+  *value = rs->host()[rs->p];
+  memcpy(grad, rs->host() + rs->p + 1, (size_t)(2 * d) * sizeof(double));
   return VB_OK;
 }
 
@@ -1488,8 +1394,8 @@ int vb_elbo_grad_meanfield_philox(vb_ctx* ctx, int slot, int64_t n, int64_t d, i
   VB_TRY(mf_call(ctx, 1, &slot, n, d, n_total, family, df, theta, flags, cv_mode, &rs, false, &gen, true));
   VB_TRY(mf_wait_blocking(ctx));
   rs->pending = false;
-  *value = rs->host[rs->p];
-  memcpy(grad, rs->host + rs->p + 1, (size_t)(2 * d) * sizeof(double));
+  *value = rs->host()[rs->p];
+  memcpy(grad, rs->host() + rs->p + 1, (size_t)(2 * d) * sizeof(double));
   return VB_OK;
 }
 
@@ -1527,12 +1433,12 @@ int vb_result_get(vb_ctx* ctx, int rslot, double* value, double* grad, int64_t p
   if (!ctx || !value || !grad) return fail(ctx, VB_ERR_INVALID, "NULL argument");
   VB_TRY(check_slot(ctx, rslot));
   ResultSlot& rs = ctx->results[rslot];
-  if (!rs.host || !rs.pending || p > rs.p)
+  if (!rs.host() || !rs.pending || p > rs.p)
     return fail(ctx, VB_ERR_STATE, "result slot %d holds no pending result of size %lld", rslot,
                 (long long)p);
   VB_TRY(wait_ticket(ctx, rs.batch_id));
-  *value = rs.host[rs.p];
-  memcpy(grad, rs.host + rs.p + 1, (size_t)p * sizeof(double));
+  *value = rs.host()[rs.p];
+  memcpy(grad, rs.host() + rs.p + 1, (size_t)p * sizeof(double));
   return VB_OK;
 }
 
@@ -1552,11 +1458,11 @@ int vb_elbo_grad_lowrank(vb_ctx* ctx, int slot_eps, int slot_z, int64_t n, int64
   const int64_t p = 2 * d + d * k;
   ResultSlot& rs = ctx->sync_result;
   VB_TRY(stage_theta(ctx, rs, theta, p));
-  VB_TRY(lr_elbo_grad_enqueue(ctx, ctx->noise[slot_eps], ctx->noise[slot_z], n, d, k, n_total, rs.dev, rs.dev + rs.p));
+  VB_TRY(lr_elbo_grad_enqueue(ctx, ctx->noise[slot_eps], ctx->noise[slot_z], n, d, k, n_total, rs.dev(), rs.dev() + rs.p));
   VB_HIP(ctx, hipStreamSynchronize(ctx->stream));
   rs.pending = false;
-  *value = rs.host[rs.p];
-  memcpy(grad, rs.host + rs.p + 1, (size_t)p * sizeof(double));
+  *value = rs.host()[rs.p];
+  memcpy(grad, rs.host() + rs.p + 1, (size_t)p * sizeof(double));
   return VB_OK;
 }
 
@@ -1587,7 +1493,7 @@ int vb_log_weights_meanfield(vb_ctx* ctx, int slot, int64_t n, int64_t d, int fa
   VB_HIP(ctx, hipSetDevice(ctx->device));
   ResultSlot& rs = ctx->sync_result;
   VB_TRY(stage_theta(ctx, rs, theta, 2 * d));
-  VB_TRY(log_weights_enqueue(ctx, ctx->noise[slot], n, d, family, df, rs.dev));
+  VB_TRY(log_weights_enqueue(ctx, ctx->noise[slot], n, d, family, df, rs.dev()));
   if (lw)
     VB_HIP(ctx, hipMemcpyAsync(lw, ctx->psis_lw.ptr, (size_t)n * sizeof(double), hipMemcpyDeviceToHost,
                                ctx->stream));
@@ -1651,11 +1557,11 @@ int vb_alpha_grad_meanfield(vb_ctx* ctx, int slot, int64_t n, int64_t d, int64_t
   VB_HIP(ctx, hipSetDevice(ctx->device));
   ResultSlot& rs = ctx->sync_result;
   VB_TRY(stage_theta(ctx, rs, theta, 2 * d));
-  VB_TRY(alpha_enqueue(ctx, ctx->noise[slot], n, n_total, d, family, df, alpha, rs.dev, rs.dev + rs.p));
+  VB_TRY(alpha_enqueue(ctx, ctx->noise[slot], n, n_total, d, family, df, alpha, rs.dev(), rs.dev() + rs.p));
   VB_TRY(wait_then_prefetch(ctx));
   rs.pending = false;
-  *value = rs.host[rs.p];
-  memcpy(grad, rs.host + rs.p + 1, (size_t)(2 * d) * sizeof(double));
+  *value = rs.host()[rs.p];
+  memcpy(grad, rs.host() + rs.p + 1, (size_t)(2 * d) * sizeof(double));
   return VB_OK;
 }
 
@@ -1706,7 +1612,7 @@ int vb_dis_refresh_meanfield(vb_ctx* ctx, int slot, int64_t n, int64_t d, int64_
   ResultSlot& rs = ctx->sync_result;
   VB_TRY(stage_theta(ctx, rs, theta, 2 * d));
   int status = 0;
-  return dis_refresh_enqueue(ctx, ctx->noise[slot], n, n_total, d, family, df, rs.dev, prior_theta, eps_prev, ess_target,
+  return dis_refresh_enqueue(ctx, ctx->noise[slot], n, n_total, d, family, df, rs.dev(), prior_theta, eps_prev, ess_target,
                              max_bisection_its, eps, ess, &status, w, log_p, log_q);
 }
 
@@ -1721,11 +1627,11 @@ int vb_dis_grad_meanfield(vb_ctx* ctx, int slot, int64_t n, int64_t d, int famil
   VB_HIP(ctx, hipSetDevice(ctx->device));
   ResultSlot& rs = ctx->sync_result;
   VB_TRY(stage_theta(ctx, rs, theta, 2 * d));
-  VB_TRY(dis_grad_enqueue(ctx, ctx->noise[slot], n, d, family, df, rs.dev, weights, scale, rs.dev + rs.p));
+  VB_TRY(dis_grad_enqueue(ctx, ctx->noise[slot], n, d, family, df, rs.dev(), weights, scale, rs.dev() + rs.p));
   VB_TRY(wait_then_prefetch(ctx));
   rs.pending = false;
-  *value = rs.host[rs.p];
-  memcpy(grad, rs.host + rs.p + 1, (size_t)(2 * d) * sizeof(double));
+  *value = rs.host()[rs.p];
+  memcpy(grad, rs.host() + rs.p + 1, (size_t)(2 * d) * sizeof(double));
   return VB_OK;
 }
 
@@ -1836,6 +1742,12 @@ int vb_host_free(void* ptr) {
   return VB_OK;
 }
 
+int vb_resource_counts(uint64_t out[4]) {
+  if (!out) return fail(nullptr, VB_ERR_INVALID, "vb_resource_counts: NULL output");
+  for (int k = 0; k < RES_NUM; ++k) out[k] = g_resources[k].load(std::memory_order_relaxed);
+  return VB_OK;
+}
+
 // ---- parking a DIS state (round 6) ---------------------------------------------------------------------
 // The reference keeps the state of a DISInclusiveKL per OBJECT (objectives.py:391-403): two objectives with
 // num_resampling_batches > 1 may take turns.  Here the state samples live in the context, one set per family kind; an
@@ -1916,11 +1828,6 @@ void dis_attach(vb_ctx* ctx, DisParked* P) {
   }
 }
 
-void dis_parked_free(DisParked* P) {
-  if (P->state.ptr) (void)hipFree(P->state.ptr);
-  if (P->noise.ptr) (void)hipFree(P->noise.ptr);
-  delete P;
-}
 }  // namespace
 
 int vb_dis_state_park(vb_ctx* ctx, int kind, int slot, void** handle) {
@@ -1947,12 +1854,12 @@ int vb_dis_state_unpark(vb_ctx* ctx, void* handle) {
   ctx->mvt_inv_pending = ctx->mvt_inv_queued = false;
   // what the context holds now (the caller parked it first if anybody still needs it) goes away with the handle
   dis_attach(ctx, P);
-  dis_parked_free(P);      // (after the swaps: the handle owns what the context held)
+  delete P;      // (after the swaps: the handle owns what the context held)
   return VB_OK;
 }
 
 int vb_dis_state_drop(void* handle) {
-  if (handle) dis_parked_free((DisParked*)handle);
+  delete (DisParked*)handle;
   return VB_OK;
 }
 

@@ -361,18 +361,14 @@ int vb_chain_open(vb_ctx* ctx, int64_t p, int64_t capacity_rows) {
   if (!ctx->chain.ptr || ctx->chain.bytes < bytes) {
     if (ctx->chain.ptr) {
       VB_TRY(sync_streams(ctx));
-      VB_HIP(ctx, hipFree(ctx->chain.ptr));
-      ctx->chain.ptr = nullptr;
-      ctx->chain.bytes = 0;
+      VB_HIP(ctx, ctx->chain.release());
     }
-    const hipError_t e = hipMalloc(&ctx->chain.ptr, bytes);
+    const hipError_t e = ctx->chain.alloc(bytes);      // (no zero fill: every row is written before it is read)
     if (e != hipSuccess) {
       (void)hipGetLastError();      // (the failed allocation must not show up as a later launch's error)
-      ctx->chain.ptr = nullptr;
       return fail(ctx, VB_ERR_HIP, "iterate chain: allocating %zu bytes (%lld rows x %lld doubles) failed: %s", bytes,
                   (long long)capacity_rows, (long long)p, hipGetErrorString(e));
     }
-    ctx->chain.bytes = bytes;
   }
   ctx->chain_p = p, ctx->chain_cap = capacity_rows, ctx->chain_rows = 0;
   ctx->chain_open = true;
@@ -386,9 +382,7 @@ int vb_chain_close(vb_ctx* ctx) {
   if (ctx->chain.ptr) {
     VB_HIP(ctx, hipSetDevice(ctx->device));
     VB_TRY(sync_streams(ctx));
-    VB_HIP(ctx, hipFree(ctx->chain.ptr));
-    ctx->chain.ptr = nullptr;
-    ctx->chain.bytes = 0;
+    VB_HIP(ctx, ctx->chain.release());
   }
   return VB_OK;
 }

@@ -14,20 +14,14 @@ namespace vb {
 // stream is drained on both sides, so the call is ordered like the RCCL kernel it stands in for
 static int host_collective(vb_ctx* ctx, hipStream_t stream, double* buf, size_t count, int op) {
   if (count == 0) return VB_OK;
-  if (ctx->host_stage_cap < count) {
-    if (ctx->host_stage) VB_HIP(ctx, hipHostFree(ctx->host_stage));
-    ctx->host_stage = nullptr;
-    ctx->host_stage_cap = 0;
-    const size_t cap = count + count / 4 + 1024;
-    VB_HIP(ctx, hipHostMalloc((void**)&ctx->host_stage, cap * sizeof(double), hipHostMallocDefault));
-    ctx->host_stage_cap = cap;
-  }
-  VB_HIP(ctx, hipMemcpyAsync(ctx->host_stage, buf, count * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (ctx->host_stage.bytes < count * sizeof(double))      // (no wait: every use ends in the synchronisation below)
+    VB_TRY(ensure_pinned(ctx, ctx->host_stage, (count + count / 4 + 1024) * sizeof(double), false));
+  VB_HIP(ctx, hipMemcpyAsync(ctx->host_stage.host, buf, count * sizeof(double), hipMemcpyDeviceToHost, stream));
   VB_HIP(ctx, hipStreamSynchronize(stream));
-  const int rc = ctx->host_fn(ctx->host_user, ctx->host_stage, count, op);
+  const int rc = ctx->host_fn(ctx->host_user, ctx->host_stage.host_as<double>(), count, op);
   if (rc != 0) return fail(ctx, VB_ERR_COMM, "host collective (%s of %zu doubles) failed with code %d",
                            op == VB_HOST_MAX ? "max" : "sum", count, rc);
-  VB_HIP(ctx, hipMemcpyAsync(buf, ctx->host_stage, count * sizeof(double), hipMemcpyHostToDevice, stream));
+  VB_HIP(ctx, hipMemcpyAsync(buf, ctx->host_stage.host, count * sizeof(double), hipMemcpyHostToDevice, stream));
   VB_HIP(ctx, hipStreamSynchronize(stream));     // the staging buffer is free again when this returns
   return VB_OK;
 }
@@ -471,9 +465,7 @@ int vb_comm_destroy(vb_ctx* ctx) {
   } else if (ctx->host_fn) {
     ctx->host_fn = nullptr;
     ctx->host_user = nullptr;
-    if (ctx->host_stage) (void)hipHostFree(ctx->host_stage);
-    ctx->host_stage = nullptr;
-    ctx->host_stage_cap = 0;
+    (void)ctx->host_stage.release();
   } else {
     ncclCommDestroy((ncclComm_t)ctx->comm);
   }

@@ -9,10 +9,12 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/viabel_hip.h"
+#include "vb_resource.h"
 
 namespace vb {
 
@@ -102,11 +104,6 @@ __device__ __forceinline__ double glm_term(int link, double aux, double y, doubl
   return y * eta - (fmax(eta, 0.0) + log1p(t));
 }
 
-struct DeviceBuffer {
-  void* ptr = nullptr;
-  size_t bytes = 0;
-};
-
 // a Philox generation request (vb_noise_generate / vb_chisq_generate): what a buffer holds
 struct NoiseReq {
   int kind = 0;
@@ -152,8 +149,8 @@ int rng_row_norms(vb_ctx* ctx, hipStream_t st, const double* src, int64_t ld, in
 // all-reduce and the epilogue so that the next batch's kernels overlap them.
 constexpr int kPipeSets = 4;
 struct Pipeline {
-  hipStream_t post = nullptr;
-  hipEvent_t ev_k1[kPipeSets] = {}, ev_fin[kPipeSets] = {};
+  Stream post;
+  Event ev_k1[kPipeSets], ev_fin[kPipeSets];
   bool fin_valid[kPipeSets] = {};
   uint64_t seq = 0;
   int last_set = 0;
@@ -161,8 +158,9 @@ struct Pipeline {
 };
 
 struct ResultSlot {
-  double* host = nullptr;   // pinned, device-mapped: [theta staging (p) | value | grad (p)]
-  double* dev = nullptr;    // device address of `host`
+  PinnedBuffer pin;         // device-mapped: [theta staging (p) | value | grad (p)]
+  double* host() const { return pin.host_as<double>(); }
+  double* dev() const { return pin.dev_as<double>(); }
   int64_t p = 0;
   bool pending = false;
   uint64_t batch_id = 0;    // enqueue ticket of the evaluation that last used this slot (0: none)
@@ -170,11 +168,14 @@ struct ResultSlot {
 
 }  // namespace vb
 
-namespace vb { struct LegacySpec; }
+namespace vb {
+struct LegacySpec;
+struct LegacySpecDelete { void operator()(LegacySpec* s) const; };      // (defined below, where the type is complete)
+}
 
 struct vb_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;
+  vb::Stream stream;                    // (first member: destroyed after everything that was used on it)
   hipDeviceProp_t prop;
   std::string last_error;
 
@@ -183,10 +184,9 @@ struct vb_ctx {
   vb::ResultSlot results[VB_MAX_SLOTS];
   vb::ResultSlot sync_result;           // used by the synchronous entry points
   // completion words of the blocking mean-field call (pinned, device-mapped): finalize workgroup g stores the call's
-  // sequence number into done_host[8 g] behind its results, the host polls them instead of waking up through
+  // sequence number into word 8 g behind its results, the host polls them instead of waking up through
   // hipStreamSynchronize
-  unsigned long long* done_host = nullptr;
-  unsigned long long* done_dev = nullptr;
+  vb::PinnedBuffer done_pin;
   unsigned long long done_seq = 0;
   int done_groups = 0;                  // workgroups that signal for the call in flight (0: wait on the stream)
 
@@ -217,8 +217,7 @@ struct vb_ctx {
   // a host callable with its gradient (vb_set_model_callback): the row "kernel" is a round trip through pinned memory
   vb_model_callback user_host_fn = nullptr;
   void* user_host_arg = nullptr;
-  double* user_host_pin = nullptr;      // [z (n x d) | f (n) | g (n x d)]
-  size_t user_host_pin_doubles = 0;
+  vb::PinnedBuffer user_host_pin;       // [z (n x d) | f (n) | g (n x d)]
   std::vector<UserModule> user_modules;
   vb::DeviceBuffer user_params;
   vb::DeviceBuffer glm_work;            // regression targets: split-K slabs of the gradient GEMM
@@ -231,26 +230,25 @@ struct vb_ctx {
                                         // DIS state's buffer: an ELBO monitor beside a DIS fit must leave its samples alone)
   std::vector<double> mvt_theta;        // parameter the device-side residuals of the DIS state belong to
   bool mvt_dev_factors = false;         // ... and its factors (L, L', L^-1) were formed on the device
-  const double* mvt_e_noise = nullptr;  // the residuals E' of that parameter are NOT stored: E'_n = noise_n / s_n (this matrix,
+  const double* mvt_e_noise = nullptr;  // alias: the residuals E' of that parameter are NOT stored: E'_n = noise_n / s_n (this matrix,
   int64_t mvt_e_noise_ld = 0;           // row stride mvt_e_noise_ld; see mvt_residuals)
   std::vector<double> mvt_stage;        // host staging of the factor uploads (one synchronisation per pass)
-  double* mvt_pin = nullptr;            // pinned staging of the throughput mode's parameter upload (no synchronisation)
-  size_t mvt_pin_doubles = 0;
+  vb::PinnedBuffer mvt_pin;             // mapped staging of the throughput mode's parameter upload (no synchronisation; the
+                                        // unpack reads the parameter in place): two slots
+  size_t mvt_pin_doubles = 0;           // ... of this many doubles each
   int mvt_pin_slot = 0;
-  hipEvent_t mvt_pin_ev[2] = {nullptr, nullptr};   // recorded behind each slot's staged copy; waited for before the slot is rewritten
-  void* push_host = nullptr;            // two mapped staging slots of push_small (vb_api.hip) and their device address
-  void* push_dev = nullptr;
+  vb::Event mvt_pin_ev[2];              // recorded behind each slot's staged copy; waited for before the slot is rewritten
+  vb::PinnedBuffer push_pin;            // two mapped staging slots of push_small (vb_api.hip)
   size_t push_bytes = 0;                // ... per slot
   int push_slot = 0;
-  hipEvent_t push_ev[2] = {nullptr, nullptr};
-  void* fetch_host = nullptr;           // mapped host memory of fetch_blocking (vb_api.hip): segments | completion word,
-  void* fetch_dev = nullptr;            // and its device address
-  size_t fetch_bytes = 0;
+  vb::Event push_ev[2];
+  vb::PinnedBuffer fetch_pin;           // mapped host memory of fetch_blocking (vb_api.hip): segments | completion word
   unsigned long long fetch_seq = 0;
   vb::DeviceBuffer fetch_ticket;        // the copy kernel's workgroup ticket (zero between launches)
-  hipStream_t mvt_side = nullptr;       // side stream of the deferred triangular inverse (mvt_factors_device)
-  hipEvent_t mvt_ev_fork = nullptr, mvt_ev_join = nullptr;
-  hipEvent_t done_ev = nullptr;      // wait_then_prefetch
+  vb::Stream mvt_side;                  // side stream of the deferred triangular inverse (mvt_factors_device)
+  hipEvent_t mvt_ev_fork = nullptr;     // alias: the staging slot's event (mvt_pin_ev)
+  vb::Event mvt_ev_join;
+  vb::Event done_ev;                    // wait_then_prefetch
   uint64_t ahead_generated = 0, ahead_adopted = 0;      // look-ahead buffers generated / adopted (vb_noise_ahead_stats)
   bool mvt_inv_pending = false;         // the main stream has not yet waited for the side stream's inverse
   bool mvt_inv_queued = false;          // ... which has been enqueued already (else mvt_inv_args describes it)
@@ -261,7 +259,6 @@ struct vb_ctx {
     bool clean = false;
     bool lfull_here = false;            // the side stream's prep also forms L = (L')' (the main stream had no prep launch)
   } mvt_inv_args;
-  double* mvt_pin_dev = nullptr;        // device address of mvt_pin (mapped: the unpack reads the parameter in place)
   std::vector<double> mvt_prior;        // tempering-prior parameter the device copy was made from
   int64_t mvt_inv_key[4] = {0, 0, 0, 0};   // (state buffer, n, n_total, d) for which the inverse's zero triangle is known clean
   vb::DeviceBuffer dis_state;           // DIS: [cols of the refresh theta | log p | base b | log prior | w]
@@ -275,7 +272,7 @@ struct vb_ctx {
   vb::DeviceBuffer bisect_work;         // DIS tempering bisection: interval / ESS tables of the look-ahead rounds
   unsigned long long bisect_bar_base = 0;   // the resident bisection kernel's barrier counter before the next launch,
   size_t bisect_bar_words = 0;              // where in bisect_work it lives (doubles) and for which allocation it was zeroed
-  void* bisect_bar_ptr = nullptr;
+  void* bisect_bar_ptr = nullptr;           // alias
   vb::DeviceBuffer mvt_elbo;            // multivariate-t ExclusiveKL: root, mean, row scales
   vb::DeviceBuffer lr_work;             // low-rank Gaussian family: workspace of the streaming pipeline
   vb::DeviceBuffer lr_obj;              // low-rank Gaussian under DIS / alpha: samples, residuals, Woodbury vectors
@@ -295,9 +292,7 @@ struct vb_ctx {
   vb::DeviceBuffer psis_work;           // the multi-workgroup smoothing's exchange area (barrier counter, histograms, tail lists)
   unsigned long long psis_bar_base = 0; // value of that counter before the next launch
   vb::DeviceBuffer loo_work;            // batched smoothing / PSIS-LOO (vb_psis_batch.hip): vectors, draws, per-vector results
-  double* pin_host = nullptr;           // pinned, device-mapped staging (vb_linalg.hip): host / device address
-  double* pin_dev = nullptr;
-  size_t pin_bytes = 0;
+  vb::PinnedBuffer pin;                 // device-mapped staging (vb_linalg.hip; ensure_pinned)
   vb::DeviceBuffer fit_work;            // device-resident fit: laid out by FitRun (vb_fit_run.h) alone
   int64_t fit_out_off = 0;
   uint64_t mvt_epi_rows_calls = 0, mvt_chain_fetch_calls = 0;      // vb_mvt_route_stats
@@ -312,28 +307,28 @@ struct vb_ctx {
   // a device fit's per-iteration rows (iterates, directions, gradients) leave while the next iterations run: a copy stream,
   // a ring of pinned slots, one event pair per slot (FitRun, vb_fit_run.h)
   static constexpr int kFitRing = 4;
-  hipStream_t fit_copy_st = nullptr;
-  double* fit_ring = nullptr;
+  vb::Stream fit_copy_st;
+  vb::PinnedBuffer fit_ring;
   size_t fit_ring_doubles = 0;          // capacity of ONE slot
-  hipEvent_t fit_ev_step[kFitRing] = {}, fit_ev_copy[kFitRing] = {};
+  vb::Event fit_ev_step[kFitRing], fit_ev_copy[kFitRing];
   vb::DeviceBuffer tri_map;             // XCD-aware tile list of the lower-triangular gradient GEMM (int pairs)
   int tri_map_key[3] = {0, 0, 0};       // (d, tile rows, tile columns) the list was built for
   int tri_map_blocks = 0;
   vb::DeviceBuffer fr_lt;               // full-rank: unpacked parameter [mu (ldz) | L' (d x ldl)]
   int64_t fr_lt_d = 0;                  // dimension the unpacked copy of fr_theta was made for (0: stale)
-  const double* fr_lt_owner = nullptr;  // a parameter other than fr_theta whose unpacked copy fr_lt currently holds (vb_fit's)
+  const double* fr_lt_owner = nullptr;  // alias: a parameter other than fr_theta whose unpacked copy fr_lt currently holds (vb_fit's)
   vb::DeviceBuffer fr_theta;            // full-rank: resident flat parameter
   vb::DeviceBuffer fr_out;              // full-rank: [value | grad] on the device
   int64_t fr_p = 0;                     // length of the resident full-rank parameter
   // numpy's legacy normal stream on the device (vb_legacy_dev.hip): scratch; where the jump polynomials were uploaded
   vb::DeviceBuffer alpha_g;             // AlphaDivergence, correlated-Gaussian target: G of the samples (see FrWeighted::g_ready)
   vb::DeviceBuffer legacy_work;
-  const void* legacy_poly_at = nullptr;
+  const void* legacy_poly_at = nullptr; // alias
   size_t legacy_poly_bytes = 0;
   bool legacy_table_ready = false;      // the double-double log's table is in this device's constant memory
-  vb::LegacySpec* legacy_spec = nullptr;   // look-ahead generation of the next call's numpy-stream draws (created on first use)
-  double* legacy_pin = nullptr;         // pinned staging of the device draw's results
-  size_t legacy_pin_doubles = 0;
+  std::unique_ptr<vb::LegacySpec, vb::LegacySpecDelete> legacy_spec;   // look-ahead generation of the next call's numpy-stream
+                                                                       // draws (created on first use)
+  vb::PinnedBuffer legacy_pin;          // staging of the device draw's results
   // fused full-rank evaluation (vb_fullrank_fused.h): ticket counter, error word and tile flags; the work list
   vb::DeviceBuffer fz_words, fz_items;
   int64_t fz_key[5] = {0, 0, 0, 0, 0};  // (n, d, splits, phases, tile_blocks) the list was built for
@@ -347,8 +342,7 @@ struct vb_ctx {
   int n_ranks = 1, rank = 0;
   vb_host_collective_fn host_fn = nullptr;   // vb_comm_init_host: the caller's collective over host memory
   void* host_user = nullptr;
-  double* host_stage = nullptr;         // pinned staging buffer of the host-staged transport
-  size_t host_stage_cap = 0;            // ... in doubles
+  vb::PinnedBuffer host_stage;          // staging buffer of the host-staged transport
   // xGMI-native transport (vb_comm_init_ipc): every rank's window [3 flag words | data cap | result cap], the peers'
   // windows mapped through IPC handles; ipc_seq counts the collectives (the flags carry it)
   struct IpcComm {
@@ -365,25 +359,28 @@ struct vb_ctx {
 
   bool profile = false;
   struct ProfLog {                      // one per profiled kernel id (VB_PROF_*)
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+    std::vector<std::pair<vb::Event, vb::Event>> events;
     size_t used = 0;
     int64_t evals = 0;                  // evaluations covered by the recorded launches
   } prof[VB_PROF_NUM];
 
   // completion tickets: enqueue k records batch_events[k % size] after its last kernel, so a
   // result slot is never re-staged while the evaluation that used it is still in flight
-  std::vector<hipEvent_t> batch_events;
+  std::vector<vb::Event> batch_events;
   uint64_t batch_id = 0, batch_done = 0;
 
   vb::Pipeline pipe;
-  hipStream_t result_stream = nullptr;  // stream the last enqueue's results are produced on
+  hipStream_t result_stream = nullptr;  // alias: stream the last enqueue's results are produced on
 };
 
 namespace vb {
 
 int fail(vb_ctx* ctx, int code, const char* fmt, ...);
 int ensure(vb_ctx* ctx, DeviceBuffer& b, size_t bytes);
-int ensure_pinned(vb_ctx* ctx, size_t bytes);   // ctx->pin_host / pin_dev hold at least `bytes`
+// `b` holds at least `bytes` (mapped: with its device address).  A block in use must be quiescent first: the caller waits
+// -- each site knows what may still be reading its block -- and zero-fills where its readers need that.
+int ensure_pinned(vb_ctx* ctx, PinnedBuffer& b, size_t bytes, bool mapped);
+int ensure_pinned(vb_ctx* ctx, size_t bytes);   // ctx->pin holds at least `bytes`
 
 #define VB_HIP(ctx, expr)                                                              \
   do {                                                                                 \
@@ -433,7 +430,7 @@ struct MfCall {
   bool prep_next = false, skip_prep = false;
   bool* prep_done = nullptr;
   bool theta_on_device = false;   // theta_src[0] is device memory (the fit loop's iterate), not a pinned staging copy
-  // blocking call: ask the finalize kernel to signal completion through these words (see vb_ctx::done_host); *done_groups
+  // blocking call: ask the finalize kernel to signal completion through these words (see vb_ctx::done_pin); *done_groups
   // reports how many workgroups will (0: this evaluation does not end in the fused finalize -- wait on the stream)
   unsigned long long* done_dev = nullptr;
   unsigned long long done_seq = 0;
@@ -457,7 +454,7 @@ constexpr int64_t kSoftmaxChunkDoubles = (int64_t)16 << 20;
 struct LegacyFinish;
 // (defer != nullptr: the kernels are enqueued, the state is left untouched and *defer describes the finish -- exact path only,
 // VB_ERR_UNSUPPORTED otherwise)
-int legacy_dev_randn(vb_ctx* ctx, uint32_t key[624], int* pos, int* has_gauss, double* gauss, const NoiseSlot& ns,
+int legacy_dev_randn(vb_ctx* ctx, uint32_t key[624], int* pos, int* has_gauss, double* gauss, double* dst, int64_t ld,
                      int64_t n_total, int64_t d, int64_t row_begin, int64_t rows, LegacyFinish* defer = nullptr);
 // numpy's legacy word stream on the device (vb_legacy_dev.hip) for the draws built on it (vb_legacy_gamma.hip)
 struct FetchSeg {                  // `bytes` (a multiple of 8) from device address `src` (8-byte aligned) to host address `dst`
@@ -557,18 +554,19 @@ struct LegacySpec {
   DeviceBuffer work;                   // the speculation's own scratch (ctx->legacy_work's twin) and what goes with it
   const void* poly_at = nullptr;
   size_t poly_bytes = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_main = nullptr;
-  unsigned long long* land_host = nullptr;   // mapped landing area of the deferred finish (kLegacyFinishWords)
-  unsigned long long* land_dev = nullptr;
+  Stream stream;
+  Event ev_main;
+  PinnedBuffer land;                   // mapped landing area of the deferred finish (kLegacyFinishWords)
   unsigned long long seq = 0;
-  ::vb_legacy_rng* clone = nullptr;
+  struct CloneDelete { void operator()(::vb_legacy_rng* g) const { (void)vb_legacy_rng_destroy(g); } };
+  std::unique_ptr<::vb_legacy_rng, CloneDelete> clone;
   uint64_t launched = 0, adopted = 0, discarded = 0;
   // a caller whose rounds look alike but whose generator moves in between (host draws: a chi-square vector below the device
   // gate, sample() calls) would pay a wasted generation and a wait for it every call: two jobs discarded in a row stop the
   // speculation for the next 64 rounds of this generator
   int discard_streak = 0, cooldown = 0;
 };
+inline void LegacySpecDelete::operator()(LegacySpec* s) const { delete s; }
 
 
 // log density of the installed tempering prior (ctx->temper.kind != 0) at the rows of X
@@ -642,11 +640,11 @@ struct FetchPlan {
   bool ok = false;
   int n = 0;
   long long first[9] = {0};            // first word of segment k in the mapped buffer (64-byte aligned); [n] = total
-  unsigned long long* host = nullptr;  // the mapped buffer, host / device address
+  unsigned long long* host = nullptr;  // alias: the mapped buffer (vb_ctx::fetch_pin), host / device address
   unsigned long long* dev = nullptr;
   size_t o_done = 0;                   // word index of the completion word
-  unsigned long long* done_dev = nullptr;
-  unsigned* ticket = nullptr;          // device counter, zero between launches
+  unsigned long long* done_dev = nullptr;      // alias
+  unsigned* ticket = nullptr;          // alias: device counter (vb_ctx::fetch_ticket), zero between launches
   unsigned long long seq = 0;
 };
 int fetch_plan(vb_ctx* ctx, const FetchSeg* segs, int n_segs, FetchPlan* plan);

@@ -124,7 +124,7 @@ struct FitRun {
     hipStream_t cs = ctx->fit_copy_st;
     VB_HIP(ctx, hipEventRecord(ctx->fit_ev_step[slot], ctx->stream));
     VB_HIP(ctx, hipStreamWaitEvent(cs, ctx->fit_ev_step[slot], 0));
-    double* dst = ctx->fit_ring + (size_t)slot * ctx->fit_ring_doubles;
+    double* dst = ctx->fit_ring.host_as<double>() + (size_t)slot * ctx->fit_ring_doubles;
     const size_t row = (size_t)p * sizeof(double);
     if (h_hist && k >= step.hist_first)
       VB_HIP(ctx, hipMemcpyAsync(dst, step.hist + (k - step.hist_first) * p, row, hipMemcpyDeviceToHost, cs));
@@ -168,19 +168,17 @@ struct FitRun {
     streamed = (h_hist || h_dirs || h_grads) && !(e && atoi(e) == 0) &&
                (size_t)p * sizeof(double) >= (m ? (size_t)atoll(m) : (size_t)1 << 18);
     if (!streamed) return VB_OK;
-    if (!ctx->fit_copy_st) VB_HIP(ctx, hipStreamCreateWithFlags(&ctx->fit_copy_st, hipStreamNonBlocking));
+    VB_HIP(ctx, ctx->fit_copy_st.create(hipStreamNonBlocking));
     const size_t slot = (size_t)round_up(3 * p, 16);
     if (ctx->fit_ring_doubles < slot) {
       VB_HIP(ctx, hipStreamSynchronize(ctx->fit_copy_st));
-      if (ctx->fit_ring) VB_HIP(ctx, hipHostFree(ctx->fit_ring));
-      ctx->fit_ring = nullptr;
       ctx->fit_ring_doubles = 0;
-      VB_HIP(ctx, hipHostMalloc((void**)&ctx->fit_ring, vb_ctx::kFitRing * slot * sizeof(double), hipHostMallocDefault));
+      VB_TRY(ensure_pinned(ctx, ctx->fit_ring, vb_ctx::kFitRing * slot * sizeof(double), false));
       ctx->fit_ring_doubles = slot;
     }
     for (int i = 0; i < vb_ctx::kFitRing; ++i) {
-      if (!ctx->fit_ev_step[i]) VB_HIP(ctx, hipEventCreateWithFlags(&ctx->fit_ev_step[i], hipEventDisableTiming));
-      if (!ctx->fit_ev_copy[i]) VB_HIP(ctx, hipEventCreateWithFlags(&ctx->fit_ev_copy[i], hipEventDisableTiming));
+      VB_HIP(ctx, ctx->fit_ev_step[i].create(hipEventDisableTiming));
+      VB_HIP(ctx, ctx->fit_ev_copy[i].create(hipEventDisableTiming));
     }
     return VB_OK;
   }
@@ -188,7 +186,7 @@ struct FitRun {
     const int64_t k = drained, p = step.p;
     const int slot = (int)(k % vb_ctx::kFitRing);
     VB_HIP(ctx, hipEventSynchronize(ctx->fit_ev_copy[slot]));
-    const double* src = ctx->fit_ring + (size_t)slot * ctx->fit_ring_doubles;
+    const double* src = ctx->fit_ring.host_as<double>() + (size_t)slot * ctx->fit_ring_doubles;
     const size_t row = (size_t)p * sizeof(double);
     if (h_hist && k >= step.hist_first) memcpy(h_hist + (k - step.hist_first) * p, src, row);
     if (h_dirs) memcpy(h_dirs + k * p, src + p, row);

@@ -323,12 +323,6 @@ bool flow_known(vb_ctx* ctx, const vb_flow* f) {
   return false;
 }
 
-void flow_free(vb_flow* f) {
-  for (vb::DeviceBuffer* b : {&f->masks, &f->table, &f->wpack, &f->theta, &f->out, &f->work})
-    if (b->ptr) (void)hipFree(b->ptr);
-  delete f;
-}
-
 int flow_ensure_work(vb_ctx* ctx, vb_flow* f, int64_t n) {
   if (n <= f->n_cap) return VB_OK;
   const FlowWork geo = flow_layout(*f, n, nullptr);
@@ -519,7 +513,7 @@ int flow_call_setup(vb_ctx* ctx, vb_flow* f, int slot, int64_t n, int prior_fami
 }  // namespace
 
 void flow_release_all(vb_ctx* ctx) {
-  for (vb_flow* f : ctx->flows) flow_free(f);
+  for (vb_flow* f : ctx->flows) delete f;
   ctx->flows.clear();
 }
 
@@ -577,11 +571,11 @@ int vb_flow_create(vb_ctx* ctx, int64_t d, int64_t k, const double* masks, int64
   auto step = [&](hipError_t e) {
     if (e != hipSuccess && rc == VB_OK) rc = fail(ctx, VB_ERR_HIP, "NVPFlow: %s", hipGetErrorString(e));
   };
-  step(hipMalloc(&f->masks.ptr, (size_t)k * d * sizeof(double)));
-  step(hipMalloc(&f->table.ptr, real.size() * sizeof(vb_flow::Layer)));
-  step(hipMalloc(&f->wpack.ptr, (size_t)(pk + 32) * sizeof(double)));
-  step(hipMalloc(&f->theta.ptr, (size_t)(al32(f->p) + 2 * d + 32) * sizeof(double)));
-  step(hipMalloc(&f->out.ptr, (size_t)(1 + f->p + 32) * sizeof(double)));
+  step(f->masks.alloc((size_t)k * d * sizeof(double)));
+  step(f->table.alloc(real.size() * sizeof(vb_flow::Layer)));
+  step(f->wpack.alloc((size_t)(pk + 32) * sizeof(double)));
+  step(f->theta.alloc((size_t)(al32(f->p) + 2 * d + 32) * sizeof(double)));
+  step(f->out.alloc((size_t)(1 + f->p + 32) * sizeof(double)));
   if (rc == VB_OK) {
     step(hipMemsetAsync(f->wpack.ptr, 0, (size_t)(pk + 32) * sizeof(double), ctx->stream));
     step(hipMemcpyAsync(f->masks.ptr, masks, (size_t)k * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -590,7 +584,7 @@ int vb_flow_create(vb_ctx* ctx, int64_t d, int64_t k, const double* masks, int64
     step(hipStreamSynchronize(ctx->stream));
   }
   if (rc != VB_OK) {
-    flow_free(f);
+    delete f;
     return rc;
   }
   ctx->flows.push_back(f);
@@ -605,7 +599,7 @@ int vb_flow_destroy(vb_ctx* ctx, vb_flow* flow) {
       (void)hipSetDevice(ctx->device);
       VB_TRY(sync_streams(ctx));
       ctx->flows.erase(ctx->flows.begin() + (long)i);
-      flow_free(flow);
+      delete flow;
       return VB_OK;
     }
   return fail(ctx, VB_ERR_INVALID, "unknown NVPFlow handle for this context");

@@ -650,9 +650,9 @@ int legacy_finish_complete(vb_ctx* ctx, const LegacyFinish& f, const unsigned lo
 }
 
 // The draws s.randn(n_total, d) of the generator whose state is (key, pos, has_gauss, gauss): rows [row_begin,
-// row_begin + rows) into `ns`; the state afterwards in the same variables.  VB_ERR_UNSUPPORTED: nothing changed, draw on
+// row_begin + rows) into `dst` (row stride ld); the state afterwards in the same variables.  VB_ERR_UNSUPPORTED: nothing changed, draw on
 // the host.
-int legacy_dev_randn(vb_ctx* ctx, uint32_t key[624], int* pos, int* has_gauss, double* gauss, const NoiseSlot& ns,
+int legacy_dev_randn(vb_ctx* ctx, uint32_t key[624], int* pos, int* has_gauss, double* gauss, double* dst, int64_t ld,
                      int64_t n_total, int64_t d, int64_t row_begin, int64_t rows, LegacyFinish* defer) {
   hipStream_t st = ctx->stream;
   if (!ctx->legacy_table_ready) {      // (constant memory is per device: once per context, not once per process)
@@ -714,8 +714,8 @@ int legacy_dev_randn(vb_ctx* ctx, uint32_t key[624], int* pos, int* has_gauss, d
   EmitArgs a;
   a.words = words, a.attempts = attempts, a.base = pbase;
   a.pairs = pairs, a.n_vals = n_vals, a.first = first;
-  a.d = d, a.row_begin = row_begin, a.rows = rows, a.ld = ns.ld;
-  a.slot = (double*)ns.buf.ptr;
+  a.d = d, a.row_begin = row_begin, a.rows = rows, a.ld = ld;
+  a.slot = dst;
   a.hard_seg = exact ? nullptr : (double*)(base + o_hseg);
   a.hard_cnt = exact ? nullptr : (int*)(base + o_hcnt);
   double* hard_list = (double*)(base + o_hard);
@@ -765,15 +765,11 @@ int legacy_dev_randn(vb_ctx* ctx, uint32_t key[624], int* pos, int* has_gauss, d
   // results through one pinned buffer: [scalars 4 | accepted | list (first `spec` entries, speculatively) | fixed]
   const int64_t spec = std::min<int64_t>(hard_cap, pairs / 20 + 256);      // ~1.7 x the expected list length
   const size_t pin_doubles = 8 + (exact ? 0 : (size_t)4 * hard_cap + (size_t)3 * hard_cap) + 8;
-  if (ctx->legacy_pin_doubles < pin_doubles) {
-    if (ctx->legacy_pin) VB_HIP(ctx, hipHostFree(ctx->legacy_pin));
-    ctx->legacy_pin = nullptr;
-    VB_HIP(ctx, hipHostMalloc((void**)&ctx->legacy_pin, pin_doubles * sizeof(double), hipHostMallocDefault));
-    ctx->legacy_pin_doubles = pin_doubles;
-  }
-  int64_t* res = (int64_t*)ctx->legacy_pin;                 // [0] a*, [1] last pair listed?, [2] list length, [3] f x1 bits
+  if (ctx->legacy_pin.bytes < pin_doubles * sizeof(double))      // (no wait: every use below ends in a synchronisation)
+    VB_TRY(ensure_pinned(ctx, ctx->legacy_pin, pin_doubles * sizeof(double), false));
+  int64_t* res = ctx->legacy_pin.host_as<int64_t>();                // [0] a*, [1] last pair listed?, [2] list length, [3] f x1 bits
   int64_t* accepted = res + 4;
-  double* list = ctx->legacy_pin + 8;
+  double* list = ctx->legacy_pin.host_as<double>() + 8;
   double* fixed = list + 4 * hard_cap;
   res[2] = 0, res[5] = 0;
   VB_HIP(ctx, hipMemcpyAsync(res, scal, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));

@@ -87,7 +87,7 @@ int sym_sqrt(vb_ctx* ctx, const double* a, const double* e, int64_t d, double* r
   double* base = (double*)ctx->scratch.ptr;
   double *Y[2] = {base, base + mat}, *Z[2] = {base + 2 * mat, base + 3 * mat}, *T = base + 4 * mat,
          *M0 = base + 5 * mat;
-  double* h = ctx->pin_host;
+  double* h = ctx->pin.host_as<double>();
   hipStream_t st = ctx->stream;
 
   // scale: the infinity norm max_i sum_j |a_ij| >= lambda_max (round 5; rounds 2-4 used the Frobenius norm, which leaves a
@@ -129,8 +129,8 @@ int sym_sqrt(vb_ctx* ctx, const double* a, const double* e, int64_t d, double* r
   VB_HIP(ctx, hipMemcpyAsync(M0, h, (size_t)mat * sizeof(double), hipMemcpyHostToDevice, st));
 
   // residual slots: one per step (the epilogue of step k's first GEMM adds into slot k), read a GROUP of steps at a time
-  double* hp_base = ctx->pin_host + mat;
-  double* part_base = ctx->pin_dev + mat;
+  double* hp_base = ctx->pin.host_as<double>() + mat;
+  double* part_base = ctx->pin.dev_as<double>() + mat;
   for (int64_t i = 0; i < (kMaxSteps + 2) * pstride; ++i) hp_base[i] = 0.0;
   auto residual = [&](int slot) {
     double s = 0.0;
@@ -323,7 +323,7 @@ static int ns_run(vb_ctx* ctx, int m, int64_t ld, double* set0, double* set1, co
     for (int k = 0; k < count; ++k) {
       double *Y = set[cur], *T = Y + mat, *Z = Y + 2 * mat;
       // T = (3 I - Z Y) / 2 with ||I - Z Y||_F^2 of the state BEFORE this step into partial slot `applied + k`
-      gemm_f64_launch<true>(st, square(Z, Y, ld, m), 1, n_cu, EpiNsT{T, ld, ctx->pin_dev + (int64_t)(applied + k) * n_part});
+      gemm_f64_launch<true>(st, square(Z, Y, ld, m), 1, n_cu, EpiNsT{T, ld, ctx->pin.dev_as<double>() + (int64_t)(applied + k) * n_part});
       GemmArgs g = square(Y, T, ld, m);      // batch 0: Y T, batch 1: T Z
       g.batch = 1;
       g.batch_a = mat, g.batch_b = mat;
@@ -334,7 +334,7 @@ static int ns_run(vb_ctx* ctx, int m, int64_t ld, double* set0, double* set1, co
   auto read_residuals = [&](int count) {      // (after a synchronisation)
     for (int k = 0; k < count; ++k) {
       double s = 0.0;
-      const double* hp = ctx->pin_host + (int64_t)(applied + k) * n_part;
+      const double* hp = ctx->pin.host_as<double>() + (int64_t)(applied + k) * n_part;
       for (int64_t i = 0; i < n_part; ++i) s += hp[i];
       residual.push_back(sqrt(s));
     }
@@ -376,7 +376,7 @@ static int ns_run(vb_ctx* ctx, int m, int64_t ld, double* set0, double* set1, co
   // control wanted) the other one, whose Y and Z the extra step only read
   cur = c.done & 1;
   double* Y = set[cur];
-  gemm_f64_launch<true>(st, square(Y, Y, ld, m), 1, n_cu, EpiResidual{M0, ld, d_check, ctx->pin_dev + (int64_t)kNsMaxSteps * n_part, d_cols});
+  gemm_f64_launch<true>(st, square(Y, Y, ld, m), 1, n_cu, EpiResidual{M0, ld, d_check, ctx->pin.dev_as<double>() + (int64_t)kNsMaxSteps * n_part, d_cols});
   VB_HIP(ctx, hipGetLastError());
   *cur_out = cur;
   info[0] = (double)c.done, info[1] = c.res, info[2] = -1.0;      // [2]: read by the caller after its own last launch + sync
@@ -406,7 +406,7 @@ int sym_sqrt_dev(vb_ctx* ctx, const double* Lfull, const double* Lt, int64_t d, 
   double loc[3];
   const bool hint_on = !(getenv("VB_NS_HINT") && atoi(getenv("VB_NS_HINT")) == 0);      // (0: the step-by-step control only)
   for (int attempt = 0; attempt < 2; ++attempt) {
-    VB_HIP(ctx, hipMemsetAsync(ctx->pin_dev, 0, (size_t)((kNsMaxSteps + 2) * n_part) * sizeof(double), st));
+    VB_HIP(ctx, hipMemsetAsync(ctx->pin.dev_as<double>(), 0, (size_t)((kNsMaxSteps + 2) * n_part) * sizeof(double), st));
     VB_HIP(ctx, hipMemsetAsync(scal, 0, sizeof(double), st));
     gemm_f64_launch<true>(st, square(Lfull, Lt, ld, m), 1, n_cu, EpiStore{M0, ld});
     hipLaunchKernelGGL(ns_norm_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, st, (const double*)M0, m, ld, scal);
@@ -430,7 +430,7 @@ int sym_sqrt_dev(vb_ctx* ctx, const double* Lfull, const double* Lt, int64_t d, 
   VB_HIP(ctx, hipStreamSynchronize(st));
   legacy_poll(ctx);
   double acc = 0.0;
-  for (int64_t i = 0; i < n_part; ++i) acc += ctx->pin_host[(int64_t)kNsMaxSteps * n_part + i];
+  for (int64_t i = 0; i < n_part; ++i) acc += ctx->pin.host_as<double>()[(int64_t)kNsMaxSteps * n_part + i];
   acc = sqrt(acc);
   if (info) info[0] = loc[0], info[1] = loc[1], info[2] = acc;
   if (!(acc < tol)) return VB_ERR_UNSUPPORTED;
@@ -511,7 +511,7 @@ int sym_sqrt_frechet_dev(vb_ctx* ctx, const double* Lfull, const double* Lt, con
   double loc[3];
   const bool hint_on = !(getenv("VB_NS_HINT") && atoi(getenv("VB_NS_HINT")) == 0);
   for (int attempt = 0; attempt < 2; ++attempt) {
-    VB_HIP(ctx, hipMemsetAsync(ctx->pin_dev, 0, (size_t)((kNsMaxSteps + 2) * n_part) * sizeof(double), st));      // (as sym_sqrt_dev)
+    VB_HIP(ctx, hipMemsetAsync(ctx->pin.dev_as<double>(), 0, (size_t)((kNsMaxSteps + 2) * n_part) * sizeof(double), st));      // (as sym_sqrt_dev)
     VB_HIP(ctx, hipMemsetAsync(scal, 0, 4 * sizeof(double), st));
     gemm_f64_launch<true>(st, square(Lfull, Lt, ld, (int)d), 1, n_cu, EpiStore{A, ld});
     hipLaunchKernelGGL(ns_norm_kernel, dim3((unsigned)((d + 3) / 4)), dim3(256), 0, st, (const double*)A, (int)d, ld, scal);
@@ -535,7 +535,7 @@ int sym_sqrt_frechet_dev(vb_ctx* ctx, const double* Lfull, const double* Lt, con
   VB_HIP(ctx, hipStreamSynchronize(st));
   legacy_poll(ctx);
   double acc = 0.0;
-  for (int64_t i = 0; i < n_part; ++i) acc += ctx->pin_host[(int64_t)kNsMaxSteps * n_part + i];
+  for (int64_t i = 0; i < n_part; ++i) acc += ctx->pin.host_as<double>()[(int64_t)kNsMaxSteps * n_part + i];
   acc = sqrt(acc);
   if (info) info[0] = loc[0], info[1] = loc[1], info[2] = acc;
   if (!(acc < tol)) return VB_ERR_UNSUPPORTED;

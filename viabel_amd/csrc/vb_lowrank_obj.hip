@@ -736,8 +736,8 @@ int lr_elbo_sums_any_rank(vb_ctx* ctx, const NoiseSlot& ns, const NoiseSlot& nz,
   // the parameter goes up as it is, through the pinned staging area (no synchronisation: the call's last statement
   // waits for the stream, so the area is free again when the next call writes it)
   VB_TRY(ensure_pinned(ctx, (size_t)(p + n_out) * sizeof(double)));
-  memcpy(ctx->pin_host, theta_host, (size_t)p * sizeof(double));
-  VB_HIP(ctx, hipMemcpyAsync(base + o_theta, ctx->pin_host, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
+  memcpy(ctx->pin.host_as<double>(), theta_host, (size_t)p * sizeof(double));
+  VB_HIP(ctx, hipMemcpyAsync(base + o_theta, ctx->pin.host_as<double>(), (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(lrs_prep_kernel, dim3((unsigned)(((kp + 1) * ld + 255) / 256)), dim3(256), 0, st,
                      (const double*)(base + o_theta), (int)d, (int)k, ld, (int)kp, base + o_mu, base + o_sig, base + o_bt);
   VB_HIP(ctx, hipGetLastError());

@@ -1938,10 +1938,10 @@ int mf_enqueue(vb_ctx* ctx, const MfCall& c) {
 int pipe_init(vb_ctx* ctx) {
   Pipeline& P = ctx->pipe;
   if (P.post) return VB_OK;
-  VB_HIP(ctx, hipStreamCreateWithFlags(&P.post, hipStreamNonBlocking));
+  VB_HIP(ctx, P.post.create(hipStreamNonBlocking));
   for (int i = 0; i < kPipeSets; ++i) {
-    VB_HIP(ctx, hipEventCreateWithFlags(&P.ev_k1[i], hipEventDisableTiming));
-    VB_HIP(ctx, hipEventCreateWithFlags(&P.ev_fin[i], hipEventDisableTiming));
+    VB_HIP(ctx, P.ev_k1[i].create(hipEventDisableTiming));
+    VB_HIP(ctx, P.ev_fin[i].create(hipEventDisableTiming));
   }
   return VB_OK;
 }

@@ -853,26 +853,23 @@ static int mvt_factors_device(vb_ctx* ctx, const MvtLayout& L, double* base, int
   // the caller keeps ownership of theta_host: it goes through a pinned staging buffer of the context, so the copy is
   // asynchronous and nothing here waits for the stream
   if (ctx->mvt_pin_doubles < p) {
-    if (ctx->mvt_pin) {
+    if (ctx->mvt_pin.host) {
       legacy_poll(ctx);      // (before the wait: the host enqueues a look-ahead draw instead of idling; after it: what landed meanwhile)
       VB_HIP(ctx, hipStreamSynchronize(st));
       legacy_poll(ctx);
-      VB_HIP(ctx, hipHostFree(ctx->mvt_pin));
-      ctx->mvt_pin = nullptr;
     }
     const size_t pr = (p + 7) / 8 * 8;      // (whole 64-byte lines per slot: mvt_unpack_kernel reads 16-byte pairs)
-    VB_HIP(ctx, hipHostMalloc((void**)&ctx->mvt_pin, 2 * pr * sizeof(double), hipHostMallocMapped));
-    VB_HIP(ctx, hipHostGetDevicePointer((void**)&ctx->mvt_pin_dev, ctx->mvt_pin, 0));
+    VB_TRY(ensure_pinned(ctx, ctx->mvt_pin, 2 * pr * sizeof(double), true));
     ctx->mvt_pin_doubles = pr;
   }
   // two staging slots taken in turn; an event behind each slot's copy is waited for before the slot is rewritten (a
   // deferred refresh returns without a synchronisation, so back-to-back refreshes could otherwise overwrite a slot
   // whose copy is still queued behind kernels)
   ctx->mvt_pin_slot ^= 1;
-  hipEvent_t& slot_ev = ctx->mvt_pin_ev[ctx->mvt_pin_slot];
-  if (!slot_ev) VB_HIP(ctx, hipEventCreateWithFlags(&slot_ev, hipEventDisableTiming));
+  Event& slot_ev = ctx->mvt_pin_ev[ctx->mvt_pin_slot];
+  if (!slot_ev) VB_HIP(ctx, slot_ev.create(hipEventDisableTiming));
   else VB_HIP(ctx, hipEventSynchronize(slot_ev));
-  double* stage = ctx->mvt_pin + (size_t)ctx->mvt_pin_slot * ctx->mvt_pin_doubles;
+  double* stage = ctx->mvt_pin.host_as<double>() + (size_t)ctx->mvt_pin_slot * ctx->mvt_pin_doubles;
   memcpy(stage, theta_host, p * sizeof(double));
   if (L.ld != d)      // (pad columns of mu and c: the unpack and the prep kernel write columns [0, d) only)
     VB_HIP(ctx, hipMemsetAsync(base + L.o_mu, 0, (size_t)(2 * L.ld) * sizeof(double), st));
@@ -883,7 +880,7 @@ static int mvt_factors_device(vb_ctx* ctx, const MvtLayout& L, double* base, int
   // (the one-launch front: nothing but the unpack in front of the sampling product -- row scales and scalars ride along, L goes
   // to the side stream)
   const bool front = unpack_env && defer_inverse && side_env && !lfull_main;
-  const double* theta_mapped = ctx->mvt_pin_dev + (size_t)ctx->mvt_pin_slot * ctx->mvt_pin_doubles;
+  const double* theta_mapped = ctx->mvt_pin.dev_as<double>() + (size_t)ctx->mvt_pin_slot * ctx->mvt_pin_doubles;
   if (unpack_env) {
     const int nt = (D + 31) / 32, nb_t = (int)((p + 1023) / 1024), nb_z = nt * (nt + 1) / 2;
     int nb_i = front && chi ? (int)((n_inv + 1023) / 1024) : 0;
@@ -904,10 +901,8 @@ static int mvt_factors_device(vb_ctx* ctx, const MvtLayout& L, double* base, int
   // (the transposes write every entry of the d x d blocks; the pad columns hold the zeros of the allocation)
   const int tiles = (D + 31) / 32, gx = tiles * tiles > (D + 3) / 4 ? tiles * tiles : (D + 3) / 4;
   if (defer_inverse && side_env) {
-    if (!ctx->mvt_side) {
-      VB_HIP(ctx, hipStreamCreateWithFlags(&ctx->mvt_side, hipStreamNonBlocking));
-      VB_HIP(ctx, hipEventCreateWithFlags(&ctx->mvt_ev_join, hipEventDisableTiming));
-    }
+    VB_HIP(ctx, ctx->mvt_side.create(hipStreamNonBlocking));
+    VB_HIP(ctx, ctx->mvt_ev_join.create(hipEventDisableTiming));
     // (the fork: the staging slot's event, recorded right behind the unpack above -- no event of its own)
     ctx->mvt_ev_fork = slot_ev;
     auto& a = ctx->mvt_inv_args;

@@ -476,17 +476,11 @@ int user_model_set_callback(vb_ctx* ctx, int64_t dim, vb_model_callback fn, void
 static int user_rows_host(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
                           int64_t ldg, double* f) {
   const size_t nd = (size_t)n * (size_t)d, need = 2 * nd + (size_t)n;
-  if (ctx->user_host_pin_doubles < need) {
-    if (ctx->user_host_pin) {
-      VB_HIP(ctx, hipStreamSynchronize(st));
-      VB_HIP(ctx, hipHostFree(ctx->user_host_pin));
-      ctx->user_host_pin = nullptr;
-      ctx->user_host_pin_doubles = 0;
-    }
-    VB_HIP(ctx, hipHostMalloc((void**)&ctx->user_host_pin, need * sizeof(double), hipHostMallocDefault));
-    ctx->user_host_pin_doubles = need;
+  if (ctx->user_host_pin.bytes < need * sizeof(double)) {
+    if (ctx->user_host_pin.host) VB_HIP(ctx, hipStreamSynchronize(st));
+    VB_TRY(ensure_pinned(ctx, ctx->user_host_pin, need * sizeof(double), false));
   }
-  double *zh = ctx->user_host_pin, *fh = zh + nd, *gh = fh + n;
+  double *zh = ctx->user_host_pin.host_as<double>(), *fh = zh + nd, *gh = fh + n;
   const size_t row = (size_t)d * sizeof(double);
   VB_HIP(ctx, hipMemcpy2DAsync(zh, row, Z, (size_t)ldz * sizeof(double), row, (size_t)n, hipMemcpyDeviceToHost, st));
   VB_HIP(ctx, hipStreamSynchronize(st));
