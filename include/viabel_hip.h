@@ -60,6 +60,14 @@ typedef struct vb_ctx vb_ctx;
                                   dparams=[X(n_data x p)|y(n_data)|prior_sd], iparams=[n_data, n_classes];
                                   y holds integer labels in [0, n_classes).  Taken by every route that takes a
                                   VB_MODEL_SOURCE target (per-row f and gradient formed before the streaming pass) */
+#define VB_MODEL_MULTILEVEL 6  /* varying-intercept (multilevel) GLM, non-centred: D = p + n_groups + 1,
+                                  theta = [b (p) | u (n_groups) | omega], tau = exp(omega), eta_i = x_i' b + tau u_{g_i};
+                                  b ~ N(0, prior_sd), u ~ N(0, 1), tau ~ HalfNormal(tau_sd) (Jacobian included), any
+                                  VB_GLM_* likelihood.  The observations arrive SORTED by group:
+                                  dparams=[X(n_data x p)|y(n_data)|prior_sd|tau_sd|noise_sd],
+                                  iparams=[n_data, n_groups, link | offsets(n_groups + 1) | group of each observation(n_data)]
+                                  with offsets[j] .. offsets[j + 1] the run of group j (empty runs allowed).  Taken by
+                                  every route that takes a VB_MODEL_SOURCE target, like VB_MODEL_SOFTMAX */
 
 /* noise kinds for vb_noise_generate */
 /* likelihoods of the regression target VB_MODEL_LOGISTIC (iparams = [n_data, link]; default Bernoulli-logit):
@@ -478,6 +486,11 @@ int vb_glm_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double*
  * eta_ic = x_i' b_c of draw s (s x d row-major, d = n_classes * p); the prior not included.  VB_ERR_STATE without a
  * bound model, VB_ERR_UNSUPPORTED for any other model.                                                          */
 int vb_softmax_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out);
+/* The same for the bound VB_MODEL_MULTILEVEL target: ll_out[s * n_data + i] = log p(y_i | eta_i) at eta_i = x_i' b +
+ * tau u_{g_i} of draw s (s x d row-major, d = p + n_groups + 1) as a NORMALISED density (the Poisson -log y_i!, the
+ * Gaussian -log noise_sd - log(2 pi) / 2 included), the priors not; observations in the order of the bound (sorted)
+ * data.  VB_ERR_STATE without a bound model, VB_ERR_UNSUPPORTED for any other model.                               */
+int vb_multilevel_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out);
 int vb_glm_psis_loo(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const double* log_ratios,
                     const double* log_w, double reff, double* loo, double* khat, double* lpd);
 

@@ -22,11 +22,15 @@ VB_OK, VB_ERR_INVALID, VB_ERR_HIP, VB_ERR_UNSUPPORTED, VB_ERR_STATE, VB_ERR_NUME
 FAMILY_MF_GAUSSIAN, FAMILY_MF_STUDENT_T, FAMILY_FULLRANK_GAUSSIAN, FAMILY_MULTIVARIATE_T, FAMILY_LOWRANK_GAUSSIAN = \
     range(5)
 MODEL_GAUSS_DIAG, MODEL_FUNNEL, MODEL_GAUSS_FULL, MODEL_LOGISTIC, MODEL_SOURCE, MODEL_SOFTMAX = range(6)
-# targets that hand every pipeline finished rows (f, grad f): a softmax target goes wherever a source model goes
-MODELS_WITH_ROWS = (MODEL_SOURCE, MODEL_SOFTMAX)
+MODEL_MULTILEVEL = 6
+# targets that hand every pipeline finished rows (f, grad f): a softmax or multilevel target goes wherever a source model goes
+MODELS_WITH_ROWS = (MODEL_SOURCE, MODEL_SOFTMAX, MODEL_MULTILEVEL)
 # doubles of predictor matrix one row chunk of the softmax pipeline may hold (csrc/vb_common.h: kSoftmaxChunkDoubles);
 # a chunk is max(8, SOFTMAX_CHUNK_DOUBLES // (n_classes * round_up(n_data, 16))) rows
 SOFTMAX_CHUNK_DOUBLES = 16 << 20
+# ... and of the multilevel pipeline (kMultilevelChunkDoubles): a chunk is max(8, MULTILEVEL_CHUNK_DOUBLES //
+# round_up(n_data, 16)) rows
+MULTILEVEL_CHUNK_DOUBLES = 16 << 20
 GLM_BERNOULLI_LOGIT, GLM_POISSON, GLM_GAUSSIAN = range(3)
 NOISE_NORMAL, NOISE_STUDENT_T = range(2)
 FLAG_PATH_DERIV = 1
@@ -145,6 +149,7 @@ SIGNATURES = {
                                             ctypes.c_double, _c_double_p, _c_double_p]),
     'vb_glm_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
     'vb_softmax_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
+    'vb_multilevel_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
     'vb_glm_psis_loo': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p,
                                        ctypes.c_double, _c_double_p, _c_double_p, _c_double_p]),
     'vb_alpha_grad_meanfield': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
@@ -739,6 +744,15 @@ class Engine:
         s, d = x.shape
         out = np.empty((s, int(n_data)), dtype=np.float64)
         self._check(self._lib.vb_softmax_pointwise(self._ctx, _dptr(x), s, d, _dptr(out)))
+        return out
+
+    def multilevel_pointwise(self, x, n_data):
+        """``(S, n_data)`` normalised terms ``log p(y_i | x_i' b + tau u_{g_i})`` of the bound multilevel regression target
+        at the draws ``x`` (S x D), observations in the bound (group-sorted) order."""
+        x = _f64(x)
+        s, d = x.shape
+        out = np.empty((s, int(n_data)), dtype=np.float64)
+        self._check(self._lib.vb_multilevel_pointwise(self._ctx, _dptr(x), s, d, _dptr(out)))
         return out
 
     def glm_psis_loo(self, x, n_data, log_ratios=None, log_w=None, reff=1.0):

@@ -764,6 +764,78 @@ int vb_set_model(vb_ctx* ctx, int model_id, int64_t dim, const double* dparams, 
         dev[(size_t)nd * m.ldp + (size_t)j * m.ldq + i] = v;
       }
     for (int64_t i = 0; i < nd; ++i) dev[(size_t)nd * m.ldp + (size_t)p * m.ldq + i] = dparams[nd * p + i];
+  } else if (model_id == VB_MODEL_MULTILEVEL) {
+    const char* kExpect =
+        "multilevel regression expects dparams = [X(n_data x p) | y(n_data) | prior_sd | tau_sd | noise_sd], iparams = "
+        "[n_data, n_groups, link | offsets(n_groups + 1) | group of each observation(n_data)] and a dimension of "
+        "p + n_groups + 1";
+    if (n_iparams < 3 || !iparams || !dparams || iparams[0] <= 0 || iparams[1] < 1 || iparams[0] > 0x7fffffffll ||
+        iparams[1] > 0x7fffffffll || dim > 0x7fffffffll || dim - iparams[1] - 1 < 1 ||
+        iparams[2] < VB_GLM_BERNOULLI_LOGIT || iparams[2] > VB_GLM_GAUSSIAN ||
+        n_iparams != (size_t)(3 + iparams[1] + 1 + iparams[0]) ||
+        n_dparams != (size_t)(iparams[0] * (dim - iparams[1] - 1) + iparams[0]) + 3)
+      return fail(ctx, VB_ERR_INVALID, "%s", kExpect);
+    const int64_t nd = iparams[0], ng = iparams[1], p = dim - ng - 1;
+    const int link = (int)iparams[2];
+    const int64_t* off = iparams + 3;
+    const int64_t* grp = off + ng + 1;
+    const double sd = dparams[nd * p + nd], tsd = dparams[nd * p + nd + 1], nsd = dparams[nd * p + nd + 2];
+    if (!(sd > 0.0)) return fail(ctx, VB_ERR_INVALID, "multilevel prior_sd must be positive");
+    if (!(tsd > 0.0)) return fail(ctx, VB_ERR_INVALID, "multilevel tau_sd must be positive");
+    if (!(nsd > 0.0)) return fail(ctx, VB_ERR_INVALID, "multilevel noise_sd must be positive");
+    if (off[0] != 0 || off[ng] != nd)
+      return fail(ctx, VB_ERR_INVALID, "multilevel offsets must run from 0 to n_data (offsets[0] = %lld, offsets[%lld] = %lld)",
+                  (long long)off[0], (long long)ng, (long long)off[ng]);
+    for (int64_t j = 0; j < ng; ++j)
+      if (off[j + 1] < off[j])
+        return fail(ctx, VB_ERR_INVALID, "multilevel offsets must be monotone (offsets[%lld] = %lld > offsets[%lld] = %lld)",
+                    (long long)j, (long long)off[j], (long long)(j + 1), (long long)off[j + 1]);
+    for (int64_t i = 0; i < nd; ++i)
+      if (grp[i] < 0 || grp[i] >= ng)
+        return fail(ctx, VB_ERR_INVALID, "multilevel group labels must lie in [0, n_groups) (groups[%lld] = %lld)", (long long)i,
+                    (long long)grp[i]);
+    for (int64_t j = 0; j < ng; ++j)
+      for (int64_t i = off[j]; i < off[j + 1]; ++i)
+        if (grp[i] != j)
+          return fail(ctx, VB_ERR_INVALID, "multilevel observations must be sorted by group: observation %lld lies in the run of "
+                                           "group %lld and carries the label %lld", (long long)i, (long long)j, (long long)grp[i]);
+    m.n_data = nd;
+    m.n_groups = (int)ng;
+    m.n_feat = (int)p;
+    m.ldp = round_up(p, 16);
+    m.ldq = round_up(nd, 16);
+    m.tau = sd;
+    m.hyper_sd = tsd;
+    m.link = link;
+    m.aux = link == VB_GLM_GAUSSIAN ? nsd : 1.0;
+    m.c0 = 0.0;      // (the rows carry priors and constants themselves: see ModelDev::f0)
+    // b ~ N(0, sd), u ~ N(0, 1), tau ~ HalfNormal(tsd); the likelihood's constant as the flat regression target has it
+    m.f0 = -(double)p * (log(sd) + 0.5 * kLog2Pi) - 0.5 * (double)ng * kLog2Pi + log(2.0) - log(tsd) - 0.5 * kLog2Pi;
+    if (link == VB_GLM_POISSON) {
+      for (int64_t i = 0; i < nd; ++i) {
+        const double yi = dparams[nd * p + i];
+        if (!(yi >= 0.0)) return fail(ctx, VB_ERR_INVALID, "Poisson counts must be non-negative");
+        m.f0 -= lgamma(yi + 1.0);
+      }
+    } else if (link == VB_GLM_GAUSSIAN) {
+      m.f0 -= (double)nd * (log(nsd) + 0.5 * kLog2Pi);
+    }
+    // [X (nd x ldp) | X' (p x ldq) | y (ldq) | offsets (ng + 1 ints) | group of each observation (nd ints)]: the logistic
+    // target's layout with p in place of dim, then the two int arrays, each starting on a 16-byte boundary
+    const size_t o_off = (size_t)nd * m.ldp + (size_t)p * m.ldq + (size_t)m.ldq;
+    const size_t o_grp = o_off + (size_t)round_up((ng + 2) / 2, 2);
+    dev.assign(o_grp + (size_t)round_up((nd + 1) / 2, 2), 0.0);
+    for (int64_t i = 0; i < nd; ++i)
+      for (int64_t j = 0; j < p; ++j) {
+        const double v = dparams[i * p + j];
+        dev[(size_t)i * m.ldp + j] = v;
+        dev[(size_t)nd * m.ldp + (size_t)j * m.ldq + i] = v;
+      }
+    for (int64_t i = 0; i < nd; ++i) dev[(size_t)nd * m.ldp + (size_t)p * m.ldq + i] = dparams[nd * p + i];
+    int* off32 = reinterpret_cast<int*>(dev.data() + o_off);
+    int* grp32 = reinterpret_cast<int*>(dev.data() + o_grp);
+    for (int64_t j = 0; j <= ng; ++j) off32[j] = (int)off[j];
+    for (int64_t i = 0; i < nd; ++i) grp32[i] = (int)grp[i];
   } else {
     return fail(ctx, VB_ERR_INVALID, "unknown model id %d", model_id);
   }
@@ -781,6 +853,12 @@ int vb_set_model(vb_ctx* ctx, int model_id, int64_t dim, const double* dparams, 
     if (model_id == VB_MODEL_SOFTMAX) {
       m.p1 = m.p0 + (size_t)m.n_data * m.ldp;
       m.p2 = m.p1 + (size_t)m.n_feat * m.ldq;
+    }
+    if (model_id == VB_MODEL_MULTILEVEL) {
+      m.p1 = m.p0 + (size_t)m.n_data * m.ldp;
+      m.p2 = m.p1 + (size_t)m.n_feat * m.ldq;
+      m.grp_off = reinterpret_cast<const int*>(m.p2 + m.ldq);
+      m.grp_of = m.grp_off + 2 * round_up((m.n_groups + 2) / 2, 2);
     }
   }
   ctx->model = m;

@@ -79,12 +79,21 @@ struct ModelDev {
   // rows (f, G) with the prior and the constant inside, so c0 -- which the pipelines' epilogues add per sample -- stays 0
   // and the normalising constant lives in f0.
   int n_classes = 0;            // softmax: C
-  int n_feat = 0;               // softmax: p (dim = C p)
+  int n_feat = 0;               // softmax: p (dim = C p); multilevel: p (dim = p + J + 1)
   double f0 = 0.0;              // softmax: -C p (log sd + log(2 pi) / 2), added to every row's f
+  // VB_MODEL_MULTILEVEL (vb_multilevel.hip): theta = [b (n_feat) | u (n_groups) | omega]; p0 = X, p1 = X', p2 = y as for the
+  // softmax target, the observations sorted by group; tau = prior_sd of b, link / aux as for the regression target.  A rows
+  // target as well: c0 stays 0, f0 holds the likelihood's and the three priors' constants.
+  int n_groups = 0;             // multilevel: J
+  double hyper_sd = 1.0;        // multilevel: tau_sd, the scale of the half-normal prior on exp(omega)
+  const int* grp_off = nullptr; // multilevel: offsets [J + 1]: group j owns the observations grp_off[j] .. grp_off[j + 1]
+  const int* grp_of = nullptr;  // multilevel: group of each observation [n_data]
 };
 
 // targets whose rows (f, grad f) are formed before a pipeline's streaming pass and loaded by it (model_rows_enqueue)
-__host__ __device__ __forceinline__ bool model_has_rows(int id) { return id == VB_MODEL_SOURCE || id == VB_MODEL_SOFTMAX; }
+__host__ __device__ __forceinline__ bool model_has_rows(int id) {
+  return id == VB_MODEL_SOURCE || id == VB_MODEL_SOFTMAX || id == VB_MODEL_MULTILEVEL;
+}
 
 // per-observation log-likelihood term (without constants) and its derivative with respect to eta = x' b
 __device__ __forceinline__ double glm_term(int link, double aux, double y, double eta, double* dl) {
@@ -222,6 +231,7 @@ struct vb_ctx {
   vb::DeviceBuffer user_params;
   vb::DeviceBuffer glm_work;            // regression targets: split-K slabs of the gradient GEMM
   vb::DeviceBuffer sm_work;             // softmax target: packed samples, predictors / residuals, packed gradient, partials
+  vb::DeviceBuffer ml_work;             // multilevel target: predictors / residuals, strip partials, pointwise staging
   vb::DeviceBuffer mvt_state;           // multivariate-t DIS: state samples X, scratch
   int64_t mvt_n = 0, mvt_d = 0, mvt_n_total = 0;
   int64_t mvt_lq_off = 0;               // where this rank's log q of the residual pass start inside o_lq (the refresh writes them
@@ -446,11 +456,17 @@ void user_model_release(vb_ctx* ctx);
 // NULL, G[row] = grad f(Z[row]) (row stride ldg; columns >= d are not written)
 int softmax_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
                          int64_t ldg, double* f);
-// rows of the bound target by whichever of the two forms them: a source model's kernel or the softmax pipeline
+// rows of the bound target by whichever forms them: a source model's kernel, the softmax or the multilevel pipeline
 int model_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
                        int64_t ldg, double* f);
 // doubles of predictor matrix H one row chunk of the softmax pipeline may hold (mirrored by _lib.SOFTMAX_CHUNK_DOUBLES)
 constexpr int64_t kSoftmaxChunkDoubles = (int64_t)16 << 20;
+// multilevel GLM target (vb_multilevel.hip), the same contract; Z and G must be 16-byte aligned with ldg == ldz even (the
+// predictor product reads Z and the coefficient gradient's epilogue writes G in place: every pipeline's buffers are)
+int multilevel_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
+                            int64_t ldg, double* f);
+// doubles of predictor matrix H one row chunk of the multilevel pipeline may hold (mirrored by _lib.MULTILEVEL_CHUNK_DOUBLES)
+constexpr int64_t kMultilevelChunkDoubles = (int64_t)16 << 20;
 struct LegacyFinish;
 // (defer != nullptr: the kernels are enqueued, the state is left untouched and *defer describes the finish -- exact path only,
 // VB_ERR_UNSUPPORTED otherwise)

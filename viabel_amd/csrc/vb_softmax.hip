@@ -210,6 +210,7 @@ int softmax_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t l
 int model_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G, int64_t ldg,
                        double* f) {
   if (ctx->model.id == VB_MODEL_SOFTMAX) return softmax_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
+  if (ctx->model.id == VB_MODEL_MULTILEVEL) return multilevel_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
   return user_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
 }
 

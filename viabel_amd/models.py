@@ -14,7 +14,7 @@ from . import _lib
 
 __all__ = ['Model', 'DeviceModel', 'GaussianModel', 'FunnelModel', 'CorrelatedGaussianModel',
            'LogisticRegressionModel', 'PoissonRegressionModel', 'LinearRegressionModel', 'SoftmaxRegressionModel',
-           'SourceModel', 'CallableModel']
+           'MultilevelRegressionModel', 'SourceModel', 'CallableModel']
 
 
 class Model(object):
@@ -458,3 +458,109 @@ class SoftmaxRegressionModel(DeviceModel):
         eng = _lib.default_engine()
         eng.set_model(self.device_spec())
         return eng.softmax_pointwise(x, self.n_data)
+
+
+class MultilevelRegressionModel(DeviceModel):
+    """A varying-intercept (multilevel) GLM: ``eta_i = x_i' b + a_{g_i}`` with group effects ``a_j ~ N(0, tau)`` whose
+    scale ``tau`` is itself a parameter -- the hierarchical posterior with funnel geometry that ``vi_diagnostics`` exists
+    to expose.
+
+    ``X`` is ``(n_data, p)``, ``groups`` holds integer labels in ``[0, n_groups)`` (an integer array, or a float array
+    with integral values; groups without observations are legal), ``likelihood`` is ``'logistic'`` (``y`` in
+    ``{0, 1}``), ``'poisson'`` (``y >= 0``) or ``'gaussian'`` (known ``noise_sd``).  The parameter is non-centred and
+    unconstrained, ``dim = p + n_groups + 1``::
+
+        theta    = [ b (p) | u (J) | omega ],   tau = exp(omega),   group effects a = tau * u
+        eta_i    = x_i' b + tau * u_{g_i}
+        f(theta) = sum_i log p(y_i | eta_i)                             normalised, as the flat regression targets have it
+                   - |b|^2 / (2 prior_sd^2) - p (log prior_sd + log(2 pi) / 2)          b ~ N(0, prior_sd)
+                   - |u|^2 / 2 - J log(2 pi) / 2                                        u ~ N(0, 1)
+                   + log 2 - log tau_sd - log(2 pi) / 2 - tau^2 / (2 tau_sd^2) + omega  tau ~ HalfNormal(tau_sd), Jacobian
+        df/db    = X' r - b / prior_sd^2,   r_i = d log p(y_i | eta_i) / d eta_i
+        df/du_j  = tau * sum_{i: g_i = j} r_i - u_j
+        df/domega= tau * sum_i r_i u_{g_i} - tau^2 / tau_sd^2 + 1
+
+    There is no intercept: add a column of ones to ``X``.  The constructor sorts the observations by group (stably) so
+    that the device sees contiguous group runs; :meth:`pointwise_log_likelihood` answers in the caller's order.  The
+    engine forms all predictors with one fp64 MFMA product, applies the link in a kernel of its own, takes the coefficient
+    gradient with the regression targets' second product and the group gradients by segmented sums
+    (``csrc/vb_multilevel.hip``, ``DESIGN.md`` 4.16).  To every objective it looks like a :class:`SourceModel` and is
+    accepted wherever one is: ``ExclusiveKL`` (both estimator forms, the RGE control variates, ``NVPFlow``),
+    ``AlphaDivergence`` and ``DISInclusiveKL`` with every family, ``bbvi``, ``vi_diagnostics`` and the device-resident
+    fit.  Not in the reference."""
+
+    _LINKS = {'logistic': _lib.GLM_BERNOULLI_LOGIT, 'poisson': _lib.GLM_POISSON, 'gaussian': _lib.GLM_GAUSSIAN}
+
+    def __init__(self, X, y, groups, n_groups, likelihood='logistic', prior_sd=10.0, tau_sd=1.0, noise_sd=1.0):
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        g_in = np.asarray(groups)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1 or y.shape != (X.shape[0],) or g_in.shape != (X.shape[0],):
+            raise ValueError('X must be (n_data, p) with p >= 1, y and groups (n_data,)')
+        if isinstance(n_groups, bool) or int(n_groups) != n_groups or int(n_groups) < 1:
+            raise ValueError('n_groups must be an integer >= 1')
+        n_groups = int(n_groups)
+        if g_in.dtype.kind not in 'iuf':
+            raise ValueError('groups must hold integer labels (an integer array, or floats with integral values)')
+        g = g_in.astype(np.float64)
+        if not np.all(np.isfinite(g)) or np.any(g != np.floor(g)):
+            raise ValueError('groups must hold integral labels')
+        if np.any(g < 0) or np.any(g >= n_groups):
+            raise ValueError('group labels must lie in [0, n_groups)')
+        if likelihood not in self._LINKS:
+            raise ValueError("likelihood must be 'logistic', 'poisson' or 'gaussian'")
+        if not prior_sd > 0 or not tau_sd > 0 or not noise_sd > 0:
+            raise ValueError('prior_sd, tau_sd and noise_sd must be positive')
+        if not np.all(np.isfinite(y)):
+            raise ValueError('y must be finite')
+        if likelihood == 'logistic' and np.any((y != 0) & (y != 1)):
+            raise ValueError('y must lie in {0, 1}')
+        if likelihood == 'poisson' and np.any(y < 0):
+            raise ValueError('counts must be non-negative')
+        g = g.astype(np.int64)
+        # contiguous group runs for the device: a stable sort, undone by pointwise_log_likelihood
+        self.perm = np.argsort(g, kind='stable')
+        self.X, self.y, self.groups = np.ascontiguousarray(X[self.perm]), y[self.perm], g[self.perm]
+        self.offsets = np.concatenate([[0], np.cumsum(np.bincount(g, minlength=n_groups))]).astype(np.int64)
+        self.likelihood = likelihood
+        self.prior_sd, self.tau_sd, self.noise_sd = float(prior_sd), float(tau_sd), float(noise_sd)
+        self._n_groups = n_groups
+        super().__init__(X.shape[1] + n_groups + 1)
+
+    def _build_spec(self):
+        return (_lib.MODEL_MULTILEVEL, self._dim,
+                np.concatenate([self.X.ravel(), self.y, [self.prior_sd, self.tau_sd, self.noise_sd]]),
+                np.concatenate([[self.n_data, self._n_groups, self._LINKS[self.likelihood]], self.offsets,
+                                self.groups]).astype(np.int64))
+
+    @property
+    def n_data(self):
+        return self.X.shape[0]
+
+    @property
+    def n_groups(self):
+        return self._n_groups
+
+    @property
+    def n_features(self):
+        return self.X.shape[1]
+
+    def unpack(self, theta):
+        """``(b, u, tau)`` of ``theta`` ``(D,)`` or ``(N, D)``; the group effects are ``tau[..., None] * u``."""
+        theta = np.asarray(theta, dtype=np.float64)
+        if theta.ndim not in (1, 2) or theta.shape[-1] != self._dim:
+            raise ValueError('theta must have shape (N, {0}) or ({0},)'.format(self._dim))
+        p = self.n_features
+        return theta[..., :p], theta[..., p:p + self._n_groups], np.exp(theta[..., -1])
+
+    def pointwise_log_likelihood(self, x):
+        """``log p(y_i | x_i' b_s + tau_s u_{s, g_i})`` for every draw (row of ``x``) and observation, in the order the
+        observations were given to the constructor: ``(S, n_data)``, the ``log_lik`` argument of :func:`psisloo`
+        (``psisloo(log_lik, log_ratios)`` is this model's route to LOO).  Normalised densities, without the priors
+        (``vb_multilevel_pointwise``).  ``x``: (S, D), or (D,) for one draw."""
+        x, _ = self._rows(x)
+        eng = _lib.default_engine()
+        eng.set_model(self.device_spec())
+        out = np.empty((x.shape[0], self.n_data))
+        out[:, self.perm] = eng.multilevel_pointwise(x, self.n_data)
+        return out
