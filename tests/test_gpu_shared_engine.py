@@ -9,6 +9,7 @@ kinds): each objective's values and gradients must be EXACTLY what it computes a
 fixed order -- or, where an interleaving cannot be served, the call raises an ``EngineError`` that names the remedy.  Never
 another number.  The anchor at the end compares interleaved runs with the oracle, so the numbers are the reference's and not
 merely repeatable ones."""
+import gc
 import itertools
 
 import numpy as np
@@ -89,19 +90,28 @@ def test_triple_parks_states_across_kinds(vb, engine, a, c):
 @pytest.mark.parametrize('a,b', [('dis_mf_np', 'dis_fr_px'), ('dis_mf_np', 'dis_lr'), ('dis_mf_np', 'dis_mf_np'),
                                  ('dis_fr_px', 'dis_mf_np'), ('dis_mvt_np', 'dis_mvt_np'), ('dis_lr', 'dis_lr'),
                                  ('ekl_mvt_np', 'dis_mvt_np'), ('dis_mvt_np', 'ekl_mvt_np'), ('dis_mft_px', 'ekl_mf_px')])
-def test_shape_mismatch_is_exact_or_refused(vb, engine, a, b):
+def test_shape_mismatch_is_exact_or_refused(vb, a, b):
     """B has another dimension and more samples: A and B compute what they compute alone, or the call raises an
-    EngineError that tells the user to give each objective its own engine -- never another number, never a crash."""
+    EngineError that tells the user to give each objective its own engine -- never another number, never a crash.  The
+    second partner shape is ragged (d2 = 37: pad columns up to the row stride of 48, which it shares with D): a refusal
+    there must not stand in for a wrong number, so a pair refused at the ragged shape must be refused at (32, 6000) too."""
     from viabel_amd import _lib
-    d2, n2 = 32, 6000
-    want_a, want_b = solo(vb, a), solo(vb, b, 0, d2, n2)
-    ra, rb = Runner(vb, a), Runner(vb, b, 0, d2, n2)
-    try:
-        _turns([ra, rb])
-    except _lib.EngineError as e:
-        assert 'own engine' in str(e), str(e)
-    _same(want_a[:len(ra.out)], ra.out, a)
-    _same(want_b[:len(rb.out)], rb.out, b)
+    refused = {}
+    for d2, n2 in [(32, 6000), (37, 4099)]:
+        want_a, want_b = solo(vb, a), solo(vb, b, 0, d2, n2)
+        with _fresh_engine():
+            ra, rb = Runner(vb, a), Runner(vb, b, 0, d2, n2)
+            try:
+                _turns([ra, rb])
+                refused[d2] = False
+            except _lib.EngineError as e:
+                assert 'own engine' in str(e), str(e)
+                refused[d2] = True
+            _same(want_a[:len(ra.out)], ra.out, (a, d2, n2))
+            _same(want_b[:len(rb.out)], rb.out, (b, d2, n2))
+            del ra, rb
+            gc.collect()
+    assert refused[32] or not refused[37], 'refused at (37, 4099) but served at (32, 6000)'
 
 
 @pytest.mark.parametrize('partner', ['dis_fr_px', 'dis_lr'])
