@@ -68,6 +68,18 @@ typedef struct vb_ctx vb_ctx;
                                   iparams=[n_data, n_groups, link | offsets(n_groups + 1) | group of each observation(n_data)]
                                   with offsets[j] .. offsets[j + 1] the run of group j (empty runs allowed).  Taken by
                                   every route that takes a VB_MODEL_SOURCE target, like VB_MODEL_SOFTMAX */
+#define VB_MODEL_LOCSCALE 7    /* location-scale regression, mean and log-scale both linear: D = p + q,
+                                  theta = [b (p) | g (q)], eta_i = x_i' b, sigma_i = exp(w_i' g), z_i = (y_i - eta_i) / sigma_i,
+                                  y_i ~ N(eta_i, sigma_i) or eta_i + sigma_i t_df; b ~ N(0, prior_sd), g ~ N(0, scale_prior_sd),
+                                  unconstrained, no Jacobian.
+                                  dparams=[X(n_data x p)|y(n_data)|W(n_data x q), absent with a constant scale|
+                                           prior_sd|scale_prior_sd|df],
+                                  iparams=[n_data, p, q, likelihood (VB_LOCSCALE_*), constant_scale]; constant_scale = 1:
+                                  q = 1, no W, log sigma_i = g_0 for every observation (theta[D - 1] = log sigma).  Taken by
+                                  every route that takes a VB_MODEL_SOURCE target, like VB_MODEL_SOFTMAX */
+/* likelihoods of VB_MODEL_LOCSCALE */
+#define VB_LOCSCALE_GAUSSIAN 0
+#define VB_LOCSCALE_STUDENT_T 1
 
 /* noise kinds for vb_noise_generate */
 /* likelihoods of the regression target VB_MODEL_LOGISTIC (iparams = [n_data, link]; default Bernoulli-logit):
@@ -491,6 +503,11 @@ int vb_softmax_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, dou
  * Gaussian -log noise_sd - log(2 pi) / 2 included), the priors not; observations in the order of the bound (sorted)
  * data.  VB_ERR_STATE without a bound model, VB_ERR_UNSUPPORTED for any other model.                               */
 int vb_multilevel_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out);
+/* The same for the bound VB_MODEL_LOCSCALE target: ll_out[s * n_data + i] = log p(y_i | eta_i, sigma_i) at eta_i = x_i' b,
+ * sigma_i = exp(w_i' g) of draw s (s x d row-major, d = p + q) as a NORMALISED density (-log sigma_i, the Gaussian
+ * -log(2 pi) / 2 or the Student-t constant included), the priors not.  VB_ERR_STATE without a bound model,
+ * VB_ERR_UNSUPPORTED for any other model.                                                                          */
+int vb_locscale_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out);
 int vb_glm_psis_loo(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const double* log_ratios,
                     const double* log_w, double reff, double* loo, double* khat, double* lpd);
 

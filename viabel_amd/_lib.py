@@ -23,14 +23,20 @@ FAMILY_MF_GAUSSIAN, FAMILY_MF_STUDENT_T, FAMILY_FULLRANK_GAUSSIAN, FAMILY_MULTIV
     range(5)
 MODEL_GAUSS_DIAG, MODEL_FUNNEL, MODEL_GAUSS_FULL, MODEL_LOGISTIC, MODEL_SOURCE, MODEL_SOFTMAX = range(6)
 MODEL_MULTILEVEL = 6
-# targets that hand every pipeline finished rows (f, grad f): a softmax or multilevel target goes wherever a source model goes
-MODELS_WITH_ROWS = (MODEL_SOURCE, MODEL_SOFTMAX, MODEL_MULTILEVEL)
+MODEL_LOCSCALE = 7
+# targets that hand every pipeline finished rows (f, grad f): a softmax, multilevel or location-scale target goes wherever a
+# source model goes
+MODELS_WITH_ROWS = (MODEL_SOURCE, MODEL_SOFTMAX, MODEL_MULTILEVEL, MODEL_LOCSCALE)
 # doubles of predictor matrix one row chunk of the softmax pipeline may hold (csrc/vb_common.h: kSoftmaxChunkDoubles);
 # a chunk is max(8, SOFTMAX_CHUNK_DOUBLES // (n_classes * round_up(n_data, 16))) rows
 SOFTMAX_CHUNK_DOUBLES = 16 << 20
 # ... and of the multilevel pipeline (kMultilevelChunkDoubles): a chunk is max(8, MULTILEVEL_CHUNK_DOUBLES //
 # round_up(n_data, 16)) rows
 MULTILEVEL_CHUNK_DOUBLES = 16 << 20
+# ... and of the location-scale pipeline (kLocScaleChunkDoubles), whose two predictor matrices share the bound: a chunk is
+# max(8, LOCSCALE_CHUNK_DOUBLES // (2 * round_up(n_data, 16))) rows
+LOCSCALE_CHUNK_DOUBLES = 16 << 20
+LOCSCALE_GAUSSIAN, LOCSCALE_STUDENT_T = range(2)
 GLM_BERNOULLI_LOGIT, GLM_POISSON, GLM_GAUSSIAN = range(3)
 NOISE_NORMAL, NOISE_STUDENT_T = range(2)
 FLAG_PATH_DERIV = 1
@@ -150,6 +156,7 @@ SIGNATURES = {
     'vb_glm_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
     'vb_softmax_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
     'vb_multilevel_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
+    'vb_locscale_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
     'vb_glm_psis_loo': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p,
                                        ctypes.c_double, _c_double_p, _c_double_p, _c_double_p]),
     'vb_alpha_grad_meanfield': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
@@ -753,6 +760,15 @@ class Engine:
         s, d = x.shape
         out = np.empty((s, int(n_data)), dtype=np.float64)
         self._check(self._lib.vb_multilevel_pointwise(self._ctx, _dptr(x), s, d, _dptr(out)))
+        return out
+
+    def locscale_pointwise(self, x, n_data):
+        """``(S, n_data)`` normalised terms ``log p(y_i | x_i' b, exp(w_i' g))`` of the bound location-scale regression
+        target at the draws ``x`` (S x D)."""
+        x = _f64(x)
+        s, d = x.shape
+        out = np.empty((s, int(n_data)), dtype=np.float64)
+        self._check(self._lib.vb_locscale_pointwise(self._ctx, _dptr(x), s, d, _dptr(out)))
         return out
 
     def glm_psis_loo(self, x, n_data, log_ratios=None, log_w=None, reff=1.0):

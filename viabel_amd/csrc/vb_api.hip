@@ -836,6 +836,63 @@ int vb_set_model(vb_ctx* ctx, int model_id, int64_t dim, const double* dparams, 
     int* grp32 = reinterpret_cast<int*>(dev.data() + o_grp);
     for (int64_t j = 0; j <= ng; ++j) off32[j] = (int)off[j];
     for (int64_t i = 0; i < nd; ++i) grp32[i] = (int)grp[i];
+  } else if (model_id == VB_MODEL_LOCSCALE) {
+    const char* kExpect =
+        "location-scale regression expects dparams = [X(n_data x p) | y(n_data) | W(n_data x q), absent with a constant scale "
+        "| prior_sd | scale_prior_sd | df], iparams = [n_data, p, q, likelihood, constant_scale] (constant_scale = 1: q = 1) "
+        "and a dimension of p + q";
+    if (n_iparams != 5 || !iparams || !dparams || iparams[0] <= 0 || iparams[1] < 1 || iparams[2] < 1 ||
+        iparams[0] > 0x7fffffffll || iparams[1] > 0x7fffffffll || iparams[2] > 0x7fffffffll || dim > 0x7fffffffll ||
+        dim != iparams[1] + iparams[2] || iparams[3] < VB_LOCSCALE_GAUSSIAN || iparams[3] > VB_LOCSCALE_STUDENT_T ||
+        iparams[4] < 0 || iparams[4] > 1 || (iparams[4] == 1 && iparams[2] != 1) ||
+        n_dparams != (size_t)(iparams[0] * iparams[1] + iparams[0] + (iparams[4] ? 0 : iparams[0] * iparams[2])) + 3)
+      return fail(ctx, VB_ERR_INVALID, "%s", kExpect);
+    const int64_t nd = iparams[0], p = iparams[1], q = iparams[2];
+    const int lik = (int)iparams[3];
+    const bool cs = iparams[4] == 1;
+    const double* wsrc = dparams + nd * p + nd;
+    const double* tail = wsrc + (cs ? 0 : nd * q);
+    const double sd = tail[0], ssd = tail[1], nu = tail[2];
+    if (!(sd > 0.0)) return fail(ctx, VB_ERR_INVALID, "location-scale prior_sd must be positive");
+    if (!(ssd > 0.0)) return fail(ctx, VB_ERR_INVALID, "location-scale scale_prior_sd must be positive");
+    if (!(nu > 0.0) || !std::isfinite(nu)) return fail(ctx, VB_ERR_INVALID, "location-scale df must be positive and finite");
+    m.n_data = nd;
+    m.n_feat = (int)p;
+    m.n_scale = (int)q;
+    m.const_scale = cs ? 1 : 0;
+    m.ldp = round_up(p, 16);
+    m.ldq = round_up(nd, 16);
+    m.ldw = cs ? 0 : round_up(q, 16);
+    m.tau = sd;
+    m.scale_sd = ssd;
+    m.df = nu;
+    m.link = lik;
+    m.c0 = 0.0;      // (the rows carry priors and constants themselves: see ModelDev::f0)
+    // b ~ N(0, sd), g ~ N(0, ssd); the likelihood's constant: n_data times -log(2 pi) / 2, or c(nu) of the Student t
+    m.f0 = -(double)p * (log(sd) + 0.5 * kLog2Pi) - (double)q * (log(ssd) + 0.5 * kLog2Pi);
+    if (lik == VB_LOCSCALE_STUDENT_T)
+      m.f0 += (double)nd * (lgamma(0.5 * (nu + 1.0)) - lgamma(0.5 * nu) - 0.5 * (log(nu) + kLog2Pi - log(2.0)));
+    else
+      m.f0 -= (double)nd * 0.5 * kLog2Pi;
+    // [X (nd x ldp) | X' (p x ldq) | y (ldq) | W (nd x ldw) | W' (q x ldq)]: the softmax target's layout, then the scale
+    // design in the same two forms (absent with a constant scale)
+    const size_t o_w = (size_t)nd * m.ldp + (size_t)p * m.ldq + (size_t)m.ldq;
+    const size_t o_wt = o_w + (size_t)nd * m.ldw;
+    dev.assign(o_wt + (cs ? 0 : (size_t)q * m.ldq), 0.0);
+    for (int64_t i = 0; i < nd; ++i)
+      for (int64_t j = 0; j < p; ++j) {
+        const double v = dparams[i * p + j];
+        dev[(size_t)i * m.ldp + j] = v;
+        dev[(size_t)nd * m.ldp + (size_t)j * m.ldq + i] = v;
+      }
+    for (int64_t i = 0; i < nd; ++i) dev[(size_t)nd * m.ldp + (size_t)p * m.ldq + i] = dparams[nd * p + i];
+    if (!cs)
+      for (int64_t i = 0; i < nd; ++i)
+        for (int64_t j = 0; j < q; ++j) {
+          const double v = wsrc[i * q + j];
+          dev[o_w + (size_t)i * m.ldw + j] = v;
+          dev[o_wt + (size_t)j * m.ldq + i] = v;
+        }
   } else {
     return fail(ctx, VB_ERR_INVALID, "unknown model id %d", model_id);
   }
@@ -859,6 +916,14 @@ int vb_set_model(vb_ctx* ctx, int model_id, int64_t dim, const double* dparams, 
       m.p2 = m.p1 + (size_t)m.n_feat * m.ldq;
       m.grp_off = reinterpret_cast<const int*>(m.p2 + m.ldq);
       m.grp_of = m.grp_off + 2 * round_up((m.n_groups + 2) / 2, 2);
+    }
+    if (model_id == VB_MODEL_LOCSCALE) {
+      m.p1 = m.p0 + (size_t)m.n_data * m.ldp;
+      m.p2 = m.p1 + (size_t)m.n_feat * m.ldq;
+      if (!m.const_scale) {
+        m.w0 = m.p2 + m.ldq;
+        m.w1 = m.w0 + (size_t)m.n_data * m.ldw;
+      }
     }
   }
   ctx->model = m;

@@ -88,11 +88,21 @@ struct ModelDev {
   double hyper_sd = 1.0;        // multilevel: tau_sd, the scale of the half-normal prior on exp(omega)
   const int* grp_off = nullptr; // multilevel: offsets [J + 1]: group j owns the observations grp_off[j] .. grp_off[j + 1]
   const int* grp_of = nullptr;  // multilevel: group of each observation [n_data]
+  // VB_MODEL_LOCSCALE (vb_locscale.hip): theta = [b (n_feat) | g (n_scale)], eta_i = x_i' b, log sigma_i = w_i' g; p0 = X,
+  // p1 = X', p2 = y as for the softmax target, tau = prior_sd of b, link = VB_LOCSCALE_* likelihood.  A rows target as well:
+  // c0 stays 0, f0 holds the likelihood's and the two priors' constants.
+  const double* w0 = nullptr;   // locscale: W [n_data x ldw]; NULL with a constant scale
+  const double* w1 = nullptr;   // locscale: W' [n_scale x ldq]; NULL with a constant scale
+  int64_t ldw = 0;              // locscale: row stride of W (W' shares ldq with X')
+  int n_scale = 0;              // locscale: q (dim = p + q)
+  int const_scale = 0;          // locscale: 1 = no W, q = 1 and log sigma_i = g_0 for every observation
+  double scale_sd = 1.0;        // locscale: scale_prior_sd of g
+  double df = 0.0;              // locscale: degrees of freedom of the Student-t likelihood
 };
 
 // targets whose rows (f, grad f) are formed before a pipeline's streaming pass and loaded by it (model_rows_enqueue)
 __host__ __device__ __forceinline__ bool model_has_rows(int id) {
-  return id == VB_MODEL_SOURCE || id == VB_MODEL_SOFTMAX || id == VB_MODEL_MULTILEVEL;
+  return id == VB_MODEL_SOURCE || id == VB_MODEL_SOFTMAX || id == VB_MODEL_MULTILEVEL || id == VB_MODEL_LOCSCALE;
 }
 
 // per-observation log-likelihood term (without constants) and its derivative with respect to eta = x' b
@@ -232,6 +242,7 @@ struct vb_ctx {
   vb::DeviceBuffer glm_work;            // regression targets: split-K slabs of the gradient GEMM
   vb::DeviceBuffer sm_work;             // softmax target: packed samples, predictors / residuals, packed gradient, partials
   vb::DeviceBuffer ml_work;             // multilevel target: predictors / residuals, strip partials, pointwise staging
+  vb::DeviceBuffer ls_work;             // location-scale target: both predictor matrices, staged scale block, partials
   vb::DeviceBuffer mvt_state;           // multivariate-t DIS: state samples X, scratch
   int64_t mvt_n = 0, mvt_d = 0, mvt_n_total = 0;
   int64_t mvt_lq_off = 0;               // where this rank's log q of the residual pass start inside o_lq (the refresh writes them
@@ -456,7 +467,8 @@ void user_model_release(vb_ctx* ctx);
 // NULL, G[row] = grad f(Z[row]) (row stride ldg; columns >= d are not written)
 int softmax_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
                          int64_t ldg, double* f);
-// rows of the bound target by whichever forms them: a source model's kernel, the softmax or the multilevel pipeline
+// rows of the bound target by whichever forms them: a source model's kernel, the softmax, the multilevel or the
+// location-scale pipeline
 int model_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
                        int64_t ldg, double* f);
 // doubles of predictor matrix H one row chunk of the softmax pipeline may hold (mirrored by _lib.SOFTMAX_CHUNK_DOUBLES)
@@ -467,6 +479,12 @@ int multilevel_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_
                             int64_t ldg, double* f);
 // doubles of predictor matrix H one row chunk of the multilevel pipeline may hold (mirrored by _lib.MULTILEVEL_CHUNK_DOUBLES)
 constexpr int64_t kMultilevelChunkDoubles = (int64_t)16 << 20;
+// location-scale regression target (vb_locscale.hip), the same contract and the same alignment rules as the multilevel one
+int locscale_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
+                          int64_t ldg, double* f);
+// doubles of the two predictor matrices H and S together one row chunk of the location-scale pipeline may hold (mirrored by
+// _lib.LOCSCALE_CHUNK_DOUBLES): a chunk is max(8, kLocScaleChunkDoubles / (2 ldq)) rows, with and without W
+constexpr int64_t kLocScaleChunkDoubles = (int64_t)16 << 20;
 struct LegacyFinish;
 // (defer != nullptr: the kernels are enqueued, the state is left untouched and *defer describes the finish -- exact path only,
 // VB_ERR_UNSUPPORTED otherwise)

@@ -14,7 +14,7 @@ from . import _lib
 
 __all__ = ['Model', 'DeviceModel', 'GaussianModel', 'FunnelModel', 'CorrelatedGaussianModel',
            'LogisticRegressionModel', 'PoissonRegressionModel', 'LinearRegressionModel', 'SoftmaxRegressionModel',
-           'MultilevelRegressionModel', 'SourceModel', 'CallableModel']
+           'MultilevelRegressionModel', 'LocationScaleRegressionModel', 'SourceModel', 'CallableModel']
 
 
 class Model(object):
@@ -564,3 +564,100 @@ class MultilevelRegressionModel(DeviceModel):
         out = np.empty((x.shape[0], self.n_data))
         out[:, self.perm] = eng.multilevel_pointwise(x, self.n_data)
         return out
+
+
+class LocationScaleRegressionModel(DeviceModel):
+    """Location-scale regression: the mean AND the log-scale of every observation are linear in the parameter -- linear
+    regression with an unknown noise scale (``W=None``), heteroscedastic regression (a scale design ``W``) and, with
+    ``likelihood='student_t'``, the robust regression of the reference's ``docs/source/robust-regression.ipynb``.
+
+    ``X`` is ``(n_data, p)``, ``W`` is ``(n_data, q)`` or ``None``, ``likelihood`` is ``'gaussian'`` or ``'student_t'``
+    (``df > 0`` fixed, used by ``'student_t'`` only).  The parameter is unconstrained, ``dim = p + q``, no Jacobian::
+
+        theta    = [ b (p) | g (q) ]
+        eta_i    = x_i' b,   s_i = w_i' g,   sigma_i = exp(s_i),   z_i = (y_i - eta_i) exp(-s_i)
+        gaussian : l_i = -s_i - z_i^2 / 2 - log(2 pi) / 2
+        student_t: l_i = c(nu) - s_i - (nu + 1) / 2 log1p(z_i^2 / nu),
+                   c(nu) = lgamma((nu + 1) / 2) - lgamma(nu / 2) - log(nu pi) / 2
+        f(theta) = sum_i l_i - |b|^2 / (2 prior_sd^2)       - p (log prior_sd       + log(2 pi) / 2)
+                             - |g|^2 / (2 scale_prior_sd^2) - q (log scale_prior_sd + log(2 pi) / 2)
+
+    With ``W=None`` the scale is one constant: ``q = 1``, ``s_i = g_0``, so ``theta[-1] = log sigma`` under a log-normal
+    prior ``log sigma ~ N(0, scale_prior_sd)``; this case does not pay for a second design matrix.  There is no intercept
+    in either predictor: add a column of ones to ``X`` (and to ``W``).  The engine forms both predictors with fp64 MFMA
+    products, applies the likelihood in a link kernel and takes both gradient blocks with the regression targets' second
+    product (``csrc/vb_locscale.hip``, ``DESIGN.md`` 4.17).  To every objective it looks like a :class:`SourceModel` and is
+    accepted wherever one is: ``ExclusiveKL`` (both estimator forms, the RGE control variates, ``NVPFlow``),
+    ``AlphaDivergence`` and ``DISInclusiveKL`` with every family, ``bbvi``, ``vi_diagnostics`` and the device-resident
+    fit.  ``loo()`` takes the one-predictor regression targets only: this model's route to LOO is
+    ``psisloo(model.pointwise_log_likelihood(x), log_ratios)``.  Not in the reference as a model class."""
+
+    _LIKELIHOODS = {'gaussian': _lib.LOCSCALE_GAUSSIAN, 'student_t': _lib.LOCSCALE_STUDENT_T}
+
+    def __init__(self, X, y, W=None, likelihood='gaussian', df=4.0, prior_sd=10.0, scale_prior_sd=1.0):
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1 or y.shape != (X.shape[0],):
+            raise ValueError('X must be (n_data, p) with p >= 1 and y (n_data,)')
+        if W is not None:
+            W = np.ascontiguousarray(W, dtype=np.float64)
+            if W.ndim != 2 or W.shape[0] != X.shape[0] or W.shape[1] < 1:
+                raise ValueError('W must be (n_data, q) with q >= 1, or None for a constant scale')
+            if not np.all(np.isfinite(W)):
+                raise ValueError('W must be finite')
+        if likelihood not in self._LIKELIHOODS:
+            raise ValueError("likelihood must be 'gaussian' or 'student_t'")
+        if not prior_sd > 0 or not scale_prior_sd > 0:
+            raise ValueError('prior_sd and scale_prior_sd must be positive')
+        if not df > 0 or not np.isfinite(df):
+            raise ValueError('df must be positive and finite')
+        if not np.all(np.isfinite(y)) or not np.all(np.isfinite(X)):
+            raise ValueError('X and y must be finite')
+        self.X, self.y, self.W = X, y, W
+        self.likelihood, self.df = likelihood, float(df)
+        self.prior_sd, self.scale_prior_sd = float(prior_sd), float(scale_prior_sd)
+        super().__init__(X.shape[1] + (1 if W is None else W.shape[1]))
+
+    def _build_spec(self):
+        w = np.zeros(0) if self.W is None else self.W.ravel()
+        return (_lib.MODEL_LOCSCALE, self._dim,
+                np.concatenate([self.X.ravel(), self.y, w, [self.prior_sd, self.scale_prior_sd, self.df]]),
+                np.array([self.n_data, self.n_features, self.n_scale_features, self._LIKELIHOODS[self.likelihood],
+                          1 if self.W is None else 0], dtype=np.int64))
+
+    @property
+    def n_data(self):
+        return self.X.shape[0]
+
+    @property
+    def n_features(self):
+        return self.X.shape[1]
+
+    @property
+    def n_scale_features(self):
+        return 1 if self.W is None else self.W.shape[1]
+
+    def unpack(self, theta):
+        """``(b, g)`` of ``theta`` ``(D,)`` or ``(N, D)``."""
+        theta = np.asarray(theta, dtype=np.float64)
+        if theta.ndim not in (1, 2) or theta.shape[-1] != self._dim:
+            raise ValueError('theta must have shape (N, {0}) or ({0},)'.format(self._dim))
+        p = self.n_features
+        return theta[..., :p], theta[..., p:]
+
+    def sigma(self, theta):
+        """The per-observation scales ``exp(W g)`` at ``theta``: ``(n_data,)`` for ``(D,)``, ``(N, n_data)`` for ``(N, D)``
+        (evaluated on the host)."""
+        g = self.unpack(theta)[1]
+        if self.W is None:
+            return np.exp(g) * np.ones(self.n_data)
+        return np.exp(g @ self.W.T)
+
+    def pointwise_log_likelihood(self, x):
+        """The normalised terms ``l_i`` for every draw (row of ``x``) and observation: ``(S, n_data)``, the ``log_lik``
+        argument of :func:`psisloo` (``psisloo(log_lik, log_ratios)`` is this model's route to LOO).  Without the priors
+        (``vb_locscale_pointwise``).  ``x``: (S, D), or (D,) for one draw."""
+        x, _ = self._rows(x)
+        eng = _lib.default_engine()
+        eng.set_model(self.device_spec())
+        return eng.locscale_pointwise(x, self.n_data)
