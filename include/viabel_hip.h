@@ -510,6 +510,25 @@ int vb_multilevel_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, 
 int vb_locscale_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out);
 int vb_glm_psis_loo(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const double* log_ratios,
                     const double* log_w, double reff, double* loo, double* khat, double* lpd);
+/* vb_glm_predict: posterior prediction with the bound regression target (VB_MODEL_LOGISTIC, any VB_GLM_* likelihood; the
+ * model supplies dim, link and noise_sd) from the s host draws x (s x d, row-major) and their log weights log_w[s] (NULL:
+ * uniform).  The entry normalises the weights itself, w_s = exp(log_w[s] - logsumexp(log_w)); a weight of -inf adds
+ * nothing.  x_new: an m x d host design, row-major; NULL predicts the bound design (m must equal n_data, and y_new NULL
+ * then means the bound responses).  With x_new given, y_new (m responses) and lpd go together: both or neither.
+ * Outputs, m doubles each, with eta_is = x_new_i' theta_s, mu = sigmoid / exp / identity and V = mu (1 - mu) / mu /
+ * noise_sd^2:
+ *   eta_mean[i] = sum_s w_s eta_is                 eta_var[i] = sum_s w_s (eta_is - eta_mean[i])^2
+ *   mean[i]     = sum_s w_s mu(eta_is)             var[i]     = sum_s w_s V(eta_is) + sum_s w_s (mu(eta_is) - mean[i])^2
+ *   lpd[i]      = logsumexp_s(log w_s + log p(y_i | eta_is))      (normalised density: vb_glm_pointwise's constants)
+ * One fp64 MFMA product per chunk of observations and a reduction kernel (one workgroup per observation, two passes:
+ * the variances are sums of squared deviations from the weighted means); the m x s matrix stays on the device, in
+ * chunks of observations above 1 GiB, and only the five m-vectors come back.  Every sum has a fixed order: results are
+ * bit-reproducible.  No capacity limit in s beyond vb_glm_pointwise's.  VB_ERR_STATE without a bound model,
+ * VB_ERR_UNSUPPORTED for any other model, VB_ERR_INVALID for a wrong d, s <= 0, m <= 0, x_new NULL with m != n_data,
+ * y_new / lpd mismatched, negative Poisson responses, or no finite log weight.                                          */
+int vb_glm_predict(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const double* log_w, const double* x_new,
+                   int64_t m, const double* y_new, double* mean, double* var, double* eta_mean, double* eta_var,
+                   double* lpd);
 
 /* ---- ExclusiveKL, multivariate t family ------------------------------------------------
  * ExclusiveKL closure (objectives.py:154-164, entropy form) for MultivariateT

@@ -159,6 +159,9 @@ SIGNATURES = {
     'vb_locscale_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
     'vb_glm_psis_loo': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p,
                                        ctypes.c_double, _c_double_p, _c_double_p, _c_double_p]),
+    'vb_glm_predict': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p,
+                                      ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                      _c_double_p]),
     'vb_alpha_grad_meanfield': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                ctypes.c_int, ctypes.c_double, _c_double_p, ctypes.c_double,
                                                _c_double_p, _c_double_p]),
@@ -789,6 +792,47 @@ class Engine:
                                               None if log_w is None else _dptr(log_w), float(reff), _dptr(loo),
                                               _dptr(khat), None if lpd is None else _dptr(lpd)))
         return loo, khat, lpd
+
+    def glm_predict(self, x, log_w=None, X_new=None, y_new=None):
+        """Posterior prediction with the bound regression target from the draws ``x`` (S x D) and their log weights
+        ``log_w`` (S,; None: uniform; normalised by the entry) (``vb_glm_predict``).  ``X_new`` (m x D): the design to
+        predict at, ``y_new`` (m,) its responses; ``X_new=None`` predicts the bound design and ``y_new=None`` then means
+        the bound responses.  Returns a dict of ``(m,)`` arrays: ``mean``, ``var``, ``eta_mean``, ``eta_var`` and -- with
+        a response -- ``lpd``.  The (m x S) matrix of linear predictors stays on the device."""
+        x = _f64(x)
+        if x.ndim != 2:
+            raise ValueError('x must be (S, D)')
+        s, d = x.shape
+        if log_w is not None:
+            if np.shape(log_w) != (s,):
+                raise ValueError('log_w must have shape ({},)'.format(s))
+            log_w = _f64(log_w)
+            if not np.any(np.isfinite(log_w)):
+                raise ValueError('no log weight is finite')
+        if X_new is None:
+            # the bound design: its row count is the first integer parameter of the regression targets (0 lets the C
+            # entry say what is wrong: no model bound, or one without observations)
+            iparams = self._model_arrays[1] if self._model_key is not None and len(self._model_arrays) > 1 else ()
+            m = int(iparams[0]) if len(iparams) else 0
+        else:
+            X_new = _f64(X_new)
+            if X_new.ndim != 2 or X_new.shape[1] != d:
+                raise ValueError('X_new must be (m, {}); got {}'.format(d, X_new.shape))
+            m = X_new.shape[0]
+        if y_new is not None:
+            if np.shape(y_new) != (m,):
+                raise ValueError('y_new must have shape ({},)'.format(m))
+            y_new = _f64(y_new)
+        mean, var, eta_mean, eta_var = (np.empty(m, dtype=np.float64) for _ in range(4))
+        lpd = np.empty(m, dtype=np.float64) if X_new is None or y_new is not None else None
+        self._check(self._lib.vb_glm_predict(self._ctx, _dptr(x), s, d, None if log_w is None else _dptr(log_w),
+                                             None if X_new is None else _dptr(X_new), m,
+                                             None if y_new is None else _dptr(y_new), _dptr(mean), _dptr(var),
+                                             _dptr(eta_mean), _dptr(eta_var), None if lpd is None else _dptr(lpd)))
+        out = dict(mean=mean, var=var, eta_mean=eta_mean, eta_var=eta_var)
+        if lpd is not None:
+            out['lpd'] = lpd
+        return out
 
     # ------------------------------------------------------------------ AlphaDivergence, mean field
     def alpha_grad_meanfield(self, slot, n, d, theta, family, alpha, df=0.0, n_total=None):

@@ -16,7 +16,7 @@ from .models import CallableModel, DeviceModel, LogisticRegressionModel, SourceM
 from .objectives import ExclusiveKL, _stage_prior_noise
 from .optimization import FASO, RAABBVI, RMSProp
 
-__all__ = ['bbvi', 'vi_diagnostics', 'psis_correction', 'samples_and_log_weights', 'loo', 'psisloo']
+__all__ = ['bbvi', 'vi_diagnostics', 'psis_correction', 'samples_and_log_weights', 'loo', 'psisloo', 'predict']
 
 
 def bbvi(dimension, *, n_iters=10000, num_mc_samples=10, log_density=None, approx=None, objective=None,
@@ -223,4 +223,63 @@ def loo(var_param, *, objective=None, model=None, approx=None, n_samples=4000, R
     print('{} of {} observations have Pareto khat > 0.7 (full-data ratios: khat = {:.2f})'.format(n_bad, n, khat_full))
     if n_bad:
         print('WARNING: khat > 0.7 means the leave-one-out terms of those observations are unreliable.')
+    return results
+
+
+def predict(var_param, *, objective=None, model=None, approx=None, X_new=None, y_new=None, n_samples=4000, weights='psis',
+            Reff=1.0):
+    """Posterior prediction with a fitted regression model: predictive means, standard deviations and -- with responses
+    -- the log predictive density of each observation, at the rows of ``X_new`` (the model's own design without it;
+    ``y_new=None`` then means its own responses).
+
+    ``n_samples`` draws ``theta_s ~ q`` and their log ratios ``log p(theta_s, y) - log q(theta_s)``
+    (:func:`samples_and_log_weights`).  ``weights='psis'`` corrects the draws towards the posterior with the
+    Pareto-smoothed, normalised ratios (``psislw``); ``weights=None`` takes the draws as they are.  The
+    ``m x n_samples`` matrix of linear predictors is formed and reduced on the device (``vb_glm_predict``,
+    :meth:`LogisticRegressionModel.predict_from_draws`); five ``m``-vectors come back.  Returns a dict: ``mean`` and ``sd``
+    of the response, ``eta_mean`` and ``eta_sd`` of the linear predictor, ``khat`` (of the ratios; None with
+    ``weights=None``), ``n_samples`` and, with a response, ``lpd`` (``log p(y_i | y)`` per observation), ``elpd``
+    (their sum: on held-out rows the number ``loo()``'s ``elpd_loo`` estimates) and ``se_elpd = sqrt(m var(lpd))``.
+    Runs on the calling process's engine."""
+    if objective is None:
+        if model is None or approx is None:
+            raise ValueError('either objective or both model and approx must be specified')
+    elif model is not None or approx is not None:
+        raise ValueError('model and/or approx cannot be specified if objective is')
+    else:
+        model, approx = objective.model, objective.approx
+    if n_samples < 1:
+        raise ValueError('n_samples must be positive')
+    if weights not in ('psis', None):
+        raise ValueError("weights must be 'psis' or None")
+    if weights == 'psis' and n_samples < 2:
+        raise ValueError('n_samples must be at least 2 to smooth the weights')
+    if not (Reff > 0):
+        raise ValueError('Reff must be positive')
+    if not isinstance(model, LogisticRegressionModel):
+        raise NotImplementedError(
+            'predict covers LogisticRegressionModel, PoissonRegressionModel and LinearRegressionModel; {} has no '
+            'predict_from_draws. What exists for it: pointwise_log_likelihood(draws) where the model defines it, to be '
+            'reduced on the host'.format(type(model).__name__))
+    var_param = np.asarray(var_param, dtype=np.float64)
+    samples, log_ratios = samples_and_log_weights(var_param, model, approx, n_samples)
+    log_w, khat = None, None
+    if weights == 'psis':
+        log_w, khat = psislw(log_ratios, Reff=Reff)
+        khat = float(khat)
+    out = model.predict_from_draws(samples, X_new=X_new, y_new=y_new, log_weights=log_w)
+    m = out['mean'].size
+    results = dict(mean=out['mean'], sd=np.sqrt(out['var']), eta_mean=out['eta_mean'], eta_sd=np.sqrt(out['eta_var']),
+                   khat=khat, n_samples=int(n_samples))
+    if 'lpd' in out:
+        lpd = out['lpd']
+        results.update(lpd=lpd, elpd=float(lpd.sum()), se_elpd=float(np.sqrt(m * np.var(lpd))))
+        print('elpd = {:.2f} (SE {:.2f}) over {} observations, {:.4f} per observation'.format(
+            results['elpd'], results['se_elpd'], m, results['elpd'] / m))
+    else:
+        print('predicted {} observations from {} draws (no response: no elpd)'.format(m, int(n_samples)))
+    if khat is not None:
+        print('Pareto k is estimated to be khat = {:.2f}'.format(khat))
+        if khat > 0.7:
+            print('WARNING: khat > 0.7 means importance sampling is not feasible.')
     return results

@@ -123,6 +123,30 @@ __device__ __forceinline__ double glm_term(int link, double aux, double y, doubl
   return y * eta - (fmax(eta, 0.0) + log1p(t));
 }
 
+// what a prediction needs of one element, from ONE exponential: the mean mu(eta) of the response, its variance V(eta)
+// given eta (Bernoulli mu (1 - mu), Poisson mu, Gaussian aux^2) and -- returned -- glm_term's log-likelihood term of the
+// response y (the same expressions; meaningless without a response: pass any finite y and ignore it).  The logistic
+// variance is t / (1 + t)^2 with t = exp(-|eta|): no 1 - mu, which is 0 in double precision from |eta| = 37 on.
+__device__ __forceinline__ double glm_predict_term(int link, double aux, double y, double eta, double* mu, double* var) {
+  if (link == VB_GLM_POISSON) {
+    const double m = exp(eta);
+    *mu = m;
+    *var = m;
+    return y * eta - m;
+  }
+  if (link == VB_GLM_GAUSSIAN) {
+    const double r = (y - eta) / (aux * aux);
+    *mu = eta;
+    *var = aux * aux;
+    return -0.5 * r * (y - eta);
+  }
+  const double t = exp(-fabs(eta));
+  const double q = 1.0 / (1.0 + t);
+  *mu = eta >= 0.0 ? q : t * q;
+  *var = t * q * q;
+  return y * eta - (fmax(eta, 0.0) + log1p(t));
+}
+
 // a Philox generation request (vb_noise_generate / vb_chisq_generate): what a buffer holds
 struct NoiseReq {
   int kind = 0;

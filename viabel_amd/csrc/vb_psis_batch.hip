@@ -32,12 +32,23 @@
 // result lanes hold adjacent COLUMNS: with draws as columns a lane pair stores 16 contiguous bytes and a quad 64,
 // whereas the transposed store would put every lane of a row on its own line, S doubles apart.  The transpose of the
 // draws is S x D doubles, negligible next to the n_data x S result.
+//
+// Posterior prediction (vb_glm_predict): the same product with a plain store (EpiStoreEta), against the bound design or an
+// uploaded one (chunks of observations, padded like the bound X), followed by glm_predict_kernel: one 256-thread workgroup
+// per observation streams its S linear predictors twice -- weighted means and the log-sum-exp of the predictive density,
+// then the weighted squared deviations from those means -- and writes five doubles.  The weights are normalised once per
+// call on the host (S values); the m x S matrix is written once and read twice on the device and nothing of that order
+// crosses the bus.  No sort, so no cap on S.  Resources (as above; scratch 0 in all three; LDS 32 B per workgroup):
+//     Bernoulli-logit: 105 VGPRs -> 4 workgroups per CU
+//     Poisson:          82 VGPRs -> 5 workgroups per CU
+//     Gaussian:         74 VGPRs -> 6 workgroups per CU
 #include "vb_gemm_f64.h"
 #include "vb_psis_util.h"
 
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
+#include <vector>
 
 namespace vb {
 
@@ -564,15 +575,21 @@ static GlmLayout glm_layout(const ModelDev& m, int64_t s, int64_t d, bool with_t
   return L;
 }
 
-// draws up (S x D, host) and transposed (D x lds); the per-observation constants
+// draws up and transposed; the per-observation constants
+// the draws (S x D, host) into X (row stride ldx) and transposed into Xt (D x lds, the padding zeroed)
+static int glm_stage_draws(vb_ctx* ctx, hipStream_t st, double* X, int64_t ldx, double* Xt, int64_t lds, const double* x_host,
+                           int64_t s, int64_t d) {
+  VB_HIP(ctx, hipMemsetAsync(Xt, 0, (size_t)d * lds * sizeof(double), st));
+  VB_HIP(ctx, hipMemcpy2DAsync(X, (size_t)ldx * sizeof(double), x_host, (size_t)d * sizeof(double), (size_t)d * sizeof(double),
+                               (size_t)s, hipMemcpyHostToDevice, st));
+  return pb_transpose(ctx, st, X, ldx, s, d, Xt, lds);
+}
+
 static int glm_stage(vb_ctx* ctx, hipStream_t st, const GlmLayout& L, const double* x_host, int64_t s, int64_t d) {
   const ModelDev& m = ctx->model;
   VB_TRY(ensure(ctx, ctx->loo_work, (size_t)L.total * sizeof(double)));
   double* base = (double*)ctx->loo_work.ptr;
-  VB_HIP(ctx, hipMemsetAsync(base + L.o_xt, 0, (size_t)d * L.lds * sizeof(double), st));
-  VB_HIP(ctx, hipMemcpy2DAsync(base + L.o_x, (size_t)L.ldx * sizeof(double), x_host, (size_t)d * sizeof(double),
-                               (size_t)d * sizeof(double), (size_t)s, hipMemcpyHostToDevice, st));
-  VB_TRY(pb_transpose(ctx, st, base + L.o_x, L.ldx, s, d, base + L.o_xt, L.lds));
+  VB_TRY(glm_stage_draws(ctx, st, base + L.o_x, L.ldx, base + L.o_xt, L.lds, x_host, s, d));
   hipLaunchKernelGGL(glm_const_kernel, dim3((unsigned)((m.n_data + 255) / 256)), dim3(256), 0, st, m.p2, m.n_data, m.link, m.aux,
                      base + L.o_c);
   VB_HIP(ctx, hipGetLastError());
@@ -591,6 +608,170 @@ static int glm_pointwise_enqueue(vb_ctx* ctx, hipStream_t st, const GlmLayout& L
                         EpiPointwise{base + L.o_ll, L.lds, m.p2 + r0, base + L.o_c + r0, m.link, m.aux});
   VB_HIP(ctx, hipGetLastError());
   return VB_OK;
+}
+
+
+// ---- posterior prediction of the regression targets (vb_glm_predict) ------------------------------------------------
+// ETA[observation][draw] = x_obs' theta_draw: the product of glm_pointwise_enqueue with a plain store, against the bound
+// design or a chunk of an uploaded one
+struct EpiStoreEta {
+  double* E;
+  int64_t ld;
+  __device__ void operator()(int, int row, int col, double eta) const { E[(int64_t)row * ld + col] = eta; }
+  __device__ d2v pair(int, int row, int col, double e0, double e1) const {
+    const d2v v = (d2v){e0, e1};
+    *reinterpret_cast<d2v*>(E + (int64_t)row * ld + col) = v;
+    return v;
+  }
+};
+
+struct PredictArgs {
+  const double* eta;          // rows observations of n draws, observation j at eta + j * ld
+  int64_t ld;
+  int n;
+  const double* w;            // [n] normalised weights (sum 1) and ...
+  const double* log_w;        // [n] ... their logarithms (-inf where the weight is 0)
+  const double* y;            // [rows] responses, or nullptr: no lpd
+  double aux;
+  double *mean, *var, *eta_mean, *eta_var, *lpd;      // [rows]
+};
+
+// One 256-thread workgroup per observation, two passes over its n linear predictors (8 n bytes the workgroup has just
+// read: the second pass comes from the cache).  Pass 1: the weighted sums of eta, mu(eta), V(eta) and the running
+// log-sum-exp of log w + log p(y | eta) (glm_predict_term: one exponential per element for all three).  Pass 2: the
+// weighted squared deviations of eta and mu from those means -- never E[x^2] - E[x]^2.  Thread t takes the elements
+// t + 256 k in order, the workgroup's sums are pb_block_sum's fixed tree: bit-reproducible.  An element of weight 0 adds
+// nothing, whatever its value (the guard keeps 0 * inf out of the sums).
+template <int LINK>
+__global__ void __launch_bounds__(kPbThreads) glm_predict_kernel(const PredictArgs a) {
+  __shared__ double sh[kPbWaves];
+  constexpr int CH = 4;
+  const int t = threadIdx.x;
+  const int64_t n = a.n;
+  const double* __restrict__ row = a.eta + (int64_t)blockIdx.x * a.ld;
+  const bool has_y = a.y != nullptr;
+  const double y = has_y ? a.y[blockIdx.x] : 0.0;
+
+  double s_eta = 0.0, s_mu = 0.0, s_v = 0.0;
+  PbLse lse;
+  for (int64_t i0 = t; i0 < n; i0 += CH * kPbThreads) {
+    double e[CH], w[CH], lw[CH], tl[CH];
+#pragma unroll
+    for (int q = 0; q < CH; ++q) {      // (clamped, not branched over: the loads of a round are issued together)
+      const int64_t i = i0 + q * kPbThreads, ic = i < n ? i : n - 1;
+      e[q] = row[ic];
+      w[q] = a.w[ic];
+      lw[q] = a.log_w[ic];
+    }
+#pragma unroll
+    for (int q = 0; q < CH; ++q) {
+      const bool live = i0 + q * kPbThreads < n && w[q] > 0.0;
+      double mu, v;
+      const double ll = glm_predict_term(LINK, a.aux, y, e[q], &mu, &v);
+      s_eta += live ? w[q] * e[q] : 0.0;
+      s_mu += live ? w[q] * mu : 0.0;
+      s_v += live ? w[q] * v : 0.0;
+      tl[q] = i0 + q * kPbThreads < n ? lw[q] + ll : -INFINITY;
+    }
+    if (has_y) lse.add(tl);
+  }
+  const double eta_mean = pb_block_sum(s_eta, sh);
+  const double mean = pb_block_sum(s_mu, sh);
+  const double within = pb_block_sum(s_v, sh);
+
+  double d_eta = 0.0, d_mu = 0.0;
+  for (int64_t i0 = t; i0 < n; i0 += CH * kPbThreads) {
+    double e[CH], w[CH];
+#pragma unroll
+    for (int q = 0; q < CH; ++q) {
+      const int64_t i = i0 + q * kPbThreads, ic = i < n ? i : n - 1;
+      e[q] = row[ic];
+      w[q] = a.w[ic];
+    }
+#pragma unroll
+    for (int q = 0; q < CH; ++q) {
+      const bool live = i0 + q * kPbThreads < n && w[q] > 0.0;
+      double mu, v;
+      glm_predict_term(LINK, a.aux, 0.0, e[q], &mu, &v);
+      const double de = e[q] - eta_mean, dm = mu - mean;
+      d_eta += live ? w[q] * (de * de) : 0.0;
+      d_mu += live ? w[q] * (dm * dm) : 0.0;
+    }
+  }
+  const double eta_var = pb_block_sum(d_eta, sh);
+  const double between = pb_block_sum(d_mu, sh);
+  if (t == 0) {
+    a.eta_mean[blockIdx.x] = eta_mean;
+    a.eta_var[blockIdx.x] = eta_var;
+    a.mean[blockIdx.x] = mean;
+    a.var[blockIdx.x] = within + between;
+  }
+  if (has_y) {      // what glm_term leaves out of log p(y | eta) does not depend on the draw: added to the log-sum-exp
+    const double total = lse.total(sh);
+    if (t == 0) {
+      double c = 0.0;
+      if (LINK == VB_GLM_POISSON) c = -lgamma(y + 1.0);
+      else if (LINK == VB_GLM_GAUSSIAN) c = -log(a.aux) - 0.91893853320467274178;
+      a.lpd[blockIdx.x] = total + c;
+    }
+  }
+}
+
+static int glm_predict_enqueue(vb_ctx* ctx, hipStream_t st, int link, const PredictArgs& a, int64_t rows) {
+  const dim3 grid((unsigned)rows), block(kPbThreads);
+  if (link == VB_GLM_POISSON) hipLaunchKernelGGL(glm_predict_kernel<VB_GLM_POISSON>, grid, block, 0, st, a);
+  else if (link == VB_GLM_GAUSSIAN) hipLaunchKernelGGL(glm_predict_kernel<VB_GLM_GAUSSIAN>, grid, block, 0, st, a);
+  else hipLaunchKernelGGL(glm_predict_kernel<VB_GLM_BERNOULLI_LOGIT>, grid, block, 0, st, a);
+  VB_HIP(ctx, hipGetLastError());
+  return VB_OK;
+}
+
+// Where the pieces of a prediction live in ctx->loo_work (doubles from the base); the chunk of observations is the one of
+// the LOO layout: what fits kLooBudgetBytes at round_up(S, 16) doubles per observation
+struct PredictLayout {
+  int64_t lds, ldx, mp;                    // row strides: draws-as-columns, draws-as-rows / design rows; round_up(m, 16)
+  int64_t o_x, o_xt, o_w, o_xn, o_y, o_res, o_eta, total;
+  int64_t chunk;
+};
+static PredictLayout predict_layout(int64_t s, int64_t d, int64_t m, bool own_design) {
+  PredictLayout L;
+  L.lds = round_up(s, 16), L.ldx = round_up(d, 16), L.mp = round_up(m, 16);
+  int64_t chunk = kLooBudgetDoubles / L.lds;
+  chunk = chunk < 1 ? 1 : (chunk > m ? m : chunk);
+  L.chunk = chunk;
+  int64_t off = 0;
+  auto carve = [&off](int64_t doubles) {
+    const int64_t o = off;
+    off += round_up(doubles, 16);
+    return o;
+  };
+  L.o_x = carve(s * L.ldx), L.o_xt = carve(d * L.lds), L.o_w = carve(2 * L.lds), L.o_xn = carve(own_design ? chunk * L.ldx : 0),
+  L.o_y = carve(L.mp), L.o_res = carve(5 * L.mp), L.o_eta = carve(chunk * L.lds);
+  L.total = off;
+  return L;
+}
+
+// w | log w (2 s doubles) of the s log weights, normalised in a fixed order on the host; uniform without them.  False when
+// no weight is finite (or one is NaN / +inf: the sum is then not a number).
+static bool predict_weights(const double* log_w, int64_t s, std::vector<double>& out) {
+  out.resize((size_t)(2 * s));
+  double *w = out.data(), *lw = w + s;
+  if (!log_w) {
+    const double u = 1.0 / (double)s, lu = -log((double)s);
+    for (int64_t i = 0; i < s; ++i) w[i] = u, lw[i] = lu;
+    return true;
+  }
+  double mx = -INFINITY, sum = 0.0;
+  for (int64_t i = 0; i < s; ++i) mx = log_w[i] > mx ? log_w[i] : mx;
+  if (!std::isfinite(mx)) return false;
+  for (int64_t i = 0; i < s; ++i) sum += exp(log_w[i] - mx);
+  const double lse = mx + log(sum);
+  if (!std::isfinite(lse)) return false;
+  for (int64_t i = 0; i < s; ++i) {
+    lw[i] = log_w[i] - lse;
+    w[i] = exp(lw[i]);
+  }
+  return true;
 }
 
 }  // namespace vb
@@ -683,6 +864,66 @@ int vb_glm_psis_loo(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const do
   VB_HIP(ctx, hipMemcpyAsync(loo, res, (size_t)nd * sizeof(double), hipMemcpyDeviceToHost, st));
   VB_HIP(ctx, hipMemcpyAsync(khat, res + L.ndp, (size_t)nd * sizeof(double), hipMemcpyDeviceToHost, st));
   if (lpd) VB_HIP(ctx, hipMemcpyAsync(lpd, res + 2 * L.ndp, (size_t)nd * sizeof(double), hipMemcpyDeviceToHost, st));
+  VB_HIP(ctx, hipStreamSynchronize(st));
+  return VB_OK;
+}
+
+int vb_glm_predict(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const double* log_w, const double* x_new, int64_t m,
+                   const double* y_new, double* mean, double* var, double* eta_mean, double* eta_var, double* lpd) {
+  if (!ctx || !x || !mean || !var || !eta_mean || !eta_var) return fail(ctx, VB_ERR_INVALID, "NULL argument");
+  VB_TRY(glm_check(ctx, s, d));
+  const ModelDev& md = ctx->model;
+  if (m <= 0 || m > 0x7fffffffll) return fail(ctx, VB_ERR_INVALID, "the number of observations to predict must be positive");
+  if (!x_new && m != md.n_data)
+    return fail(ctx, VB_ERR_INVALID, "without x_new the bound design is predicted: m = %lld, the model has %lld observations",
+                (long long)m, (long long)md.n_data);
+  if (x_new ? (y_new == nullptr) != (lpd == nullptr) : (y_new && !lpd))
+    return fail(ctx, VB_ERR_INVALID, "y_new and lpd go together (both or neither)");
+  if (y_new && md.link == VB_GLM_POISSON)
+    for (int64_t i = 0; i < m; ++i)
+      if (!(y_new[i] >= 0.0)) return fail(ctx, VB_ERR_INVALID, "Poisson counts must be non-negative");
+  std::vector<double> wv;
+  if (!predict_weights(log_w, s, wv)) return fail(ctx, VB_ERR_INVALID, "no log weight is finite (or one is NaN or +inf)");
+  VB_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  struct Drain {      // the host buffers of the asynchronous uploads outlive them on every way out
+    hipStream_t st;
+    ~Drain() { (void)hipStreamSynchronize(st); }
+  } drain{st};
+  const PredictLayout L = predict_layout(s, d, m, x_new != nullptr);
+  VB_TRY(ensure(ctx, ctx->loo_work, (size_t)L.total * sizeof(double)));
+  double* base = (double*)ctx->loo_work.ptr;
+  VB_TRY(glm_stage_draws(ctx, st, base + L.o_x, L.ldx, base + L.o_xt, L.lds, x, s, d));
+  double *w_d = base + L.o_w, *lw_d = w_d + L.lds, *xn = base + L.o_xn, *res = base + L.o_res;
+  VB_HIP(ctx, hipMemcpyAsync(w_d, wv.data(), (size_t)s * sizeof(double), hipMemcpyHostToDevice, st));
+  VB_HIP(ctx, hipMemcpyAsync(lw_d, wv.data() + s, (size_t)s * sizeof(double), hipMemcpyHostToDevice, st));
+  const double* y_d = x_new ? nullptr : md.p2;
+  if (y_new) {
+    VB_HIP(ctx, hipMemcpyAsync(base + L.o_y, y_new, (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
+    y_d = base + L.o_y;
+  }
+  for (int64_t r0 = 0; r0 < m; r0 += L.chunk) {
+    const int64_t rows = m - r0 < L.chunk ? m - r0 : L.chunk;
+    GemmArgs g;                        // ETA = X_new theta'   [rows x S x D]
+    if (x_new) {                       // the chunk of the design, padded like the bound one: row stride ldx, padding zeroed
+      if (L.ldx != d) VB_HIP(ctx, hipMemsetAsync(xn, 0, (size_t)rows * L.ldx * sizeof(double), st));
+      VB_HIP(ctx, hipMemcpy2DAsync(xn, (size_t)L.ldx * sizeof(double), x_new + r0 * d, (size_t)d * sizeof(double),
+                                   (size_t)d * sizeof(double), (size_t)rows, hipMemcpyHostToDevice, st));
+      g.A = xn, g.lda = L.ldx;
+    } else {
+      g.A = md.p0 + r0 * md.ldp, g.lda = md.ldp;
+    }
+    g.B = base + L.o_xt, g.ldb = L.lds;
+    g.M = (int)rows, g.N = (int)s, g.K = (int)d, g.tri_mode = 0;
+    gemm_f64_launch<true>(st, g, 1, ctx->prop.multiProcessorCount, EpiStoreEta{base + L.o_eta, L.lds});
+    VB_HIP(ctx, hipGetLastError());
+    const PredictArgs a{base + L.o_eta, L.lds, (int)s, w_d, lw_d, y_d ? y_d + r0 : nullptr, md.aux,
+                        res + r0, res + L.mp + r0, res + 2 * L.mp + r0, res + 3 * L.mp + r0, res + 4 * L.mp + r0};
+    VB_TRY(glm_predict_enqueue(ctx, st, md.link, a, rows));
+  }
+  double* outs[5] = {mean, var, eta_mean, eta_var, y_d ? lpd : nullptr};
+  for (int k = 0; k < 5; ++k)
+    if (outs[k]) VB_HIP(ctx, hipMemcpyAsync(outs[k], res + k * L.mp, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
   VB_HIP(ctx, hipStreamSynchronize(st));
   return VB_OK;
 }

@@ -362,6 +362,41 @@ class LogisticRegressionModel(DeviceModel):
         eng.set_model(self.device_spec())
         return eng.glm_pointwise(x, self.n_data)
 
+    def predict_from_draws(self, x, X_new=None, y_new=None, log_weights=None):
+        """Posterior prediction from the draws ``x`` (S, D) -- or (D,) for one -- and their log weights ``log_weights``
+        (S,; None: equal weights; normalised on the way, ``-inf`` drops a draw).  ``X_new`` (m, D): the design to predict
+        at, ``y_new`` (m,) held-out responses; ``X_new=None`` predicts the model's own design, ``y_new=None`` then means
+        its own responses.  Returns a dict of ``(m,)`` arrays with ``eta_is = x_new_i' theta_s``: ``eta_mean``,
+        ``eta_var`` (weighted mean and variance of the linear predictor), ``mean`` (of the response: sigmoid / exp /
+        identity of eta, averaged), ``var`` (of the response, by the law of total variance) and -- with a response --
+        ``lpd[i] = log sum_s w_s p(y_i | eta_is)`` as a normalised density.  One fp64 MFMA product and one reduction
+        kernel (``vb_glm_predict``): the (m, S) matrix stays on the device, five m-vectors come back."""
+        x, _ = self._rows(x)
+        if X_new is not None:
+            X_new = np.ascontiguousarray(X_new, dtype=np.float64)
+            if X_new.ndim != 2 or X_new.shape[1] != self._dim:
+                raise ValueError('X_new must have shape (m, {}); got {}'.format(self._dim, X_new.shape))
+            if X_new.shape[0] < 1:
+                raise ValueError('X_new must have at least one row')
+        m = self.n_data if X_new is None else X_new.shape[0]
+        if y_new is not None:
+            y_new = np.asarray(y_new, dtype=np.float64)
+            if y_new.shape != (m,):
+                raise ValueError('y_new must have shape ({},); got {}'.format(m, y_new.shape))
+            self._check_response(y_new)
+        if log_weights is not None:
+            log_weights = np.asarray(log_weights, dtype=np.float64)
+            if log_weights.shape != (x.shape[0],):
+                raise ValueError('log_weights must have shape ({},)'.format(x.shape[0]))
+            if not np.any(np.isfinite(log_weights)):
+                raise ValueError('no log weight is finite')
+        eng = _lib.default_engine()
+        eng.set_model(self.device_spec())
+        return eng.glm_predict(x, log_w=log_weights, X_new=X_new, y_new=y_new)
+
+    def _check_response(self, y):
+        pass
+
 
 class PoissonRegressionModel(LogisticRegressionModel):
     """Bayesian Poisson regression ``y_i ~ Poisson(exp(x_i' b))`` with a ``N(0, prior_sd)`` prior: the same two-GEMM
@@ -369,7 +404,10 @@ class PoissonRegressionModel(LogisticRegressionModel):
 
     def __init__(self, X, y, prior_sd=10.0):
         super().__init__(X, y, prior_sd)
-        if np.any(self.y < 0):
+        self._check_response(self.y)
+
+    def _check_response(self, y):
+        if np.any(y < 0):
             raise ValueError('counts must be non-negative')
 
     def _build_spec(self):
