@@ -77,6 +77,16 @@ typedef struct vb_ctx vb_ctx;
                                   iparams=[n_data, p, q, likelihood (VB_LOCSCALE_*), constant_scale]; constant_scale = 1:
                                   q = 1, no W, log sigma_i = g_0 for every observation (theta[D - 1] = log sigma).  Taken by
                                   every route that takes a VB_MODEL_SOURCE target, like VB_MODEL_SOFTMAX */
+#define VB_MODEL_SPARSE_GLM 8  /* the regression target VB_MODEL_LOGISTIC (any VB_GLM_* likelihood, the same normalised density,
+                                  D = p) on a SPARSE design: X as CSR and, for the gradient, X' as CSR (the CSC form of X), both
+                                  canonical -- indices strictly increasing within a row / column, no explicit zeros needed.
+                                  dparams=[csr values (nnz)|csc values (nnz)|y(n_data)|prior_sd|noise_sd],
+                                  iparams=[n_data, p, link (VB_GLM_*), nnz | csr indptr (n_data + 1) | csr indices (nnz) |
+                                           csc indptr (p + 1) | csc indices (nnz)];
+                                  n_data, p and nnz below 2^31; empty rows (eta_i = 0) and empty columns (prior only) are
+                                  legal; noise_sd is read by VB_GLM_GAUSSIAN only.  vb_set_model checks every pointer and
+                                  index and that the CSC form is the transpose of the CSR form.  Taken by every route that
+                                  takes a VB_MODEL_SOURCE target, like VB_MODEL_SOFTMAX */
 /* likelihoods of VB_MODEL_LOCSCALE */
 #define VB_LOCSCALE_GAUSSIAN 0
 #define VB_LOCSCALE_STUDENT_T 1
@@ -508,6 +518,10 @@ int vb_multilevel_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, 
  * -log(2 pi) / 2 or the Student-t constant included), the priors not.  VB_ERR_STATE without a bound model,
  * VB_ERR_UNSUPPORTED for any other model.                                                                          */
 int vb_locscale_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out);
+/* The same for the bound VB_MODEL_SPARSE_GLM target: ll_out[s * n_data + i] = log p(y_i | eta_i) at eta_i = x_i' theta of
+ * draw s (s x d row-major, d = p) as a NORMALISED density (the Poisson -log y_i!, the Gaussian -log noise_sd - log(2 pi) / 2
+ * included), the prior not.  VB_ERR_STATE without a bound model, VB_ERR_UNSUPPORTED for any other model.            */
+int vb_sparse_glm_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out);
 int vb_glm_psis_loo(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const double* log_ratios,
                     const double* log_w, double reff, double* loo, double* khat, double* lpd);
 /* vb_glm_predict: posterior prediction with the bound regression target (VB_MODEL_LOGISTIC, any VB_GLM_* likelihood; the

@@ -24,9 +24,10 @@ FAMILY_MF_GAUSSIAN, FAMILY_MF_STUDENT_T, FAMILY_FULLRANK_GAUSSIAN, FAMILY_MULTIV
 MODEL_GAUSS_DIAG, MODEL_FUNNEL, MODEL_GAUSS_FULL, MODEL_LOGISTIC, MODEL_SOURCE, MODEL_SOFTMAX = range(6)
 MODEL_MULTILEVEL = 6
 MODEL_LOCSCALE = 7
-# targets that hand every pipeline finished rows (f, grad f): a softmax, multilevel or location-scale target goes wherever a
-# source model goes
-MODELS_WITH_ROWS = (MODEL_SOURCE, MODEL_SOFTMAX, MODEL_MULTILEVEL, MODEL_LOCSCALE)
+MODEL_SPARSE_GLM = 8
+# targets that hand every pipeline finished rows (f, grad f): a softmax, multilevel, location-scale or sparse regression
+# target goes wherever a source model goes
+MODELS_WITH_ROWS = (MODEL_SOURCE, MODEL_SOFTMAX, MODEL_MULTILEVEL, MODEL_LOCSCALE, MODEL_SPARSE_GLM)
 # doubles of predictor matrix one row chunk of the softmax pipeline may hold (csrc/vb_common.h: kSoftmaxChunkDoubles);
 # a chunk is max(8, SOFTMAX_CHUNK_DOUBLES // (n_classes * round_up(n_data, 16))) rows
 SOFTMAX_CHUNK_DOUBLES = 16 << 20
@@ -37,6 +38,19 @@ MULTILEVEL_CHUNK_DOUBLES = 16 << 20
 # max(8, LOCSCALE_CHUNK_DOUBLES // (2 * round_up(n_data, 16))) rows
 LOCSCALE_CHUNK_DOUBLES = 16 << 20
 LOCSCALE_GAUSSIAN, LOCSCALE_STUDENT_T = range(2)
+# entries of a row or column of a sparse design that one wave sums (csrc/vb_common.h: kSparseSegment); longer lists are cut
+# into segments of this many entries, summed by separate waves and combined in segment order
+SPARSE_SEGMENT = 256
+# doubles of workspace per chunk of samples of the sparse pipeline (kSparseChunkDoubles)
+SPARSE_CHUNK_DOUBLES = 16 << 20
+
+
+def sparse_chunk_rows(n_data, p):
+    """Samples per chunk of the sparse regression pipeline for an ``(n_data, p)`` design: the arithmetic of
+    ``sparse_chunk_rows`` in ``csrc/vb_common.h``."""
+    return min(8192, max(64, SPARSE_CHUNK_DOUBLES // (2 * (int(n_data) + int(p))) // 64 * 64))
+
+
 GLM_BERNOULLI_LOGIT, GLM_POISSON, GLM_GAUSSIAN = range(3)
 NOISE_NORMAL, NOISE_STUDENT_T = range(2)
 FLAG_PATH_DERIV = 1
@@ -157,6 +171,7 @@ SIGNATURES = {
     'vb_softmax_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
     'vb_multilevel_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
     'vb_locscale_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
+    'vb_sparse_glm_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
     'vb_glm_psis_loo': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p,
                                        ctypes.c_double, _c_double_p, _c_double_p, _c_double_p]),
     'vb_glm_predict': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p,
@@ -772,6 +787,15 @@ class Engine:
         s, d = x.shape
         out = np.empty((s, int(n_data)), dtype=np.float64)
         self._check(self._lib.vb_locscale_pointwise(self._ctx, _dptr(x), s, d, _dptr(out)))
+        return out
+
+    def sparse_glm_pointwise(self, x, n_data):
+        """``(S, n_data)`` normalised terms ``log p(y_i | x_i' theta)`` of the bound sparse regression target at the draws
+        ``x`` (S x D)."""
+        x = _f64(x)
+        s, d = x.shape
+        out = np.empty((s, int(n_data)), dtype=np.float64)
+        self._check(self._lib.vb_sparse_glm_pointwise(self._ctx, _dptr(x), s, d, _dptr(out)))
         return out
 
     def glm_psis_loo(self, x, n_data, log_ratios=None, log_w=None, reff=1.0):

@@ -663,6 +663,7 @@ int vb_set_model(vb_ctx* ctx, int model_id, int64_t dim, const double* dparams, 
   m.id = model_id;
   m.dim = (int)dim;
   std::vector<double> dev;   // what is uploaded
+  size_t sp_off[8] = {};     // sparse regression: where its int arrays start inside dev (in doubles)
   if (model_id == VB_MODEL_GAUSS_DIAG) {
     if (n_dparams != (size_t)(2 * dim) || !dparams)
       return fail(ctx, VB_ERR_INVALID, "gauss_diag expects dparams = [mean(D) | stdev(D)]");
@@ -893,6 +894,115 @@ int vb_set_model(vb_ctx* ctx, int model_id, int64_t dim, const double* dparams, 
           dev[o_w + (size_t)i * m.ldw + j] = v;
           dev[o_wt + (size_t)j * m.ldq + i] = v;
         }
+  } else if (model_id == VB_MODEL_SPARSE_GLM) {
+    const char* kExpect =
+        "sparse regression expects dparams = [csr values (nnz) | csc values (nnz) | y(n_data) | prior_sd | noise_sd], iparams = "
+        "[n_data, p, link, nnz | csr indptr (n_data + 1) | csr indices (nnz) | csc indptr (p + 1) | csc indices (nnz)] and a "
+        "dimension of p, with n_data, p and nnz below 2^31";
+    if (n_iparams < 4 || !iparams || !dparams || iparams[0] <= 0 || iparams[1] <= 0 || iparams[3] < 0 ||
+        iparams[0] > 0x7fffffffll || iparams[1] > 0x7fffffffll || iparams[3] > 0x7fffffffll || dim != iparams[1] ||
+        iparams[2] < VB_GLM_BERNOULLI_LOGIT || iparams[2] > VB_GLM_GAUSSIAN ||
+        n_iparams != (size_t)(4 + iparams[0] + 1 + iparams[1] + 1 + 2 * iparams[3]) ||
+        n_dparams != (size_t)(2 * iparams[3] + iparams[0] + 2))
+      return fail(ctx, VB_ERR_INVALID, "%s", kExpect);
+    const int64_t nd = iparams[0], p = iparams[1], nnz = iparams[3];
+    const int link = (int)iparams[2];
+    const int64_t* ptr[2] = {iparams + 4, iparams + 4 + nd + 1 + nnz};
+    const int64_t* idx[2] = {ptr[0] + nd + 1, ptr[1] + p + 1};
+    const double* val[2] = {dparams, dparams + nnz};
+    const double* ys = dparams + 2 * nnz;
+    const double sd = ys[nd], nsd = ys[nd + 1];
+    if (!(sd > 0.0)) return fail(ctx, VB_ERR_INVALID, "sparse regression prior_sd must be positive");
+    if (!(nsd > 0.0)) return fail(ctx, VB_ERR_INVALID, "sparse regression noise_sd must be positive");
+    const int64_t n_lists[2] = {nd, p}, n_other[2] = {p, nd};
+    const char* form[2] = {"csr", "csc"};
+    for (int w = 0; w < 2; ++w) {
+      const int64_t nl = n_lists[w];
+      if (ptr[w][0] != 0 || ptr[w][nl] != nnz)
+        return fail(ctx, VB_ERR_INVALID, "sparse regression: the %s indptr must run from 0 to nnz = %lld (indptr[0] = %lld, "
+                                         "indptr[%lld] = %lld)", form[w], (long long)nnz, (long long)ptr[w][0], (long long)nl,
+                    (long long)ptr[w][nl]);
+      for (int64_t t = 0; t < nl; ++t)
+        if (ptr[w][t + 1] < ptr[w][t] || ptr[w][t + 1] > nnz)
+          return fail(ctx, VB_ERR_INVALID, "sparse regression: the %s indptr must be monotone within [0, nnz] (indptr[%lld] = "
+                                           "%lld, indptr[%lld] = %lld)", form[w], (long long)t, (long long)ptr[w][t],
+                      (long long)(t + 1), (long long)ptr[w][t + 1]);
+      for (int64_t t = 0; t < nl; ++t)
+        for (int64_t k = ptr[w][t]; k < ptr[w][t + 1]; ++k) {
+          if (idx[w][k] < 0 || idx[w][k] >= n_other[w])
+            return fail(ctx, VB_ERR_INVALID, "sparse regression: %s indices must lie in [0, %lld) (indices[%lld] = %lld)", form[w],
+                        (long long)n_other[w], (long long)k, (long long)idx[w][k]);
+          if (k > ptr[w][t] && idx[w][k] <= idx[w][k - 1])
+            return fail(ctx, VB_ERR_INVALID, "sparse regression: %s indices must increase strictly within list %lld "
+                                             "(indices[%lld] = %lld after %lld)", form[w], (long long)t, (long long)k,
+                        (long long)idx[w][k], (long long)idx[w][k - 1]);
+          if (!std::isfinite(val[w][k]))
+            return fail(ctx, VB_ERR_INVALID, "sparse regression: %s values must be finite (values[%lld])", form[w], (long long)k);
+        }
+    }
+    {   // the CSC form must be the transpose: walking the CSR in row order meets every column's entries in stored order
+      std::vector<int64_t> cur(ptr[1], ptr[1] + p);
+      for (int64_t i = 0; i < nd; ++i)
+        for (int64_t k = ptr[0][i]; k < ptr[0][i + 1]; ++k) {
+          const int64_t j = idx[0][k], c = cur[j]++;
+          if (c >= ptr[1][j + 1] || idx[1][c] != i || val[1][c] != val[0][k])
+            return fail(ctx, VB_ERR_INVALID, "sparse regression: the csc form is not the transpose of the csr form (csr entry "
+                                             "%lld: row %lld, column %lld)", (long long)k, (long long)i, (long long)j);
+        }
+    }
+    m.n_data = nd;
+    m.nnz = nnz;
+    m.tau = sd;
+    m.link = link;
+    m.aux = link == VB_GLM_GAUSSIAN ? nsd : 1.0;
+    m.c0 = 0.0;      // (the rows carry prior and constants themselves: see ModelDev::f0)
+    m.f0 = -(double)p * (log(sd) + 0.5 * kLog2Pi);
+    for (int64_t i = 0; i < nd; ++i) {
+      const double yi = ys[i];
+      if (!std::isfinite(yi)) return fail(ctx, VB_ERR_INVALID, "sparse regression: y must be finite (y[%lld])", (long long)i);
+      if (link == VB_GLM_BERNOULLI_LOGIT && yi != 0.0 && yi != 1.0)
+        return fail(ctx, VB_ERR_INVALID, "sparse regression: logistic responses must lie in {0, 1} (y[%lld] = %g)", (long long)i, yi);
+      if (link == VB_GLM_POISSON) {
+        if (!(yi >= 0.0))
+          return fail(ctx, VB_ERR_INVALID, "sparse regression: Poisson counts must be non-negative (y[%lld] = %g)", (long long)i, yi);
+        m.f0 -= lgamma(yi + 1.0);
+      }
+    }
+    if (link == VB_GLM_GAUSSIAN) m.f0 -= (double)nd * (log(nsd) + 0.5 * kLog2Pi);
+    // lists longer than a segment: (list, begin, end) per segment, (list, first segment, segments) per cut list
+    std::vector<int> seg[2], split[2];
+    for (int w = 0; w < 2; ++w)
+      for (int64_t t = 0; t < n_lists[w]; ++t) {
+        const int64_t b = ptr[w][t], e = ptr[w][t + 1];
+        if (e - b <= kSparseSegment) continue;
+        const int first = (int)(seg[w].size() / 3), n_seg = (int)((e - b + kSparseSegment - 1) / kSparseSegment);
+        for (int s = 0; s < n_seg; ++s) {
+          const int64_t sb = b + (int64_t)s * kSparseSegment;
+          seg[w].insert(seg[w].end(), {(int)t, (int)sb, (int)(sb + kSparseSegment < e ? sb + kSparseSegment : e)});
+        }
+        split[w].insert(split[w].end(), {(int)t, first, n_seg});
+      }
+    m.sp_n_seg[0] = (int)(seg[0].size() / 3), m.sp_n_seg[1] = (int)(seg[1].size() / 3);
+    m.sp_n_split[0] = (int)(split[0].size() / 3), m.sp_n_split[1] = (int)(split[1].size() / 3);
+    // [csr values | csc values | y] as doubles, then the int arrays, each starting on a 16-byte boundary: csr indptr, csr
+    // indices, csc indptr, csc indices, csr segments, csr cut lists, csc segments, csc cut lists
+    const size_t lens[8] = {(size_t)nd + 1, (size_t)nnz, (size_t)p + 1, (size_t)nnz,
+                            seg[0].size(), split[0].size(), seg[1].size(), split[1].size()};
+    size_t at = (size_t)round_up(2 * nnz + nd, 2);
+    for (int a = 0; a < 8; ++a) {
+      sp_off[a] = at;
+      at += (size_t)round_up((int64_t)(lens[a] + 1) / 2, 2);
+    }
+    dev.assign(at, 0.0);
+    for (int64_t k = 0; k < 2 * nnz + nd; ++k) dev[k] = dparams[k];
+    for (int w = 0; w < 2; ++w) {
+      int* ptr32 = reinterpret_cast<int*>(dev.data() + sp_off[2 * w]);
+      int* idx32 = reinterpret_cast<int*>(dev.data() + sp_off[2 * w + 1]);
+      for (int64_t t = 0; t <= n_lists[w]; ++t) ptr32[t] = (int)ptr[w][t];
+      for (int64_t k = 0; k < nnz; ++k) idx32[k] = (int)idx[w][k];
+      if (!seg[w].empty()) memcpy(dev.data() + sp_off[4 + 2 * w], seg[w].data(), seg[w].size() * sizeof(int));
+      if (!split[w].empty()) memcpy(dev.data() + sp_off[5 + 2 * w], split[w].data(), split[w].size() * sizeof(int));
+    }
   } else {
     return fail(ctx, VB_ERR_INVALID, "unknown model id %d", model_id);
   }
@@ -923,6 +1033,17 @@ int vb_set_model(vb_ctx* ctx, int model_id, int64_t dim, const double* dparams, 
       if (!m.const_scale) {
         m.w0 = m.p2 + m.ldq;
         m.w1 = m.w0 + (size_t)m.n_data * m.ldw;
+      }
+    }
+    if (model_id == VB_MODEL_SPARSE_GLM) {
+      m.p1 = nullptr;
+      m.p2 = m.p0 + 2 * m.nnz;
+      for (int w = 0; w < 2; ++w) {
+        m.sp_val[w] = m.p0 + (size_t)w * m.nnz;
+        m.sp_ptr[w] = reinterpret_cast<const int*>(m.p0 + sp_off[2 * w]);
+        m.sp_idx[w] = reinterpret_cast<const int*>(m.p0 + sp_off[2 * w + 1]);
+        m.sp_seg[w] = reinterpret_cast<const int*>(m.p0 + sp_off[4 + 2 * w]);
+        m.sp_split[w] = reinterpret_cast<const int*>(m.p0 + sp_off[5 + 2 * w]);
       }
     }
   }

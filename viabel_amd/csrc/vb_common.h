@@ -98,11 +98,25 @@ struct ModelDev {
   int const_scale = 0;          // locscale: 1 = no W, q = 1 and log sigma_i = g_0 for every observation
   double scale_sd = 1.0;        // locscale: scale_prior_sd of g
   double df = 0.0;              // locscale: degrees of freedom of the Student-t likelihood
+  // VB_MODEL_SPARSE_GLM (vb_sparse.hip): the flat regression target's density (dim = p, tau = prior_sd, link / aux, p2 = y)
+  // on a design held as CSR ([0]: the lists are the rows of X) and as the CSR of X' ([1]: the lists are its columns).  A rows
+  // target as well: c0 stays 0, f0 holds the likelihood's and the prior's constants.
+  const double* sp_val[2] = {nullptr, nullptr};   // values [nnz]
+  const int* sp_ptr[2] = {nullptr, nullptr};      // list pointers [n_data + 1] / [p + 1]
+  const int* sp_idx[2] = {nullptr, nullptr};      // column of each CSR entry / observation of each CSC entry [nnz]
+  // lists longer than kSparseSegment entries, cut by vb_set_model: sp_seg holds a triple (list, begin, end) per segment,
+  // sp_split a triple (list, its first segment, its segments) per cut list
+  const int* sp_seg[2] = {nullptr, nullptr};
+  const int* sp_split[2] = {nullptr, nullptr};
+  int sp_n_seg[2] = {0, 0};
+  int sp_n_split[2] = {0, 0};
+  int64_t nnz = 0;
 };
 
 // targets whose rows (f, grad f) are formed before a pipeline's streaming pass and loaded by it (model_rows_enqueue)
 __host__ __device__ __forceinline__ bool model_has_rows(int id) {
-  return id == VB_MODEL_SOURCE || id == VB_MODEL_SOFTMAX || id == VB_MODEL_MULTILEVEL || id == VB_MODEL_LOCSCALE;
+  return id == VB_MODEL_SOURCE || id == VB_MODEL_SOFTMAX || id == VB_MODEL_MULTILEVEL || id == VB_MODEL_LOCSCALE ||
+         id == VB_MODEL_SPARSE_GLM;
 }
 
 // per-observation log-likelihood term (without constants) and its derivative with respect to eta = x' b
@@ -267,6 +281,7 @@ struct vb_ctx {
   vb::DeviceBuffer sm_work;             // softmax target: packed samples, predictors / residuals, packed gradient, partials
   vb::DeviceBuffer ml_work;             // multilevel target: predictors / residuals, strip partials, pointwise staging
   vb::DeviceBuffer ls_work;             // location-scale target: both predictor matrices, staged scale block, partials
+  vb::DeviceBuffer sp_work;             // sparse regression target: transposed samples, predictors / residuals, gradient, partials
   vb::DeviceBuffer mvt_state;           // multivariate-t DIS: state samples X, scratch
   int64_t mvt_n = 0, mvt_d = 0, mvt_n_total = 0;
   int64_t mvt_lq_off = 0;               // where this rank's log q of the residual pass start inside o_lq (the refresh writes them
@@ -491,8 +506,8 @@ void user_model_release(vb_ctx* ctx);
 // NULL, G[row] = grad f(Z[row]) (row stride ldg; columns >= d are not written)
 int softmax_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
                          int64_t ldg, double* f);
-// rows of the bound target by whichever forms them: a source model's kernel, the softmax, the multilevel or the
-// location-scale pipeline
+// rows of the bound target by whichever forms them: a source model's kernel, the softmax, the multilevel, the
+// location-scale or the sparse regression pipeline
 int model_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
                        int64_t ldg, double* f);
 // doubles of predictor matrix H one row chunk of the softmax pipeline may hold (mirrored by _lib.SOFTMAX_CHUNK_DOUBLES)
@@ -509,6 +524,23 @@ int locscale_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t 
 // doubles of the two predictor matrices H and S together one row chunk of the location-scale pipeline may hold (mirrored by
 // _lib.LOCSCALE_CHUNK_DOUBLES): a chunk is max(8, kLocScaleChunkDoubles / (2 ldq)) rows, with and without W
 constexpr int64_t kLocScaleChunkDoubles = (int64_t)16 << 20;
+// sparse-design GLM target (vb_sparse.hip), the same contract; Z and G need no alignment beyond their element type, and
+// ldz, ldg >= d
+int sparse_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G, int64_t ldg,
+                        double* f);
+// entries of a row or column of the sparse design one wave sums; longer lists are cut into segments of this many entries,
+// summed by separate waves and combined in segment order (mirrored by _lib.SPARSE_SEGMENT)
+constexpr int kSparseSegment = 256;
+// doubles of workspace per chunk of samples of the sparse pipeline (mirrored by _lib.SPARSE_CHUNK_DOUBLES): every sample of
+// a chunk holds at most 2 (n_data + p) doubles plus partials (transposed samples, predictors, transposed gradient; for the
+// pointwise entry the uploaded draws and the term matrix), so a chunk is kSparseChunkDoubles / (2 (n_data + p)) samples,
+// rounded down to a multiple of 64 and kept within [64, 8192] (mirrored by _lib.sparse_chunk_rows).  The segment partials
+// of the cut lists come on top: at most 2 nnz / kSparseSegment rows of one chunk's samples.
+constexpr int64_t kSparseChunkDoubles = (int64_t)16 << 20;
+inline int64_t sparse_chunk_rows(int64_t n_data, int64_t p) {
+  const int64_t rows = kSparseChunkDoubles / (2 * (n_data + p)) / 64 * 64;
+  return rows < 64 ? 64 : rows > 8192 ? 8192 : rows;
+}
 struct LegacyFinish;
 // (defer != nullptr: the kernels are enqueued, the state is left untouched and *defer describes the finish -- exact path only,
 // VB_ERR_UNSUPPORTED otherwise)

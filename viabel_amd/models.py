@@ -14,7 +14,8 @@ from . import _lib
 
 __all__ = ['Model', 'DeviceModel', 'GaussianModel', 'FunnelModel', 'CorrelatedGaussianModel',
            'LogisticRegressionModel', 'PoissonRegressionModel', 'LinearRegressionModel', 'SoftmaxRegressionModel',
-           'MultilevelRegressionModel', 'LocationScaleRegressionModel', 'SourceModel', 'CallableModel']
+           'MultilevelRegressionModel', 'LocationScaleRegressionModel', 'SparseRegressionModel', 'SourceModel',
+           'CallableModel']
 
 
 class Model(object):
@@ -699,3 +700,154 @@ class LocationScaleRegressionModel(DeviceModel):
         eng = _lib.default_engine()
         eng.set_model(self.device_spec())
         return eng.locscale_pointwise(x, self.n_data)
+
+
+def _canonical_csr(data, indices, indptr, n_rows, n_cols):
+    """Validate a CSR triple and return it canonical: indices sorted within each row, duplicates summed in input order,
+    entries that are exactly 0 after summing dropped.  ``(data float64, indices int32, indptr int64)``."""
+    data = np.asarray(data, dtype=np.float64).ravel()
+    indices_in, indptr_in = np.asarray(indices).ravel(), np.asarray(indptr).ravel()
+    if indices_in.dtype.kind not in 'iu' and indices_in.size or indptr_in.dtype.kind not in 'iu':
+        raise ValueError('indices and indptr must be integer arrays')
+    indices, indptr = indices_in.astype(np.int64), indptr_in.astype(np.int64)
+    if n_rows < 1 or n_cols < 1:
+        raise ValueError('the design must have at least one row and one column')
+    if n_rows >= 2 ** 31 or n_cols >= 2 ** 31 or data.size >= 2 ** 31:
+        raise ValueError('n_data, p and nnz must be below 2^31')
+    if indptr.shape != (n_rows + 1,):
+        raise ValueError('indptr must have n_data + 1 = {} entries; got {}'.format(n_rows + 1, indptr.size))
+    if data.shape != indices.shape:
+        raise ValueError('data and indices must have the same length')
+    if indptr[0] != 0 or indptr[-1] != data.size or np.any(np.diff(indptr) < 0):
+        raise ValueError('indptr must be monotone from 0 to nnz = {}'.format(data.size))
+    if not np.all(np.isfinite(data)):
+        raise ValueError('the design must be finite')
+    if indices.size and (indices.min() < 0 or indices.max() >= n_cols):
+        raise ValueError('column indices must lie in [0, {})'.format(n_cols))
+    rows = np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(indptr))
+    order = np.lexsort((indices, rows))                  # stable: duplicates keep their input order
+    rows, cols, vals = rows[order], indices[order], data[order]
+    first = np.ones(vals.size, dtype=bool)
+    first[1:] = (rows[1:] != rows[:-1]) | (cols[1:] != cols[:-1])
+    summed = np.zeros(int(np.count_nonzero(first)))
+    np.add.at(summed, np.cumsum(first) - 1, vals)        # unbuffered: one addition after the other, in order
+    rows, cols = rows[first], cols[first]
+    keep = summed != 0.0
+    rows, cols, summed = rows[keep], cols[keep], summed[keep]
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n_rows))]).astype(np.int64)
+    return np.ascontiguousarray(summed), cols.astype(np.int32), ptr
+
+
+class SparseRegressionModel(DeviceModel):
+    """Bayesian GLM ``y_i ~ p(. | x_i' theta)`` with a ``N(0, prior_sd)`` prior on a SPARSE design matrix: one-hot factors,
+    interaction dummies, bag-of-words counts, hashed features.  ``likelihood`` is ``'logistic'`` (``y`` in ``{0, 1}``),
+    ``'poisson'`` (``y >= 0``) or ``'gaussian'`` (known ``noise_sd``); ``dim = p``.  The density is exactly the one of
+    :class:`LogisticRegressionModel`, :class:`PoissonRegressionModel` and :class:`LinearRegressionModel` on
+    ``model.to_dense()``, normalised the same way::
+
+        f(theta) = sum_i log p(y_i | x_i' theta) - |theta|^2 / (2 prior_sd^2) - p (log prior_sd + log(2 pi) / 2)
+
+    (the Poisson ``- log y_i!`` and the Gaussian ``- log noise_sd - log(2 pi) / 2`` included), but the device holds only the
+    non-zeros -- a design with 200 000 rows, 50 000 columns and ten entries per row is 2 M numbers, not 160 GB.
+
+    ``X`` is anything with a ``.tocsr()`` method (a ``scipy.sparse`` matrix or array; the package itself does not import
+    scipy), or a CSR triple ``(data, indices, indptr)`` together with ``shape=(n_data, p)``.  A dense array is refused: use
+    :meth:`from_dense` (zeros dropped; for tests and small problems) or the dense classes.  The input is made canonical on
+    the host: indices sorted within each row, duplicates summed in input order, entries that are exactly 0 dropped.
+    ``model.csr = (data float64, indices int32, indptr int64)``; ``model.csc`` is the same matrix as the CSR of ``X'``
+    (every column lists its entries in increasing observation order).  Empty rows (``eta_i = 0``) and empty columns (prior
+    only) are legal.  There is no intercept: add a column of ones.
+
+    The engine transposes each chunk of samples, forms the predictors with a gather kernel over the CSR arrays, applies the
+    link, and takes the gradient with the same kernel over the CSC arrays; rows and columns longer than
+    ``_lib.SPARSE_SEGMENT`` entries (an intercept) are cut into segments summed by separate waves (``csrc/vb_sparse.hip``,
+    ``DESIGN.md`` 4.19).  No atomics: two calls return the same bits.  To every objective it looks like a
+    :class:`SourceModel` and is accepted wherever one is: ``ExclusiveKL`` (both estimator forms, the RGE control variates,
+    ``NVPFlow``), ``AlphaDivergence`` and ``DISInclusiveKL`` with every family, ``bbvi``, ``vi_diagnostics`` and the
+    device-resident fit.  ``loo()`` and ``predict()`` take the dense one-predictor regression targets only: this model's
+    route to LOO is ``psisloo(model.pointwise_log_likelihood(x), log_ratios)``.  Not in the reference."""
+
+    _LINKS = {'logistic': _lib.GLM_BERNOULLI_LOGIT, 'poisson': _lib.GLM_POISSON, 'gaussian': _lib.GLM_GAUSSIAN}
+
+    def __init__(self, X, y, likelihood='logistic', prior_sd=10.0, noise_sd=1.0, shape=None):
+        if hasattr(X, 'tocsr'):
+            X = X.tocsr()
+            if shape is not None and tuple(shape) != tuple(X.shape):
+                raise ValueError('shape {} does not match the matrix ({})'.format(tuple(shape), tuple(X.shape)))
+            data, indices, indptr, shape = X.data, X.indices, X.indptr, X.shape
+        elif isinstance(X, (tuple, list)) and len(X) == 3 and shape is not None:
+            data, indices, indptr = X
+        else:
+            raise ValueError('X must be a sparse matrix (anything with .tocsr()) or a CSR triple (data, indices, indptr) with '
+                             'shape=(n_data, p); for a dense array use SparseRegressionModel.from_dense, or the dense classes '
+                             'LogisticRegressionModel, PoissonRegressionModel and LinearRegressionModel')
+        if len(shape) != 2 or int(shape[0]) != shape[0] or int(shape[1]) != shape[1]:
+            raise ValueError('shape must be (n_data, p)')
+        n_data, p = int(shape[0]), int(shape[1])
+        if likelihood not in self._LINKS:
+            raise ValueError("likelihood must be 'logistic', 'poisson' or 'gaussian'")
+        if not prior_sd > 0 or not noise_sd > 0:
+            raise ValueError('prior_sd and noise_sd must be positive')
+        self.csr = _canonical_csr(data, indices, indptr, n_data, p)
+        y = np.asarray(y, dtype=np.float64)
+        if y.shape != (n_data,):
+            raise ValueError('y must have shape ({},); got {}'.format(n_data, y.shape))
+        if not np.all(np.isfinite(y)):
+            raise ValueError('y must be finite')
+        if likelihood == 'logistic' and np.any((y != 0) & (y != 1)):
+            raise ValueError('y must lie in {0, 1}')
+        if likelihood == 'poisson' and np.any(y < 0):
+            raise ValueError('counts must be non-negative')
+        vals, cols, ptr = self.csr
+        rows = np.repeat(np.arange(n_data, dtype=np.int64), np.diff(ptr))
+        order = np.argsort(cols, kind='stable')          # row-major input: rows increase within every column
+        self.csc = (np.ascontiguousarray(vals[order]), rows[order].astype(np.int32),
+                    np.concatenate([[0], np.cumsum(np.bincount(cols, minlength=p))]).astype(np.int64))
+        self.y, self.likelihood = y, likelihood
+        self.prior_sd, self.noise_sd = float(prior_sd), float(noise_sd)
+        self._n_data = n_data
+        super().__init__(p)
+
+    @classmethod
+    def from_dense(cls, X, y, likelihood='logistic', prior_sd=10.0, noise_sd=1.0):
+        """The model of a dense ``(n_data, p)`` array, its zeros dropped (for tests and small problems)."""
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2:
+            raise ValueError('X must be (n_data, p)')
+        rows, cols = np.nonzero(X)                        # row-major order
+        ptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=X.shape[0]))]).astype(np.int64)
+        return cls((X[rows, cols], cols, ptr), y, likelihood=likelihood, prior_sd=prior_sd, noise_sd=noise_sd, shape=X.shape)
+
+    def _build_spec(self):
+        (v, c, ptr), (vt, r, ptr_t) = self.csr, self.csc
+        return (_lib.MODEL_SPARSE_GLM, self._dim, np.concatenate([v, vt, self.y, [self.prior_sd, self.noise_sd]]),
+                np.concatenate([[self._n_data, self._dim, self._LINKS[self.likelihood], v.size], ptr, c, ptr_t,
+                                r]).astype(np.int64))
+
+    @property
+    def n_data(self):
+        return self._n_data
+
+    @property
+    def n_features(self):
+        return self._dim
+
+    @property
+    def nnz(self):
+        return int(self.csr[0].size)
+
+    def to_dense(self):
+        """The design as a dense ``(n_data, p)`` array (meant for small models)."""
+        vals, cols, ptr = self.csr
+        X = np.zeros((self._n_data, self._dim))
+        X[np.repeat(np.arange(self._n_data), np.diff(ptr)), cols] = vals
+        return X
+
+    def pointwise_log_likelihood(self, x):
+        """``log p(y_i | x_i' theta_s)`` for every draw (row of ``x``) and observation: ``(S, n_data)``, the ``log_lik``
+        argument of :func:`psisloo` (``psisloo(log_lik, log_ratios)`` is this model's route to LOO).  Normalised densities,
+        without the prior (``vb_sparse_glm_pointwise``).  ``x``: (S, D), or (D,) for one draw."""
+        x, _ = self._rows(x)
+        eng = _lib.default_engine()
+        eng.set_model(self.device_spec())
+        return eng.sparse_glm_pointwise(x, self.n_data)
