@@ -92,8 +92,10 @@ def test_solo_run_is_the_oracles(vb, sid, regime):
 
 # ---- 2. targets that carry data --------------------------------------------------------------------------------------------
 # One engine, one kind of family (throughput mode: no host generator to keep in step), the target changed between
-# objectives: rows_work, glm_work and the chunk buffers of the softmax and multilevel pipelines are laid out from
-# (n_data, p, classes / groups); ldq = round_up(n_data, 16) and ldp = round_up(p, 16) are ragged at every size here.
+# objectives: rows_work, glm_work and target_work -- the ONE chunk workspace of the softmax, multilevel, location-scale and
+# sparse pipelines -- are laid out from (n_data, p, classes / groups / scale columns / entries); ldq = round_up(n_data, 16)
+# and ldp = round_up(p, 16) are ragged at every size here.  The sparse targets carry a column of ones: n_data entries, more
+# than SPARSE_SEGMENT = 256 at n_data = 333 (the segment and combine kernels run) and fewer at n_data = 77 (they do not).
 N_DRAWS = 203
 TARGET_CALLS = 2
 GAUSS_SRC = r'''
@@ -123,9 +125,20 @@ def _target(vb, name):
         return vb.PoissonRegressionModel(X, rng.poisson(np.exp(eta)).astype(float), prior_sd=3.0)
     if kind == 'softmax':                            # (n_data, p, classes)
         return vb.SoftmaxRegressionModel(X, rng.randint(c, size=n_data), c, prior_sd=3.0)
-    assert kind == 'multilevel'                      # (n_data, p, groups)
-    return vb.MultilevelRegressionModel(X, (rng.rand(n_data) < 0.5).astype(float), rng.randint(c, size=n_data), c,
-                                        prior_sd=3.0)
+    if kind == 'multilevel':                         # (n_data, p, groups)
+        return vb.MultilevelRegressionModel(X, (rng.rand(n_data) < 0.5).astype(float), rng.randint(c, size=n_data), c,
+                                            prior_sd=3.0)
+    if kind in ('locscale', 'locscale_const'):       # (n_data, p, q): Student-t, with a scale design / a constant scale
+        W = rng.randn(n_data, c) / np.sqrt(c) if kind == 'locscale' else None
+        y = eta + np.exp(0.3 * rng.randn(n_data)) * rng.standard_t(4.5, size=n_data)
+        return vb.LocationScaleRegressionModel(X, y, W, 'student_t', 4.5, prior_sd=3.0, scale_prior_sd=0.8)
+    assert kind == 'sparse'                          # (n_data, p, entries per row): logistic, plus a column of ones
+    A = np.zeros((n_data, p + 1))
+    for i in range(n_data):
+        A[i, rng.choice(p, size=c, replace=False)] = rng.randn(c) / np.sqrt(c)
+    A[:, p] = 1.0
+    y = (rng.rand(n_data) < 1.0 / (1.0 + np.exp(-A[:, :p] @ rng.randn(p)))).astype(float)
+    return vb.SparseRegressionModel.from_dense(A, y, likelihood='logistic', prior_sd=3.0)
 
 
 def _target_calls(vb, family, name):
@@ -164,13 +177,22 @@ LOGI, LOGI_S = ('logistic', 333, 37, 0), ('logistic', 77, 37, 0)
 POIS, POIS_S = ('poisson', 333, 37, 0), ('poisson', 77, 37, 0)
 SOFT, SOFT_S = ('softmax', 333, 9, 5), ('softmax', 77, 7, 3)             # dim 45 and 21
 MULT, MULT_S = ('multilevel', 333, 14, 11), ('multilevel', 77, 9, 6)     # dim 26 and 16
+LOCS, LOCS_S = ('locscale', 333, 14, 5), ('locscale', 77, 9, 3)           # dim 19 and 12
+LOCC, LOCC_S = ('locscale_const', 333, 14, 5), ('locscale_const', 77, 9, 3)      # dim 15 and 10 (q = 1)
+SPAR, SPAR_S = ('sparse', 333, 14, 5), ('sparse', 77, 9, 3)               # dim 15 and 10
 TARGET_SEQUENCES = {
     'logistic': [LOGI, LOGI_S, LOGI],
     'poisson': [POIS, POIS_S],
     'softmax': [SOFT, SOFT_S, SOFT],
     'multilevel': [MULT, MULT_S, MULT],
+    'locscale': [LOCS, LOCS_S, LOCS],
+    'locscale_const': [LOCC, LOCC_S, LOCC],
+    'sparse': [SPAR, SPAR_S, SPAR],
     'source': [('source', 48, 0, 0), ('source', 37, 0, 0)],
     'mixed': [LOGI, SOFT_S, POIS_S, MULT_S, SOFT, LOGI_S, MULT],
+    # the four rows targets on one workspace: large, small, large, each in the order softmax, sparse, location-scale,
+    # multilevel, then softmax again
+    'rows_mixed': [SOFT, SPAR, LOCS, MULT, SOFT_S, SPAR_S, LOCS_S, MULT_S, SOFT, SPAR, LOCS, MULT, SOFT],
 }
 
 

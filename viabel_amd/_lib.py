@@ -753,50 +753,37 @@ class Engine:
         self._check(self._lib.vb_psis_smooth_batch(self._ctx, _dptr(lw), n, m, n, float(reff), _dptr(out), _dptr(khat)))
         return out, khat
 
-    def glm_pointwise(self, x, n_data):
-        """``(S, n_data)`` pointwise log-likelihoods of the bound regression target (``n_data`` observations) at the
-        draws ``x`` (S x D)."""
+    def _pointwise(self, symbol, x, n_data):
         x = _f64(x)
         s, d = x.shape
         out = np.empty((s, int(n_data)), dtype=np.float64)
-        self._check(self._lib.vb_glm_pointwise(self._ctx, _dptr(x), s, d, _dptr(out)))
+        self._check(getattr(self._lib, symbol)(self._ctx, _dptr(x), s, d, _dptr(out)))
         return out
+
+    def glm_pointwise(self, x, n_data):
+        """``(S, n_data)`` pointwise log-likelihoods of the bound regression target (``n_data`` observations) at the
+        draws ``x`` (S x D)."""
+        return self._pointwise('vb_glm_pointwise', x, n_data)
 
     def softmax_pointwise(self, x, n_data):
         """``(S, n_data)`` terms ``eta_{i, y_i} - logsumexp_c eta_ic`` of the bound softmax regression target at the draws
         ``x`` (S x D)."""
-        x = _f64(x)
-        s, d = x.shape
-        out = np.empty((s, int(n_data)), dtype=np.float64)
-        self._check(self._lib.vb_softmax_pointwise(self._ctx, _dptr(x), s, d, _dptr(out)))
-        return out
+        return self._pointwise('vb_softmax_pointwise', x, n_data)
 
     def multilevel_pointwise(self, x, n_data):
         """``(S, n_data)`` normalised terms ``log p(y_i | x_i' b + tau u_{g_i})`` of the bound multilevel regression target
         at the draws ``x`` (S x D), observations in the bound (group-sorted) order."""
-        x = _f64(x)
-        s, d = x.shape
-        out = np.empty((s, int(n_data)), dtype=np.float64)
-        self._check(self._lib.vb_multilevel_pointwise(self._ctx, _dptr(x), s, d, _dptr(out)))
-        return out
+        return self._pointwise('vb_multilevel_pointwise', x, n_data)
 
     def locscale_pointwise(self, x, n_data):
         """``(S, n_data)`` normalised terms ``log p(y_i | x_i' b, exp(w_i' g))`` of the bound location-scale regression
         target at the draws ``x`` (S x D)."""
-        x = _f64(x)
-        s, d = x.shape
-        out = np.empty((s, int(n_data)), dtype=np.float64)
-        self._check(self._lib.vb_locscale_pointwise(self._ctx, _dptr(x), s, d, _dptr(out)))
-        return out
+        return self._pointwise('vb_locscale_pointwise', x, n_data)
 
     def sparse_glm_pointwise(self, x, n_data):
         """``(S, n_data)`` normalised terms ``log p(y_i | x_i' theta)`` of the bound sparse regression target at the draws
         ``x`` (S x D)."""
-        x = _f64(x)
-        s, d = x.shape
-        out = np.empty((s, int(n_data)), dtype=np.float64)
-        self._check(self._lib.vb_sparse_glm_pointwise(self._ctx, _dptr(x), s, d, _dptr(out)))
-        return out
+        return self._pointwise('vb_sparse_glm_pointwise', x, n_data)
 
     def glm_psis_loo(self, x, n_data, log_ratios=None, log_w=None, reff=1.0):
         """PSIS-LOO of the bound regression target (``n_data`` observations) from the draws ``x``

@@ -1,6 +1,6 @@
 // C ABI of libviabel_hip.so: contexts, noise slots, model binding, synchronous / asynchronous
 // evaluators.  See include/viabel_hip.h for the contract and the reference seam it replaces.
-#include "vb_common.h"
+#include "vb_rows_target.h"
 
 #include <mutex>
 
@@ -445,6 +445,115 @@ static int ticket(vb_ctx* ctx, ResultSlot** rs, int count) {
   return VB_OK;
 }
 
+// ---- vb_set_model by model id (the rows targets': vb_softmax.hip, vb_multilevel.hip, vb_locscale.hip, vb_sparse.hip) ------
+int upload_model_params(vb_ctx* ctx, const std::vector<double>& dev, const double** base) {
+  VB_TRY(ensure(ctx, ctx->model_params, dev.size() * sizeof(double)));
+  VB_HIP(ctx, hipMemcpyAsync(ctx->model_params.ptr, dev.data(), dev.size() * sizeof(double), hipMemcpyHostToDevice,
+                             ctx->stream));
+  VB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *base = (const double*)ctx->model_params.ptr;
+  return VB_OK;
+}
+
+static int gauss_diag_set_model(vb_ctx* ctx, int64_t dim, const double* dparams, size_t n_dparams) {
+  if (n_dparams != (size_t)(2 * dim) || !dparams)
+    return fail(ctx, VB_ERR_INVALID, "gauss_diag expects dparams = [mean(D) | stdev(D)]");
+  ModelDev m;
+  m.id = VB_MODEL_GAUSS_DIAG;
+  m.dim = (int)dim;
+  std::vector<double> dev(2 * dim);      // [mean (D) | 1 / sd^2 (D)]
+  double c0 = -0.5 * dim * kLog2Pi;
+  for (int64_t i = 0; i < dim; ++i) {
+    const double sd = dparams[dim + i];
+    if (!(sd > 0.0)) return fail(ctx, VB_ERR_INVALID, "gauss_diag stdev must be positive");
+    dev[i] = dparams[i];
+    dev[dim + i] = 1.0 / (sd * sd);
+    c0 -= log(sd);
+  }
+  m.c0 = c0;
+  VB_TRY(upload_model_params(ctx, dev, &m.p0));
+  m.p1 = m.p0 + dim;
+  ctx->model = m;
+  return VB_OK;
+}
+
+static int funnel_set_model(vb_ctx* ctx, int64_t dim, const double* dparams, size_t n_dparams, const int64_t* iparams,
+                            size_t n_iparams) {
+  if (n_dparams != 1 || n_iparams != 1 || !dparams || !iparams)
+    return fail(ctx, VB_ERR_INVALID, "funnel expects dparams = [log_sigma_stdev], iparams = [scale_index]");
+  if (iparams[0] < 0 || iparams[0] >= dim || !(dparams[0] > 0.0))
+    return fail(ctx, VB_ERR_INVALID, "funnel scale_index / log_sigma_stdev out of range");
+  ModelDev m;
+  m.id = VB_MODEL_FUNNEL;
+  m.dim = (int)dim;
+  m.k = (int)iparams[0];
+  m.tau = dparams[0];
+  m.c0 = -log(m.tau) - 0.5 * kLog2Pi - 0.5 * (double)(dim - 1) * kLog2Pi;
+  ctx->model = m;      // (no device parameters)
+  return VB_OK;
+}
+
+static int gauss_full_set_model(vb_ctx* ctx, int64_t dim, const double* dparams, size_t n_dparams) {
+  if (n_dparams != (size_t)(dim + dim * dim + 1) || !dparams)
+    return fail(ctx, VB_ERR_INVALID, "gauss_full expects dparams = [mean(D) | P(DxD) | logdet P]");
+  ModelDev m;
+  m.id = VB_MODEL_GAUSS_FULL;
+  m.dim = (int)dim;
+  m.c0 = 0.5 * dparams[dim + dim * dim] - 0.5 * dim * kLog2Pi;
+  m.ldp = round_up(dim, 16);
+  // [mean (ldp) | P (dim x ldp)], rows padded so every GEMM operand row is 16-B aligned
+  std::vector<double> dev((size_t)m.ldp * (dim + 1), 0.0);
+  for (int64_t i = 0; i < dim; ++i) dev[i] = dparams[i];
+  for (int64_t i = 0; i < dim; ++i)
+    for (int64_t j = 0; j < dim; ++j) dev[(size_t)m.ldp * (i + 1) + j] = dparams[dim + i * dim + j];
+  VB_TRY(upload_model_params(ctx, dev, &m.p0));
+  m.p1 = m.p0 + m.ldp;
+  ctx->model = m;
+  return VB_OK;
+}
+
+static int logistic_set_model(vb_ctx* ctx, int64_t dim, const double* dparams, size_t n_dparams, const int64_t* iparams,
+                              size_t n_iparams) {
+  const int link = (n_iparams == 2 && iparams) ? (int)iparams[1] : VB_GLM_BERNOULLI_LOGIT;
+  const size_t extra = link == VB_GLM_GAUSSIAN ? 2 : 1;
+  if ((n_iparams != 1 && n_iparams != 2) || !iparams || iparams[0] <= 0 || !dparams ||
+      link < VB_GLM_BERNOULLI_LOGIT || link > VB_GLM_GAUSSIAN ||
+      n_dparams != (size_t)(iparams[0] * dim + iparams[0]) + extra)
+    return fail(ctx, VB_ERR_INVALID,
+                "regression target expects dparams = [X(n_data x D) | y(n_data) | prior_sd (| noise_sd)], "
+                "iparams = [n_data (, link)]");
+  const int64_t nd = iparams[0];
+  const double* ys = dparams + nd * dim;
+  const double sd = ys[nd];
+  if (!(sd > 0.0)) return fail(ctx, VB_ERR_INVALID, "logistic prior_sd must be positive");
+  ModelDev m;
+  m.id = VB_MODEL_LOGISTIC;
+  m.dim = (int)dim;
+  m.n_data = nd;
+  m.ldp = round_up(dim, 16);
+  m.ldq = round_up(nd, 16);
+  m.tau = sd;
+  m.link = link;
+  if (link == VB_GLM_POISSON) {
+    for (int64_t i = 0; i < nd; ++i)
+      if (!(ys[i] >= 0.0)) return fail(ctx, VB_ERR_INVALID, "Poisson counts must be non-negative");
+  } else if (link == VB_GLM_GAUSSIAN) {
+    m.aux = ys[nd + 1];
+    if (!(m.aux > 0.0)) return fail(ctx, VB_ERR_INVALID, "noise_sd must be positive");
+  }
+  m.c0 = glm_const_continue(-(double)dim * (log(sd) + 0.5 * kLog2Pi), link, m.aux, ys, nd);
+  // [X (nd x ldp) | X' (dim x ldq) | y (ldq)], rows padded for the GEMM operand loads
+  const size_t o_xt = (size_t)nd * m.ldp, o_y = o_xt + (size_t)dim * m.ldq;
+  std::vector<double> dev(o_y + (size_t)m.ldq, 0.0);
+  pack_design(dev, 0, dparams, nd, dim, m.ldp, m.ldq);
+  for (int64_t i = 0; i < nd; ++i) dev[o_y + i] = ys[i];
+  VB_TRY(upload_model_params(ctx, dev, &m.p0));
+  m.p1 = m.p0 + o_xt;
+  m.p2 = m.p0 + o_y;
+  ctx->model = m;
+  return VB_OK;
+}
+
 }  // namespace vb
 
 using namespace vb;
@@ -658,397 +767,17 @@ int vb_set_model(vb_ctx* ctx, int model_id, int64_t dim, const double* dparams, 
   if (dim <= 0) return fail(ctx, VB_ERR_INVALID, "model dimension must be positive");
   VB_HIP(ctx, hipSetDevice(ctx->device));
   VB_TRY(main_stream_write(ctx));
-  const double kLog2Pi = 1.8378770664093454835606594728112;
-  ModelDev m;
-  m.id = model_id;
-  m.dim = (int)dim;
-  std::vector<double> dev;   // what is uploaded
-  size_t sp_off[8] = {};     // sparse regression: where its int arrays start inside dev (in doubles)
-  if (model_id == VB_MODEL_GAUSS_DIAG) {
-    if (n_dparams != (size_t)(2 * dim) || !dparams)
-      return fail(ctx, VB_ERR_INVALID, "gauss_diag expects dparams = [mean(D) | stdev(D)]");
-    dev.resize(2 * dim);
-    double c0 = -0.5 * dim * kLog2Pi;
-    for (int64_t i = 0; i < dim; ++i) {
-      const double sd = dparams[dim + i];
-      if (!(sd > 0.0)) return fail(ctx, VB_ERR_INVALID, "gauss_diag stdev must be positive");
-      dev[i] = dparams[i];
-      dev[dim + i] = 1.0 / (sd * sd);
-      c0 -= log(sd);
-    }
-    m.c0 = c0;
-  } else if (model_id == VB_MODEL_FUNNEL) {
-    if (n_dparams != 1 || n_iparams != 1 || !dparams || !iparams)
-      return fail(ctx, VB_ERR_INVALID, "funnel expects dparams = [log_sigma_stdev], iparams = [scale_index]");
-    if (iparams[0] < 0 || iparams[0] >= dim || !(dparams[0] > 0.0))
-      return fail(ctx, VB_ERR_INVALID, "funnel scale_index / log_sigma_stdev out of range");
-    m.k = (int)iparams[0];
-    m.tau = dparams[0];
-    m.c0 = -log(m.tau) - 0.5 * kLog2Pi - 0.5 * (double)(dim - 1) * kLog2Pi;
-  } else if (model_id == VB_MODEL_GAUSS_FULL) {
-    if (n_dparams != (size_t)(dim + dim * dim + 1) || !dparams)
-      return fail(ctx, VB_ERR_INVALID, "gauss_full expects dparams = [mean(D) | P(DxD) | logdet P]");
-    m.c0 = 0.5 * dparams[dim + dim * dim] - 0.5 * dim * kLog2Pi;
-    m.ldp = round_up(dim, 16);
-    // [mean (ldp) | P (dim x ldp)], rows padded so every GEMM operand row is 16-B aligned
-    dev.assign((size_t)m.ldp * (dim + 1), 0.0);
-    for (int64_t i = 0; i < dim; ++i) dev[i] = dparams[i];
-    for (int64_t i = 0; i < dim; ++i)
-      for (int64_t j = 0; j < dim; ++j) dev[(size_t)m.ldp * (i + 1) + j] = dparams[dim + i * dim + j];
-  } else if (model_id == VB_MODEL_LOGISTIC) {
-    const int link = (n_iparams == 2 && iparams) ? (int)iparams[1] : VB_GLM_BERNOULLI_LOGIT;
-    const size_t extra = link == VB_GLM_GAUSSIAN ? 2 : 1;
-    if ((n_iparams != 1 && n_iparams != 2) || !iparams || iparams[0] <= 0 || !dparams ||
-        link < VB_GLM_BERNOULLI_LOGIT || link > VB_GLM_GAUSSIAN ||
-        n_dparams != (size_t)(iparams[0] * dim + iparams[0]) + extra)
-      return fail(ctx, VB_ERR_INVALID,
-                  "regression target expects dparams = [X(n_data x D) | y(n_data) | prior_sd (| noise_sd)], "
-                  "iparams = [n_data (, link)]");
-    const int64_t nd = iparams[0];
-    const double sd = dparams[nd * dim + nd];
-    if (!(sd > 0.0)) return fail(ctx, VB_ERR_INVALID, "logistic prior_sd must be positive");
-    m.n_data = nd;
-    m.ldp = round_up(dim, 16);
-    m.ldq = round_up(nd, 16);
-    m.tau = sd;
-    m.link = link;
-    m.c0 = -(double)dim * (log(sd) + 0.5 * kLog2Pi);
-    if (link == VB_GLM_POISSON) {           // - sum_i log(y_i !)
-      for (int64_t i = 0; i < nd; ++i) {
-        const double yi = dparams[nd * dim + i];
-        if (!(yi >= 0.0)) return fail(ctx, VB_ERR_INVALID, "Poisson counts must be non-negative");
-        m.c0 -= lgamma(yi + 1.0);
-      }
-    } else if (link == VB_GLM_GAUSSIAN) {
-      m.aux = dparams[nd * dim + nd + 1];
-      if (!(m.aux > 0.0)) return fail(ctx, VB_ERR_INVALID, "noise_sd must be positive");
-      m.c0 -= (double)nd * (log(m.aux) + 0.5 * kLog2Pi);
-    }
-    // [X (nd x ldp) | X' (dim x ldq) | y (ldq)], rows padded for the GEMM operand loads
-    dev.assign((size_t)nd * m.ldp + (size_t)dim * m.ldq + (size_t)m.ldq, 0.0);
-    for (int64_t i = 0; i < nd; ++i)
-      for (int64_t j = 0; j < dim; ++j) {
-        const double v = dparams[i * dim + j];
-        dev[(size_t)i * m.ldp + j] = v;
-        dev[(size_t)nd * m.ldp + (size_t)j * m.ldq + i] = v;
-      }
-    for (int64_t i = 0; i < nd; ++i) dev[(size_t)nd * m.ldp + (size_t)dim * m.ldq + i] = dparams[nd * dim + i];
-  } else if (model_id == VB_MODEL_SOFTMAX) {
-    if (n_iparams != 2 || !iparams || !dparams || iparams[0] <= 0 || iparams[1] < 2 || dim % iparams[1] != 0 ||
-        iparams[0] > 0x7fffffffll || dim > 0x7fffffffll ||
-        n_dparams != (size_t)(iparams[0] * (dim / iparams[1]) + iparams[0]) + 1)
-      return fail(ctx, VB_ERR_INVALID,
-                  "softmax regression expects dparams = [X(n_data x p) | y(n_data) | prior_sd], iparams = [n_data, n_classes] "
-                  "and a dimension of n_classes * p");
-    const int64_t nd = iparams[0], nc = iparams[1], p = dim / nc;
-    const double sd = dparams[nd * p + nd];
-    if (!(sd > 0.0)) return fail(ctx, VB_ERR_INVALID, "softmax prior_sd must be positive");
-    for (int64_t i = 0; i < nd; ++i) {
-      const double yi = dparams[nd * p + i];
-      if (!(yi >= 0.0 && yi < (double)nc) || yi != floor(yi))
-        return fail(ctx, VB_ERR_INVALID, "softmax labels must be integers in [0, n_classes) (y[%lld] = %g)", (long long)i, yi);
-    }
-    m.n_data = nd;
-    m.n_classes = (int)nc;
-    m.n_feat = (int)p;
-    m.ldp = round_up(p, 16);
-    m.ldq = round_up(nd, 16);
-    m.tau = sd;
-    m.c0 = 0.0;      // (the rows carry prior and constant themselves, like a source model's: see ModelDev::f0)
-    m.f0 = -(double)dim * (log(sd) + 0.5 * kLog2Pi);
-    // [X (nd x ldp) | X' (p x ldq) | y (ldq)]: the logistic target's layout with p in place of dim
-    dev.assign((size_t)nd * m.ldp + (size_t)p * m.ldq + (size_t)m.ldq, 0.0);
-    for (int64_t i = 0; i < nd; ++i)
-      for (int64_t j = 0; j < p; ++j) {
-        const double v = dparams[i * p + j];
-        dev[(size_t)i * m.ldp + j] = v;
-        dev[(size_t)nd * m.ldp + (size_t)j * m.ldq + i] = v;
-      }
-    for (int64_t i = 0; i < nd; ++i) dev[(size_t)nd * m.ldp + (size_t)p * m.ldq + i] = dparams[nd * p + i];
-  } else if (model_id == VB_MODEL_MULTILEVEL) {
-    const char* kExpect =
-        "multilevel regression expects dparams = [X(n_data x p) | y(n_data) | prior_sd | tau_sd | noise_sd], iparams = "
-        "[n_data, n_groups, link | offsets(n_groups + 1) | group of each observation(n_data)] and a dimension of "
-        "p + n_groups + 1";
-    if (n_iparams < 3 || !iparams || !dparams || iparams[0] <= 0 || iparams[1] < 1 || iparams[0] > 0x7fffffffll ||
-        iparams[1] > 0x7fffffffll || dim > 0x7fffffffll || dim - iparams[1] - 1 < 1 ||
-        iparams[2] < VB_GLM_BERNOULLI_LOGIT || iparams[2] > VB_GLM_GAUSSIAN ||
-        n_iparams != (size_t)(3 + iparams[1] + 1 + iparams[0]) ||
-        n_dparams != (size_t)(iparams[0] * (dim - iparams[1] - 1) + iparams[0]) + 3)
-      return fail(ctx, VB_ERR_INVALID, "%s", kExpect);
-    const int64_t nd = iparams[0], ng = iparams[1], p = dim - ng - 1;
-    const int link = (int)iparams[2];
-    const int64_t* off = iparams + 3;
-    const int64_t* grp = off + ng + 1;
-    const double sd = dparams[nd * p + nd], tsd = dparams[nd * p + nd + 1], nsd = dparams[nd * p + nd + 2];
-    if (!(sd > 0.0)) return fail(ctx, VB_ERR_INVALID, "multilevel prior_sd must be positive");
-    if (!(tsd > 0.0)) return fail(ctx, VB_ERR_INVALID, "multilevel tau_sd must be positive");
-    if (!(nsd > 0.0)) return fail(ctx, VB_ERR_INVALID, "multilevel noise_sd must be positive");
-    if (off[0] != 0 || off[ng] != nd)
-      return fail(ctx, VB_ERR_INVALID, "multilevel offsets must run from 0 to n_data (offsets[0] = %lld, offsets[%lld] = %lld)",
-                  (long long)off[0], (long long)ng, (long long)off[ng]);
-    for (int64_t j = 0; j < ng; ++j)
-      if (off[j + 1] < off[j])
-        return fail(ctx, VB_ERR_INVALID, "multilevel offsets must be monotone (offsets[%lld] = %lld > offsets[%lld] = %lld)",
-                    (long long)j, (long long)off[j], (long long)(j + 1), (long long)off[j + 1]);
-    for (int64_t i = 0; i < nd; ++i)
-      if (grp[i] < 0 || grp[i] >= ng)
-        return fail(ctx, VB_ERR_INVALID, "multilevel group labels must lie in [0, n_groups) (groups[%lld] = %lld)", (long long)i,
-                    (long long)grp[i]);
-    for (int64_t j = 0; j < ng; ++j)
-      for (int64_t i = off[j]; i < off[j + 1]; ++i)
-        if (grp[i] != j)
-          return fail(ctx, VB_ERR_INVALID, "multilevel observations must be sorted by group: observation %lld lies in the run of "
-                                           "group %lld and carries the label %lld", (long long)i, (long long)j, (long long)grp[i]);
-    m.n_data = nd;
-    m.n_groups = (int)ng;
-    m.n_feat = (int)p;
-    m.ldp = round_up(p, 16);
-    m.ldq = round_up(nd, 16);
-    m.tau = sd;
-    m.hyper_sd = tsd;
-    m.link = link;
-    m.aux = link == VB_GLM_GAUSSIAN ? nsd : 1.0;
-    m.c0 = 0.0;      // (the rows carry priors and constants themselves: see ModelDev::f0)
-    // b ~ N(0, sd), u ~ N(0, 1), tau ~ HalfNormal(tsd); the likelihood's constant as the flat regression target has it
-    m.f0 = -(double)p * (log(sd) + 0.5 * kLog2Pi) - 0.5 * (double)ng * kLog2Pi + log(2.0) - log(tsd) - 0.5 * kLog2Pi;
-    if (link == VB_GLM_POISSON) {
-      for (int64_t i = 0; i < nd; ++i) {
-        const double yi = dparams[nd * p + i];
-        if (!(yi >= 0.0)) return fail(ctx, VB_ERR_INVALID, "Poisson counts must be non-negative");
-        m.f0 -= lgamma(yi + 1.0);
-      }
-    } else if (link == VB_GLM_GAUSSIAN) {
-      m.f0 -= (double)nd * (log(nsd) + 0.5 * kLog2Pi);
-    }
-    // [X (nd x ldp) | X' (p x ldq) | y (ldq) | offsets (ng + 1 ints) | group of each observation (nd ints)]: the logistic
-    // target's layout with p in place of dim, then the two int arrays, each starting on a 16-byte boundary
-    const size_t o_off = (size_t)nd * m.ldp + (size_t)p * m.ldq + (size_t)m.ldq;
-    const size_t o_grp = o_off + (size_t)round_up((ng + 2) / 2, 2);
-    dev.assign(o_grp + (size_t)round_up((nd + 1) / 2, 2), 0.0);
-    for (int64_t i = 0; i < nd; ++i)
-      for (int64_t j = 0; j < p; ++j) {
-        const double v = dparams[i * p + j];
-        dev[(size_t)i * m.ldp + j] = v;
-        dev[(size_t)nd * m.ldp + (size_t)j * m.ldq + i] = v;
-      }
-    for (int64_t i = 0; i < nd; ++i) dev[(size_t)nd * m.ldp + (size_t)p * m.ldq + i] = dparams[nd * p + i];
-    int* off32 = reinterpret_cast<int*>(dev.data() + o_off);
-    int* grp32 = reinterpret_cast<int*>(dev.data() + o_grp);
-    for (int64_t j = 0; j <= ng; ++j) off32[j] = (int)off[j];
-    for (int64_t i = 0; i < nd; ++i) grp32[i] = (int)grp[i];
-  } else if (model_id == VB_MODEL_LOCSCALE) {
-    const char* kExpect =
-        "location-scale regression expects dparams = [X(n_data x p) | y(n_data) | W(n_data x q), absent with a constant scale "
-        "| prior_sd | scale_prior_sd | df], iparams = [n_data, p, q, likelihood, constant_scale] (constant_scale = 1: q = 1) "
-        "and a dimension of p + q";
-    if (n_iparams != 5 || !iparams || !dparams || iparams[0] <= 0 || iparams[1] < 1 || iparams[2] < 1 ||
-        iparams[0] > 0x7fffffffll || iparams[1] > 0x7fffffffll || iparams[2] > 0x7fffffffll || dim > 0x7fffffffll ||
-        dim != iparams[1] + iparams[2] || iparams[3] < VB_LOCSCALE_GAUSSIAN || iparams[3] > VB_LOCSCALE_STUDENT_T ||
-        iparams[4] < 0 || iparams[4] > 1 || (iparams[4] == 1 && iparams[2] != 1) ||
-        n_dparams != (size_t)(iparams[0] * iparams[1] + iparams[0] + (iparams[4] ? 0 : iparams[0] * iparams[2])) + 3)
-      return fail(ctx, VB_ERR_INVALID, "%s", kExpect);
-    const int64_t nd = iparams[0], p = iparams[1], q = iparams[2];
-    const int lik = (int)iparams[3];
-    const bool cs = iparams[4] == 1;
-    const double* wsrc = dparams + nd * p + nd;
-    const double* tail = wsrc + (cs ? 0 : nd * q);
-    const double sd = tail[0], ssd = tail[1], nu = tail[2];
-    if (!(sd > 0.0)) return fail(ctx, VB_ERR_INVALID, "location-scale prior_sd must be positive");
-    if (!(ssd > 0.0)) return fail(ctx, VB_ERR_INVALID, "location-scale scale_prior_sd must be positive");
-    if (!(nu > 0.0) || !std::isfinite(nu)) return fail(ctx, VB_ERR_INVALID, "location-scale df must be positive and finite");
-    m.n_data = nd;
-    m.n_feat = (int)p;
-    m.n_scale = (int)q;
-    m.const_scale = cs ? 1 : 0;
-    m.ldp = round_up(p, 16);
-    m.ldq = round_up(nd, 16);
-    m.ldw = cs ? 0 : round_up(q, 16);
-    m.tau = sd;
-    m.scale_sd = ssd;
-    m.df = nu;
-    m.link = lik;
-    m.c0 = 0.0;      // (the rows carry priors and constants themselves: see ModelDev::f0)
-    // b ~ N(0, sd), g ~ N(0, ssd); the likelihood's constant: n_data times -log(2 pi) / 2, or c(nu) of the Student t
-    m.f0 = -(double)p * (log(sd) + 0.5 * kLog2Pi) - (double)q * (log(ssd) + 0.5 * kLog2Pi);
-    if (lik == VB_LOCSCALE_STUDENT_T)
-      m.f0 += (double)nd * (lgamma(0.5 * (nu + 1.0)) - lgamma(0.5 * nu) - 0.5 * (log(nu) + kLog2Pi - log(2.0)));
-    else
-      m.f0 -= (double)nd * 0.5 * kLog2Pi;
-    // [X (nd x ldp) | X' (p x ldq) | y (ldq) | W (nd x ldw) | W' (q x ldq)]: the softmax target's layout, then the scale
-    // design in the same two forms (absent with a constant scale)
-    const size_t o_w = (size_t)nd * m.ldp + (size_t)p * m.ldq + (size_t)m.ldq;
-    const size_t o_wt = o_w + (size_t)nd * m.ldw;
-    dev.assign(o_wt + (cs ? 0 : (size_t)q * m.ldq), 0.0);
-    for (int64_t i = 0; i < nd; ++i)
-      for (int64_t j = 0; j < p; ++j) {
-        const double v = dparams[i * p + j];
-        dev[(size_t)i * m.ldp + j] = v;
-        dev[(size_t)nd * m.ldp + (size_t)j * m.ldq + i] = v;
-      }
-    for (int64_t i = 0; i < nd; ++i) dev[(size_t)nd * m.ldp + (size_t)p * m.ldq + i] = dparams[nd * p + i];
-    if (!cs)
-      for (int64_t i = 0; i < nd; ++i)
-        for (int64_t j = 0; j < q; ++j) {
-          const double v = wsrc[i * q + j];
-          dev[o_w + (size_t)i * m.ldw + j] = v;
-          dev[o_wt + (size_t)j * m.ldq + i] = v;
-        }
-  } else if (model_id == VB_MODEL_SPARSE_GLM) {
-    const char* kExpect =
-        "sparse regression expects dparams = [csr values (nnz) | csc values (nnz) | y(n_data) | prior_sd | noise_sd], iparams = "
-        "[n_data, p, link, nnz | csr indptr (n_data + 1) | csr indices (nnz) | csc indptr (p + 1) | csc indices (nnz)] and a "
-        "dimension of p, with n_data, p and nnz below 2^31";
-    if (n_iparams < 4 || !iparams || !dparams || iparams[0] <= 0 || iparams[1] <= 0 || iparams[3] < 0 ||
-        iparams[0] > 0x7fffffffll || iparams[1] > 0x7fffffffll || iparams[3] > 0x7fffffffll || dim != iparams[1] ||
-        iparams[2] < VB_GLM_BERNOULLI_LOGIT || iparams[2] > VB_GLM_GAUSSIAN ||
-        n_iparams != (size_t)(4 + iparams[0] + 1 + iparams[1] + 1 + 2 * iparams[3]) ||
-        n_dparams != (size_t)(2 * iparams[3] + iparams[0] + 2))
-      return fail(ctx, VB_ERR_INVALID, "%s", kExpect);
-    const int64_t nd = iparams[0], p = iparams[1], nnz = iparams[3];
-    const int link = (int)iparams[2];
-    const int64_t* ptr[2] = {iparams + 4, iparams + 4 + nd + 1 + nnz};
-    const int64_t* idx[2] = {ptr[0] + nd + 1, ptr[1] + p + 1};
-    const double* val[2] = {dparams, dparams + nnz};
-    const double* ys = dparams + 2 * nnz;
-    const double sd = ys[nd], nsd = ys[nd + 1];
-    if (!(sd > 0.0)) return fail(ctx, VB_ERR_INVALID, "sparse regression prior_sd must be positive");
-    if (!(nsd > 0.0)) return fail(ctx, VB_ERR_INVALID, "sparse regression noise_sd must be positive");
-    const int64_t n_lists[2] = {nd, p}, n_other[2] = {p, nd};
-    const char* form[2] = {"csr", "csc"};
-    for (int w = 0; w < 2; ++w) {
-      const int64_t nl = n_lists[w];
-      if (ptr[w][0] != 0 || ptr[w][nl] != nnz)
-        return fail(ctx, VB_ERR_INVALID, "sparse regression: the %s indptr must run from 0 to nnz = %lld (indptr[0] = %lld, "
-                                         "indptr[%lld] = %lld)", form[w], (long long)nnz, (long long)ptr[w][0], (long long)nl,
-                    (long long)ptr[w][nl]);
-      for (int64_t t = 0; t < nl; ++t)
-        if (ptr[w][t + 1] < ptr[w][t] || ptr[w][t + 1] > nnz)
-          return fail(ctx, VB_ERR_INVALID, "sparse regression: the %s indptr must be monotone within [0, nnz] (indptr[%lld] = "
-                                           "%lld, indptr[%lld] = %lld)", form[w], (long long)t, (long long)ptr[w][t],
-                      (long long)(t + 1), (long long)ptr[w][t + 1]);
-      for (int64_t t = 0; t < nl; ++t)
-        for (int64_t k = ptr[w][t]; k < ptr[w][t + 1]; ++k) {
-          if (idx[w][k] < 0 || idx[w][k] >= n_other[w])
-            return fail(ctx, VB_ERR_INVALID, "sparse regression: %s indices must lie in [0, %lld) (indices[%lld] = %lld)", form[w],
-                        (long long)n_other[w], (long long)k, (long long)idx[w][k]);
-          if (k > ptr[w][t] && idx[w][k] <= idx[w][k - 1])
-            return fail(ctx, VB_ERR_INVALID, "sparse regression: %s indices must increase strictly within list %lld "
-                                             "(indices[%lld] = %lld after %lld)", form[w], (long long)t, (long long)k,
-                        (long long)idx[w][k], (long long)idx[w][k - 1]);
-          if (!std::isfinite(val[w][k]))
-            return fail(ctx, VB_ERR_INVALID, "sparse regression: %s values must be finite (values[%lld])", form[w], (long long)k);
-        }
-    }
-    {   // the CSC form must be the transpose: walking the CSR in row order meets every column's entries in stored order
-      std::vector<int64_t> cur(ptr[1], ptr[1] + p);
-      for (int64_t i = 0; i < nd; ++i)
-        for (int64_t k = ptr[0][i]; k < ptr[0][i + 1]; ++k) {
-          const int64_t j = idx[0][k], c = cur[j]++;
-          if (c >= ptr[1][j + 1] || idx[1][c] != i || val[1][c] != val[0][k])
-            return fail(ctx, VB_ERR_INVALID, "sparse regression: the csc form is not the transpose of the csr form (csr entry "
-                                             "%lld: row %lld, column %lld)", (long long)k, (long long)i, (long long)j);
-        }
-    }
-    m.n_data = nd;
-    m.nnz = nnz;
-    m.tau = sd;
-    m.link = link;
-    m.aux = link == VB_GLM_GAUSSIAN ? nsd : 1.0;
-    m.c0 = 0.0;      // (the rows carry prior and constants themselves: see ModelDev::f0)
-    m.f0 = -(double)p * (log(sd) + 0.5 * kLog2Pi);
-    for (int64_t i = 0; i < nd; ++i) {
-      const double yi = ys[i];
-      if (!std::isfinite(yi)) return fail(ctx, VB_ERR_INVALID, "sparse regression: y must be finite (y[%lld])", (long long)i);
-      if (link == VB_GLM_BERNOULLI_LOGIT && yi != 0.0 && yi != 1.0)
-        return fail(ctx, VB_ERR_INVALID, "sparse regression: logistic responses must lie in {0, 1} (y[%lld] = %g)", (long long)i, yi);
-      if (link == VB_GLM_POISSON) {
-        if (!(yi >= 0.0))
-          return fail(ctx, VB_ERR_INVALID, "sparse regression: Poisson counts must be non-negative (y[%lld] = %g)", (long long)i, yi);
-        m.f0 -= lgamma(yi + 1.0);
-      }
-    }
-    if (link == VB_GLM_GAUSSIAN) m.f0 -= (double)nd * (log(nsd) + 0.5 * kLog2Pi);
-    // lists longer than a segment: (list, begin, end) per segment, (list, first segment, segments) per cut list
-    std::vector<int> seg[2], split[2];
-    for (int w = 0; w < 2; ++w)
-      for (int64_t t = 0; t < n_lists[w]; ++t) {
-        const int64_t b = ptr[w][t], e = ptr[w][t + 1];
-        if (e - b <= kSparseSegment) continue;
-        const int first = (int)(seg[w].size() / 3), n_seg = (int)((e - b + kSparseSegment - 1) / kSparseSegment);
-        for (int s = 0; s < n_seg; ++s) {
-          const int64_t sb = b + (int64_t)s * kSparseSegment;
-          seg[w].insert(seg[w].end(), {(int)t, (int)sb, (int)(sb + kSparseSegment < e ? sb + kSparseSegment : e)});
-        }
-        split[w].insert(split[w].end(), {(int)t, first, n_seg});
-      }
-    m.sp_n_seg[0] = (int)(seg[0].size() / 3), m.sp_n_seg[1] = (int)(seg[1].size() / 3);
-    m.sp_n_split[0] = (int)(split[0].size() / 3), m.sp_n_split[1] = (int)(split[1].size() / 3);
-    // [csr values | csc values | y] as doubles, then the int arrays, each starting on a 16-byte boundary: csr indptr, csr
-    // indices, csc indptr, csc indices, csr segments, csr cut lists, csc segments, csc cut lists
-    const size_t lens[8] = {(size_t)nd + 1, (size_t)nnz, (size_t)p + 1, (size_t)nnz,
-                            seg[0].size(), split[0].size(), seg[1].size(), split[1].size()};
-    size_t at = (size_t)round_up(2 * nnz + nd, 2);
-    for (int a = 0; a < 8; ++a) {
-      sp_off[a] = at;
-      at += (size_t)round_up((int64_t)(lens[a] + 1) / 2, 2);
-    }
-    dev.assign(at, 0.0);
-    for (int64_t k = 0; k < 2 * nnz + nd; ++k) dev[k] = dparams[k];
-    for (int w = 0; w < 2; ++w) {
-      int* ptr32 = reinterpret_cast<int*>(dev.data() + sp_off[2 * w]);
-      int* idx32 = reinterpret_cast<int*>(dev.data() + sp_off[2 * w + 1]);
-      for (int64_t t = 0; t <= n_lists[w]; ++t) ptr32[t] = (int)ptr[w][t];
-      for (int64_t k = 0; k < nnz; ++k) idx32[k] = (int)idx[w][k];
-      if (!seg[w].empty()) memcpy(dev.data() + sp_off[4 + 2 * w], seg[w].data(), seg[w].size() * sizeof(int));
-      if (!split[w].empty()) memcpy(dev.data() + sp_off[5 + 2 * w], split[w].data(), split[w].size() * sizeof(int));
-    }
-  } else {
-    return fail(ctx, VB_ERR_INVALID, "unknown model id %d", model_id);
+  switch (model_id) {
+    case VB_MODEL_GAUSS_DIAG: return gauss_diag_set_model(ctx, dim, dparams, n_dparams);
+    case VB_MODEL_FUNNEL: return funnel_set_model(ctx, dim, dparams, n_dparams, iparams, n_iparams);
+    case VB_MODEL_GAUSS_FULL: return gauss_full_set_model(ctx, dim, dparams, n_dparams);
+    case VB_MODEL_LOGISTIC: return logistic_set_model(ctx, dim, dparams, n_dparams, iparams, n_iparams);
+    case VB_MODEL_SOFTMAX: return softmax_set_model(ctx, dim, dparams, n_dparams, iparams, n_iparams);
+    case VB_MODEL_MULTILEVEL: return multilevel_set_model(ctx, dim, dparams, n_dparams, iparams, n_iparams);
+    case VB_MODEL_LOCSCALE: return locscale_set_model(ctx, dim, dparams, n_dparams, iparams, n_iparams);
+    case VB_MODEL_SPARSE_GLM: return sparse_set_model(ctx, dim, dparams, n_dparams, iparams, n_iparams);
   }
-  if (!dev.empty()) {
-    VB_TRY(ensure(ctx, ctx->model_params, dev.size() * sizeof(double)));
-    VB_HIP(ctx, hipMemcpyAsync(ctx->model_params.ptr, dev.data(), dev.size() * sizeof(double),
-                               hipMemcpyHostToDevice, ctx->stream));
-    VB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    m.p0 = (const double*)ctx->model_params.ptr;
-    m.p1 = m.p0 + (model_id == VB_MODEL_GAUSS_FULL ? m.ldp : dim);
-    if (model_id == VB_MODEL_LOGISTIC) {
-      m.p1 = m.p0 + (size_t)m.n_data * m.ldp;
-      m.p2 = m.p1 + (size_t)dim * m.ldq;
-    }
-    if (model_id == VB_MODEL_SOFTMAX) {
-      m.p1 = m.p0 + (size_t)m.n_data * m.ldp;
-      m.p2 = m.p1 + (size_t)m.n_feat * m.ldq;
-    }
-    if (model_id == VB_MODEL_MULTILEVEL) {
-      m.p1 = m.p0 + (size_t)m.n_data * m.ldp;
-      m.p2 = m.p1 + (size_t)m.n_feat * m.ldq;
-      m.grp_off = reinterpret_cast<const int*>(m.p2 + m.ldq);
-      m.grp_of = m.grp_off + 2 * round_up((m.n_groups + 2) / 2, 2);
-    }
-    if (model_id == VB_MODEL_LOCSCALE) {
-      m.p1 = m.p0 + (size_t)m.n_data * m.ldp;
-      m.p2 = m.p1 + (size_t)m.n_feat * m.ldq;
-      if (!m.const_scale) {
-        m.w0 = m.p2 + m.ldq;
-        m.w1 = m.w0 + (size_t)m.n_data * m.ldw;
-      }
-    }
-    if (model_id == VB_MODEL_SPARSE_GLM) {
-      m.p1 = nullptr;
-      m.p2 = m.p0 + 2 * m.nnz;
-      for (int w = 0; w < 2; ++w) {
-        m.sp_val[w] = m.p0 + (size_t)w * m.nnz;
-        m.sp_ptr[w] = reinterpret_cast<const int*>(m.p0 + sp_off[2 * w]);
-        m.sp_idx[w] = reinterpret_cast<const int*>(m.p0 + sp_off[2 * w + 1]);
-        m.sp_seg[w] = reinterpret_cast<const int*>(m.p0 + sp_off[4 + 2 * w]);
-        m.sp_split[w] = reinterpret_cast<const int*>(m.p0 + sp_off[5 + 2 * w]);
-      }
-    }
-  }
-  ctx->model = m;
-  return VB_OK;
+  return fail(ctx, VB_ERR_INVALID, "unknown model id %d", model_id);
 }
 
 int vb_set_model_source(vb_ctx* ctx, int64_t dim, const char* source, const double* params, size_t n_params) {

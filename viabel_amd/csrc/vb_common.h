@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -278,10 +279,9 @@ struct vb_ctx {
   std::vector<UserModule> user_modules;
   vb::DeviceBuffer user_params;
   vb::DeviceBuffer glm_work;            // regression targets: split-K slabs of the gradient GEMM
-  vb::DeviceBuffer sm_work;             // softmax target: packed samples, predictors / residuals, packed gradient, partials
-  vb::DeviceBuffer ml_work;             // multilevel target: predictors / residuals, strip partials, pointwise staging
-  vb::DeviceBuffer ls_work;             // location-scale target: both predictor matrices, staged scale block, partials
-  vb::DeviceBuffer sp_work;             // sparse regression target: transposed samples, predictors / residuals, gradient, partials
+  // the bound rows target's chunk workspace (softmax, multilevel, location-scale, sparse regression): one model is bound at
+  // a time, every call lays the buffer out from scratch and writes each piece before it reads it
+  vb::DeviceBuffer target_work;
   vb::DeviceBuffer mvt_state;           // multivariate-t DIS: state samples X, scratch
   int64_t mvt_n = 0, mvt_d = 0, mvt_n_total = 0;
   int64_t mvt_lq_off = 0;               // where this rank's log q of the residual pass start inside o_lq (the refresh writes them
@@ -507,7 +507,7 @@ void user_model_release(vb_ctx* ctx);
 int softmax_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
                          int64_t ldg, double* f);
 // rows of the bound target by whichever forms them: a source model's kernel, the softmax, the multilevel, the
-// location-scale or the sparse regression pipeline
+// location-scale or the sparse regression pipeline (vb_rows.hip)
 int model_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
                        int64_t ldg, double* f);
 // doubles of predictor matrix H one row chunk of the softmax pipeline may hold (mirrored by _lib.SOFTMAX_CHUNK_DOUBLES)
@@ -541,6 +541,25 @@ inline int64_t sparse_chunk_rows(int64_t n_data, int64_t p) {
   const int64_t rows = kSparseChunkDoubles / (2 * (n_data + p)) / 64 * 64;
   return rows < 64 ? 64 : rows > 8192 ? 8192 : rows;
 }
+// The pointwise entry of a rows target (vb_rows.hip): the argument checks of `api_name` against the bound model, then the
+// draws x [s x d] in chunks -- each uploaded into ctx->target_work with row stride round_up(d, 16), evaluated by `body` into
+// a term matrix there and downloaded to ll_out [s x n_data].  `plan` lays the workspace out for s draws and makes the
+// target's own checks; `body` enqueues the chunk's kernels on ctx->stream (the workspace is ctx->target_work.ptr by then).
+struct RowsPointwisePlan {
+  int64_t chunk = 0, total = 0;      // draws per chunk; doubles of workspace
+  int64_t o_x = 0, o_ll = 0, ldl = 0;      // where the chunk's draws and its term matrix (row stride ldl) live
+};
+using RowsPointwiseBody = std::function<int(int64_t rows, const double* X, int64_t ldx, double* LL, int64_t ldl)>;
+int rows_pointwise(vb_ctx* ctx, const char* api_name, int model_id, const char* target_name, const double* x, int64_t s,
+                   int64_t d, double* ll_out, const std::function<int(RowsPointwisePlan*)>& plan,
+                   const RowsPointwiseBody& body);
+// vb_set_model by model id: each validates everything, fills the ModelDev scalars, packs the host image, uploads it
+// (upload_model_params, after its last validation) and sets the device pointers from the offsets it packed with; ctx->model
+// is assigned last.  The rows targets' live beside the kernels that read the layout.
+int upload_model_params(vb_ctx* ctx, const std::vector<double>& dev, const double** base);      // vb_api.hip
+using SetModelFn = int(vb_ctx* ctx, int64_t dim, const double* dparams, size_t n_dparams, const int64_t* iparams,
+                       size_t n_iparams);
+SetModelFn softmax_set_model, multilevel_set_model, locscale_set_model, sparse_set_model;
 struct LegacyFinish;
 // (defer != nullptr: the kernels are enqueued, the state is left untouched and *defer describes the finish -- exact path only,
 // VB_ERR_UNSUPPORTED otherwise)

@@ -27,32 +27,13 @@
 // row-sum kernel writes G[r][p].
 // Every sum has a fixed order (a lane's elements in index order, the wave by shuffles, the four waves in a fixed tree) and
 // there are no atomics anywhere: two calls give the same bits.
-#include "vb_common.h"
-#include "vb_gemm_f64.h"
+#include "vb_rows_target.h"
 
 namespace vb {
 
 namespace {
 
 constexpr int kLsStrip = 1024;           // observations per workgroup of the link kernel: 256 lanes x 4
-constexpr double kHalfLog2Pi = 0.91893853320467274178;
-
-struct EpiStorePred {        // H = acc
-  double* Y;
-  int64_t ldy;
-  __device__ void operator()(int, int row, int col, double acc) const { Y[(int64_t)row * ldy + col] = acc; }
-  __device__ d2v pair(int, int row, int col, double a0, double a1) const {
-    const d2v v = (d2v){a0, a1};
-    *reinterpret_cast<d2v*>(Y + (int64_t)row * ldy + col) = v;
-    return v;
-  }
-};
-
-__device__ __forceinline__ double ls_wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-  return x;
-}
 
 // Zs[r][j] = Z[r][p + j] (j < q), zero in the pad columns (the products read pairs, the gradient's epilogue too)
 __global__ void __launch_bounds__(256) ls_pack_kernel(const double* __restrict__ Z, int64_t ldz, int64_t rows, int p, int q,
@@ -116,18 +97,7 @@ __global__ void __launch_bounds__(256) ls_link_kernel(double* __restrict__ H, do
     }
   }
   if (MODE == 2) return;
-  __shared__ double wsum[8];
-  ll = ls_wave_sum(ll);
-  rs = ls_wave_sum(rs);
-  if ((threadIdx.x & 63) == 0) {
-    wsum[threadIdx.x >> 6] = ll;
-    wsum[4 + (threadIdx.x >> 6)] = rs;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part[2 * (int64_t)blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-    part[2 * (int64_t)blockIdx.x + 1] = (wsum[4] + wsum[5]) + (wsum[6] + wsum[7]);
-  }
+  strip_partials_store<2>(ll, rs, part);
 }
 
 // f[r] = sum_s ll[r][s] - |b_r|^2 / (2 sd^2) - |g_r|^2 / (2 ssd^2) + f0 and, with a gradient and a constant scale,
@@ -147,10 +117,10 @@ __global__ void __launch_bounds__(256) ls_rowsum_kernel(const double* __restrict
   }
   for (int c = lane; c < p; c += 64) sb = fma(zr[c], zr[c], sb);
   for (int c = lane; c < q; c += 64) sg = fma(zr[p + c], zr[p + c], sg);
-  ll = ls_wave_sum(ll);
-  rs = ls_wave_sum(rs);
-  sb = ls_wave_sum(sb);
-  sg = ls_wave_sum(sg);
+  ll = wave_sum(ll);
+  rs = wave_sum(rs);
+  sb = wave_sum(sb);
+  sg = wave_sum(sg);
   if (lane != 0) return;
   f[r] = fma(neg_half_ivp, sb, ll) + fma(-0.5 * ivs, sg, f0);
   if (Gconst) Gconst[r * ldg + p] = fma(-ivs, zr[p], rs);
@@ -169,15 +139,8 @@ LsLayout ls_layout(const ModelDev& m, int64_t n, bool grad, bool pointwise) {
   L.ldh = m.ldq;
   L.lds = round_up(m.n_scale, 16);
   L.n_strips = (int)((m.n_data + kLsStrip - 1) / kLsStrip);
-  int64_t chunk = kLocScaleChunkDoubles / (2 * L.ldh);
-  chunk = chunk < 8 ? 8 : chunk;
-  L.chunk = chunk > n ? n : chunk;
-  int64_t off = 0;
-  auto carve = [&off](int64_t doubles) {      // (multiples of 32 doubles: every piece starts 256-B aligned)
-    const int64_t o = off;
-    off += round_up(doubles, 32);
-    return o;
-  };
+  L.chunk = rows_chunk(kLocScaleChunkDoubles, 2 * L.ldh, n);
+  Carver carve;
   L.o_h = carve(L.chunk * L.ldh);
   L.o_s = carve(general ? L.chunk * L.ldh : 0);
   L.o_zs = carve(general ? L.chunk * L.lds : 0);
@@ -185,7 +148,7 @@ LsLayout ls_layout(const ModelDev& m, int64_t n, bool grad, bool pointwise) {
   L.o_part = carve(2 * L.chunk * L.n_strips);
   L.o_x = carve(pointwise ? L.chunk * round_up(m.dim, 16) : 0);
   L.o_ll = carve(pointwise ? L.chunk * L.ldh : 0);
-  L.total = off;
+  L.total = carve.off;
   return L;
 }
 
@@ -205,7 +168,7 @@ int ls_predictors(vb_ctx* ctx, hipStream_t st, const LsLayout& L, double* base, 
   const ModelDev& m = ctx->model;
   const int n_cu = ctx->prop.multiProcessorCount;
   const GemmArgs gh = gemm_product(Z, ldz, m.p1, m.ldq, (int)rows, (int)m.n_data, m.n_feat, 0);
-  gemm_f64_launch<true>(st, gh, 1, n_cu, EpiStorePred{base + L.o_h, L.ldh});
+  gemm_f64_launch<true>(st, gh, 1, n_cu, EpiStorePlain{base + L.o_h, L.ldh});
   VB_HIP(ctx, hipGetLastError());
   if (m.const_scale) return VB_OK;
   const int64_t items = rows * L.lds;
@@ -213,7 +176,7 @@ int ls_predictors(vb_ctx* ctx, hipStream_t st, const LsLayout& L, double* base, 
                      base + L.o_zs, L.lds);
   VB_HIP(ctx, hipGetLastError());
   const GemmArgs gs = gemm_product(base + L.o_zs, L.lds, m.w1, m.ldq, (int)rows, (int)m.n_data, m.n_scale, 0);
-  gemm_f64_launch<true>(st, gs, 1, n_cu, EpiStorePred{base + L.o_s, L.ldh});
+  gemm_f64_launch<true>(st, gs, 1, n_cu, EpiStorePlain{base + L.o_s, L.ldh});
   VB_HIP(ctx, hipGetLastError());
   return VB_OK;
 }
@@ -232,17 +195,11 @@ int locscale_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t 
   if (m.id != VB_MODEL_LOCSCALE) return fail(ctx, VB_ERR_STATE, "no location-scale regression model bound");
   const LsLayout L = ls_layout(m, n > 0 ? n : 1, G != nullptr, false);
   VB_TRY(ls_check(ctx, L, n, d));
-  // the GEMMs move 16-byte pairs of Z and G, and the gradient's epilogue addresses both with one stride
-  if (((uintptr_t)Z & 15) || (ldz & 1) || ldz < d)
-    return fail(ctx, VB_ERR_INVALID, "location-scale rows: the samples must be 16-byte aligned with an even row stride >= %d",
-                d);
-  if (G && (((uintptr_t)G & 15) || ldg != ldz))
-    return fail(ctx, VB_ERR_INVALID, "location-scale rows: the gradient must be 16-byte aligned and share the samples' row "
-                                     "stride (%lld, not %lld)", (long long)ldz, (long long)ldg);
+  VB_TRY(rows_operands_check(ctx, "location-scale", Z, ldz, d, G, ldg));
   const int p = m.n_feat, q = m.n_scale;
   const bool general = !m.const_scale;
-  VB_TRY(ensure(ctx, ctx->ls_work, (size_t)L.total * sizeof(double)));
-  double* base = (double*)ctx->ls_work.ptr;
+  VB_TRY(ensure(ctx, ctx->target_work, (size_t)L.total * sizeof(double)));
+  double* base = (double*)ctx->target_work.ptr;
   double* S = general ? base + L.o_s : nullptr;
   const double ivp = 1.0 / (m.tau * m.tau), ivs = 1.0 / (m.scale_sd * m.scale_sd);
   ModelDev ms = m;           // the scale gradient is the same product on the scale design and the scale prior
@@ -281,6 +238,68 @@ int locscale_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t 
   return VB_OK;
 }
 
+int locscale_set_model(vb_ctx* ctx, int64_t dim, const double* dparams, size_t n_dparams, const int64_t* iparams,
+                       size_t n_iparams) {
+  const char* kExpect =
+      "location-scale regression expects dparams = [X(n_data x p) | y(n_data) | W(n_data x q), absent with a constant scale "
+      "| prior_sd | scale_prior_sd | df], iparams = [n_data, p, q, likelihood, constant_scale] (constant_scale = 1: q = 1) "
+      "and a dimension of p + q";
+  if (n_iparams != 5 || !iparams || !dparams || iparams[0] <= 0 || iparams[1] < 1 || iparams[2] < 1 ||
+      iparams[0] > 0x7fffffffll || iparams[1] > 0x7fffffffll || iparams[2] > 0x7fffffffll || dim > 0x7fffffffll ||
+      dim != iparams[1] + iparams[2] || iparams[3] < VB_LOCSCALE_GAUSSIAN || iparams[3] > VB_LOCSCALE_STUDENT_T ||
+      iparams[4] < 0 || iparams[4] > 1 || (iparams[4] == 1 && iparams[2] != 1) ||
+      n_dparams != (size_t)(iparams[0] * iparams[1] + iparams[0] + (iparams[4] ? 0 : iparams[0] * iparams[2])) + 3)
+    return fail(ctx, VB_ERR_INVALID, "%s", kExpect);
+  const int64_t nd = iparams[0], p = iparams[1], q = iparams[2];
+  const int lik = (int)iparams[3];
+  const bool cs = iparams[4] == 1;
+  const double* ys = dparams + nd * p;
+  const double* wsrc = ys + nd;
+  const double* tail = wsrc + (cs ? 0 : nd * q);
+  const double sd = tail[0], ssd = tail[1], nu = tail[2];
+  if (!(sd > 0.0)) return fail(ctx, VB_ERR_INVALID, "location-scale prior_sd must be positive");
+  if (!(ssd > 0.0)) return fail(ctx, VB_ERR_INVALID, "location-scale scale_prior_sd must be positive");
+  if (!(nu > 0.0) || !std::isfinite(nu)) return fail(ctx, VB_ERR_INVALID, "location-scale df must be positive and finite");
+  ModelDev m;
+  m.id = VB_MODEL_LOCSCALE;
+  m.dim = (int)dim;
+  m.n_data = nd;
+  m.n_feat = (int)p;
+  m.n_scale = (int)q;
+  m.const_scale = cs ? 1 : 0;
+  m.ldp = round_up(p, 16);
+  m.ldq = round_up(nd, 16);
+  m.ldw = cs ? 0 : round_up(q, 16);
+  m.tau = sd;
+  m.scale_sd = ssd;
+  m.df = nu;
+  m.link = lik;
+  m.c0 = 0.0;      // (the rows carry priors and constants themselves: see ModelDev::f0)
+  // b ~ N(0, sd), g ~ N(0, ssd); the likelihood's constant: n_data times -log(2 pi) / 2, or c(nu) of the Student t
+  m.f0 = -(double)p * (log(sd) + 0.5 * kLog2Pi) - (double)q * (log(ssd) + 0.5 * kLog2Pi);
+  if (lik == VB_LOCSCALE_STUDENT_T)
+    m.f0 += (double)nd * (lgamma(0.5 * (nu + 1.0)) - lgamma(0.5 * nu) - 0.5 * (log(nu) + kLog2Pi - log(2.0)));
+  else
+    m.f0 -= (double)nd * 0.5 * kLog2Pi;
+  // [X (nd x ldp) | X' (p x ldq) | y (ldq) | W (nd x ldw) | W' (q x ldq)]: the softmax target's layout, then the scale
+  // design in the same two forms (absent with a constant scale)
+  const size_t o_xt = (size_t)nd * m.ldp, o_y = o_xt + (size_t)p * m.ldq, o_w = o_y + (size_t)m.ldq;
+  const size_t o_wt = o_w + (size_t)nd * m.ldw;
+  std::vector<double> dev(o_wt + (cs ? 0 : (size_t)q * m.ldq), 0.0);
+  pack_design(dev, 0, dparams, nd, p, m.ldp, m.ldq);
+  for (int64_t i = 0; i < nd; ++i) dev[o_y + i] = ys[i];
+  if (!cs) pack_design(dev, o_w, wsrc, nd, q, m.ldw, m.ldq);
+  VB_TRY(upload_model_params(ctx, dev, &m.p0));
+  m.p1 = m.p0 + o_xt;
+  m.p2 = m.p0 + o_y;
+  if (!cs) {
+    m.w0 = m.p0 + o_w;
+    m.w1 = m.p0 + o_wt;
+  }
+  ctx->model = m;
+  return VB_OK;
+}
+
 }  // namespace vb
 
 using namespace vb;
@@ -288,38 +307,24 @@ using namespace vb;
 extern "C" {
 
 int vb_locscale_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out) {
-  if (!ctx || !x || !ll_out) return fail(ctx, VB_ERR_INVALID, "NULL argument");
-  if (ctx->model.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model)");
-  if (ctx->model.id != VB_MODEL_LOCSCALE)
-    return fail(ctx, VB_ERR_UNSUPPORTED, "vb_locscale_pointwise needs a location-scale regression target (model id %d bound)",
-                ctx->model.id);
-  if (d != ctx->model.dim)
-    return fail(ctx, VB_ERR_INVALID, "x has %lld columns, model dimension is %d", (long long)d, ctx->model.dim);
-  if (s <= 0) return fail(ctx, VB_ERR_INVALID, "the number of draws must be positive");
-  const ModelDev& m = ctx->model;
-  const LsLayout L = ls_layout(m, s, false, true);
-  VB_TRY(ls_check(ctx, L, s, (int)d));
-  VB_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int64_t nd = m.n_data, ldx = round_up(d, 16);
-  VB_TRY(ensure(ctx, ctx->ls_work, (size_t)L.total * sizeof(double)));
-  double* base = (double*)ctx->ls_work.ptr;
-  double* S = m.const_scale ? nullptr : base + L.o_s;
-  const double c_obs = ls_obs_const(m);
-  for (int64_t r0 = 0; r0 < s; r0 += L.chunk) {
-    const int64_t rows = s - r0 < L.chunk ? s - r0 : L.chunk;
-    VB_HIP(ctx, hipMemcpy2DAsync(base + L.o_x, (size_t)ldx * sizeof(double), x + r0 * d, (size_t)d * sizeof(double),
-                                 (size_t)d * sizeof(double), (size_t)rows, hipMemcpyHostToDevice, st));
-    VB_TRY(ls_predictors(ctx, st, L, base, base + L.o_x, ldx, rows));
-    hipLaunchKernelGGL(ls_link_kernel<2>, dim3((unsigned)(rows * L.n_strips)), dim3(256), 0, st, base + L.o_h, S, L.ldh,
-                       (const double*)(base + L.o_x), ldx, m.n_feat, (int)nd, m.p2, m.link, m.df, c_obs, L.n_strips,
-                       (double*)nullptr, base + L.o_ll, L.ldh);
-    VB_HIP(ctx, hipGetLastError());
-    VB_HIP(ctx, hipMemcpy2DAsync(ll_out + r0 * nd, (size_t)nd * sizeof(double), base + L.o_ll, (size_t)L.ldh * sizeof(double),
-                                 (size_t)nd * sizeof(double), (size_t)rows, hipMemcpyDeviceToHost, st));
-    VB_HIP(ctx, hipStreamSynchronize(st));
-  }
-  return VB_OK;
+  LsLayout L;
+  return rows_pointwise(
+      ctx, "vb_locscale_pointwise", VB_MODEL_LOCSCALE, "location-scale regression", x, s, d, ll_out,
+      [&](RowsPointwisePlan* plan) {
+        L = ls_layout(ctx->model, s, false, true);
+        *plan = {L.chunk, L.total, L.o_x, L.o_ll, L.ldh};
+        return ls_check(ctx, L, s, (int)d);
+      },
+      [&](int64_t rows, const double* X, int64_t ldx, double* LL, int64_t ldl) {
+        const ModelDev& m = ctx->model;
+        double* base = (double*)ctx->target_work.ptr;
+        VB_TRY(ls_predictors(ctx, ctx->stream, L, base, X, ldx, rows));
+        hipLaunchKernelGGL(ls_link_kernel<2>, dim3((unsigned)(rows * L.n_strips)), dim3(256), 0, ctx->stream, base + L.o_h,
+                           m.const_scale ? (double*)nullptr : base + L.o_s, L.ldh, X, ldx, m.n_feat, (int)m.n_data, m.p2, m.link,
+                           m.df, ls_obs_const(m), L.n_strips, (double*)nullptr, LL, ldl);
+        VB_HIP(ctx, hipGetLastError());
+        return VB_OK;
+      });
 }
 
 }  // extern "C"

@@ -18,8 +18,7 @@
 //   rowsum    f[r] and G[r][p + J] from the row's strip partials, |b|^2, |u|^2 and omega: a wave per row
 // Every sum has a fixed order (a lane's elements in index order, the wave by shuffles, the four waves in a fixed tree) and
 // there are no atomics anywhere: two calls give the same bits.
-#include "vb_common.h"
-#include "vb_gemm_f64.h"
+#include "vb_rows_target.h"
 
 namespace vb {
 
@@ -27,23 +26,6 @@ namespace {
 
 constexpr int kMlStrip = 1024;           // observations per workgroup of the link kernel: 256 lanes x 4
 constexpr int kMlGroupsPerBlock = 64;    // groups per workgroup of the group kernel: 16 per wave
-
-struct EpiStoreEta {         // H = acc
-  double* Y;
-  int64_t ldy;
-  __device__ void operator()(int, int row, int col, double acc) const { Y[(int64_t)row * ldy + col] = acc; }
-  __device__ d2v pair(int, int row, int col, double a0, double a1) const {
-    const d2v v = (d2v){a0, a1};
-    *reinterpret_cast<d2v*>(Y + (int64_t)row * ldy + col) = v;
-    return v;
-  }
-};
-
-__device__ __forceinline__ double ml_wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-  return x;
-}
 
 // MODE 0: log-likelihood partials; 1: ... and the partials of sum r_i u_{g_i}, H overwritten by the residuals r_i; 2: the
 // normalised per-observation terms to LL, no sums.
@@ -69,32 +51,15 @@ __global__ void __launch_bounds__(256) ml_link_kernel(double* __restrict__ H, in
     const double yi = y[i];
     double dl;
     const double t = glm_term(link, aux, yi, fma(tau, ug, Hr[i]), &dl);
-    if (MODE == 2) {      // what glm_term leaves out of log p(y_i | eta_i)
-      double c = 0.0;
-      if (link == VB_GLM_POISSON) c = -lgamma(yi + 1.0);
-      else if (link == VB_GLM_GAUSSIAN) c = -log(aux) - 0.91893853320467274178;
-      LL[r * ldl + i] = t + c;
-    } else {
-      ll += t;
-    }
+    if (MODE == 2) LL[r * ldl + i] = t + glm_obs_const(link, aux, yi);
+    else ll += t;
     if (MODE == 1) {
       Hr[i] = dl;
       ru = fma(dl, ug, ru);
     }
   }
   if (MODE == 2) return;
-  __shared__ double wsum[8];
-  ll = ml_wave_sum(ll);
-  ru = ml_wave_sum(ru);
-  if ((threadIdx.x & 63) == 0) {
-    wsum[threadIdx.x >> 6] = ll;
-    wsum[4 + (threadIdx.x >> 6)] = ru;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part[2 * (int64_t)blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-    part[2 * (int64_t)blockIdx.x + 1] = (wsum[4] + wsum[5]) + (wsum[6] + wsum[7]);
-  }
+  strip_partials_store<2>(ll, ru, part);
 }
 
 // G[r][p + j] = tau_r sum_{i in run j} R[r][i] - u_rj.  Workgroup (row r, block of 64 groups), a wave per group in turn:
@@ -116,7 +81,7 @@ __global__ void __launch_bounds__(256) ml_group_kernel(const double* __restrict_
     const int end = grp_off[j + 1];
     double sum = 0.0;
     for (int i = grp_off[j] + lane; i < end; i += 64) sum += Rr[i];
-    sum = ml_wave_sum(sum);
+    sum = wave_sum(sum);
     if (lane == 0) G[r * ldg + p + j] = fma(tau, sum, -ur[j]);
   }
 }
@@ -138,10 +103,10 @@ __global__ void __launch_bounds__(256) ml_rowsum_kernel(const double* __restrict
   }
   for (int c = lane; c < p; c += 64) sb = fma(zr[c], zr[c], sb);
   for (int c = lane; c < J; c += 64) su = fma(zr[p + c], zr[p + c], su);
-  ll = ml_wave_sum(ll);
-  ru = ml_wave_sum(ru);
-  sb = ml_wave_sum(sb);
-  su = ml_wave_sum(su);
+  ll = wave_sum(ll);
+  ru = wave_sum(ru);
+  sb = wave_sum(sb);
+  su = wave_sum(su);
   if (lane != 0) return;
   const double omega = zr[p + J], tau = exp(omega), t2 = tau * tau;
   f[r] = (fma(neg_half_ivp, sb, ll) - 0.5 * su) + (fma(-0.5 * ivt, t2, omega) + f0);
@@ -159,20 +124,13 @@ MlLayout ml_layout(const ModelDev& m, int64_t n, bool pointwise) {
   L.ldh = m.ldq;
   L.n_strips = (int)((m.n_data + kMlStrip - 1) / kMlStrip);
   L.n_gblocks = (m.n_groups + kMlGroupsPerBlock - 1) / kMlGroupsPerBlock;
-  int64_t chunk = kMultilevelChunkDoubles / L.ldh;
-  chunk = chunk < 8 ? 8 : chunk;
-  L.chunk = chunk > n ? n : chunk;
-  int64_t off = 0;
-  auto carve = [&off](int64_t doubles) {      // (multiples of 32 doubles: every piece starts 256-B aligned)
-    const int64_t o = off;
-    off += round_up(doubles, 32);
-    return o;
-  };
+  L.chunk = rows_chunk(kMultilevelChunkDoubles, L.ldh, n);
+  Carver carve;
   L.o_h = carve(L.chunk * L.ldh);
   L.o_part = carve(2 * L.chunk * L.n_strips);
   L.o_x = carve(pointwise ? L.chunk * round_up(m.dim, 16) : 0);
   L.o_ll = carve(pointwise ? L.chunk * L.ldh : 0);
-  L.total = off;
+  L.total = carve.off;
   return L;
 }
 
@@ -190,7 +148,7 @@ int ml_check(vb_ctx* ctx, const MlLayout& L, int64_t n, int d) {
 int ml_predictors(vb_ctx* ctx, hipStream_t st, const MlLayout& L, double* base, const double* Z, int64_t ldz, int64_t rows) {
   const ModelDev& m = ctx->model;
   const GemmArgs g = gemm_product(Z, ldz, m.p1, m.ldq, (int)rows, (int)m.n_data, m.n_feat, 0);
-  gemm_f64_launch<true>(st, g, 1, ctx->prop.multiProcessorCount, EpiStoreEta{base + L.o_h, L.ldh});
+  gemm_f64_launch<true>(st, g, 1, ctx->prop.multiProcessorCount, EpiStorePlain{base + L.o_h, L.ldh});
   VB_HIP(ctx, hipGetLastError());
   return VB_OK;
 }
@@ -203,15 +161,10 @@ int multilevel_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_
   if (m.id != VB_MODEL_MULTILEVEL) return fail(ctx, VB_ERR_STATE, "no multilevel regression model bound");
   const MlLayout L = ml_layout(m, n > 0 ? n : 1, false);
   VB_TRY(ml_check(ctx, L, n, d));
-  // the GEMMs move 16-byte pairs of Z and G, and the gradient's epilogue addresses both with one stride
-  if (((uintptr_t)Z & 15) || (ldz & 1) || ldz < d)
-    return fail(ctx, VB_ERR_INVALID, "multilevel rows: the samples must be 16-byte aligned with an even row stride >= %d", d);
-  if (G && (((uintptr_t)G & 15) || ldg != ldz))
-    return fail(ctx, VB_ERR_INVALID, "multilevel rows: the gradient must be 16-byte aligned and share the samples' row stride "
-                                     "(%lld, not %lld)", (long long)ldz, (long long)ldg);
+  VB_TRY(rows_operands_check(ctx, "multilevel", Z, ldz, d, G, ldg));
   const int p = m.n_feat, J = m.n_groups;
-  VB_TRY(ensure(ctx, ctx->ml_work, (size_t)L.total * sizeof(double)));
-  double* base = (double*)ctx->ml_work.ptr;
+  VB_TRY(ensure(ctx, ctx->target_work, (size_t)L.total * sizeof(double)));
+  double* base = (double*)ctx->target_work.ptr;
   const double ivp = 1.0 / (m.tau * m.tau), ivt = 1.0 / (m.hyper_sd * m.hyper_sd);
   for (int64_t r0 = 0; r0 < n; r0 += L.chunk) {
     const int64_t rows = n - r0 < L.chunk ? n - r0 : L.chunk;
@@ -241,6 +194,82 @@ int multilevel_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_
   return VB_OK;
 }
 
+int multilevel_set_model(vb_ctx* ctx, int64_t dim, const double* dparams, size_t n_dparams, const int64_t* iparams,
+                         size_t n_iparams) {
+  const char* kExpect =
+      "multilevel regression expects dparams = [X(n_data x p) | y(n_data) | prior_sd | tau_sd | noise_sd], iparams = "
+      "[n_data, n_groups, link | offsets(n_groups + 1) | group of each observation(n_data)] and a dimension of "
+      "p + n_groups + 1";
+  if (n_iparams < 3 || !iparams || !dparams || iparams[0] <= 0 || iparams[1] < 1 || iparams[0] > 0x7fffffffll ||
+      iparams[1] > 0x7fffffffll || dim > 0x7fffffffll || dim - iparams[1] - 1 < 1 ||
+      iparams[2] < VB_GLM_BERNOULLI_LOGIT || iparams[2] > VB_GLM_GAUSSIAN ||
+      n_iparams != (size_t)(3 + iparams[1] + 1 + iparams[0]) ||
+      n_dparams != (size_t)(iparams[0] * (dim - iparams[1] - 1) + iparams[0]) + 3)
+    return fail(ctx, VB_ERR_INVALID, "%s", kExpect);
+  const int64_t nd = iparams[0], ng = iparams[1], p = dim - ng - 1;
+  const int link = (int)iparams[2];
+  const int64_t* off = iparams + 3;
+  const int64_t* grp = off + ng + 1;
+  const double* ys = dparams + nd * p;
+  const double sd = ys[nd], tsd = ys[nd + 1], nsd = ys[nd + 2];
+  if (!(sd > 0.0)) return fail(ctx, VB_ERR_INVALID, "multilevel prior_sd must be positive");
+  if (!(tsd > 0.0)) return fail(ctx, VB_ERR_INVALID, "multilevel tau_sd must be positive");
+  if (!(nsd > 0.0)) return fail(ctx, VB_ERR_INVALID, "multilevel noise_sd must be positive");
+  if (off[0] != 0 || off[ng] != nd)
+    return fail(ctx, VB_ERR_INVALID, "multilevel offsets must run from 0 to n_data (offsets[0] = %lld, offsets[%lld] = %lld)",
+                (long long)off[0], (long long)ng, (long long)off[ng]);
+  for (int64_t j = 0; j < ng; ++j)
+    if (off[j + 1] < off[j])
+      return fail(ctx, VB_ERR_INVALID, "multilevel offsets must be monotone (offsets[%lld] = %lld > offsets[%lld] = %lld)",
+                  (long long)j, (long long)off[j], (long long)(j + 1), (long long)off[j + 1]);
+  for (int64_t i = 0; i < nd; ++i)
+    if (grp[i] < 0 || grp[i] >= ng)
+      return fail(ctx, VB_ERR_INVALID, "multilevel group labels must lie in [0, n_groups) (groups[%lld] = %lld)", (long long)i,
+                  (long long)grp[i]);
+  for (int64_t j = 0; j < ng; ++j)
+    for (int64_t i = off[j]; i < off[j + 1]; ++i)
+      if (grp[i] != j)
+        return fail(ctx, VB_ERR_INVALID, "multilevel observations must be sorted by group: observation %lld lies in the run of "
+                                         "group %lld and carries the label %lld", (long long)i, (long long)j, (long long)grp[i]);
+  if (link == VB_GLM_POISSON)
+    for (int64_t i = 0; i < nd; ++i)
+      if (!(ys[i] >= 0.0)) return fail(ctx, VB_ERR_INVALID, "Poisson counts must be non-negative");
+  ModelDev m;
+  m.id = VB_MODEL_MULTILEVEL;
+  m.dim = (int)dim;
+  m.n_data = nd;
+  m.n_groups = (int)ng;
+  m.n_feat = (int)p;
+  m.ldp = round_up(p, 16);
+  m.ldq = round_up(nd, 16);
+  m.tau = sd;
+  m.hyper_sd = tsd;
+  m.link = link;
+  m.aux = link == VB_GLM_GAUSSIAN ? nsd : 1.0;
+  m.c0 = 0.0;      // (the rows carry priors and constants themselves: see ModelDev::f0)
+  // b ~ N(0, sd), u ~ N(0, 1), tau ~ HalfNormal(tsd); the likelihood's constant as the flat regression target has it
+  m.f0 = -(double)p * (log(sd) + 0.5 * kLog2Pi) - 0.5 * (double)ng * kLog2Pi + log(2.0) - log(tsd) - 0.5 * kLog2Pi;
+  m.f0 = glm_const_continue(m.f0, link, nsd, ys, nd);
+  // [X (nd x ldp) | X' (p x ldq) | y (ldq) | offsets (ng + 1 ints) | group of each observation (nd ints)]: the logistic
+  // target's layout with p in place of dim, then the two int arrays, each starting on a 16-byte boundary
+  const size_t o_xt = (size_t)nd * m.ldp, o_y = o_xt + (size_t)p * m.ldq, o_off = o_y + (size_t)m.ldq;
+  const size_t o_grp = o_off + (size_t)round_up((ng + 2) / 2, 2);
+  std::vector<double> dev(o_grp + (size_t)round_up((nd + 1) / 2, 2), 0.0);
+  pack_design(dev, 0, dparams, nd, p, m.ldp, m.ldq);
+  for (int64_t i = 0; i < nd; ++i) dev[o_y + i] = ys[i];
+  int* off32 = reinterpret_cast<int*>(dev.data() + o_off);
+  int* grp32 = reinterpret_cast<int*>(dev.data() + o_grp);
+  for (int64_t j = 0; j <= ng; ++j) off32[j] = (int)off[j];
+  for (int64_t i = 0; i < nd; ++i) grp32[i] = (int)grp[i];
+  VB_TRY(upload_model_params(ctx, dev, &m.p0));
+  m.p1 = m.p0 + o_xt;
+  m.p2 = m.p0 + o_y;
+  m.grp_off = reinterpret_cast<const int*>(m.p0 + o_off);
+  m.grp_of = reinterpret_cast<const int*>(m.p0 + o_grp);
+  ctx->model = m;
+  return VB_OK;
+}
+
 }  // namespace vb
 
 using namespace vb;
@@ -248,36 +277,24 @@ using namespace vb;
 extern "C" {
 
 int vb_multilevel_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out) {
-  if (!ctx || !x || !ll_out) return fail(ctx, VB_ERR_INVALID, "NULL argument");
-  if (ctx->model.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model)");
-  if (ctx->model.id != VB_MODEL_MULTILEVEL)
-    return fail(ctx, VB_ERR_UNSUPPORTED, "vb_multilevel_pointwise needs a multilevel regression target (model id %d bound)",
-                ctx->model.id);
-  if (d != ctx->model.dim)
-    return fail(ctx, VB_ERR_INVALID, "x has %lld columns, model dimension is %d", (long long)d, ctx->model.dim);
-  if (s <= 0) return fail(ctx, VB_ERR_INVALID, "the number of draws must be positive");
-  const ModelDev& m = ctx->model;
-  const MlLayout L = ml_layout(m, s, true);
-  VB_TRY(ml_check(ctx, L, s, (int)d));
-  VB_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int64_t nd = m.n_data, ldx = round_up(d, 16);
-  VB_TRY(ensure(ctx, ctx->ml_work, (size_t)L.total * sizeof(double)));
-  double* base = (double*)ctx->ml_work.ptr;
-  for (int64_t r0 = 0; r0 < s; r0 += L.chunk) {
-    const int64_t rows = s - r0 < L.chunk ? s - r0 : L.chunk;
-    VB_HIP(ctx, hipMemcpy2DAsync(base + L.o_x, (size_t)ldx * sizeof(double), x + r0 * d, (size_t)d * sizeof(double),
-                                 (size_t)d * sizeof(double), (size_t)rows, hipMemcpyHostToDevice, st));
-    VB_TRY(ml_predictors(ctx, st, L, base, base + L.o_x, ldx, rows));
-    hipLaunchKernelGGL(ml_link_kernel<2>, dim3((unsigned)(rows * L.n_strips)), dim3(256), 0, st, base + L.o_h, L.ldh,
-                       (const double*)(base + L.o_x), ldx, m.n_feat, m.n_groups, (int)nd, m.p2, m.grp_of, m.link, m.aux,
-                       L.n_strips, (double*)nullptr, base + L.o_ll, L.ldh);
-    VB_HIP(ctx, hipGetLastError());
-    VB_HIP(ctx, hipMemcpy2DAsync(ll_out + r0 * nd, (size_t)nd * sizeof(double), base + L.o_ll, (size_t)L.ldh * sizeof(double),
-                                 (size_t)nd * sizeof(double), (size_t)rows, hipMemcpyDeviceToHost, st));
-    VB_HIP(ctx, hipStreamSynchronize(st));
-  }
-  return VB_OK;
+  MlLayout L;
+  return rows_pointwise(
+      ctx, "vb_multilevel_pointwise", VB_MODEL_MULTILEVEL, "multilevel regression", x, s, d, ll_out,
+      [&](RowsPointwisePlan* plan) {
+        L = ml_layout(ctx->model, s, true);
+        *plan = {L.chunk, L.total, L.o_x, L.o_ll, L.ldh};
+        return ml_check(ctx, L, s, (int)d);
+      },
+      [&](int64_t rows, const double* X, int64_t ldx, double* LL, int64_t ldl) {
+        const ModelDev& m = ctx->model;
+        double* base = (double*)ctx->target_work.ptr;
+        VB_TRY(ml_predictors(ctx, ctx->stream, L, base, X, ldx, rows));
+        hipLaunchKernelGGL(ml_link_kernel<2>, dim3((unsigned)(rows * L.n_strips)), dim3(256), 0, ctx->stream, base + L.o_h,
+                           L.ldh, X, ldx, m.n_feat, m.n_groups, (int)m.n_data, m.p2, m.grp_of, m.link, m.aux, L.n_strips,
+                           (double*)nullptr, LL, ldl);
+        VB_HIP(ctx, hipGetLastError());
+        return VB_OK;
+      });
 }
 
 }  // extern "C"

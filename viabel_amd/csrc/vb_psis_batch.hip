@@ -33,7 +33,7 @@
 // whereas the transposed store would put every lane of a row on its own line, S doubles apart.  The transpose of the
 // draws is S x D doubles, negligible next to the n_data x S result.
 //
-// Posterior prediction (vb_glm_predict): the same product with a plain store (EpiStoreEta), against the bound design or an
+// Posterior prediction (vb_glm_predict): the same product with a plain store (EpiStorePlain), against the bound design or an
 // uploaded one (chunks of observations, padded like the bound X), followed by glm_predict_kernel: one 256-thread workgroup
 // per observation streams its S linear predictors twice -- weighted means and the log-sum-exp of the predictive density,
 // then the weighted squared deviations from those means -- and writes five doubles.  The weights are normalised once per
@@ -42,7 +42,7 @@
 //     Bernoulli-logit: 105 VGPRs -> 4 workgroups per CU
 //     Poisson:          82 VGPRs -> 5 workgroups per CU
 //     Gaussian:         74 VGPRs -> 6 workgroups per CU
-#include "vb_gemm_f64.h"
+#include "vb_rows_target.h"
 #include "vb_psis_util.h"
 
 #include <cfloat>
@@ -484,10 +484,7 @@ __global__ void __launch_bounds__(256) glm_const_kernel(const double* __restrict
                                                         double* __restrict__ cst) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  double c = 0.0;
-  if (link == VB_GLM_POISSON) c = -lgamma(y[i] + 1.0);
-  else if (link == VB_GLM_GAUSSIAN) c = -log(aux) - 0.91893853320467274178;
-  cst[i] = c;
+  cst[i] = glm_obs_const(link, aux, y[i]);
 }
 
 struct EpiPointwise {        // LL[observation][draw] = log p(y_obs | eta): row = observation, col = draw
@@ -613,18 +610,7 @@ static int glm_pointwise_enqueue(vb_ctx* ctx, hipStream_t st, const GlmLayout& L
 
 // ---- posterior prediction of the regression targets (vb_glm_predict) ------------------------------------------------
 // ETA[observation][draw] = x_obs' theta_draw: the product of glm_pointwise_enqueue with a plain store, against the bound
-// design or a chunk of an uploaded one
-struct EpiStoreEta {
-  double* E;
-  int64_t ld;
-  __device__ void operator()(int, int row, int col, double eta) const { E[(int64_t)row * ld + col] = eta; }
-  __device__ d2v pair(int, int row, int col, double e0, double e1) const {
-    const d2v v = (d2v){e0, e1};
-    *reinterpret_cast<d2v*>(E + (int64_t)row * ld + col) = v;
-    return v;
-  }
-};
-
+// design or a chunk of an uploaded one (EpiStorePlain)
 struct PredictArgs {
   const double* eta;          // rows observations of n draws, observation j at eta + j * ld
   int64_t ld;
@@ -915,7 +901,7 @@ int vb_glm_predict(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const dou
     }
     g.B = base + L.o_xt, g.ldb = L.lds;
     g.M = (int)rows, g.N = (int)s, g.K = (int)d, g.tri_mode = 0;
-    gemm_f64_launch<true>(st, g, 1, ctx->prop.multiProcessorCount, EpiStoreEta{base + L.o_eta, L.lds});
+    gemm_f64_launch<true>(st, g, 1, ctx->prop.multiProcessorCount, EpiStorePlain{base + L.o_eta, L.lds});
     VB_HIP(ctx, hipGetLastError());
     const PredictArgs a{base + L.o_eta, L.lds, (int)s, w_d, lw_d, y_d ? y_d + r0 : nullptr, md.aux,
                         res + r0, res + L.mp + r0, res + 2 * L.mp + r0, res + 3 * L.mp + r0, res + 4 * L.mp + r0};

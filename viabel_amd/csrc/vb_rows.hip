@@ -4,16 +4,9 @@
 // diagnostics-side callers (convenience.py:176-179) and by the DIS / alpha objectives for the
 // per-sample log weights (objectives.py:394-395, :445).  One wave per row, lanes stride the
 // columns (coalesced), DPP/shuffle reduction over the wave.
-#include "vb_common.h"
-#include "vb_gemm_f64.h"
+#include "vb_rows_target.h"
 
 namespace vb {
-
-__device__ __forceinline__ double wave_sum_rows(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-  return x;
-}
 
 // PRIOR: the same pass also evaluates a diagonal Gaussian (mean q0, inverse variances q1, constant qc) into out2 --
 // the tempering prior of DISInclusiveKL (objectives.py:316-318) next to the model, one read of the samples instead of two
@@ -79,8 +72,8 @@ __global__ void __launch_bounds__(256) model_logp_rows_kernel(const double* __re
   }
 #pragma unroll
   for (int r = 0; r < kRowsPerWave; ++r) {
-    const double a = wave_sum_rows(acc[r]);
-    const double a2 = PRIOR ? wave_sum_rows(acc2[r]) : 0.0;
+    const double a = wave_sum(acc[r]);
+    const double a2 = PRIOR ? wave_sum(acc2[r]) : 0.0;
     if (lane == 0 && row0 + r < n) {
       out[row0 + r] = a + m.c0;
       if (PRIOR) out2[row0 + r] = a2 + qc;
@@ -141,7 +134,7 @@ __global__ void __launch_bounds__(256) model_prior_maha_rows_kernel(const double
   }
 #pragma unroll
   for (int r = 0; r < kRowsPerWave; ++r) {
-    const double a = wave_sum_rows(acc[r]), a2 = wave_sum_rows(acc2[r]), t = wave_sum_rows(ss[r]);
+    const double a = wave_sum(acc[r]), a2 = wave_sum(acc2[r]), t = wave_sum(ss[r]);
     if (lane == 0 && row0 + r < n) {
       const int64_t row = row0 + r;
       out[row] = a + m.c0;
@@ -243,8 +236,8 @@ __global__ void __launch_bounds__(256) rows_dot_kernel(const double* __restrict_
   for (int c = lane; c < width; c += 64) acc += a[row * lda + c] * (b ? b[row * ldb + c] : 1.0);
   if (sq)
     for (int c = lane; c < sq_width; c += 64) s2 = fma(sq[row * ldsq + c], sq[row * ldsq + c], s2);
-  acc = wave_sum_rows(acc);
-  s2 = wave_sum_rows(s2);
+  acc = wave_sum(acc);
+  s2 = wave_sum(s2);
   if (lane == 0) out[row] = fma(scale, acc, fma(add_sq, s2, c0));
 }
 
@@ -333,6 +326,45 @@ int glm_grad_enqueue(vb_ctx* ctx, hipStream_t st, const ModelDev& m, const doubl
   return VB_OK;
 }
 
+// ---- rows targets: f and grad f come finished from the target's own pipeline -------------------------------------
+int model_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G, int64_t ldg,
+                       double* f) {
+  if (ctx->model.id == VB_MODEL_SOFTMAX) return softmax_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
+  if (ctx->model.id == VB_MODEL_MULTILEVEL) return multilevel_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
+  if (ctx->model.id == VB_MODEL_LOCSCALE) return locscale_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
+  if (ctx->model.id == VB_MODEL_SPARSE_GLM) return sparse_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
+  return user_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
+}
+
+int rows_pointwise(vb_ctx* ctx, const char* api_name, int model_id, const char* target_name, const double* x, int64_t s,
+                   int64_t d, double* ll_out, const std::function<int(RowsPointwisePlan*)>& plan,
+                   const RowsPointwiseBody& body) {
+  if (!ctx || !x || !ll_out) return fail(ctx, VB_ERR_INVALID, "NULL argument");
+  if (ctx->model.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model)");
+  if (ctx->model.id != model_id)
+    return fail(ctx, VB_ERR_UNSUPPORTED, "%s needs a %s target (model id %d bound)", api_name, target_name, ctx->model.id);
+  if (d != ctx->model.dim)
+    return fail(ctx, VB_ERR_INVALID, "x has %lld columns, model dimension is %d", (long long)d, ctx->model.dim);
+  if (s <= 0) return fail(ctx, VB_ERR_INVALID, "the number of draws must be positive");
+  RowsPointwisePlan P;
+  VB_TRY(plan(&P));
+  VB_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int64_t nd = ctx->model.n_data, ldx = round_up(d, 16);
+  VB_TRY(ensure(ctx, ctx->target_work, (size_t)P.total * sizeof(double)));
+  double* base = (double*)ctx->target_work.ptr;
+  for (int64_t r0 = 0; r0 < s; r0 += P.chunk) {
+    const int64_t rows = s - r0 < P.chunk ? s - r0 : P.chunk;
+    VB_HIP(ctx, hipMemcpy2DAsync(base + P.o_x, (size_t)ldx * sizeof(double), x + r0 * d, (size_t)d * sizeof(double),
+                                 (size_t)d * sizeof(double), (size_t)rows, hipMemcpyHostToDevice, st));
+    VB_TRY(body(rows, base + P.o_x, ldx, base + P.o_ll, P.ldl));
+    VB_HIP(ctx, hipMemcpy2DAsync(ll_out + r0 * nd, (size_t)nd * sizeof(double), base + P.o_ll, (size_t)P.ldl * sizeof(double),
+                                 (size_t)nd * sizeof(double), (size_t)rows, hipMemcpyDeviceToHost, st));
+    VB_HIP(ctx, hipStreamSynchronize(st));
+  }
+  return VB_OK;
+}
+
 // ---- per-sample gradients (vb_model_grad): f and grad f of given points ----------------------------------------
 // The reference gets them from autograd (models.py:17-39; tests/test_models.py:13-15 checks the vjp); here every
 // target has its own device gradient, and this is the entry that shows it to the caller -- a hand-written
@@ -356,7 +388,7 @@ __global__ void __launch_bounds__(256) model_grad_rows_kernel(const double* __re
       g[c] = -x[c] * w;
       ss = fma(x[c], x[c], ss);
     }
-  ss = wave_sum_rows(ss);
+  ss = wave_sum(ss);
   if (lane == 0) g[m.k] = fma(-v, 1.0 / (m.tau * m.tau), -(double)(d - 1)) + w * ss;
 }
 

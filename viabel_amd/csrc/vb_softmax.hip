@@ -14,25 +14,13 @@
 //   unpack    G[r][c p + j] = Gc[(r C + c)][j]
 // and f[r] = sum of the row's strip partials (fixed order) - |z_r|^2 / (2 sd^2) + f0.  No atomics anywhere: two calls
 // give the same bits.
-#include "vb_common.h"
-#include "vb_gemm_f64.h"
+#include "vb_rows_target.h"
 
 namespace vb {
 
 namespace {
 
 constexpr int kSmStrip = 1024;      // observations per workgroup of the coupling kernel: 256 lanes x 4
-
-struct EpiStoreH {           // H = acc
-  double* Y;
-  int64_t ldy;
-  __device__ void operator()(int, int row, int col, double acc) const { Y[(int64_t)row * ldy + col] = acc; }
-  __device__ d2v pair(int, int row, int col, double a0, double a1) const {
-    const d2v v = (d2v){a0, a1};
-    *reinterpret_cast<d2v*>(Y + (int64_t)row * ldy + col) = v;
-    return v;
-  }
-};
 
 __global__ void __launch_bounds__(256) sm_pack_kernel(const double* __restrict__ Z, int64_t ldz, int64_t rows, int C, int p,
                                                       double* __restrict__ Zc, int64_t ldc) {
@@ -89,12 +77,7 @@ __global__ void __launch_bounds__(256) sm_couple_kernel(double* __restrict__ H, 
     }
   }
   if (MODE == 2) return;
-  __shared__ double wsum[4];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+  strip_partials_store<1>(acc, 0.0, part);
 }
 
 // f[r] = sum_s part[r][s] - |z_r|^2 / (2 sd^2) + f0: one wave per row, a lane adds its strips / columns in order
@@ -107,11 +90,8 @@ __global__ void __launch_bounds__(256) sm_rowsum_kernel(const double* __restrict
   double ll = 0.0, s2 = 0.0;
   for (int s = lane; s < n_strips; s += 64) ll += part[r * n_strips + s];
   for (int c = lane; c < d; c += 64) s2 = fma(Z[r * ldz + c], Z[r * ldz + c], s2);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    ll += __shfl_down(ll, off, 64);
-    s2 += __shfl_down(s2, off, 64);
-  }
+  ll = wave_sum(ll);
+  s2 = wave_sum(s2);
   if (lane == 0) f[r] = fma(neg_half_ivp, s2, ll) + f0;
 }
 
@@ -127,22 +107,15 @@ SmLayout sm_layout(const ModelDev& m, int64_t n, bool grad, bool pointwise) {
   L.ldc = round_up(m.n_feat, 16);
   L.ldh = m.ldq;
   L.n_strips = (int)((m.n_data + kSmStrip - 1) / kSmStrip);
-  int64_t chunk = kSoftmaxChunkDoubles / (C * L.ldh);
-  chunk = chunk < 8 ? 8 : chunk;
-  L.chunk = chunk > n ? n : chunk;
-  int64_t off = 0;
-  auto carve = [&off](int64_t doubles) {      // (multiples of 32 doubles: every piece starts 256-B aligned)
-    const int64_t o = off;
-    off += round_up(doubles, 32);
-    return o;
-  };
+  L.chunk = rows_chunk(kSoftmaxChunkDoubles, C * L.ldh, n);
+  Carver carve;
   L.o_zc = carve(L.chunk * C * L.ldc);
   L.o_h = carve(L.chunk * C * L.ldh);
   L.o_gc = carve(grad ? L.chunk * C * L.ldc : 0);
   L.o_part = carve(L.chunk * L.n_strips);
   L.o_x = carve(pointwise ? L.chunk * round_up(m.dim, 16) : 0);
   L.o_ll = carve(pointwise ? L.chunk * L.ldh : 0);
-  L.total = off;
+  L.total = carve.off;
   return L;
 }
 
@@ -167,7 +140,7 @@ int sm_predictors(vb_ctx* ctx, hipStream_t st, const SmLayout& L, double* base, 
                      L.ldc);
   VB_HIP(ctx, hipGetLastError());
   const GemmArgs g = gemm_product(base + L.o_zc, L.ldc, m.p1, m.ldq, (int)(rows * C), (int)m.n_data, p, 0);
-  gemm_f64_launch<true>(st, g, 1, ctx->prop.multiProcessorCount, EpiStoreH{base + L.o_h, L.ldh});
+  gemm_f64_launch<true>(st, g, 1, ctx->prop.multiProcessorCount, EpiStorePlain{base + L.o_h, L.ldh});
   VB_HIP(ctx, hipGetLastError());
   return VB_OK;
 }
@@ -180,8 +153,8 @@ int softmax_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t l
   const ModelDev& m = ctx->model;
   const int C = m.n_classes, p = m.n_feat;
   const SmLayout L = sm_layout(m, n, G != nullptr, false);
-  VB_TRY(ensure(ctx, ctx->sm_work, (size_t)L.total * sizeof(double)));
-  double* base = (double*)ctx->sm_work.ptr;
+  VB_TRY(ensure(ctx, ctx->target_work, (size_t)L.total * sizeof(double)));
+  double* base = (double*)ctx->target_work.ptr;
   const double ivp = 1.0 / (m.tau * m.tau);
   for (int64_t r0 = 0; r0 < n; r0 += L.chunk) {
     const int64_t rows = n - r0 < L.chunk ? n - r0 : L.chunk;
@@ -207,13 +180,42 @@ int softmax_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t l
   return VB_OK;
 }
 
-int model_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G, int64_t ldg,
-                       double* f) {
-  if (ctx->model.id == VB_MODEL_SOFTMAX) return softmax_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
-  if (ctx->model.id == VB_MODEL_MULTILEVEL) return multilevel_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
-  if (ctx->model.id == VB_MODEL_LOCSCALE) return locscale_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
-  if (ctx->model.id == VB_MODEL_SPARSE_GLM) return sparse_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
-  return user_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
+int softmax_set_model(vb_ctx* ctx, int64_t dim, const double* dparams, size_t n_dparams, const int64_t* iparams,
+                      size_t n_iparams) {
+  if (n_iparams != 2 || !iparams || !dparams || iparams[0] <= 0 || iparams[1] < 2 || dim % iparams[1] != 0 ||
+      iparams[0] > 0x7fffffffll || dim > 0x7fffffffll ||
+      n_dparams != (size_t)(iparams[0] * (dim / iparams[1]) + iparams[0]) + 1)
+    return fail(ctx, VB_ERR_INVALID,
+                "softmax regression expects dparams = [X(n_data x p) | y(n_data) | prior_sd], iparams = [n_data, n_classes] "
+                "and a dimension of n_classes * p");
+  const int64_t nd = iparams[0], nc = iparams[1], p = dim / nc;
+  const double* ys = dparams + nd * p;
+  const double sd = ys[nd];
+  if (!(sd > 0.0)) return fail(ctx, VB_ERR_INVALID, "softmax prior_sd must be positive");
+  for (int64_t i = 0; i < nd; ++i)
+    if (!(ys[i] >= 0.0 && ys[i] < (double)nc) || ys[i] != floor(ys[i]))
+      return fail(ctx, VB_ERR_INVALID, "softmax labels must be integers in [0, n_classes) (y[%lld] = %g)", (long long)i, ys[i]);
+  ModelDev m;
+  m.id = VB_MODEL_SOFTMAX;
+  m.dim = (int)dim;
+  m.n_data = nd;
+  m.n_classes = (int)nc;
+  m.n_feat = (int)p;
+  m.ldp = round_up(p, 16);
+  m.ldq = round_up(nd, 16);
+  m.tau = sd;
+  m.c0 = 0.0;      // (the rows carry prior and constant themselves, like a source model's: see ModelDev::f0)
+  m.f0 = -(double)dim * (log(sd) + 0.5 * kLog2Pi);
+  // [X (nd x ldp) | X' (p x ldq) | y (ldq)]: the logistic target's layout with p in place of dim
+  const size_t o_xt = (size_t)nd * m.ldp, o_y = o_xt + (size_t)p * m.ldq;
+  std::vector<double> dev(o_y + (size_t)m.ldq, 0.0);
+  pack_design(dev, 0, dparams, nd, p, m.ldp, m.ldq);
+  for (int64_t i = 0; i < nd; ++i) dev[o_y + i] = ys[i];
+  VB_TRY(upload_model_params(ctx, dev, &m.p0));
+  m.p1 = m.p0 + o_xt;
+  m.p2 = m.p0 + o_y;
+  ctx->model = m;
+  return VB_OK;
 }
 
 }  // namespace vb
@@ -223,35 +225,24 @@ using namespace vb;
 extern "C" {
 
 int vb_softmax_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out) {
-  if (!ctx || !x || !ll_out) return fail(ctx, VB_ERR_INVALID, "NULL argument");
-  if (ctx->model.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model)");
-  if (ctx->model.id != VB_MODEL_SOFTMAX)
-    return fail(ctx, VB_ERR_UNSUPPORTED, "vb_softmax_pointwise needs a softmax regression target (model id %d bound)",
-                ctx->model.id);
-  if (d != ctx->model.dim)
-    return fail(ctx, VB_ERR_INVALID, "x has %lld columns, model dimension is %d", (long long)d, ctx->model.dim);
-  if (s <= 0) return fail(ctx, VB_ERR_INVALID, "the number of draws must be positive");
-  VB_TRY(sm_check(ctx, s, (int)d));
-  VB_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const ModelDev& m = ctx->model;
-  const int64_t nd = m.n_data, ldx = round_up(d, 16);
-  const SmLayout L = sm_layout(m, s, false, true);
-  VB_TRY(ensure(ctx, ctx->sm_work, (size_t)L.total * sizeof(double)));
-  double* base = (double*)ctx->sm_work.ptr;
-  for (int64_t r0 = 0; r0 < s; r0 += L.chunk) {
-    const int64_t rows = s - r0 < L.chunk ? s - r0 : L.chunk;
-    VB_HIP(ctx, hipMemcpy2DAsync(base + L.o_x, (size_t)ldx * sizeof(double), x + r0 * d, (size_t)d * sizeof(double),
-                                 (size_t)d * sizeof(double), (size_t)rows, hipMemcpyHostToDevice, st));
-    VB_TRY(sm_predictors(ctx, st, L, base, base + L.o_x, ldx, rows));
-    hipLaunchKernelGGL(sm_couple_kernel<2>, dim3((unsigned)(rows * L.n_strips)), dim3(256), 0, st, base + L.o_h, L.ldh,
-                       m.n_classes, (int)nd, m.p2, L.n_strips, (double*)nullptr, base + L.o_ll, L.ldh);
-    VB_HIP(ctx, hipGetLastError());
-    VB_HIP(ctx, hipMemcpy2DAsync(ll_out + r0 * nd, (size_t)nd * sizeof(double), base + L.o_ll, (size_t)L.ldh * sizeof(double),
-                                 (size_t)nd * sizeof(double), (size_t)rows, hipMemcpyDeviceToHost, st));
-    VB_HIP(ctx, hipStreamSynchronize(st));
-  }
-  return VB_OK;
+  SmLayout L;
+  return rows_pointwise(
+      ctx, "vb_softmax_pointwise", VB_MODEL_SOFTMAX, "softmax regression", x, s, d, ll_out,
+      [&](RowsPointwisePlan* plan) {
+        VB_TRY(sm_check(ctx, s, (int)d));
+        L = sm_layout(ctx->model, s, false, true);
+        *plan = {L.chunk, L.total, L.o_x, L.o_ll, L.ldh};
+        return VB_OK;
+      },
+      [&](int64_t rows, const double* X, int64_t ldx, double* LL, int64_t ldl) {
+        const ModelDev& m = ctx->model;
+        double* base = (double*)ctx->target_work.ptr;
+        VB_TRY(sm_predictors(ctx, ctx->stream, L, base, X, ldx, rows));
+        hipLaunchKernelGGL(sm_couple_kernel<2>, dim3((unsigned)(rows * L.n_strips)), dim3(256), 0, ctx->stream, base + L.o_h,
+                           L.ldh, m.n_classes, (int)m.n_data, m.p2, L.n_strips, (double*)nullptr, LL, ldl);
+        VB_HIP(ctx, hipGetLastError());
+        return VB_OK;
+      });
 }
 
 }  // extern "C"

@@ -18,14 +18,13 @@
 // wave: vb_set_model cuts them into segments of kSparseSegment entries, a second launch of the gather kernel gives every
 // segment a wave of its own and writes a partial row per segment, and a combine kernel adds each list's partials in segment
 // order.  Every sum has a fixed order and there are no atomics anywhere: two calls give the same bits.
-#include "vb_common.h"
+#include "vb_rows_target.h"
 
 namespace vb {
 
 namespace {
 
 constexpr int kSpStrip = 256;            // observations per workgroup of the link kernel: 16 waves x 16 in turn
-constexpr double kHalfLog2Pi = 0.91893853320467274178;
 
 // Zt[j][c0 + r] = Z[r][j] for a 64 x 64 tile (j0 = 64 blockIdx.x, samples 64 blockIdx.y ..), zero where r >= rows; with
 // SQ the tile's sum_j Z[r][j]^2 goes to sq[blockIdx.x][sample]: a thread adds its 16 columns in order, the four waves are
@@ -164,14 +163,8 @@ __global__ void __launch_bounds__(1024) sp_link_kernel(double* __restrict__ Ht, 
     const double yi = y[i];
     double dl;
     const double t = glm_term(link, aux, yi, Ht[i * ldt + c], &dl);
-    if (MODE == 2) {      // what glm_term leaves out of log p(y_i | eta_i)
-      double k = 0.0;
-      if (link == VB_GLM_POISSON) k = -lgamma(yi + 1.0);
-      else if (link == VB_GLM_GAUSSIAN) k = -log(aux) - kHalfLog2Pi;
-      Ht[i * ldt + c] = t + k;
-    } else {
-      ll += t;
-    }
+    if (MODE == 2) Ht[i * ldt + c] = t + glm_obs_const(link, aux, yi);
+    else ll += t;
     if (MODE == 1) Ht[i * ldt + c] = dl;
   }
   if (MODE == 2) return;
@@ -201,7 +194,7 @@ __global__ void __launch_bounds__(1024) sp_rowsum_kernel(const double* __restric
 }
 
 struct SpLayout {
-  int64_t chunk, ldt, ldx, o_zt, o_ht, o_gt, o_part, o_sq, o_seg, o_x, o_ll, total;
+  int64_t chunk, ldt, o_zt, o_ht, o_gt, o_part, o_sq, o_seg, o_x, o_ll, total;
   int n_strips, n_cblocks;
 };
 
@@ -212,25 +205,19 @@ SpLayout sp_layout(const ModelDev& m, int64_t n, bool grad, bool pointwise) {
   const int64_t chunk = sparse_chunk_rows(nd, p);
   L.chunk = chunk > n ? n : chunk;
   L.ldt = round_up(L.chunk, 64);
-  L.ldx = round_up(p, 16);
   L.n_strips = (int)((nd + kSpStrip - 1) / kSpStrip);
   L.n_cblocks = (int)((p + 63) / 64);
   const int64_t slots = m.sp_n_seg[0] > m.sp_n_seg[1] ? m.sp_n_seg[0] : m.sp_n_seg[1];
-  int64_t off = 0;
-  auto carve = [&off](int64_t doubles) {      // (multiples of 32 doubles: every piece starts 256-B aligned)
-    const int64_t o = off;
-    off += round_up(doubles, 32);
-    return o;
-  };
+  Carver carve;
   L.o_zt = carve(p * L.ldt);
   L.o_ht = carve(nd * L.ldt);
   L.o_gt = carve(grad ? p * L.ldt : 0);
   L.o_part = carve(pointwise ? 0 : L.n_strips * L.ldt);
   L.o_sq = carve(pointwise ? 0 : L.n_cblocks * L.ldt);
   L.o_seg = carve(slots * L.ldt);            // the segment partials of the long lists: at most 2 nnz / kSparseSegment rows
-  L.o_x = carve(pointwise ? L.chunk * L.ldx : 0);
+  L.o_x = carve(pointwise ? L.chunk * round_up(p, 16) : 0);
   L.o_ll = carve(pointwise ? L.chunk * nd : 0);
-  L.total = off;
+  L.total = carve.off;
   return L;
 }
 
@@ -275,8 +262,8 @@ int sparse_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ld
   if (ldz < d || (G && ldg < d))
     return fail(ctx, VB_ERR_INVALID, "sparse regression rows: the row strides (%lld, %lld) must be >= %d", (long long)ldz,
                 (long long)ldg, d);
-  VB_TRY(ensure(ctx, ctx->sp_work, (size_t)L.total * sizeof(double)));
-  double* base = (double*)ctx->sp_work.ptr;
+  VB_TRY(ensure(ctx, ctx->target_work, (size_t)L.total * sizeof(double)));
+  double* base = (double*)ctx->target_work.ptr;
   const int p = m.dim;
   const int64_t nd = m.n_data;
   const double ivp = 1.0 / (m.tau * m.tau);
@@ -311,50 +298,165 @@ int sparse_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ld
   return VB_OK;
 }
 
+
+
+int sparse_set_model(vb_ctx* ctx, int64_t dim, const double* dparams, size_t n_dparams, const int64_t* iparams,
+                     size_t n_iparams) {
+  const char* kExpect =
+      "sparse regression expects dparams = [csr values (nnz) | csc values (nnz) | y(n_data) | prior_sd | noise_sd], iparams = "
+      "[n_data, p, link, nnz | csr indptr (n_data + 1) | csr indices (nnz) | csc indptr (p + 1) | csc indices (nnz)] and a "
+      "dimension of p, with n_data, p and nnz below 2^31";
+  if (n_iparams < 4 || !iparams || !dparams || iparams[0] <= 0 || iparams[1] <= 0 || iparams[3] < 0 ||
+      iparams[0] > 0x7fffffffll || iparams[1] > 0x7fffffffll || iparams[3] > 0x7fffffffll || dim != iparams[1] ||
+      iparams[2] < VB_GLM_BERNOULLI_LOGIT || iparams[2] > VB_GLM_GAUSSIAN ||
+      n_iparams != (size_t)(4 + iparams[0] + 1 + iparams[1] + 1 + 2 * iparams[3]) ||
+      n_dparams != (size_t)(2 * iparams[3] + iparams[0] + 2))
+    return fail(ctx, VB_ERR_INVALID, "%s", kExpect);
+  const int64_t nd = iparams[0], p = iparams[1], nnz = iparams[3];
+  const int link = (int)iparams[2];
+  const int64_t* ptr[2] = {iparams + 4, iparams + 4 + nd + 1 + nnz};
+  const int64_t* idx[2] = {ptr[0] + nd + 1, ptr[1] + p + 1};
+  const double* val[2] = {dparams, dparams + nnz};
+  const double* ys = dparams + 2 * nnz;
+  const double sd = ys[nd], nsd = ys[nd + 1];
+  if (!(sd > 0.0)) return fail(ctx, VB_ERR_INVALID, "sparse regression prior_sd must be positive");
+  if (!(nsd > 0.0)) return fail(ctx, VB_ERR_INVALID, "sparse regression noise_sd must be positive");
+  const int64_t n_lists[2] = {nd, p}, n_other[2] = {p, nd};
+  const char* form[2] = {"csr", "csc"};
+  for (int w = 0; w < 2; ++w) {
+    const int64_t nl = n_lists[w];
+    if (ptr[w][0] != 0 || ptr[w][nl] != nnz)
+      return fail(ctx, VB_ERR_INVALID, "sparse regression: the %s indptr must run from 0 to nnz = %lld (indptr[0] = %lld, "
+                                       "indptr[%lld] = %lld)", form[w], (long long)nnz, (long long)ptr[w][0], (long long)nl,
+                  (long long)ptr[w][nl]);
+    for (int64_t t = 0; t < nl; ++t)
+      if (ptr[w][t + 1] < ptr[w][t] || ptr[w][t + 1] > nnz)
+        return fail(ctx, VB_ERR_INVALID, "sparse regression: the %s indptr must be monotone within [0, nnz] (indptr[%lld] = "
+                                         "%lld, indptr[%lld] = %lld)", form[w], (long long)t, (long long)ptr[w][t],
+                    (long long)(t + 1), (long long)ptr[w][t + 1]);
+    for (int64_t t = 0; t < nl; ++t)
+      for (int64_t k = ptr[w][t]; k < ptr[w][t + 1]; ++k) {
+        if (idx[w][k] < 0 || idx[w][k] >= n_other[w])
+          return fail(ctx, VB_ERR_INVALID, "sparse regression: %s indices must lie in [0, %lld) (indices[%lld] = %lld)", form[w],
+                      (long long)n_other[w], (long long)k, (long long)idx[w][k]);
+        if (k > ptr[w][t] && idx[w][k] <= idx[w][k - 1])
+          return fail(ctx, VB_ERR_INVALID, "sparse regression: %s indices must increase strictly within list %lld "
+                                           "(indices[%lld] = %lld after %lld)", form[w], (long long)t, (long long)k,
+                      (long long)idx[w][k], (long long)idx[w][k - 1]);
+        if (!std::isfinite(val[w][k]))
+          return fail(ctx, VB_ERR_INVALID, "sparse regression: %s values must be finite (values[%lld])", form[w], (long long)k);
+      }
+  }
+  {   // the CSC form must be the transpose: walking the CSR in row order meets every column's entries in stored order
+    std::vector<int64_t> cur(ptr[1], ptr[1] + p);
+    for (int64_t i = 0; i < nd; ++i)
+      for (int64_t k = ptr[0][i]; k < ptr[0][i + 1]; ++k) {
+        const int64_t j = idx[0][k], c = cur[j]++;
+        if (c >= ptr[1][j + 1] || idx[1][c] != i || val[1][c] != val[0][k])
+          return fail(ctx, VB_ERR_INVALID, "sparse regression: the csc form is not the transpose of the csr form (csr entry "
+                                           "%lld: row %lld, column %lld)", (long long)k, (long long)i, (long long)j);
+      }
+  }
+  for (int64_t i = 0; i < nd; ++i) {
+    const double yi = ys[i];
+    if (!std::isfinite(yi)) return fail(ctx, VB_ERR_INVALID, "sparse regression: y must be finite (y[%lld])", (long long)i);
+    if (link == VB_GLM_BERNOULLI_LOGIT && yi != 0.0 && yi != 1.0)
+      return fail(ctx, VB_ERR_INVALID, "sparse regression: logistic responses must lie in {0, 1} (y[%lld] = %g)", (long long)i, yi);
+    if (link == VB_GLM_POISSON && !(yi >= 0.0))
+      return fail(ctx, VB_ERR_INVALID, "sparse regression: Poisson counts must be non-negative (y[%lld] = %g)", (long long)i, yi);
+  }
+  ModelDev m;
+  m.id = VB_MODEL_SPARSE_GLM;
+  m.dim = (int)dim;
+  m.n_data = nd;
+  m.nnz = nnz;
+  m.tau = sd;
+  m.link = link;
+  m.aux = link == VB_GLM_GAUSSIAN ? nsd : 1.0;
+  m.c0 = 0.0;      // (the rows carry prior and constants themselves: see ModelDev::f0)
+  m.f0 = glm_const_continue(-(double)p * (log(sd) + 0.5 * kLog2Pi), link, nsd, ys, nd);
+  // lists longer than a segment: (list, begin, end) per segment, (list, first segment, segments) per cut list
+  std::vector<int> seg[2], split[2];
+  for (int w = 0; w < 2; ++w)
+    for (int64_t t = 0; t < n_lists[w]; ++t) {
+      const int64_t b = ptr[w][t], e = ptr[w][t + 1];
+      if (e - b <= kSparseSegment) continue;
+      const int first = (int)(seg[w].size() / 3), n_seg = (int)((e - b + kSparseSegment - 1) / kSparseSegment);
+      for (int s = 0; s < n_seg; ++s) {
+        const int64_t sb = b + (int64_t)s * kSparseSegment;
+        seg[w].insert(seg[w].end(), {(int)t, (int)sb, (int)(sb + kSparseSegment < e ? sb + kSparseSegment : e)});
+      }
+      split[w].insert(split[w].end(), {(int)t, first, n_seg});
+    }
+  m.sp_n_seg[0] = (int)(seg[0].size() / 3), m.sp_n_seg[1] = (int)(seg[1].size() / 3);
+  m.sp_n_split[0] = (int)(split[0].size() / 3), m.sp_n_split[1] = (int)(split[1].size() / 3);
+  // [csr values | csc values | y] as doubles, then the int arrays, each starting on a 16-byte boundary: csr indptr, csr
+  // indices, csc indptr, csc indices, csr segments, csr cut lists, csc segments, csc cut lists
+  const size_t lens[8] = {(size_t)nd + 1, (size_t)nnz, (size_t)p + 1, (size_t)nnz,
+                          seg[0].size(), split[0].size(), seg[1].size(), split[1].size()};
+  size_t at[8], end = (size_t)round_up(2 * nnz + nd, 2);      // where each int array starts inside the image (in doubles)
+  for (int a = 0; a < 8; ++a) {
+    at[a] = end;
+    end += (size_t)round_up((int64_t)(lens[a] + 1) / 2, 2);
+  }
+  std::vector<double> dev(end, 0.0);
+  for (int64_t k = 0; k < 2 * nnz + nd; ++k) dev[k] = dparams[k];
+  for (int w = 0; w < 2; ++w) {
+    int* ptr32 = reinterpret_cast<int*>(dev.data() + at[2 * w]);
+    int* idx32 = reinterpret_cast<int*>(dev.data() + at[2 * w + 1]);
+    for (int64_t t = 0; t <= n_lists[w]; ++t) ptr32[t] = (int)ptr[w][t];
+    for (int64_t k = 0; k < nnz; ++k) idx32[k] = (int)idx[w][k];
+    if (!seg[w].empty()) memcpy(dev.data() + at[4 + 2 * w], seg[w].data(), seg[w].size() * sizeof(int));
+    if (!split[w].empty()) memcpy(dev.data() + at[5 + 2 * w], split[w].data(), split[w].size() * sizeof(int));
+  }
+  VB_TRY(upload_model_params(ctx, dev, &m.p0));
+  m.p2 = m.p0 + 2 * nnz;
+  for (int w = 0; w < 2; ++w) {
+    m.sp_val[w] = m.p0 + (size_t)w * nnz;
+    m.sp_ptr[w] = reinterpret_cast<const int*>(m.p0 + at[2 * w]);
+    m.sp_idx[w] = reinterpret_cast<const int*>(m.p0 + at[2 * w + 1]);
+    m.sp_seg[w] = reinterpret_cast<const int*>(m.p0 + at[4 + 2 * w]);
+    m.sp_split[w] = reinterpret_cast<const int*>(m.p0 + at[5 + 2 * w]);
+  }
+  ctx->model = m;
+  return VB_OK;
+}
+
 }  // namespace vb
 
 using namespace vb;
 
 extern "C" {
 
+// (the term matrix is dense [rows x n_data]: ldl = n_data, and the download's 2-D copy with equal pitches is one transfer)
 int vb_sparse_glm_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out) {
-  if (!ctx || !x || !ll_out) return fail(ctx, VB_ERR_INVALID, "NULL argument");
-  if (ctx->model.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model)");
-  if (ctx->model.id != VB_MODEL_SPARSE_GLM)
-    return fail(ctx, VB_ERR_UNSUPPORTED, "vb_sparse_glm_pointwise needs a sparse regression target (model id %d bound)",
-                ctx->model.id);
-  if (d != ctx->model.dim)
-    return fail(ctx, VB_ERR_INVALID, "x has %lld columns, model dimension is %d", (long long)d, ctx->model.dim);
-  if (s <= 0) return fail(ctx, VB_ERR_INVALID, "the number of draws must be positive");
-  const ModelDev& m = ctx->model;
-  const SpLayout L = sp_layout(m, s, false, true);
-  VB_TRY(sp_check(ctx, L, s, d));
-  VB_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const int64_t nd = m.n_data;
-  VB_TRY(ensure(ctx, ctx->sp_work, (size_t)L.total * sizeof(double)));
-  double* base = (double*)ctx->sp_work.ptr;
-  for (int64_t r0 = 0; r0 < s; r0 += L.chunk) {
-    const int64_t rows = s - r0 < L.chunk ? s - r0 : L.chunk;
-    const unsigned gy = (unsigned)((rows + 63) / 64);
-    VB_HIP(ctx, hipMemcpy2DAsync(base + L.o_x, (size_t)L.ldx * sizeof(double), x + r0 * d, (size_t)d * sizeof(double),
-                                 (size_t)d * sizeof(double), (size_t)rows, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(sp_transpose_in_kernel<false>, dim3((unsigned)L.n_cblocks, gy), dim3(256), 0, st,
-                       (const double*)(base + L.o_x), L.ldx, rows, (int)d, base + L.o_zt, L.ldt, (double*)nullptr);
-    VB_HIP(ctx, hipGetLastError());
-    VB_TRY(sp_product(ctx, st, L, base, gy, 0, nd, base + L.o_zt, base + L.o_ht));
-    hipLaunchKernelGGL(sp_link_kernel<2>, dim3((unsigned)L.n_strips, gy), dim3(1024), 0, st, base + L.o_ht,
-                       L.ldt, (int)nd, m.p2, m.link, m.aux, (double*)nullptr);
-    VB_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(sp_transpose_out_kernel, dim3((unsigned)((nd + 63) / 64), gy), dim3(256), 0, st,
-                       (const double*)(base + L.o_ht), L.ldt, rows, (int)nd, (const double*)nullptr, (int64_t)0, 0.0,
-                       base + L.o_ll, nd);
-    VB_HIP(ctx, hipGetLastError());
-    VB_HIP(ctx, hipMemcpyAsync(ll_out + r0 * nd, base + L.o_ll, (size_t)(rows * nd) * sizeof(double), hipMemcpyDeviceToHost,
-                               st));
-    VB_HIP(ctx, hipStreamSynchronize(st));
-  }
-  return VB_OK;
+  SpLayout L;
+  return rows_pointwise(
+      ctx, "vb_sparse_glm_pointwise", VB_MODEL_SPARSE_GLM, "sparse regression", x, s, d, ll_out,
+      [&](RowsPointwisePlan* plan) {
+        L = sp_layout(ctx->model, s, false, true);
+        *plan = {L.chunk, L.total, L.o_x, L.o_ll, ctx->model.n_data};
+        return sp_check(ctx, L, s, d);
+      },
+      [&](int64_t rows, const double* X, int64_t ldx, double* LL, int64_t ldl) {
+        const ModelDev& m = ctx->model;
+        hipStream_t st = ctx->stream;
+        double* base = (double*)ctx->target_work.ptr;
+        const int64_t nd = m.n_data;
+        const unsigned gy = (unsigned)((rows + 63) / 64);
+        hipLaunchKernelGGL(sp_transpose_in_kernel<false>, dim3((unsigned)L.n_cblocks, gy), dim3(256), 0, st, X, ldx, rows,
+                           m.dim, base + L.o_zt, L.ldt, (double*)nullptr);
+        VB_HIP(ctx, hipGetLastError());
+        VB_TRY(sp_product(ctx, st, L, base, gy, 0, nd, base + L.o_zt, base + L.o_ht));
+        hipLaunchKernelGGL(sp_link_kernel<2>, dim3((unsigned)L.n_strips, gy), dim3(1024), 0, st, base + L.o_ht, L.ldt, (int)nd,
+                           m.p2, m.link, m.aux, (double*)nullptr);
+        VB_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(sp_transpose_out_kernel, dim3((unsigned)((nd + 63) / 64), gy), dim3(256), 0, st,
+                           (const double*)(base + L.o_ht), L.ldt, rows, (int)nd, (const double*)nullptr, (int64_t)0, 0.0, LL,
+                           ldl);
+        VB_HIP(ctx, hipGetLastError());
+        return VB_OK;
+      });
 }
 
 }  // extern "C"

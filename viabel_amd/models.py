@@ -85,6 +85,18 @@ class DeviceModel(Model):
             raise ValueError('model_param must have shape (N, {0}) or ({0},)'.format(self._dim))
         return np.ascontiguousarray(x), one
 
+    _pointwise_entry = None      # the Engine method behind pointwise_log_likelihood (the classes that have one)
+
+    def _pointwise(self, x):
+        x, _ = self._rows(x)
+        eng = _lib.default_engine()
+        eng.set_model(self.device_spec())
+        return self._pointwise_order(getattr(eng, self._pointwise_entry)(x, self.n_data))
+
+    def _pointwise_order(self, out):
+        """Hook: the engine's ``(S, n_data)`` terms in the order in which the caller gave the observations."""
+        return out
+
     def grad(self, x):
         """Gradient of the log density at each row of ``x`` -- what ``autograd.elementwise_grad(model)`` gives in the
         reference (``objectives.py:191``; ``tests/test_models.py:13-15`` checks it) -- from the device code the
@@ -335,6 +347,8 @@ class LogisticRegressionModel(DeviceModel):
     evaluates it with two fp64 MFMA GEMMs per objective call.
     """
 
+    _pointwise_entry = 'glm_pointwise'
+
     def __init__(self, X, y, prior_sd=10.0):
         X = np.ascontiguousarray(X, dtype=np.float64)
         y = np.asarray(y, dtype=np.float64).ravel()
@@ -358,10 +372,7 @@ class LogisticRegressionModel(DeviceModel):
         argument of :func:`psisloo`.  Normalised densities (the Poisson ``- log y_i!``, the Gaussian
         ``- log noise_sd - log(2 pi) / 2`` included), without the prior; one fp64 MFMA product with the likelihood in
         its epilogue (``vb_glm_pointwise``).  ``x``: (S, D), or (D,) for one draw."""
-        x, _ = self._rows(x)
-        eng = _lib.default_engine()
-        eng.set_model(self.device_spec())
-        return eng.glm_pointwise(x, self.n_data)
+        return self._pointwise(x)
 
     def predict_from_draws(self, x, X_new=None, y_new=None, log_weights=None):
         """Posterior prediction from the draws ``x`` (S, D) -- or (D,) for one -- and their log weights ``log_weights``
@@ -455,6 +466,8 @@ class SoftmaxRegressionModel(DeviceModel):
     estimator forms, the RGE control variates, ``NVPFlow``), ``AlphaDivergence`` and ``DISInclusiveKL`` with every
     family, ``bbvi``, ``vi_diagnostics`` and the device-resident fit.  Not in the reference."""
 
+    _pointwise_entry = 'softmax_pointwise'
+
     def __init__(self, X, y, n_classes, prior_sd=10.0):
         X = np.ascontiguousarray(X, dtype=np.float64)
         y_in = np.asarray(y)
@@ -493,10 +506,20 @@ class SoftmaxRegressionModel(DeviceModel):
         ``(S, n_data)``, the ``log_lik`` argument of :func:`psisloo` (``psisloo(log_lik, log_ratios)`` is this model's
         route to LOO; ``loo()`` takes the one-predictor regression targets only).  Without the prior
         (``vb_softmax_pointwise``).  ``x``: (S, D), or (D,) for one draw."""
-        x, _ = self._rows(x)
-        eng = _lib.default_engine()
-        eng.set_model(self.device_spec())
-        return eng.softmax_pointwise(x, self.n_data)
+        return self._pointwise(x)
+
+
+# the one-predictor GLM likelihoods of the multilevel and the sparse target, and what each asks of the response
+_GLM_LINKS = {'logistic': _lib.GLM_BERNOULLI_LOGIT, 'poisson': _lib.GLM_POISSON, 'gaussian': _lib.GLM_GAUSSIAN}
+
+
+def _check_glm_response(likelihood, y):
+    if not np.all(np.isfinite(y)):
+        raise ValueError('y must be finite')
+    if likelihood == 'logistic' and np.any((y != 0) & (y != 1)):
+        raise ValueError('y must lie in {0, 1}')
+    if likelihood == 'poisson' and np.any(y < 0):
+        raise ValueError('counts must be non-negative')
 
 
 class MultilevelRegressionModel(DeviceModel):
@@ -528,7 +551,8 @@ class MultilevelRegressionModel(DeviceModel):
     ``AlphaDivergence`` and ``DISInclusiveKL`` with every family, ``bbvi``, ``vi_diagnostics`` and the device-resident
     fit.  Not in the reference."""
 
-    _LINKS = {'logistic': _lib.GLM_BERNOULLI_LOGIT, 'poisson': _lib.GLM_POISSON, 'gaussian': _lib.GLM_GAUSSIAN}
+    _LINKS = _GLM_LINKS
+    _pointwise_entry = 'multilevel_pointwise'
 
     def __init__(self, X, y, groups, n_groups, likelihood='logistic', prior_sd=10.0, tau_sd=1.0, noise_sd=1.0):
         X = np.ascontiguousarray(X, dtype=np.float64)
@@ -550,12 +574,7 @@ class MultilevelRegressionModel(DeviceModel):
             raise ValueError("likelihood must be 'logistic', 'poisson' or 'gaussian'")
         if not prior_sd > 0 or not tau_sd > 0 or not noise_sd > 0:
             raise ValueError('prior_sd, tau_sd and noise_sd must be positive')
-        if not np.all(np.isfinite(y)):
-            raise ValueError('y must be finite')
-        if likelihood == 'logistic' and np.any((y != 0) & (y != 1)):
-            raise ValueError('y must lie in {0, 1}')
-        if likelihood == 'poisson' and np.any(y < 0):
-            raise ValueError('counts must be non-negative')
+        _check_glm_response(likelihood, y)
         g = g.astype(np.int64)
         # contiguous group runs for the device: a stable sort, undone by pointwise_log_likelihood
         self.perm = np.argsort(g, kind='stable')
@@ -597,12 +616,12 @@ class MultilevelRegressionModel(DeviceModel):
         observations were given to the constructor: ``(S, n_data)``, the ``log_lik`` argument of :func:`psisloo`
         (``psisloo(log_lik, log_ratios)`` is this model's route to LOO).  Normalised densities, without the priors
         (``vb_multilevel_pointwise``).  ``x``: (S, D), or (D,) for one draw."""
-        x, _ = self._rows(x)
-        eng = _lib.default_engine()
-        eng.set_model(self.device_spec())
-        out = np.empty((x.shape[0], self.n_data))
-        out[:, self.perm] = eng.multilevel_pointwise(x, self.n_data)
-        return out
+        return self._pointwise(x)
+
+    def _pointwise_order(self, out):
+        back = np.empty_like(out)
+        back[:, self.perm] = out
+        return back
 
 
 class LocationScaleRegressionModel(DeviceModel):
@@ -632,6 +651,7 @@ class LocationScaleRegressionModel(DeviceModel):
     ``psisloo(model.pointwise_log_likelihood(x), log_ratios)``.  Not in the reference as a model class."""
 
     _LIKELIHOODS = {'gaussian': _lib.LOCSCALE_GAUSSIAN, 'student_t': _lib.LOCSCALE_STUDENT_T}
+    _pointwise_entry = 'locscale_pointwise'
 
     def __init__(self, X, y, W=None, likelihood='gaussian', df=4.0, prior_sd=10.0, scale_prior_sd=1.0):
         X = np.ascontiguousarray(X, dtype=np.float64)
@@ -696,10 +716,7 @@ class LocationScaleRegressionModel(DeviceModel):
         """The normalised terms ``l_i`` for every draw (row of ``x``) and observation: ``(S, n_data)``, the ``log_lik``
         argument of :func:`psisloo` (``psisloo(log_lik, log_ratios)`` is this model's route to LOO).  Without the priors
         (``vb_locscale_pointwise``).  ``x``: (S, D), or (D,) for one draw."""
-        x, _ = self._rows(x)
-        eng = _lib.default_engine()
-        eng.set_model(self.device_spec())
-        return eng.locscale_pointwise(x, self.n_data)
+        return self._pointwise(x)
 
 
 def _canonical_csr(data, indices, indptr, n_rows, n_cols):
@@ -767,7 +784,8 @@ class SparseRegressionModel(DeviceModel):
     device-resident fit.  ``loo()`` and ``predict()`` take the dense one-predictor regression targets only: this model's
     route to LOO is ``psisloo(model.pointwise_log_likelihood(x), log_ratios)``.  Not in the reference."""
 
-    _LINKS = {'logistic': _lib.GLM_BERNOULLI_LOGIT, 'poisson': _lib.GLM_POISSON, 'gaussian': _lib.GLM_GAUSSIAN}
+    _LINKS = _GLM_LINKS
+    _pointwise_entry = 'sparse_glm_pointwise'
 
     def __init__(self, X, y, likelihood='logistic', prior_sd=10.0, noise_sd=1.0, shape=None):
         if hasattr(X, 'tocsr'):
@@ -792,12 +810,7 @@ class SparseRegressionModel(DeviceModel):
         y = np.asarray(y, dtype=np.float64)
         if y.shape != (n_data,):
             raise ValueError('y must have shape ({},); got {}'.format(n_data, y.shape))
-        if not np.all(np.isfinite(y)):
-            raise ValueError('y must be finite')
-        if likelihood == 'logistic' and np.any((y != 0) & (y != 1)):
-            raise ValueError('y must lie in {0, 1}')
-        if likelihood == 'poisson' and np.any(y < 0):
-            raise ValueError('counts must be non-negative')
+        _check_glm_response(likelihood, y)
         vals, cols, ptr = self.csr
         rows = np.repeat(np.arange(n_data, dtype=np.int64), np.diff(ptr))
         order = np.argsort(cols, kind='stable')          # row-major input: rows increase within every column
@@ -847,7 +860,4 @@ class SparseRegressionModel(DeviceModel):
         """``log p(y_i | x_i' theta_s)`` for every draw (row of ``x``) and observation: ``(S, n_data)``, the ``log_lik``
         argument of :func:`psisloo` (``psisloo(log_lik, log_ratios)`` is this model's route to LOO).  Normalised densities,
         without the prior (``vb_sparse_glm_pointwise``).  ``x``: (S, D), or (D,) for one draw."""
-        x, _ = self._rows(x)
-        eng = _lib.default_engine()
-        eng.set_model(self.device_spec())
-        return eng.sparse_glm_pointwise(x, self.n_data)
+        return self._pointwise(x)
