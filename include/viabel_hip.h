@@ -543,6 +543,23 @@ int vb_glm_psis_loo(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const do
 int vb_glm_predict(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const double* log_w, const double* x_new,
                    int64_t m, const double* y_new, double* mean, double* var, double* eta_mean, double* eta_var,
                    double* lpd);
+/* vb_glm_value_grad_hessian: log density, gradient and Hessian of the bound regression target (VB_MODEL_LOGISTIC, any
+ * VB_GLM_* likelihood) at the ONE host point x[d] -- what a Newton step and the Laplace approximation need.
+ *   *f      the log density as vb_model_logp gives it: likelihood, prior and all constants
+ *   grad[d] its gradient as vb_model_grad gives it: X' r - x / prior_sd^2, r_i = d log p(y_i | eta_i) / d eta
+ *   hess    d x d row-major, the full symmetric matrix -X' diag(w) X - I / prior_sd^2 with w_i = -d^2 log p(y_i | eta_i) /
+ *           d eta^2: Bernoulli-logit t / (1 + t)^2 at t = exp(-|eta|) (finite and non-negative at any eta), Poisson exp(eta),
+ *           Gaussian 1 / noise_sd^2.  hess[i * d + j] == hess[j * d + i] bit for bit.  NULL: value and gradient only -- no
+ *           scaled copy of the design, no Gram product (a line search's evaluations).
+ * One streaming pass over the bound design (linear predictor, term, residual, weight, the gradient's row-block sums and the
+ * scaled rows w_i x_i together), one lower-triangular fp64 MFMA Gram product X' (W X) split over the observations, one
+ * finishing kernel.  Every sum has a fixed order: results are bit-reproducible, and f and grad do not depend on whether
+ * hess is asked for.  The scaled copy is as large as the bound design (n_data x round_up(d, 16) doubles) and is not chunked:
+ * the device holds the design twice already.  Capacity: d <= 8192.  Runs on the calling process's engine only: no
+ * all-reduce (like vb_glm_psis_loo).  VB_ERR_STATE without a bound model, VB_ERR_UNSUPPORTED for any other model or beyond
+ * the capacity, VB_ERR_INVALID for a wrong d or a NULL ctx / x / f / grad; a failing call leaves the bound model and the
+ * context usable.                                                                                                        */
+int vb_glm_value_grad_hessian(vb_ctx* ctx, const double* x, int64_t d, double* f, double* grad, double* hess);
 
 /* ---- ExclusiveKL, multivariate t family ------------------------------------------------
  * ExclusiveKL closure (objectives.py:154-164, entropy form) for MultivariateT

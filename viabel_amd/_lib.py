@@ -177,6 +177,7 @@ SIGNATURES = {
     'vb_glm_predict': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p,
                                       ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
                                       _c_double_p]),
+    'vb_glm_value_grad_hessian': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p]),
     'vb_alpha_grad_meanfield': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                ctypes.c_int, ctypes.c_double, _c_double_p, ctypes.c_double,
                                                _c_double_p, _c_double_p]),
@@ -844,6 +845,22 @@ class Engine:
         if lpd is not None:
             out['lpd'] = lpd
         return out
+
+    def glm_value_grad_hessian(self, x, want_hessian=True):
+        """``(f, grad, hess)`` of the bound regression target at the one point ``x`` (D,) (``vb_glm_value_grad_hessian``):
+        the log density with all constants, its gradient ``(D,)`` and the exactly symmetric Hessian ``(D, D)`` --
+        ``None`` with ``want_hessian=False``, which skips the scaled copy of the design and the Gram product and returns
+        the same ``f`` and ``grad`` bits."""
+        x = _f64(x)
+        if x.ndim != 1:
+            raise ValueError('x must be (D,)')
+        d = x.shape[0]
+        f = ctypes.c_double(0.0)
+        grad = np.empty(d, dtype=np.float64)
+        hess = np.empty((d, d), dtype=np.float64) if want_hessian else None
+        self._check(self._lib.vb_glm_value_grad_hessian(self._ctx, _dptr(x), d, ctypes.addressof(f), _dptr(grad),
+                                                        None if hess is None else _dptr(hess)))
+        return f.value, grad, hess
 
     # ------------------------------------------------------------------ AlphaDivergence, mean field
     def alpha_grad_meanfield(self, slot, n, d, theta, family, alpha, df=0.0, n_total=None):

@@ -10,13 +10,14 @@ import numpy as np
 
 from . import _lib
 from ._psis import _tail_size, batch_capacity, psislw, psisloo
-from .approximations import MFGaussian, MFStudentT, NVPFlow
+from .approximations import FullRankGaussian, MFGaussian, MFStudentT, NVPFlow
 from .diagnostics import all_diagnostics
 from .models import CallableModel, DeviceModel, LogisticRegressionModel, SourceModel
 from .objectives import ExclusiveKL, _stage_prior_noise
 from .optimization import FASO, RAABBVI, RMSProp
 
-__all__ = ['bbvi', 'vi_diagnostics', 'psis_correction', 'samples_and_log_weights', 'loo', 'psisloo', 'predict']
+__all__ = ['bbvi', 'vi_diagnostics', 'psis_correction', 'samples_and_log_weights', 'loo', 'psisloo', 'predict',
+           'laplace_approximation']
 
 
 def bbvi(dimension, *, n_iters=10000, num_mc_samples=10, log_density=None, approx=None, objective=None,
@@ -283,3 +284,41 @@ def predict(var_param, *, objective=None, model=None, approx=None, X_new=None, y
         if khat > 0.7:
             print('WARNING: khat > 0.7 means importance sampling is not feasible.')
     return results
+
+
+def laplace_approximation(model, x0=None, max_iter=100, tol=1e-10, seed=1, rng='numpy'):
+    """The Gaussian at the mode of a device model: ``N(mode, (-H)^-1)`` with ``H`` the Hessian of the log density there.
+
+    The mode comes from :meth:`DeviceModel.find_mode` (damped Newton from ``x0``; for the flat regression targets every
+    evaluation is one device call -- a streaming pass over the design and an fp64 MFMA Gram product --, for every other
+    device model the Hessian is a fourth-order difference of the device gradient); the ``D x D`` factorisations are host
+    LAPACK.  Returns a dict: ``mode``, ``hessian``, ``n_iter``, ``converged`` (as ``find_mode`` gives them),
+    ``cov = (-H)^-1`` (symmetrised), ``approx = FullRankGaussian(dim, seed=seed, rng=rng)``,
+    ``var_param = approx.pack(mode, cholesky(cov))`` and the Laplace evidence estimate
+    ``log_evidence = f(mode) + D / 2 log(2 pi) - 1/2 log det(-H)``, to be read beside an ELBO.  ``var_param`` and
+    ``approx`` go as they are into ``vi_diagnostics(var_param, model=, approx=)``, ``bbvi(..., approx=, init_var_param=)``,
+    ``loo`` and ``predict``.  Raises ``ValueError`` when ``-H`` at the returned point is not positive definite (a saddle, a
+    search that did not converge: there is no Gaussian there) and ``TypeError`` for a model that is not a
+    ``DeviceModel``."""
+    from scipy.linalg import cho_factor, cho_solve
+    if not isinstance(model, DeviceModel):
+        raise TypeError('laplace_approximation needs a viabel_amd device model (its gradient and Hessian are device code); '
+                        'got {}'.format(type(model).__name__))
+    found = model.find_mode(x0=x0, max_iter=max_iter, tol=tol)
+    mode, H = found['mode'], found['hessian']
+    d = model.dim
+    try:
+        if not np.all(np.isfinite(H)):
+            raise np.linalg.LinAlgError('non-finite Hessian')
+        factor = cho_factor(-H, lower=True)
+    except np.linalg.LinAlgError:
+        raise ValueError('the negated Hessian at the point find_mode returned is not positive definite: no Gaussian '
+                         'there (converged = {})'.format(found['converged'])) from None
+    cov = cho_solve(factor, np.eye(d))
+    cov = 0.5 * (cov + cov.T)
+    approx = FullRankGaussian(d, seed=seed, rng=rng)
+    var_param = approx.pack(mode, np.linalg.cholesky(cov))
+    log_det = 2.0 * float(np.sum(np.log(np.diag(factor[0]))))
+    log_evidence = found['value'] + 0.5 * d * np.log(2.0 * np.pi) - 0.5 * log_det
+    return dict(mode=mode, hessian=H, n_iter=found['n_iter'], converged=found['converged'], cov=cov, approx=approx,
+                var_param=var_param, log_evidence=float(log_evidence))
