@@ -561,6 +561,40 @@ int vb_glm_predict(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const dou
  * context usable.                                                                                                        */
 int vb_glm_value_grad_hessian(vb_ctx* ctx, const double* x, int64_t d, double* f, double* grad, double* hess);
 
+/* ---- Hamiltonian Monte Carlo on the device gradients -----------------------------------
+ * vb_hmc_run: n_chains chains of HMC on the bound model, advanced in lock-step as one batch of the gradient pipeline
+ * (what vb_model_grad evaluates), from the host starts x0 (n_chains x d, row-major) under the diagonal metric
+ * inv_mass[d] (estimated posterior variances, all positive).  Iterations t = 0 .. n_warmup + n_draws - 1, each one
+ * trajectory of n_leapfrog leapfrog steps and an accept test; the step size of iteration t is
+ * base_t (1 + jitter (2 v_t - 1)), shared by all chains, with base_t the dual-averaging iterate (Hoffman & Gelman 2014,
+ * Algorithm 5: delta = target_accept, gamma = 0.05, t0 = 10, kappa = 0.75, mu = log(10 step_size), on the chains' mean
+ * acceptance) during warm-up, the averaged step afterwards, and step_size throughout when n_warmup = 0.  A proposal whose
+ * energy error is not finite or exceeds 1000 is divergent and rejected; a rejected chain keeps its state bit for bit.
+ * Random numbers of iteration t come from Philox stream stream_offset + t of `seed`: the momenta are the normals
+ * vb_noise_generate puts at (row = chain, col = coordinate) of that stream, the accept uniforms and v_t come from pseudo
+ * column 0xFFFFFFFE ("Philox layout"); a chain's randomness does not depend on n_chains.
+ * Outputs (host, caller-owned), n_kept = ceil(n_draws / thin), sampling iterations only except the two histories:
+ *   draws[n_kept x n_chains x d], logp[n_kept x n_chains]   states and log densities after every thin-th sampling iteration
+ *                                                          (the first included); each may be NULL
+ *   last_x[n_chains x d]            the final states
+ *   chain_mean, chain_m2[n_chains x d]   per chain and coordinate: mean and sum of squared deviations over ALL n_draws
+ *                                   sampling iterations (Welford), thinned or not
+ *   accept_rate[n_chains]           accepted share of the sampling proposals
+ *   step_hist, accept_hist[n_warmup + n_draws]   step size used and mean acceptance probability of every iteration
+ *   *final_step                     the sampling phase's base step; *n_divergent: divergent sampling proposals, all chains
+ * The whole run is enqueued on the context's stream with the step size resident in device memory: the host synchronises
+ * once, for the download.  Every sum has a fixed order: results are bit-reproducible.  The kept draws live on the device
+ * until then; above 1 GiB of them the call returns VB_ERR_UNSUPPORTED (raise thin, or pass draws = NULL).
+ * VB_ERR_INVALID: a NULL ctx / required pointer, non-positive n_chains / d / n_draws, negative n_warmup, thin < 1,
+ * n_leapfrog < 1, step_size or an inv_mass entry not positive and finite, target_accept outside (0, 1), jitter outside
+ * [0, 1), d different from the model's dimension.  VB_ERR_STATE: no model bound.  VB_ERR_UNSUPPORTED: a host-callback
+ * model (vb_set_model_callback), an attached communicator, the draw budget.  A refused call leaves the context usable. */
+int vb_hmc_run(vb_ctx* ctx, const double* x0, const double* inv_mass, int64_t n_chains, int64_t d, int64_t n_warmup,
+               int64_t n_draws, int64_t thin, int n_leapfrog, double step_size, double target_accept, double jitter,
+               uint64_t seed, uint64_t stream_offset, double* draws, double* logp, double* last_x, double* chain_mean,
+               double* chain_m2, double* accept_rate, double* step_hist, double* accept_hist, double* final_step,
+               int64_t* n_divergent);
+
 /* ---- ExclusiveKL, multivariate t family ------------------------------------------------
  * ExclusiveKL closure (objectives.py:154-164, entropy form) for MultivariateT
  * (approximations.py:322-382): x_n = mu + (z_n Sigma^{1/2}) / s_n with the normals z (n x D) in

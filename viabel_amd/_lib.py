@@ -178,6 +178,10 @@ SIGNATURES = {
                                       ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
                                       _c_double_p]),
     'vb_glm_value_grad_hessian': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p]),
+    'vb_hmc_run': (ctypes.c_int, [_ctx_p, _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                  ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                  ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64, _c_double_p, _c_double_p, _c_double_p,
+                                  _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int64_p]),
     'vb_alpha_grad_meanfield': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                ctypes.c_int, ctypes.c_double, _c_double_p, ctypes.c_double,
                                                _c_double_p, _c_double_p]),
@@ -861,6 +865,39 @@ class Engine:
         self._check(self._lib.vb_glm_value_grad_hessian(self._ctx, _dptr(x), d, ctypes.addressof(f), _dptr(grad),
                                                         None if hess is None else _dptr(hess)))
         return f.value, grad, hess
+
+    def hmc_run(self, x0, inv_mass, n_warmup, n_draws, n_leapfrog, step_size, target_accept=0.8, jitter=0.2, seed=1,
+                stream_offset=0, thin=1, keep_draws=True):
+        """Many-chain HMC on the bound model (``vb_hmc_run``): ``x0`` (C x D) starts, ``inv_mass`` (D,) the diagonal
+        metric.  The whole run is one call; the outputs are allocated here.  Returns a dict: ``draws`` (n_kept x C x D, or
+        None with ``keep_draws=False``), ``logp`` (n_kept x C), ``last`` (C x D), ``chain_mean`` and ``chain_m2`` (C x D),
+        ``accept_rate`` (C,), ``step_size_history`` and ``accept_prob`` (n_warmup + n_draws,), ``step_size`` (the
+        sampling phase's) and ``n_divergent``."""
+        x0 = _f64(x0)
+        inv_mass = _f64(inv_mass)
+        if x0.ndim != 2:
+            raise ValueError('x0 must be (n_chains, D)')
+        c, d = x0.shape
+        if inv_mass.shape != (d,):
+            raise ValueError('inv_mass must have shape ({},)'.format(d))
+        n_warmup, n_draws, thin = int(n_warmup), int(n_draws), int(thin)
+        n_iter = max(n_warmup, 0) + max(n_draws, 0)
+        n_kept = -(-max(n_draws, 0) // thin) if thin >= 1 else 0
+        draws = np.empty((n_kept, c, d), dtype=np.float64) if keep_draws else None
+        logp = np.empty((n_kept, c), dtype=np.float64)
+        last, mean, m2 = (np.empty((c, d), dtype=np.float64) for _ in range(3))
+        rate = np.empty(c, dtype=np.float64)
+        step_hist, accept_hist = np.empty(n_iter, dtype=np.float64), np.empty(n_iter, dtype=np.float64)
+        final = ctypes.c_double(0.0)
+        n_div = ctypes.c_int64(0)
+        self._check(self._lib.vb_hmc_run(self._ctx, _dptr(x0), _dptr(inv_mass), c, d, n_warmup, n_draws, thin,
+                                         int(n_leapfrog), float(step_size), float(target_accept), float(jitter),
+                                         int(seed), int(stream_offset), None if draws is None else _dptr(draws),
+                                         _dptr(logp), _dptr(last), _dptr(mean), _dptr(m2), _dptr(rate), _dptr(step_hist),
+                                         _dptr(accept_hist), ctypes.addressof(final), ctypes.byref(n_div)))
+        return dict(draws=draws, logp=logp, last=last, chain_mean=mean, chain_m2=m2, accept_rate=rate,
+                    step_size_history=step_hist, accept_prob=accept_hist, step_size=final.value,
+                    n_divergent=int(n_div.value))
 
     # ------------------------------------------------------------------ AlphaDivergence, mean field
     def alpha_grad_meanfield(self, slot, n, d, theta, family, alpha, df=0.0, n_total=None):

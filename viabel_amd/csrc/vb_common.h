@@ -283,6 +283,7 @@ struct vb_ctx {
   // a time, every call lays the buffer out from scratch and writes each piece before it reads it
   vb::DeviceBuffer target_work;
   vb::DeviceBuffer hess_work;            // vb_glm_value_grad_hessian (vb_glm_hessian.hip): laid out from scratch by every call
+  vb::DeviceBuffer hmc_work;             // vb_hmc_run (vb_hmc.hip): chain states, statistics and kept draws, laid out by every call
   vb::DeviceBuffer mvt_state;           // multivariate-t DIS: state samples X, scratch
   int64_t mvt_n = 0, mvt_d = 0, mvt_n_total = 0;
   int64_t mvt_lq_off = 0;               // where this rank's log q of the residual pass start inside o_lq (the refresh writes them

@@ -1,0 +1,124 @@
+"""Many-chain Hamiltonian Monte Carlo on the device gradients: the ground truth a variational fit is checked against.
+
+The reference's documentation compares its fits with MCMC draws (``docs/source/robust-regression.ipynb``:
+``check_accuracy(true_mean, true_cov, var_param, approx)``); :func:`hmc` produces those draws here, from the gradient
+pipeline the objectives use (``vb_hmc_run``, ``csrc/vb_hmc.hip``; ``DESIGN.md`` 4.22)."""
+import numpy as np
+
+from viabel_amd import _lib
+from viabel_amd.models import CallableModel, DeviceModel
+
+__all__ = ['hmc']
+
+
+def _combine_chains(chain_mean, chain_var, n):
+    """``(mean, sd, rhat)`` over the chains from their means and ``ddof=1`` variances of ``n`` draws each: ``W`` the mean
+    chain variance, ``B = n var(chain means, ddof=1)``, ``var+ = (n - 1) / n W + B / n``, ``sd = sqrt(var+)``,
+    ``rhat = sqrt(var+ / W)`` (Gelman et al., BDA3 11.4).  One chain has no between-chain variance: ``B = 0``."""
+    chain_mean, chain_var = np.asarray(chain_mean, dtype=np.float64), np.asarray(chain_var, dtype=np.float64)
+    w = chain_var.mean(axis=0)
+    b_over_n = chain_mean.var(axis=0, ddof=1) if chain_mean.shape[0] > 1 else np.zeros(chain_mean.shape[1])
+    var_plus = (n - 1.0) / n * w + b_over_n
+    with np.errstate(divide='ignore', invalid='ignore'):
+        rhat = np.sqrt(var_plus / w)
+    return chain_mean.mean(axis=0), np.sqrt(var_plus), rhat
+
+
+def _check_arguments(model, n_chains, n_warmup, n_draws, n_leapfrog, step_size, target_accept, jitter, init, inv_mass,
+                     var_param, approx, thin):
+    """Everything that can be refused without an engine; returns ``(init, inv_mass, step_size)`` as arrays / float."""
+    if not isinstance(model, DeviceModel):
+        raise TypeError('hmc needs a viabel_amd device model (its gradient is device code); got {}'.format(
+            type(model).__name__))
+    if isinstance(model, CallableModel):
+        raise NotImplementedError('hmc advances the chains without host synchronisation: a CallableModel (a host callback) '
+                                  'cannot be its target; write the density as a SourceModel')
+    for name, v, low in (('n_chains', n_chains, 1), ('n_warmup', n_warmup, 0), ('n_draws', n_draws, 1),
+                         ('n_leapfrog', n_leapfrog, 1), ('thin', thin, 1)):
+        if isinstance(v, bool) or int(v) != v or v < low:
+            raise ValueError('{} must be an integer >= {}'.format(name, low))
+    if not (0.0 < target_accept < 1.0):
+        raise ValueError('target_accept must lie in (0, 1)')
+    if not (0.0 <= jitter < 1.0):
+        raise ValueError('jitter must lie in [0, 1)')
+    if (var_param is None) != (approx is None):
+        raise ValueError('var_param and approx must be given together')
+    if var_param is None and init is None:
+        raise ValueError('either init or both var_param and approx must be given')
+    d = model.dim
+    step_size = d ** -0.25 if step_size is None else float(step_size)
+    if not (step_size > 0.0 and np.isfinite(step_size)):
+        raise ValueError('step_size must be positive and finite')
+    if init is not None:
+        init = np.ascontiguousarray(init, dtype=np.float64)
+        if init.shape != (n_chains, d):
+            raise ValueError('init must have shape ({}, {}); got {}'.format(n_chains, d, init.shape))
+        if not np.all(np.isfinite(init)):
+            raise ValueError('init must be finite')
+    if inv_mass is not None:
+        inv_mass = np.ascontiguousarray(inv_mass, dtype=np.float64)
+        if inv_mass.shape != (d,):
+            raise ValueError('inv_mass must have shape ({},); got {}'.format(d, inv_mass.shape))
+        if not (np.all(inv_mass > 0.0) and np.all(np.isfinite(inv_mass))):
+            raise ValueError('inv_mass must be positive and finite')
+    return init, inv_mass, step_size
+
+
+def hmc(model, *, n_chains=256, n_warmup=300, n_draws=300, n_leapfrog=16, step_size=None, target_accept=0.8, jitter=0.2,
+        init=None, inv_mass=None, var_param=None, approx=None, seed=1, stream_offset=0, thin=1, keep_draws=True):
+    """Hamiltonian Monte Carlo draws from a device model: ``n_chains`` chains advanced in lock-step on the GPU, each
+    iteration one trajectory of ``n_leapfrog`` leapfrog steps under a diagonal metric and an accept test; the step size is
+    adapted by dual averaging on the chains' mean acceptance during ``n_warmup`` iterations (target ``target_accept``)
+    and jittered by ``+- jitter`` per iteration.  No NUTS, no mass-matrix adaptation: the metric comes from a fit.
+
+    With ``var_param`` and ``approx`` (as ``bbvi`` or ``laplace_approximation`` return them) the chains start at
+    ``approx.sample(var_param, n_chains)`` unless ``init`` (n_chains x D) is given, and the metric is the diagonal of
+    ``approx.mean_and_cov(var_param)[1]`` unless ``inv_mass`` (D,; estimated posterior variances) is given.  Without
+    them ``init`` is required and ``inv_mass`` defaults to ones.  ``step_size=None`` means ``D ** -0.25``.
+
+    Returns a dict: ``draws`` (n_kept x C x D; None with ``keep_draws=False``) and ``logp`` (n_kept x C) of every
+    ``thin``-th sampling iteration, ``n_kept = ceil(n_draws / thin)``; ``last`` (C x D); ``chain_mean`` and ``chain_var``
+    (C x D; ``ddof=1`` over all ``n_draws`` sampling iterations, thinned or not); ``mean``, ``sd`` and ``rhat`` (D,) from
+    them (``W`` the mean chain variance, ``B = n var(chain means)``, ``var+ = (n - 1) / n W + B / n``, ``sd = sqrt(var+)``,
+    ``rhat = sqrt(var+ / W)``); ``accept_rate`` (C,); ``accept_prob`` and ``step_size_history`` (n_warmup + n_draws,);
+    ``step_size`` (the sampling phase's); ``n_divergent``; ``inv_mass``; ``seed`` and ``next_stream``.  A continuation
+    passes ``init=res['last']``, ``step_size=res['step_size']``, ``n_warmup=0`` and ``stream_offset=res['next_stream']``.
+    Runs on the calling process's engine; raises ``NotImplementedError`` for a ``CallableModel`` and for a sharded
+    engine."""
+    init, inv_mass, step_size = _check_arguments(model, n_chains, n_warmup, n_draws, n_leapfrog, step_size, target_accept,
+                                                 jitter, init, inv_mass, var_param, approx, thin)
+    if var_param is not None:
+        var_param = np.asarray(var_param, dtype=np.float64)
+        if inv_mass is None:
+            inv_mass = np.ascontiguousarray(np.diag(approx.mean_and_cov(var_param)[1]), dtype=np.float64)
+            if not (np.all(inv_mass > 0.0) and np.all(np.isfinite(inv_mass))):
+                raise ValueError('the approximation has no finite positive variances to take the metric from; pass inv_mass')
+        if init is None:
+            init = np.ascontiguousarray(approx.sample(var_param, int(n_chains)), dtype=np.float64)
+            if init.shape != (n_chains, model.dim):
+                raise ValueError('approx.sample returned shape {}, expected ({}, {})'.format(init.shape, n_chains, model.dim))
+    if inv_mass is None:
+        inv_mass = np.ones(model.dim)
+    eng = _lib.default_engine()
+    if eng.n_ranks > 1:
+        raise NotImplementedError('hmc runs on one process\'s engine; a sharded engine ({} ranks) is not supported'.format(
+            eng.n_ranks))
+    eng.set_model(model.device_spec())
+    out = eng.hmc_run(init, inv_mass, n_warmup, n_draws, n_leapfrog, step_size, target_accept=target_accept, jitter=jitter,
+                      seed=seed, stream_offset=stream_offset, thin=thin, keep_draws=keep_draws)
+    n = int(n_draws)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        chain_var = out['chain_m2'] / (n - 1.0) if n > 1 else np.full_like(out['chain_m2'], np.nan)
+    mean, sd, rhat = _combine_chains(out['chain_mean'], chain_var, n)
+    results = dict(draws=out['draws'], logp=out['logp'], last=out['last'], chain_mean=out['chain_mean'],
+                   chain_var=chain_var, mean=mean, sd=sd, rhat=rhat, accept_rate=out['accept_rate'],
+                   accept_prob=out['accept_prob'], step_size_history=out['step_size_history'], step_size=out['step_size'],
+                   n_divergent=out['n_divergent'], inv_mass=inv_mass, seed=int(seed),
+                   next_stream=int(stream_offset) + int(n_warmup) + int(n_draws))
+    max_rhat = float(np.max(rhat[~np.isnan(rhat)])) if not np.all(np.isnan(rhat)) else float('nan')
+    print('hmc: step size = {:.4g}, mean acceptance = {:.3f}, max rhat = {:.3f}, {} divergent of {} proposals'.format(
+        results['step_size'], float(out['accept_rate'].mean()), max_rhat, results['n_divergent'], n * int(n_chains)))
+    if max_rhat > 1.05 or results['n_divergent'] > 0:
+        print('WARNING: rhat > 1.05 means the chains have not mixed; divergences mean the step size is too large for '
+              'parts of the posterior. Run longer, start from a better fit, or lower step_size.')
+    return results
