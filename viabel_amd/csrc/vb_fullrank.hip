@@ -395,88 +395,18 @@ __global__ void __launch_bounds__(256) fr_colsum_kernel(const double* __restrict
   if (threadIdx.x == 0) fpart[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = f;
 }
 
-// ---- folded evaluation: M = sum of the split slabs of L' P, and b = P (mu - m) ------------------------------------------
+// ---- folded evaluation: b = P (mu - m), S = E' E, s = colsum(E) and colsum(G) = -s' M - n b' ---------------------------
 // The correlated-Gaussian target's G is linear in the noise: G = -(E L' + 1 c') P = -E M - 1 b', c = mu - m, M = L' P,
 // b = P c -- a D x D x D product that does not depend on the number of samples instead of the N x D x D sampling product
 // (and G itself is never formed: fr_route).
-// Blocks [0, nb_b), 8 columns each (dispatched first: each is a chain of dependent passes): b[j] = sum_k P[k][j] c[k];
-// thread (pair p = t & 3, k group t >> 2) sums its 64th of the k range, sixteen rows per pass, the groups are
-// combined through LDS in fixed order.  The remaining blocks (none for an unsplit product): one thread per pair of
-// adjacent entries of M, the slabs of the split product added in slab order (a slab whose k range ends at or below the
-// first row of the entry's `bm_rows`-row block is not written by the product -- tri_mode 4 -- and not read).
-__global__ void __launch_bounds__(256) fr_fold_msum_kernel(const double* __restrict__ Mpart, int msplits, int64_t slab,
-                                                           int d, int64_t ldz, int k_split, int bm_rows,
-                                                           double* __restrict__ Mout, int nb_b,
-                                                           const double* __restrict__ P, int64_t ldp,
-                                                           const double* __restrict__ mu,
-                                                           const double* __restrict__ mean, double* __restrict__ b) {
-  if ((int)blockIdx.x >= nb_b) {
-    // (row and first slab from the block index: wave-uniform, no per-thread division -- with idx / ldz per thread the
-    // kernel was bound by that arithmetic: 20 us at D = 1024)
-    const int bpr = (int)((ldz / 2 + 255) / 256);                  // blocks per row of M
-    const int blk = (int)blockIdx.x - nb_b, r = blk / bpr;
-    const int cp = (blk - r * bpr) * 256 + (int)threadIdx.x;       // column pair
-    if (2 * cp >= ldz) return;
-    const int64_t idx = (int64_t)r * ldz + 2 * cp;
-    const int z0 = (r / bm_rows * bm_rows) / kGemmBK * kGemmBK / k_split;
-    fr_d2 s = (fr_d2){0.0, 0.0};
-    for (int zb = z0; zb < msplits; zb += 4) {      // four slabs in flight (clamped, not predicated), added in slab order
-      fr_d2 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        v[u] = *reinterpret_cast<const fr_d2*>(Mpart + (zb + u < msplits ? zb + u : msplits - 1) * slab + idx);
-      s = zb == z0 ? v[0] : s + v[0];
-#pragma unroll
-      for (int u = 1; u < 4; ++u)
-        if (zb + u < msplits) s += v[u];
-    }
-    *reinterpret_cast<fr_d2*>(Mout + idx) = s;
-    return;
-  }
-  __shared__ fr_d2 part[64][4];
-  const int p = threadIdx.x & 3, kg = threadIdx.x >> 2;
-  const int col = (int)blockIdx.x * 8 + 2 * p;
-  const int colc = col < d ? col : 0;                        // (rows of P are padded to an even stride >= d)
-  const int kper = (d + 63) / 64;
-  const int k0 = kg * kper, k1 = k0 + kper < d ? k0 + kper : d;
-  fr_d2 s = (fr_d2){0.0, 0.0};
-  for (int kb = k0; kb < k1; kb += 16) {
-    fr_d2 v[16];
-    double c[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int k = kb + u < k1 ? kb + u : k1 - 1;
-      v[u] = *reinterpret_cast<const fr_d2*>(P + (int64_t)k * ldp + colc);
-      c[u] = mu[k] - mean[k];
-    }
-#pragma unroll
-    for (int u = 0; u < 16; ++u)
-      if (kb + u < k1) s += v[u] * c[u];
-  }
-  part[kg][p] = s;
-  __syncthreads();
-  if (kg == 0) {
-    fr_d2 tot = part[0][p];
-#pragma unroll
-    for (int q = 1; q < 64; ++q) tot += part[q][p];
-    if (col < d) b[col] = tot.x;
-    if (col + 1 < d) b[col + 1] = tot.y;
-  }
-}
-
-// k splits of the M = L' P product (64 x 64 tiles): pieces of about sixteen slabs, so that no workgroup carries the
-// 64 slabs of row block 0 at D = 1024 alone (about 40 us on a CU by itself)
-static int fr_fold_splits(int d) {
-  const int s = d / (16 * kGemmBK);
-  return s < 1 ? 1 : (s > 8 ? 8 : s);
-}
-
-// ---- folded evaluation: S = E' E, s = colsum(E) and colsum(G) = -s' M - n b' -----------------------------------------
 // The Gram product of the noise leaves the lower tiles of E' E in `gsplits` slabs (pieces of the sample axis) and one row
 // of column sums of E per slab.  One launch, three kinds of workgroups:
-//   [0, nb_cs), 8 columns each, dispatched first (each is a chain of dependent passes), as the b blocks of
-//     fr_fold_msum_kernel: colsum(G)[j] = -sum_k s[k] M[k][j] - n b[j], with s[k] added up from the rows of `colpart` in
-//     row order by the thread that needs it (M is complete: this launch follows fr_fold_msum_kernel);
+//   [0, nb_cs), 8 columns each, dispatched first (each is a chain of dependent passes): two dot products over the same
+//     eight columns, b[j] = sum_k P[k][j] c[k] (P is symmetric: its column j) and sum_k s[k] M[k][j], with s[k] added up
+//     from the rows of `colpart` in row order by the thread that needs it (M is complete: its product is an earlier
+//     launch).  Thread (pair p = t & 3, k group t >> 2) sums its 64th of the k range, sixteen rows per pass, and the
+//     groups are combined through LDS in fixed order.  The block writes b[j] -- for the gradient product's epilogue, a
+//     later launch -- and colsum(G)[j] = -sum_k s[k] M[k][j] - n b[j] from its own b[j]: no block reads another's;
 //   the next nb_s: s itself, one thread per column (the gradient product's epilogue reads it);
 //   the rest, one per 32 x 32 tile (bi, bj <= bi) of S: the slabs added in slab order,
 //     the sum written to S[i][j] and, through LDS, to S[j][i] -- both halves from the same sum, so S is exactly
@@ -486,18 +416,33 @@ static int fr_fold_splits(int d) {
 // Everything is added in a fixed order: the same inputs give the same bits.
 __global__ void __launch_bounds__(256) fr_fold_ssum_kernel(const double* __restrict__ Spart, int gsplits, int64_t slab, int d,
                                                            int64_t ldl, const double* __restrict__ colpart, int64_t ldz,
-                                                           const double* __restrict__ M, const double* __restrict__ b,
-                                                           double n_rows, int nb_cs, int nb_s,
-                                                           double* __restrict__ S, double* __restrict__ svec,
-                                                           double* __restrict__ csg) {
+                                                           const double* __restrict__ M, const double* __restrict__ P,
+                                                           int64_t ldp, const double* __restrict__ mu,
+                                                           const double* __restrict__ mean, double n_rows, int nb_cs,
+                                                           int nb_s, double* __restrict__ S, double* __restrict__ svec,
+                                                           double* __restrict__ b, double* __restrict__ csg) {
   if ((int)blockIdx.x < nb_cs) {
-    __shared__ fr_d2 part[64][4];
+    __shared__ fr_d2 part[2][64][4];
     const int p = threadIdx.x & 3, kg = threadIdx.x >> 2;
     const int col = (int)blockIdx.x * 8 + 2 * p;
-    const int colc = col < d ? col : 0;                        // (rows of M have an even stride >= d)
+    const int colc = col < d ? col : 0;                        // (rows of M and P have an even stride >= d)
     const int kper = (d + 63) / 64;
     const int k0 = kg * kper, k1 = k0 + kper < d ? k0 + kper : d;
-    fr_d2 acc = (fr_d2){0.0, 0.0};
+    fr_d2 acc = (fr_d2){0.0, 0.0}, bacc = (fr_d2){0.0, 0.0};
+    // (one dot product after the other: sixteen rows of one operand in flight at a time)
+    for (int kb = k0; kb < k1; kb += 16) {
+      fr_d2 v[16];
+      double c[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int k = kb + u < k1 ? kb + u : k1 - 1;
+        v[u] = *reinterpret_cast<const fr_d2*>(P + (int64_t)k * ldp + colc);
+        c[u] = mu[k] - mean[k];
+      }
+#pragma unroll
+      for (int u = 0; u < 16; ++u)
+        if (kb + u < k1) bacc += v[u] * c[u];
+    }
     for (int kb = k0; kb < k1; kb += 16) {
       fr_d2 v[16];
       double c[16];
@@ -514,14 +459,15 @@ __global__ void __launch_bounds__(256) fr_fold_ssum_kernel(const double* __restr
       for (int u = 0; u < 16; ++u)
         if (kb + u < k1) acc += v[u] * c[u];
     }
-    part[kg][p] = acc;
+    part[0][kg][p] = acc;
+    part[1][kg][p] = bacc;
     __syncthreads();
     if (kg == 0) {
-      fr_d2 tot = part[0][p];
-#pragma unroll
-      for (int q = 1; q < 64; ++q) tot += part[q][p];
-      if (col < d) csg[col] = -tot.x - n_rows * b[col];
-      if (col + 1 < d) csg[col + 1] = -tot.y - n_rows * b[col + 1];
+      fr_d2 tot = part[0][0][p], btot = part[1][0][p];
+#pragma unroll 16
+      for (int q = 1; q < 64; ++q) tot += part[0][q][p], btot += part[1][q][p];
+      if (col < d) b[col] = btot.x, csg[col] = -tot.x - n_rows * btot.x;
+      if (col + 1 < d) b[col + 1] = btot.y, csg[col + 1] = -tot.y - n_rows * btot.y;
     }
     return;
   }
@@ -1476,7 +1422,6 @@ struct FrRoute {
   int kparts = 1;               // short shards: pieces of the k range of the N x D x D products (1: not split)
   unsigned sum_blocks = 0;      // grid of the kernels that add those pieces
   bool fold_shape = false;      // the folded evaluation's buffers are carved
-  int msplits = 1;              // its M = L' P product: pieces of the k range
   bool fold = false;
   int csplits = 1;              // its gradient product C = -tril(M' S) - b s': pieces of the k range
   int cfgc = 0;                 // ... and its tile configuration (gemm_f64_launch's cfg)
@@ -1571,10 +1516,10 @@ static FrRoute fr_route(const vb_ctx* ctx, const ModelDev& m, int64_t n, int64_t
   // Nothing the evaluation returns needs G itself: with S = E' E, s = colsum(E) and n the rows of this rank,
   //   C = G' E = -M' S - b s'        colsum(G) = -s' M - n b'
   // so neither N x D x D product is formed and neither Z nor G is stored.  The chain:
-  //   M slabs = L' P (tri_mode 4, msplits)  ->  fr_fold_msum_kernel: M, b
+  //   M = L' P (tri_mode 4, row blocks in pairs: one launch writes M itself)
   //   Gram product of the noise: the gradient product's own shape, kernel and tile map with A = B = E, `splits` slabs of
   //     the lower tiles of S, one row of column sums of E per slab out of its LDS tiles (EpiSplitSlabCs)
-  //   fr_fold_ssum_kernel: S in full (mirrored), s, colsum(G)
+  //   fr_fold_ssum_kernel: b, S in full (mirrored), s, colsum(G)
   //   C slabs = -(M' S) - b s' (lower tiles, K = D in csplits pieces, EpiFoldSlabF: sum L o tril(C) per tile and split)
   //   fr_reduce_packed_kernel, as for every route: the slabs of C, ONE row of column sums, the f partials.
   // M and S are formed anew in EVERY evaluation: M follows the parameter, which an optimiser steps every time, and S the
@@ -1587,7 +1532,6 @@ static FrRoute fr_route(const vb_ctx* ctx, const ModelDev& m, int64_t n, int64_t
   // job may fall on different sides of the gate: both routes hand the same sums [F | colsum | C] of the rank's own rows
   // to the all-reduce.
   r.fold_shape = !mvt && gauss_full && !pd && d >= VB_FR_FOLD_MIN_D && n >= (int64_t)VB_FR_FOLD_MIN_ROWS_PER_D * d;
-  r.msplits = fr_fold_splits(D);
   r.fold = r.fold_shape && r.fused_sums && r.kparts == 1 && !wm.z_ready && !wm.g_ready && n >= d + 2;      // (fr_carve; cannot bind while the gate asks n >= 3 d)
 
   // the fused evaluation: 2 = Z and G in one persistent launch, 3 = the gradient product's split slabs as well
@@ -1644,7 +1588,7 @@ struct FrBufs {
   double *mu = nullptr, *Lt = nullptr;      // (the dense family's live in ctx->fr_lt: fr_prepare_dense)
   double *Z = nullptr, *G = nullptr, *Cpart = nullptr, *colpart = nullptr, *fpart = nullptr;
   double* Rm = nullptr;                                             // regression targets: the residuals
-  double *Mpart = nullptr, *bvec = nullptr;                         // folded evaluation: slabs of M = L' P, then M; b = P (mu - m)
+  double *Mf = nullptr, *bvec = nullptr;                            // folded evaluation: M = L' P; b = P (mu - m)
   double *Sg = nullptr, *svec = nullptr, *csg = nullptr;            // ... S = E' E (D x ldl), s = colsum(E), colsum(G)
   double *Xa = nullptr, *T = nullptr, *sq = nullptr;                // path derivative: (L')^-1, a product buffer (then L^-1),
                                                                     // partial sums of squares of the noise
@@ -1664,7 +1608,7 @@ static int fr_carve(vb_ctx* ctx, const FrRoute& r, const NoiseSlot& ns, int set,
                 o_cpart = carve((int64_t)(r.splits + 1) * slab), o_col = carve((int64_t)(r.n_rb + 1) * ldz),
                 o_fpart = carve((int64_t)r.n_fpart + (int64_t)r.n_rb * r.cs_gx + gemm_max_blocks(n, r.D) + (n * ldz) / 512 + 1),
                 o_r = carve(r.glm ? n * r.ldr : 0);
-  const int64_t o_mpart = r.fold_shape ? carve((int64_t)(r.msplits + 1) * slab) : 0, o_bvec = r.fold_shape ? carve(ldz) : 0;
+  const int64_t o_mf = r.fold_shape ? carve(slab) : 0, o_bvec = r.fold_shape ? carve(ldz) : 0;
   const int64_t o_xa = r.pd ? carve(slab) : 0, o_t = r.pd ? carve(slab) : 0, o_m2 = r.pd ? carve(256) : 0;
   // sum vector: the t family takes the full D x ldl matrix; the Gaussian family packs the lower triangle in
   // theta's own order, twice over when the all-reduce of one evaluation overlaps the kernels of the next
@@ -1679,7 +1623,7 @@ static int fr_carve(vb_ctx* ctx, const FrRoute& r, const NoiseSlot& ns, int set,
   b.lde = ns.ld;
   b.mu = base + o_mu, b.Lt = base + o_lt, b.Z = base + o_z, b.G = base + o_g, b.Cpart = base + o_cpart;
   b.colpart = base + o_col, b.fpart = base + o_fpart, b.Rm = base + o_r;
-  b.Mpart = base + o_mpart, b.bvec = base + o_bvec;
+  b.Mf = base + o_mf, b.bvec = base + o_bvec;
   // the folded evaluation writes neither Z nor G: S, s and colsum(G) live where G would (n rows of ldz, n >= d + 2); the
   // slabs of the Gram product and then the slabs of C are the split area's (csplits <= splits + 1)
   if (r.fold) b.Sg = b.G, b.svec = b.G + slab, b.csg = b.G + slab + ldz;
@@ -1816,29 +1760,27 @@ static int fr_model_glm(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const Mo
   return glm_grad_enqueue(ctx, st, m, b.Rm, r.ldr, Z, b.G, r.ldz, r.n, r.D);   // G = R X - Z / sd^2
 }
 
-// the folded evaluation (fr_route), its part that follows the parameter: M = L' P and b = P (mu - m)
+// the folded evaluation (fr_route), its product that follows the parameter alone: M = L' P
 static int fr_model_folded(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelDev& m) {
   hipStream_t st = ctx->stream;
-  const int D = r.D, msplits = r.msplits;
-  double* Mres = msplits > 1 ? b.Mpart + (int64_t)msplits * r.slab : b.Mpart;
-  // M[r][j] = sum_{k >= r} Lt[r][k] P[k][j]
+  const int D = r.D;
+  // M[r][j] = sum_{k >= r} Lt[r][k] P[k][j]: 64 x 32 tiles, row blocks b and T - 1 - b by one workgroup -- equal work per
+  // workgroup with the k range unsplit, so the launch writes M itself (D = 1024: 256 workgroups, one per CU).  Three LDS
+  // stages: a workgroup alone on its CU has nothing but its own prefetch to cover the operands' latency (two stages:
+  // 4 us more per evaluation)
   const GemmArgs gm = gemm_product(b.Lt, r.ldl, m.p1, m.ldp, D, D, D, 4);
-  gemm_f64_launch<true>(st, gm, msplits, r.n_cu, EpiSplitSlab{b.Mpart, r.ldz, r.slab}, 4);      // 64 x 64 tiles, two stages
-  const int ks = (int)round_up((D + msplits - 1) / msplits, kGemmBK);                          // (the launcher's k_split)
-  const int nb_sum = msplits > 1 ? D * (int)((r.ldz / 2 + 255) / 256) : 0, nb_b = (D + 7) / 8;
-  hipLaunchKernelGGL(fr_fold_msum_kernel, dim3((unsigned)(nb_sum + nb_b)), dim3(256), 0, st, (const double*)b.Mpart, msplits,
-                     r.slab, D, r.ldz, ks, 64, Mres, nb_b, m.p1, (int64_t)m.ldp, (const double*)b.mu, m.p0, b.bvec);
+  gemm_f64_launch<true, true>(st, gm, 1, r.n_cu, EpiSplitSlab{b.Mf, r.ldz, r.slab});
   VB_HIP(ctx, hipGetLastError());
   return VB_OK;
 }
 
 // ... and its part that follows the noise: S = E' E and s = colsum(E) (the Gram product, timed as VB_PROF_FR_GRAD_GEMM:
-// the gradient product's shape), colsum(G) = -s' M - n b', then the slabs of C = -tril(M' S) - b s' with one partial of
-// sum L o tril(C) per tile and split.  Returns in *tiles3 the number of output tiles of the C product.
-static int fr_grad_folded(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, unsigned* tiles3) {
+// the gradient product's shape), b = P (mu - m) and colsum(G) = -s' M - n b', then the slabs of C = -tril(M' S) - b s' with
+// one partial of sum L o tril(C) per tile and split.  Returns in *tiles3 the number of output tiles of the C product.
+static int fr_grad_folded(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelDev& m, unsigned* tiles3) {
   hipStream_t st = ctx->stream;
   const int D = r.D;
-  const double* M = r.msplits > 1 ? b.Mpart + (int64_t)r.msplits * r.slab : b.Mpart;
+  const double* M = b.Mf;
   GemmArgs gs = gemm_product(b.E, b.lde, b.E, b.lde, D, D, (int)r.n, 2);
   prof_events(ctx, &gs.ev0, &gs.ev1, 1, VB_PROF_FR_GRAD_GEMM);
   if (r.cfg3 == 2) VB_TRY(tri2_tile_map(ctx, D, 128, 64, &gs.tile_map, &gs.tile_blocks));
@@ -1846,8 +1788,8 @@ static int fr_grad_folded(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, unsign
   VB_HIP(ctx, hipGetLastError());
   const int nb_cs = (D + 7) / 8, nb_s = (int)((r.ldz + 255) / 256), tiles = (D + 31) / 32;
   hipLaunchKernelGGL(fr_fold_ssum_kernel, dim3((unsigned)(nb_cs + nb_s + tiles * (tiles + 1) / 2)), dim3(256), 0, st,
-                     (const double*)b.Cpart, r.splits, r.slab, D, r.ldl, (const double*)b.colpart, r.ldz, M,
-                     (const double*)b.bvec, (double)r.n, nb_cs, nb_s, b.Sg, b.svec, b.csg);
+                     (const double*)b.Cpart, r.splits, r.slab, D, r.ldl, (const double*)b.colpart, r.ldz, M, m.p1,
+                     (int64_t)m.ldp, (const double*)b.mu, m.p0, (double)r.n, nb_cs, nb_s, b.Sg, b.svec, b.bvec, b.csg);
   VB_HIP(ctx, hipGetLastError());
   // C[i][j] = sum_k M[k][i] S[k][j]: the gradient product's form, lower tiles, split over k
   GemmArgs gc = gemm_product(M, r.ldz, b.Sg, r.ldl, D, D, D, 2);
@@ -1926,10 +1868,11 @@ static int fr_score(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelD
 
 // GEMM 3: C[i][j] = sum_n G[n][i] E[n][j]: lower-triangular tiles (all tiles for the t family), split over the sample
 // axis.  Returns in *tiles3 the number of output tiles of the launch.
-static int fr_grad_product(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const double* G, unsigned* tiles3) {
+static int fr_grad_product(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelDev& m, const double* G,
+                           unsigned* tiles3) {
   hipStream_t st = ctx->stream;
   *tiles3 = 0;
-  if (r.fold) return fr_grad_folded(ctx, r, b, tiles3);      // (no G: from the noise's Gram matrix)
+  if (r.fold) return fr_grad_folded(ctx, r, b, m, tiles3);     // (no G: from the noise's Gram matrix)
   if (!r.grad_launch) return VB_OK;
   GemmArgs g3 = gemm_product(G, r.ldz, b.E, b.lde, r.D, r.D, (int)r.n, r.tri3);
   prof_events(ctx, &g3.ev0, &g3.ev1, 1, VB_PROF_FR_GRAD_GEMM);
@@ -2060,7 +2003,7 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
     VB_TRY(fr_colpass(ctx, r, b, m, G, Z, r.two_passes ? 0 : r.fmode, r.colpass_keeps_f ? b.fpart : b.fpart + r.n_fpart,
                       row_scale));
   else if (row_scale) VB_TRY(fr_rowscale(ctx, r, G, row_scale));
-  VB_TRY(fr_grad_product(ctx, r, b, G, &tiles3));
+  VB_TRY(fr_grad_product(ctx, r, b, m, G, &tiles3));
 
   if (mvt) return fr_finish_mvt(ctx, r, b, sums_out);
   const int n_fpart_red = r.fold ? (int)tiles3 * r.csplits : r.f_per_tile ? (int)tiles2 : r.n_fpart;

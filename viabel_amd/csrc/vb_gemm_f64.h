@@ -53,10 +53,10 @@ struct GemmArgs {
                     // 3: B[k][j] == 0 for k < j (the mirror image of 1; LDS-DMA kernel, otherwise computed densely)
                     // 4: A[m][k] == 0 for k < m, A given as A[m][k] (an upper-triangular left factor: M = L' P of the
                     //    folded full-rank evaluation): the k range of row block bm starts at its first row rounded down
-                    //    to a slab, row block 0 -- the longest range -- is dispatched first.  May be split over k: the
-                    //    launcher then lists on the grid's x axis only the (row block, split) pairs with a k range
-                    //    (tri4_splits; gridDim.z = 1), so slab z of C is NOT written for the row blocks that start at
-                    //    or beyond the end of split z (LDS-DMA kernel, otherwise computed densely)
+                    //    to a slab, row block 0 -- the longest range -- is dispatched first.  The launcher's TRI4_PAIRS
+                    //    gives one workgroup row blocks b and tiles_m - 1 - b of a column tile, whose k ranges add up to
+                    //    the same length for every b (gemm_f64_dma_pair_kernel).  (LDS-DMA kernel, otherwise computed
+                    //    densely)
   int k_split = 0;  // K range per blockIdx.z (multiple of kGemmBK); splits = gridDim.z
   // batch mode (batch != 0): blockIdx.z selects one of gridDim.z independent products of the same shape -- operand
   // z starts batch_a / batch_b doubles after operand z - 1, every product runs over the whole K range and the
@@ -68,7 +68,6 @@ struct GemmArgs {
   // same XCD (block x runs on XCD x % 8 and each XCD has its own L2)
   const int* tile_map = nullptr;
   int tile_blocks = 0;
-  int tri4_splits = 0;      // tri_mode 4 with a split k range: the number of splits (set by the launcher)
   // split products, optional (LDS-DMA kernel; the launcher clears it unless gridDim.z % 8 == 0): the workgroups of ONE split
   // -- which read the same k range of both operands -- are dispatched to ONE XCD.  Workgroups go to the XCDs round robin
   // in linear order (x fastest), so the gridDim.x tiles of a split land on all eight L2s and every L2 streams every
@@ -415,8 +414,11 @@ inline bool gemm_uses_dma(const GemmArgs& g) {
   return g.K % kGemmBK == 0 && g.M > 0 && g.N > 0;
 }
 
+// TRI4_PAIRS (an unsplit tri_mode 4 product, plain-store epilogue): 64 x 32 tiles with three LDS stages whatever `cfg` says,
+// row blocks b and tiles_m - 1 - b of a column tile by one workgroup (gemm_f64_dma_pair_kernel; with two stages the
+// M = L' P product of the folded full-rank evaluation took 39.5 instead of 35.7 us)
 // returns gridDim.x of the launch (the number of output tiles; reducing epilogues write one partial per tile and split)
-template <bool A_KCONTIG, class Epi>
+template <bool A_KCONTIG, bool TRI4_PAIRS = false, class Epi>
 inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu, const Epi& epi, int cfg = 0,
                                 int flags = 0) {
   // 64 x 32 tiles: only where the result cannot depend on the tiling (no per-tile partial sums, no column sums)
@@ -464,6 +466,9 @@ inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu
       if (kNarrowAuto && dma && g.tri_mode == 0 && !g.batch && gemm_count_blocks(g, 64, 64) * splits <= (long)n_cu) cfg = 7;
     }
   }
+  static_assert(!TRI4_PAIRS || kNarrowAuto, "paired row blocks: A[m][k], an epilogue that only stores");
+  const bool pairs = TRI4_PAIRS && g.tri_mode == 4 && splits == 1;      // (tri_mode 4 withdrawn above: the dense launch)
+  if (pairs) cfg = 7;
   if (!kNarrowOk && cfg >= 7) cfg = 4;
   if (!dma && cfg > 3) cfg = (cfg == 4 || cfg >= 7) ? 3 : cfg == 6 ? 1 : 2;
   const int bm_rows = (cfg == 3 || cfg == 4 || cfg >= 7) ? 64 : 128, bn_cols = cfg >= 7 ? 32 : (cfg == 1 || cfg == 6) ? 128 : 64;
@@ -471,12 +476,7 @@ inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu
   g.tiles_n = gemm_tiles(g.N, bn_cols);
   if (splits % 8 != 0 || g.batch) g.xcd_group = 0;
   dim3 grid(g.tile_map ? (unsigned)g.tile_blocks : (unsigned)gemm_count_blocks(g, bm_rows, bn_cols), 1, (unsigned)splits);
-  if (g.tri_mode == 4 && splits > 1) {      // only the (row block, split) pairs that have a k range, heaviest row block first
-    g.tri4_splits = splits;
-    long items = 0;
-    for (int bm = 0; bm < g.tiles_m; ++bm) items += (long)(splits - (bm * bm_rows / kGemmBK * kGemmBK) / g.k_split) * g.tiles_n;
-    grid = dim3((unsigned)items, 1, 1);
-  }
+  if (pairs) grid = dim3((unsigned)((g.tiles_m + 1) / 2 * g.tiles_n), 1, 1);      // one workgroup per (pair of row blocks, column tile)
   // (triangular k ranges: the tiles of a CU differ in length anyway, and the alternation costs 1 - 3 us there --
   // 4096 x 768 x 768: 55.5 -> 52.7 us, 512: 30.1 -> 29.1 us, 1024: unchanged, tools/gemm_bench.hip with it switched off)
   g.prio_div = (g.tri_mode != 1 && g.tri_mode != 3 && g.tri_mode != 4) ? n_cu : 0;
@@ -487,6 +487,12 @@ inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu
     else if (cfg == 4) gemm_f64_dma_launch<A_KCONTIG, 2, 8, 2, Epi>(st, g, grid, epi);
     else if (cfg == 6) gemm_f64_dma_launch<A_KCONTIG, 4, 16, 2, Epi>(st, g, grid, epi);
     else if (cfg >= 7) {
+      if constexpr (TRI4_PAIRS) {
+        if (pairs) {
+          gemm_f64_dma_pair_launch<2, 4, 3, Epi>(st, g, grid, epi);
+          return grid.x;
+        }
+      }
       if constexpr (kNarrowOk) {
         if (cfg == 7) gemm_f64_dma_launch<A_KCONTIG, 2, 4, 3, Epi>(st, g, grid, epi);
         else gemm_f64_dma_launch<A_KCONTIG, 2, 4, 2, Epi>(st, g, grid, epi);

@@ -42,8 +42,7 @@ struct GemmNoDep {
 // One output tile of the product: block x of a launch with gx blocks per split, split (or batch index) bz.
 template <bool A_KCONTIG, int AF, int NB, int STAGES, class Epi, class Dep>
 __device__ __forceinline__ void gemm_f64_dma_tile(const GemmArgs& g, const Epi& epi, const Dep& dep, const int bx,
-                                                  const int bz_in, const int gx) {
-  int bz = bz_in;
+                                                  const int bz, const int gx) {
   constexpr int BM = 32 * AF, BN = 8 * NB;
   constexpr int kStages = STAGES;
   static_assert(STAGES == 2 || STAGES == 3, "two or three LDS stages");
@@ -93,21 +92,6 @@ __device__ __forceinline__ void gemm_f64_dma_tile(const GemmArgs& g, const Epi& 
 #ifdef VB_GEMM_CLOCK
     if (bn < g.dbg_bn_min || bn > g.dbg_bn_max) return;
 #endif
-  } else if (g.tri_mode == 4 && g.tri4_splits > 1) {
-    // split triangular left factor: the grid's x axis lists only the (row block, split) pairs whose k range is not
-    // empty (GemmArgs::tri4_splits) -- equal pieces of work, so the workgroups a CU ends up with add up evenly
-    int idx = bx;
-    bm = 0;
-    int z0 = 0;
-    for (;;) {
-      z0 = (bm * BM / kGemmBK * kGemmBK) / g.k_split;
-      const int cnt = (g.tri4_splits - z0) * g.tiles_n;
-      if (idx < cnt || bm == g.tiles_m - 1) break;
-      idx -= cnt;
-      ++bm;
-    }
-    bz = z0 + idx / g.tiles_n;
-    bn = idx % g.tiles_n;
   } else if (g.tri_mode == 4) {      // row block 0 has the longest k range: row blocks in ascending order
     bm = bx / g.tiles_n;
     bn = bx % g.tiles_n;
@@ -551,6 +535,54 @@ inline void gemm_f64_dma_launch(hipStream_t st, const GemmArgs& g, dim3 grid, co
   }
   hipExtLaunchKernelGGL((gemm_f64_dma_kernel<A_KCONTIG, AF, NB, STAGES, Epi>), grid, dim3(256), lds, st, g.ev0, g.ev1,
                         0, g, epi);
+}
+
+// tri_mode 4, row blocks in pairs: the k range of row block b is the (tiles_m - b) blocks from its first row to K, so the
+// ranges of row blocks b and tiles_m - 1 - b add up to tiles_m + 1 blocks whatever b is.  Workgroup (pair, column tile)
+// runs the tile of row block `pair` and then, for the same column tile, the tile of row block tiles_m - 1 - pair, each
+// over its whole k range: every workgroup carries the same work (the middle block of an odd tiles_m, run once, carries
+// about half), every entry of C is written once by the one accumulator that summed it, and there are no split slabs to
+// add.  gridDim.x = ((tiles_m + 1) / 2) * tiles_n, set by the launcher.
+// The two passes share the LDS stages.  A pass ends with s_waitcnt(0) and a barrier in front of its epilogue: once a wave
+// is past that barrier, every wave's fragment reads have returned and every wave's LDS-DMA has landed, and the plain
+// epilogues admitted here do not touch LDS -- so no DMA of pass two can land in a stage that a wave of pass one still
+// reads, and nothing of pass one is in flight into a stage that pass two fills.  What pass one does leave in flight are
+// its epilogue's global stores: they sit on the same counter as the DMAs, and pass two's counted waits (vmcnt(UPW): "only
+// my newest slab is outstanding") must count DMAs only, so each wave waits for its stores between the passes.
+//
+// (GemmNoDep under a name of its own: hipcc accepts one specialisation of the tile body in one kernel only -- called from a
+// second kernel, the same template arguments are rejected as a substitution failure)
+struct GemmPairNoDep : GemmNoDep {};
+
+template <int AF, int NB, int STAGES, class Epi>
+__global__ void __launch_bounds__(256, AF * NB > 32 ? (STAGES > 2 ? 1 : 2) : (AF * NB > 16 || STAGES > 2 ? 2 : 4))
+    gemm_f64_dma_pair_kernel(const GemmArgs g, const Epi epi) {
+  static_assert(!EpiReduces<Epi>::value && !EpiColsum<Epi>::value && !EpiRowSums<Epi>::value,
+                "the epilogue between the passes must leave LDS alone");
+  const int pair = (int)blockIdx.x / g.tiles_n, bn = (int)blockIdx.x % g.tiles_n;
+  const int mirror = g.tiles_m - 1 - pair;
+  const int passes = mirror > pair ? 2 : 1;
+#pragma unroll 1
+  for (int pass = 0; pass < passes; ++pass) {
+    const int bm = pass == 0 ? pair : mirror;
+    const int bx = bm * g.tiles_n + bn, bz = 0;      // (tri_mode 4 reads the row block and the column tile back from bx)
+    gemm_f64_dma_tile<true, AF, NB, STAGES, Epi, GemmPairNoDep>(g, epi, GemmPairNoDep{}, bx, bz, (int)gridDim.x);
+    __asm__ volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0);
+    __asm__ volatile("" ::: "memory");
+  }
+}
+
+template <int AF, int NB, int STAGES, class Epi>
+inline void gemm_f64_dma_pair_launch(hipStream_t st, const GemmArgs& g, dim3 grid, const Epi& epi) {
+  constexpr size_t lds = (size_t)STAGES * (32 * AF * kGemmBK + kGemmBK * 8 * NB) * sizeof(double);
+  static bool configured = false;
+  if (!configured) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f64_dma_pair_kernel<AF, NB, STAGES, Epi>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    configured = true;
+  }
+  hipExtLaunchKernelGGL((gemm_f64_dma_pair_kernel<AF, NB, STAGES, Epi>), grid, dim3(256), lds, st, g.ev0, g.ev1, 0, g, epi);
 }
 
 }  // namespace vb
