@@ -87,6 +87,18 @@ typedef struct vb_ctx vb_ctx;
                                   legal; noise_sd is read by VB_GLM_GAUSSIAN only.  vb_set_model checks every pointer and
                                   index and that the CSC form is the transpose of the CSR form.  Taken by every route that
                                   takes a VB_MODEL_SOURCE target, like VB_MODEL_SOFTMAX */
+#define VB_MODEL_MINIBATCH_GLM 9 /* the regression target VB_MODEL_LOGISTIC (any VB_GLM_* likelihood, D = p) evaluated on a
+                                  random BATCH of B observations, the likelihood scaled by n_data / B: batch number t gives
+                                  f_t(theta) = (n_data / B) sum_{j in batch t} l(y_j, x_j' theta) + log N(theta; 0, sd) + C
+                                  with C the full-data constant of the likelihood.  The batch is a pure function of
+                                  (seed, t): positions t B .. t B + B - 1 of a stream whose position q is slot q mod n_data
+                                  of epoch q div n_data; the slot's observation is the slot itself (order 0) or a keyed
+                                  permutation of the epoch (order 1: a Philox-keyed Feistel network, cycle-walked).
+                                  dparams=[X(n_data x p)|y(n_data)|prior_sd|noise_sd],
+                                  iparams=[n_data, B, link (VB_GLM_*), order, seed (the 64 bits as an int64)];
+                                  1 <= B <= n_data < 2^31.  t is the context's batch counter (vb_minibatch_set_batch; 0
+                                  after vb_set_model), which the device-resident fits advance by one per iteration.
+                                  ExclusiveKL routes only take it meaningfully: the density changes with t */
 /* likelihoods of VB_MODEL_LOCSCALE */
 #define VB_LOCSCALE_GAUSSIAN 0
 #define VB_LOCSCALE_STUDENT_T 1
@@ -522,6 +534,18 @@ int vb_locscale_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, do
  * draw s (s x d row-major, d = p) as a NORMALISED density (the Poisson -log y_i!, the Gaussian -log noise_sd - log(2 pi) / 2
  * included), the prior not.  VB_ERR_STATE without a bound model, VB_ERR_UNSUPPORTED for any other model.            */
 int vb_sparse_glm_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out);
+/* The same for the bound VB_MODEL_MINIBATCH_GLM target and the CURRENT batch (the context's batch counter): ll_out is
+ * s x B, ll_out[s * B + i] = log p(y_j | x_j' theta_s) of the batch's i-th observation j as a NORMALISED density, unscaled
+ * (no n_data / B), the prior not included.  VB_ERR_STATE without a bound model, VB_ERR_UNSUPPORTED for any other model. */
+int vb_minibatch_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out);
+/* The batch counter of the bound VB_MODEL_MINIBATCH_GLM target: every evaluation enqueued from now on uses batch t
+ * (0 <= t, (t + 1) B < 2^62).  The counter is passed to the kernels by value when they are enqueued.  vb_set_model
+ * resets it to 0; vb_fit and vb_flow_fit add one per iteration.  VB_ERR_STATE unless such a target is bound.        */
+int vb_minibatch_set_batch(vb_ctx* ctx, int64_t t);
+int vb_minibatch_get_batch(vb_ctx* ctx, int64_t* t);
+/* out[0 .. B): the observation indices of batch t of the bound VB_MODEL_MINIBATCH_GLM target, computed by the index
+ * kernel the evaluations use and downloaded; the batch counter is not changed.                                      */
+int vb_minibatch_indices(vb_ctx* ctx, int64_t t, int64_t* out);
 int vb_glm_psis_loo(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const double* log_ratios,
                     const double* log_w, double reff, double* loo, double* khat, double* lpd);
 /* vb_glm_predict: posterior prediction with the bound regression target (VB_MODEL_LOGISTIC, any VB_GLM_* likelihood; the

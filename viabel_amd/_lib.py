@@ -25,9 +25,11 @@ MODEL_GAUSS_DIAG, MODEL_FUNNEL, MODEL_GAUSS_FULL, MODEL_LOGISTIC, MODEL_SOURCE, 
 MODEL_MULTILEVEL = 6
 MODEL_LOCSCALE = 7
 MODEL_SPARSE_GLM = 8
+MODEL_MINIBATCH_GLM = 9
 # targets that hand every pipeline finished rows (f, grad f): a softmax, multilevel, location-scale or sparse regression
-# target goes wherever a source model goes
-MODELS_WITH_ROWS = (MODEL_SOURCE, MODEL_SOFTMAX, MODEL_MULTILEVEL, MODEL_LOCSCALE, MODEL_SPARSE_GLM)
+# target goes wherever a source model goes; the minibatch target forms its rows the same way (the objectives decide what
+# may take a density that changes from batch to batch)
+MODELS_WITH_ROWS = (MODEL_SOURCE, MODEL_SOFTMAX, MODEL_MULTILEVEL, MODEL_LOCSCALE, MODEL_SPARSE_GLM, MODEL_MINIBATCH_GLM)
 # doubles of predictor matrix one row chunk of the softmax pipeline may hold (csrc/vb_common.h: kSoftmaxChunkDoubles);
 # a chunk is max(8, SOFTMAX_CHUNK_DOUBLES // (n_classes * round_up(n_data, 16))) rows
 SOFTMAX_CHUNK_DOUBLES = 16 << 20
@@ -49,6 +51,16 @@ def sparse_chunk_rows(n_data, p):
     """Samples per chunk of the sparse regression pipeline for an ``(n_data, p)`` design: the arithmetic of
     ``sparse_chunk_rows`` in ``csrc/vb_common.h``."""
     return min(8192, max(64, SPARSE_CHUNK_DOUBLES // (2 * (int(n_data) + int(p))) // 64 * 64))
+
+
+# doubles of the term and the residual matrix together per chunk of samples of the minibatch pipeline (kMinibatchChunkDoubles)
+MINIBATCH_CHUNK_DOUBLES = 16 << 20
+
+
+def minibatch_chunk_rows(batch_size):
+    """Samples per chunk of the minibatch regression pipeline for batches of ``batch_size`` observations: the arithmetic of
+    ``minibatch_chunk_rows`` in ``csrc/vb_common.h``."""
+    return max(8, MINIBATCH_CHUNK_DOUBLES // (2 * ((int(batch_size) + 15) // 16 * 16)))
 
 
 GLM_BERNOULLI_LOGIT, GLM_POISSON, GLM_GAUSSIAN = range(3)
@@ -172,6 +184,10 @@ SIGNATURES = {
     'vb_multilevel_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
     'vb_locscale_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
     'vb_sparse_glm_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
+    'vb_minibatch_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
+    'vb_minibatch_set_batch': (ctypes.c_int, [_ctx_p, ctypes.c_int64]),
+    'vb_minibatch_get_batch': (ctypes.c_int, [_ctx_p, _c_int64_p]),
+    'vb_minibatch_indices': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_void_p]),
     'vb_glm_psis_loo': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p,
                                        ctypes.c_double, _c_double_p, _c_double_p, _c_double_p]),
     'vb_glm_predict': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p,
@@ -590,7 +606,15 @@ class Engine:
         model_id, dim, dparams, iparams = spec[:4]
         # models hand out the same (cached) parameter arrays every time: identity is the cache key
         key = (model_id, dim, id(dparams), id(iparams)) + tuple(id(x) for x in spec[4:])
+        # a minibatch target's spec = (id, dim, dparams, iparams, [batch counter]): the model object owns the counter (the
+        # engine's is lost with the binding), and every binding -- a repeated one included -- pushes it
+        minibatch = model_id == MODEL_MINIBATCH_GLM
+        if minibatch and self.n_ranks > 1:
+            raise NotImplementedError('MinibatchRegressionModel on a sharded engine ({} ranks): every rank would have to '
+                                      'advance the same batch counter; not supported'.format(self.n_ranks))
         if key == self._model_key:
+            if minibatch:
+                self._check(self._lib.vb_minibatch_set_batch(self._ctx, int(spec[4][0])))
             return
         self._model_arrays = tuple(spec[2:])         # keep them alive so the ids stay unique
         if model_id == MODEL_SOURCE and isinstance(spec[4], MODEL_CALLBACK_TYPE):
@@ -611,6 +635,8 @@ class Engine:
             self._ctx, model_id, dim, _dptr(dparams) if dparams.size else None, dparams.size,
             iparams.ctypes.data_as(_c_int64_p) if iparams.size else None, iparams.size))
         self._model_key = key
+        if minibatch:
+            self._check(self._lib.vb_minibatch_set_batch(self._ctx, int(spec[4][0])))
 
     def model_logp(self, x):
         x = _f64(x)
@@ -789,6 +815,24 @@ class Engine:
         """``(S, n_data)`` normalised terms ``log p(y_i | x_i' theta)`` of the bound sparse regression target at the draws
         ``x`` (S x D)."""
         return self._pointwise('vb_sparse_glm_pointwise', x, n_data)
+
+    def minibatch_pointwise(self, x, batch_size):
+        """``(S, batch_size)`` normalised, unscaled terms ``log p(y_j | x_j' theta)`` of the current batch of the bound
+        minibatch regression target at the draws ``x`` (S x D), in batch order."""
+        return self._pointwise('vb_minibatch_pointwise', x, batch_size)
+
+    def minibatch_get_batch(self):
+        """The engine's batch counter of the bound minibatch regression target (a device fit has advanced it)."""
+        t = ctypes.c_int64(0)
+        self._check(self._lib.vb_minibatch_get_batch(self._ctx, ctypes.byref(t)))
+        return int(t.value)
+
+    def minibatch_indices(self, t, batch_size):
+        """The observation indices of batch ``t`` of the bound minibatch regression target as the index kernel computes
+        them: int64 ``(batch_size,)``."""
+        out = np.empty(int(batch_size), dtype=np.int64)
+        self._check(self._lib.vb_minibatch_indices(self._ctx, int(t), _dptr(out)))
+        return out
 
     def glm_psis_loo(self, x, n_data, log_ratios=None, log_w=None, reff=1.0):
         """PSIS-LOO of the bound regression target (``n_data`` observations) from the draws ``x``

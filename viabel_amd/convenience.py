@@ -12,7 +12,7 @@ from . import _lib
 from ._psis import _tail_size, batch_capacity, psislw, psisloo
 from .approximations import FullRankGaussian, MFGaussian, MFStudentT, NVPFlow
 from .diagnostics import all_diagnostics
-from .models import CallableModel, DeviceModel, LogisticRegressionModel, SourceModel
+from .models import CallableModel, DeviceModel, LogisticRegressionModel, SourceModel, refuse_minibatch
 from .objectives import ExclusiveKL, _stage_prior_noise
 from .optimization import FASO, RAABBVI, RMSProp
 
@@ -83,6 +83,7 @@ def vi_diagnostics(var_param, *, objective=None, model=None, approx=None, n_samp
         model, approx = objective.model, objective.approx
     if n_samples <= 0:
         raise ValueError('n_samples must be positive')
+    refuse_minibatch(model, 'vi_diagnostics')
     return _vi_diagnostics(var_param, model, approx, n_samples)
 
 
@@ -120,6 +121,7 @@ def psis_correction(var_param, model, approx, n_samples):
     (``convenience.py:166-169``).  For the mean-field families on an elementwise / funnel target the log
     weights never leave the GPU between their evaluation and the smoothing."""
     var_param = np.asarray(var_param, dtype=np.float64)
+    refuse_minibatch(model, 'psis_correction')
     if _on_device_weights(model, approx):
         eng = _lib.default_engine()
         eng.set_model(model.device_spec())
@@ -152,6 +154,7 @@ def _on_device_weights(model, approx):
 def samples_and_log_weights(var_param, model, approx, n_samples):
     """Samples from the approximation and their importance log weights (``convenience.py:176-179``);
     the model log density is evaluated on the GPU."""
+    refuse_minibatch(model, 'samples_and_log_weights')
     if isinstance(approx, NVPFlow) and isinstance(model, DeviceModel):
         # the flow's forward pass and the model on the device over the prior draws approx.sample would consume; log q
         # from the forward pass (log p0(z0) - sum s), which equals the inverse pass's up to rounding
@@ -197,6 +200,7 @@ def loo(var_param, *, objective=None, model=None, approx=None, n_samples=4000, R
         raise ValueError('n_samples must be at least 2')
     if not (Reff > 0):
         raise ValueError('Reff must be positive')
+    refuse_minibatch(model, 'loo')
     if not isinstance(model, LogisticRegressionModel):
         raise NotImplementedError(
             'loo needs a target with per-observation structure (LogisticRegressionModel, PoissonRegressionModel, '
@@ -257,6 +261,7 @@ def predict(var_param, *, objective=None, model=None, approx=None, X_new=None, y
         raise ValueError('n_samples must be at least 2 to smooth the weights')
     if not (Reff > 0):
         raise ValueError('Reff must be positive')
+    refuse_minibatch(model, 'predict')
     if not isinstance(model, LogisticRegressionModel):
         raise NotImplementedError(
             'predict covers LogisticRegressionModel, PoissonRegressionModel and LinearRegressionModel; {} has no '
@@ -304,6 +309,7 @@ def laplace_approximation(model, x0=None, max_iter=100, tol=1e-10, seed=1, rng='
     if not isinstance(model, DeviceModel):
         raise TypeError('laplace_approximation needs a viabel_amd device model (its gradient and Hessian are device code); '
                         'got {}'.format(type(model).__name__))
+    refuse_minibatch(model, 'laplace_approximation')
     found = model.find_mode(x0=x0, max_iter=max_iter, tol=tol)
     mode, H = found['mode'], found['hessian']
     d = model.dim

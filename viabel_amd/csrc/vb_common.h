@@ -112,12 +112,19 @@ struct ModelDev {
   int sp_n_seg[2] = {0, 0};
   int sp_n_split[2] = {0, 0};
   int64_t nnz = 0;
+  // VB_MODEL_MINIBATCH_GLM (vb_minibatch.hip): the flat regression target on batch t of the observations, the likelihood
+  // scaled by n_data / mb_size; p0 = X [n_data x ldp] (NO X'), p2 = y, dim = p, tau = prior_sd, link / aux.  A rows target as
+  // well: c0 stays 0, f0 holds the FULL data's likelihood constant and the prior's.  t is vb_ctx::mb_batch.
+  int64_t mb_size = 0;          // B
+  int mb_shuffle = 0;           // 1: slot -> observation through the epoch's permutation; 0: the slot itself
+  int mb_half_bits = 0;         // w: the permutation's Feistel network works on 2 w bits
+  uint64_t mb_seed = 0;         // its Philox key
 };
 
 // targets whose rows (f, grad f) are formed before a pipeline's streaming pass and loaded by it (model_rows_enqueue)
 __host__ __device__ __forceinline__ bool model_has_rows(int id) {
   return id == VB_MODEL_SOURCE || id == VB_MODEL_SOFTMAX || id == VB_MODEL_MULTILEVEL || id == VB_MODEL_LOCSCALE ||
-         id == VB_MODEL_SPARSE_GLM;
+         id == VB_MODEL_SPARSE_GLM || id == VB_MODEL_MINIBATCH_GLM;
 }
 
 // per-observation log-likelihood term (without constants) and its derivative with respect to eta = x' b
@@ -280,8 +287,16 @@ struct vb_ctx {
   vb::DeviceBuffer user_params;
   vb::DeviceBuffer glm_work;            // regression targets: split-K slabs of the gradient GEMM
   // the bound rows target's chunk workspace (softmax, multilevel, location-scale, sparse regression): one model is bound at
-  // a time, every call lays the buffer out from scratch and writes each piece before it reads it
+  // a time, every call lays the buffer out from scratch and writes each piece before it reads it (the minibatch target
+  // alone keeps something between calls: its gathered batch at the front, see mb_held)
   vb::DeviceBuffer target_work;
+  // VB_MODEL_MINIBATCH_GLM: the batch counter (vb_minibatch_set_batch; a device fit adds one per iteration), and which
+  // batch the gathered operands at the front of target_work hold: mb_held, gathered on the main stream at address
+  // mb_held_at (-1: none -- vb_set_model resets it, so another binding's batch is never taken for this one's; a gather
+  // on any other stream is not remembered)
+  int64_t mb_batch = 0, mb_held = -1;
+  const void* mb_held_at = nullptr;     // alias
+  size_t mb_held_bytes = 0;             // ... of an allocation of this size (a new one may return the old address)
   vb::DeviceBuffer hess_work;            // vb_glm_value_grad_hessian (vb_glm_hessian.hip): laid out from scratch by every call
   vb::DeviceBuffer hmc_work;             // vb_hmc_run (vb_hmc.hip): chain states, statistics and kept draws, laid out by every call
   vb::DeviceBuffer mvt_state;           // multivariate-t DIS: state samples X, scratch
@@ -509,7 +524,7 @@ void user_model_release(vb_ctx* ctx);
 int softmax_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
                          int64_t ldg, double* f);
 // rows of the bound target by whichever forms them: a source model's kernel, the softmax, the multilevel, the
-// location-scale or the sparse regression pipeline (vb_rows.hip)
+// location-scale, the sparse or the minibatch regression pipeline (vb_rows.hip)
 int model_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
                        int64_t ldg, double* f);
 // doubles of predictor matrix H one row chunk of the softmax pipeline may hold (mirrored by _lib.SOFTMAX_CHUNK_DOUBLES)
@@ -543,6 +558,18 @@ inline int64_t sparse_chunk_rows(int64_t n_data, int64_t p) {
   const int64_t rows = kSparseChunkDoubles / (2 * (n_data + p)) / 64 * 64;
   return rows < 64 ? 64 : rows > 8192 ? 8192 : rows;
 }
+// minibatch GLM target (vb_minibatch.hip), the same contract and the same alignment rules as the multilevel one; evaluates
+// batch ctx->mb_batch of the observations
+int minibatch_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G, int64_t ldg,
+                           double* f);
+// doubles of the term and the residual matrix together one row chunk of the minibatch pipeline may hold (mirrored by
+// _lib.MINIBATCH_CHUNK_DOUBLES): a chunk is max(8, kMinibatchChunkDoubles / (2 round_up(B, 16))) rows (mirrored by
+// _lib.minibatch_chunk_rows)
+constexpr int64_t kMinibatchChunkDoubles = (int64_t)16 << 20;
+inline int64_t minibatch_chunk_rows(int64_t batch_size) {
+  const int64_t rows = kMinibatchChunkDoubles / (2 * ((batch_size + 15) / 16 * 16));
+  return rows < 8 ? 8 : rows;
+}
 // The pointwise entry of a rows target (vb_rows.hip): the argument checks of `api_name` against the bound model, then the
 // draws x [s x d] in chunks -- each uploaded into ctx->target_work with row stride round_up(d, 16), evaluated by `body` into
 // a term matrix there and downloaded to ll_out [s x n_data].  `plan` lays the workspace out for s draws and makes the
@@ -550,6 +577,7 @@ inline int64_t sparse_chunk_rows(int64_t n_data, int64_t p) {
 struct RowsPointwisePlan {
   int64_t chunk = 0, total = 0;      // draws per chunk; doubles of workspace
   int64_t o_x = 0, o_ll = 0, ldl = 0;      // where the chunk's draws and its term matrix (row stride ldl) live
+  int64_t width = 0;                 // columns of the term matrix (0: the model's n_data)
 };
 using RowsPointwiseBody = std::function<int(int64_t rows, const double* X, int64_t ldx, double* LL, int64_t ldl)>;
 int rows_pointwise(vb_ctx* ctx, const char* api_name, int model_id, const char* target_name, const double* x, int64_t s,
@@ -561,7 +589,7 @@ int rows_pointwise(vb_ctx* ctx, const char* api_name, int model_id, const char* 
 int upload_model_params(vb_ctx* ctx, const std::vector<double>& dev, const double** base);      // vb_api.hip
 using SetModelFn = int(vb_ctx* ctx, int64_t dim, const double* dparams, size_t n_dparams, const int64_t* iparams,
                        size_t n_iparams);
-SetModelFn softmax_set_model, multilevel_set_model, locscale_set_model, sparse_set_model;
+SetModelFn softmax_set_model, multilevel_set_model, locscale_set_model, sparse_set_model, minibatch_set_model;
 struct LegacyFinish;
 // (defer != nullptr: the kernels are enqueued, the state is left untouched and *defer describes the finish -- exact path only,
 // VB_ERR_UNSUPPORTED otherwise)

@@ -117,6 +117,7 @@ struct FitRun {
   }
 
   int after_step(int64_t k) {      // iteration k's kernels (its step included) are enqueued on the main stream
+    if (ctx->model.id == VB_MODEL_MINIBATCH_GLM) ++ctx->mb_batch;      // the next iteration's batch, as the host loop counts
     if (!streamed) return VB_OK;
     if (k >= vb_ctx::kFitRing) VB_TRY(drain_one());      // the slot's previous tenant: iteration k - R
     const int slot = (int)(k % vb_ctx::kFitRing);

@@ -333,6 +333,7 @@ int model_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz
   if (ctx->model.id == VB_MODEL_MULTILEVEL) return multilevel_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
   if (ctx->model.id == VB_MODEL_LOCSCALE) return locscale_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
   if (ctx->model.id == VB_MODEL_SPARSE_GLM) return sparse_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
+  if (ctx->model.id == VB_MODEL_MINIBATCH_GLM) return minibatch_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
   return user_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
 }
 
@@ -350,7 +351,7 @@ int rows_pointwise(vb_ctx* ctx, const char* api_name, int model_id, const char* 
   VB_TRY(plan(&P));
   VB_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const int64_t nd = ctx->model.n_data, ldx = round_up(d, 16);
+  const int64_t nd = P.width > 0 ? P.width : ctx->model.n_data, ldx = round_up(d, 16);
   VB_TRY(ensure(ctx, ctx->target_work, (size_t)P.total * sizeof(double)));
   double* base = (double*)ctx->target_work.ptr;
   for (int64_t r0 = 0; r0 < s; r0 += P.chunk) {

@@ -6,7 +6,7 @@ pipeline the objectives use (``vb_hmc_run``, ``csrc/vb_hmc.hip``; ``DESIGN.md`` 
 import numpy as np
 
 from viabel_amd import _lib
-from viabel_amd.models import CallableModel, DeviceModel
+from viabel_amd.models import CallableModel, DeviceModel, refuse_minibatch
 
 __all__ = ['hmc']
 
@@ -85,6 +85,7 @@ def hmc(model, *, n_chains=256, n_warmup=300, n_draws=300, n_leapfrog=16, step_s
     passes ``init=res['last']``, ``step_size=res['step_size']``, ``n_warmup=0`` and ``stream_offset=res['next_stream']``.
     Runs on the calling process's engine; raises ``NotImplementedError`` for a ``CallableModel`` and for a sharded
     engine."""
+    refuse_minibatch(model, 'hmc')
     init, inv_mass, step_size = _check_arguments(model, n_chains, n_warmup, n_draws, n_leapfrog, step_size, target_accept,
                                                  jitter, init, inv_mass, var_param, approx, thin)
     if var_param is not None:

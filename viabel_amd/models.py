@@ -14,8 +14,8 @@ from . import _lib
 
 __all__ = ['Model', 'DeviceModel', 'GaussianModel', 'FunnelModel', 'CorrelatedGaussianModel',
            'LogisticRegressionModel', 'PoissonRegressionModel', 'LinearRegressionModel', 'SoftmaxRegressionModel',
-           'MultilevelRegressionModel', 'LocationScaleRegressionModel', 'SparseRegressionModel', 'SourceModel',
-           'CallableModel']
+           'MultilevelRegressionModel', 'LocationScaleRegressionModel', 'SparseRegressionModel',
+           'MinibatchRegressionModel', 'SourceModel', 'CallableModel']
 
 
 class Model(object):
@@ -947,3 +947,178 @@ class SparseRegressionModel(DeviceModel):
         argument of :func:`psisloo` (``psisloo(log_lik, log_ratios)`` is this model's route to LOO).  Normalised densities,
         without the prior (``vb_sparse_glm_pointwise``).  ``x``: (S, D), or (D,) for one draw."""
         return self._pointwise(x)
+
+
+_M32 = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+
+
+def _philox4x32_10_word0(c0, c1, c2, c3, k0, k1):
+    """Word 0 of Philox4x32-10 (Salmon et al., SC'11) on uint64 arrays holding 32-bit words: the generator of
+    ``csrc/vb_rng.h``, restated on the host for :meth:`MinibatchRegressionModel.batch_indices`."""
+    m0, m1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & _M32 for c in (c0, c1, c2, c3))
+    for r in range(10):
+        p0, p1 = m0 * c0, m1 * c2                       # 32 x 32 -> 64: no overflow in uint64
+        ka = np.uint64((k0 + 0x9E3779B9 * r) & 0xFFFFFFFF)
+        kb = np.uint64((k1 + 0xBB67AE85 * r) & 0xFFFFFFFF)
+        c0, c1, c2, c3 = (p1 >> _S32) ^ c1 ^ ka, p1 & _M32, (p0 >> _S32) ^ c3 ^ kb, p0 & _M32
+    return c0
+
+
+def refuse_minibatch(model, what):
+    """``NotImplementedError`` when ``model`` is a :class:`MinibatchRegressionModel`: ``what`` needs one fixed density."""
+    if isinstance(model, MinibatchRegressionModel):
+        raise NotImplementedError(
+            '{} needs one fixed log density; a MinibatchRegressionModel is a different density for every batch. Use '
+            'model.full_model(), the same data as a full-batch target'.format(what))
+
+
+class MinibatchRegressionModel(DeviceModel):
+    """The flat regression targets (:class:`LogisticRegressionModel`, :class:`PoissonRegressionModel`,
+    :class:`LinearRegressionModel`) evaluated on a random batch of ``batch_size`` of the ``n_data`` observations, the
+    likelihood scaled by ``n_data / batch_size``: doubly stochastic variational inference, whose cost per iteration does
+    not depend on ``n_data``.  ``likelihood`` is ``'logistic'`` (``y`` in ``{0, 1}``), ``'poisson'`` (``y >= 0``) or
+    ``'gaussian'`` (known ``noise_sd``); ``dim = p``.  Batch number ``t`` is the density::
+
+        f_t(theta) = (n_data / B) sum_{j in batch t} log p(y_j | x_j' theta)        without the likelihood's constants
+                     - |theta|^2 / (2 prior_sd^2) - p (log prior_sd + log(2 pi) / 2)
+                     + C                                the constants of ALL n_data observations, as the dense targets have
+
+    so that ``B = n_data`` gives ``full_model()``'s density and the mean of ``f_t`` over the batches of an epoch is
+    ``full_model()``'s exactly when ``B`` divides ``n_data``.  The batch is a pure function of ``(seed, t)``: batch ``t``
+    owns the positions ``t B .. t B + B - 1`` of an endless stream, position ``q`` is slot ``q mod n_data`` of epoch
+    ``q div n_data`` (a batch may straddle two epochs), and the slot's observation is the slot itself
+    (``order='sequential'``) or its image under a keyed permutation of the epoch (``order='shuffle'``: a 6-round Feistel
+    network over Philox, cycle-walked; ``DESIGN.md`` 4.23) -- every observation appears exactly once per epoch.
+    :meth:`batch_indices` restates it on the host.
+
+    ``model.batch`` is the number of the batch that ``model(x)``, ``model.grad(x)``, ``check_gradient`` and
+    ``pointwise_log_likelihood`` evaluate; they do not advance it.  One ``ExclusiveKL`` call uses one batch for everything
+    it evaluates and advances the counter by one; a device-resident fit advances it once per iteration.  The counter is
+    the model object's: models interleaved on one engine each keep their own sequence.
+
+    The device holds ``X`` once (no transpose).  Per evaluation an index kernel and a gather kernel form the batch's design
+    in both layouts, then the two fp64 MFMA products of the dense target run on ``B`` observations
+    (``csrc/vb_minibatch.hip``).  Taken by ``ExclusiveKL`` (both estimator forms) with every family, through ``bbvi``,
+    ``optimize``, ``FASO``, ``RAABBVI`` and the device-resident fit.  Everything that needs one fixed density raises
+    ``NotImplementedError`` and points to :meth:`full_model`: ``DISInclusiveKL`` and ``AlphaDivergence`` (a subsampled log
+    density inside an importance weight is biased), the RGE control variates, ``_hessian_vector_product``, ``hmc``,
+    ``find_mode``, ``hessian``, ``laplace_approximation``, ``vi_diagnostics``, ``loo``, ``predict``,
+    ``samples_and_log_weights`` and a sharded engine.  Not in the reference."""
+
+    _LINKS = _GLM_LINKS
+    _ORDERS = {'sequential': 0, 'shuffle': 1}
+    FEISTEL_ROUNDS = 6
+
+    def __init__(self, X, y, batch_size, likelihood='logistic', prior_sd=10.0, noise_sd=1.0, seed=0, order='shuffle'):
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1 or y.shape != (X.shape[0],):
+            raise ValueError('X must be (n_data, p) with n_data, p >= 1 and y (n_data,)')
+        if X.shape[0] >= 1 << 31:
+            raise ValueError('n_data must be below 2^31')
+        if isinstance(batch_size, (bool, np.bool_)) or not isinstance(batch_size, (int, np.integer)) \
+                or not 1 <= int(batch_size) <= X.shape[0]:
+            raise ValueError('batch_size must be an integer in [1, n_data = {}]; got {!r}'.format(X.shape[0], batch_size))
+        if likelihood not in self._LINKS:
+            raise ValueError("likelihood must be 'logistic', 'poisson' or 'gaussian'")
+        if order not in self._ORDERS:
+            raise ValueError("order must be 'shuffle' or 'sequential'")
+        if not prior_sd > 0 or not noise_sd > 0:
+            raise ValueError('prior_sd and noise_sd must be positive')
+        if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+            raise ValueError('seed must be an integer in [0, 2^64)')
+        _check_glm_response(likelihood, y)
+        self.X, self.y, self.likelihood, self.order = X, y, likelihood, order
+        self.prior_sd, self.noise_sd, self.seed = float(prior_sd), float(noise_sd), int(seed)
+        self._batch_size = int(batch_size)
+        self._batch_box = [0]        # shared with the engine binding through device_spec (Engine.set_model pushes it)
+        super().__init__(X.shape[1])
+
+    def _build_spec(self):
+        seed = self.seed - (1 << 64) if self.seed >= 1 << 63 else self.seed      # the 64 bits as an int64
+        return (_lib.MODEL_MINIBATCH_GLM, self._dim,
+                np.concatenate([self.X.ravel(), self.y, [self.prior_sd, self.noise_sd]]),
+                np.array([self.X.shape[0], self._batch_size, self._LINKS[self.likelihood], self._ORDERS[self.order], seed],
+                         dtype=np.int64),
+                self._batch_box)
+
+    @property
+    def n_data(self):
+        return self.X.shape[0]
+
+    @property
+    def batch_size(self):
+        return self._batch_size
+
+    @property
+    def batch(self):
+        """Number of the batch the next evaluation uses (settable; setting it back replays the same batches)."""
+        return self._batch_box[0]
+
+    @batch.setter
+    def batch(self, t):
+        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)) \
+                or not 0 <= int(t) < (1 << 62) // self._batch_size - 1:
+            raise ValueError('batch must be an integer in [0, 2^62 / batch_size - 1); got {!r}'.format(t))
+        self._batch_box[0] = int(t)
+
+    @property
+    def epoch(self):
+        """Epoch of the first position of batch ``self.batch``: ``batch * batch_size // n_data``."""
+        return self.batch * self._batch_size // self.n_data
+
+    def batch_indices(self, t=None):
+        """The observations of batch ``t`` (None: ``self.batch``) in batch order, int64 ``(batch_size,)``: the host
+        restatement of the engine's index kernel (``vb_minibatch_indices`` gives the device's)."""
+        t = self.batch if t is None else t
+        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)) \
+                or not 0 <= int(t) < (1 << 62) // self._batch_size - 1:
+            raise ValueError('t must be an integer in [0, 2^62 / batch_size - 1); got {!r}'.format(t))
+        n, B = self.n_data, self._batch_size
+        q = np.uint64(int(t) * B) + np.arange(B, dtype=np.uint64)
+        slots, epochs = q % np.uint64(n), q // np.uint64(n)
+        if self.order == 'sequential':
+            return slots.astype(np.int64)
+        w = max(1, ((n - 1).bit_length() + 1) // 2)
+        ws, mask = np.uint64(w), np.uint64((1 << w) - 1)
+        k0, k1 = self.seed & 0xFFFFFFFF, self.seed >> 32
+        x = slots.copy()
+        todo = np.arange(B)
+        while todo.size:           # cycle walk: the elements whose image is not below n_data yet
+            e = epochs[todo]
+            left, right = x[todo] >> ws, x[todo] & mask
+            for r in range(self.FEISTEL_ROUNDS):
+                f = _philox4x32_10_word0(right, np.uint64(r), e & _M32, e >> _S32, k0, k1) & mask
+                left, right = right, left ^ f
+            x[todo] = (left << ws) | right
+            todo = todo[x[todo] >= np.uint64(n)]
+        return x.astype(np.int64)
+
+    def full_model(self):
+        """The same data as a full-batch target: the :class:`LogisticRegressionModel`, :class:`PoissonRegressionModel`
+        or :class:`LinearRegressionModel` on this model's ``X`` (not copied) and ``y``."""
+        if self.likelihood == 'logistic':
+            return LogisticRegressionModel(self.X, self.y, self.prior_sd)
+        if self.likelihood == 'poisson':
+            return PoissonRegressionModel(self.X, self.y, self.prior_sd)
+        return LinearRegressionModel(self.X, self.y, self.prior_sd, self.noise_sd)
+
+    def pointwise_log_likelihood(self, x):
+        """``log p(y_j | x_j' theta_s)`` of the observations ``j`` of batch ``self.batch``, in batch order, for every draw
+        (row of ``x``): ``(S, batch_size)``.  Normalised densities, NOT scaled by ``n_data / batch_size``, without the
+        prior (``vb_minibatch_pointwise``).  ``x``: (S, D), or (D,) for one draw."""
+        x, _ = self._rows(x)
+        eng = _lib.default_engine()
+        eng.set_model(self.device_spec())
+        return eng.minibatch_pointwise(x, self._batch_size)
+
+    def hessian(self, x):
+        refuse_minibatch(self, 'hessian()')
+
+    def _value_grad_hessian(self, x, want_hessian=True):
+        refuse_minibatch(self, 'find_mode() / laplace_approximation()')
+
+    def find_mode(self, x0=None, max_iter=100, tol=1e-10):
+        refuse_minibatch(self, 'find_mode()')

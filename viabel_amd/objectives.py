@@ -24,7 +24,7 @@ from scipy import special as _special
 from . import _lib
 from .approximations import (MFGaussian, MFStudentT, FullRankGaussian, MultivariateT, LRGaussian, NVPFlow, symmetric_eig,
                              symmetric_root)
-from .models import DeviceModel, SourceModel, as_device_model
+from .models import DeviceModel, MinibatchRegressionModel, SourceModel, as_device_model
 
 __all__ = [
     'VariationalObjective',
@@ -47,6 +47,13 @@ _LR_SLOT = 3       # low-rank family: the n x k block of its noise (slot 2 belon
 # kind, and a mean-field state's kept-weights steps read their residuals straight out of its slot -- a refresh of another
 # kind must not write there
 _DIS_SLOTS = {0: 4, 1: _DIS_SLOT, 2: 5}
+
+
+def _refuse_minibatch_weights(model, what):
+    if isinstance(model, MinibatchRegressionModel):
+        raise NotImplementedError(
+            '{} puts the log density inside an importance weight, and a subsampled log density there is biased (the weight '
+            'is not linear in it); a MinibatchRegressionModel goes with ExclusiveKL only. Use model.full_model()'.format(what))
 
 
 def shard_rows(n, n_ranks, rank):
@@ -340,11 +347,21 @@ class ExclusiveKL(StochasticVariationalObjective):
                              "'loo_diag_approx', 'loo_direct_approx' or None object.")
         super().__init__(approx, model, num_mc_samples)
 
+    def __call__(self, var_param):
+        out = super().__call__(var_param)
+        if isinstance(self._model, MinibatchRegressionModel):
+            self._model.batch += 1      # one batch per call, whatever the call evaluated on it; the next call takes the next
+        return out
+
     def _update_objective_and_grad(self):
         approx = self.approx
         self._require_device_model()
         flags = _lib.FLAG_PATH_DERIV if self._use_path_deriv else 0
         cv_mode = _lib.CV_MODES[self.hessian_approx_method]
+        if cv_mode != 0 and isinstance(self.model, MinibatchRegressionModel):
+            raise NotImplementedError(
+                'the RGE control variates need the Hessian of one fixed log density at the mean; a MinibatchRegressionModel '
+                'is a different density for every batch. Use hessian_approx_method=None, or model.full_model()')
 
         if isinstance(approx, (MFGaussian, MFStudentT)):
             def objective_and_grad(var_param):
@@ -458,6 +475,10 @@ class ExclusiveKL(StochasticVariationalObjective):
         Hessian at ``theta = theta_s`` is written out (``_path_logq_hvp``)."""
         if isinstance(self.approx, NVPFlow):
             raise NotImplementedError('the Hessian-vector product is not implemented for NVPFlow')
+        if isinstance(self.model, MinibatchRegressionModel):
+            raise NotImplementedError(
+                '_hessian_vector_product differentiates one fixed stochastic objective; a MinibatchRegressionModel is a '
+                'different density for every batch. Use model.full_model()')
         approx = self.approx
         if self.hessian_approx_method is not None:
             raise AttributeError("'ExclusiveKL' object has no attribute '_hvp'")      # what the reference raises (:275)
@@ -566,6 +587,16 @@ class ExclusiveKL(StochasticVariationalObjective):
             raise ValueError('var_param must have shape ({},)'.format(approx.var_param_dim))
         eng = self._engine()
         eng.set_model(self.model.device_spec())
+        try:
+            return self._device_fit_bound(eng, n_iters, init_param, opt_kind, hyper, state, hist_len, log_directions,
+                                          log_gradients)
+        finally:
+            if isinstance(self.model, MinibatchRegressionModel):
+                # the shared fit driver advanced the engine's batch counter once per iteration it enqueued
+                self.model.batch = eng.minibatch_get_batch()
+
+    def _device_fit_bound(self, eng, n_iters, init_param, opt_kind, hyper, state, hist_len, log_directions, log_gradients):
+        approx = self.approx
         N = self.num_mc_samples
         begin, end = shard_rows(N, eng.n_ranks, eng.rank)
         if isinstance(approx, NVPFlow):
@@ -1068,6 +1099,7 @@ class DISInclusiveKL(StochasticVariationalObjective):
     def _update_objective_and_grad(self):
         approx = self.approx
         self._require_device_model()
+        _refuse_minibatch_weights(self.model, 'DISInclusiveKL')
         if not isinstance(approx, (MFGaussian, MFStudentT, MultivariateT, FullRankGaussian, LRGaussian)):
             raise NotImplementedError('DISInclusiveKL on the HIP engine supports MFGaussian, MFStudentT, MultivariateT, '
                                       'FullRankGaussian and LRGaussian; got {}'.format(type(approx).__name__))
@@ -1388,6 +1420,7 @@ class AlphaDivergence(StochasticVariationalObjective):
     def _update_objective_and_grad(self):
         approx = self.approx
         self._require_device_model()
+        _refuse_minibatch_weights(self.model, 'AlphaDivergence')
         if not isinstance(approx, (MFGaussian, MFStudentT, FullRankGaussian, MultivariateT, LRGaussian)):
             raise NotImplementedError('AlphaDivergence on the HIP engine supports MFGaussian, MFStudentT, '
                                       'MultivariateT, FullRankGaussian and LRGaussian; got {}'.format(
