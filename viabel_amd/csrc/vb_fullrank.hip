@@ -395,42 +395,55 @@ __global__ void __launch_bounds__(256) fr_colsum_kernel(const double* __restrict
   if (threadIdx.x == 0) fpart[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = f;
 }
 
-// ---- folded evaluation: b = P (mu - m), S = E' E, s = colsum(E) and colsum(G) = -s' M - n b' ---------------------------
+// ---- folded evaluation: M = L' P, b = P (mu - m), S = E' E, s = colsum(E) and colsum(G) = -s' M - n b' ---------------------
 // The correlated-Gaussian target's G is linear in the noise: G = -(E L' + 1 c') P = -E M - 1 b', c = mu - m, M = L' P,
 // b = P c -- a D x D x D product that does not depend on the number of samples instead of the N x D x D sampling product
 // (and G itself is never formed: fr_route).
 // The Gram product of the noise leaves the lower tiles of E' E in `gsplits` slabs (pieces of the sample axis) and one row
-// of column sums of E per slab.  One launch, three kinds of workgroups:
-//   [0, nb_cs), 8 columns each, dispatched first (each is a chain of dependent passes): two dot products over the same
-//     eight columns, b[j] = sum_k P[k][j] c[k] (P is symmetric: its column j) and sum_k s[k] M[k][j], with s[k] added up
-//     from the rows of `colpart` in row order by the thread that needs it (M is complete: its product is an earlier
-//     launch).  Thread (pair p = t & 3, k group t >> 2) sums its 64th of the k range, sixteen rows per pass, and the
-//     groups are combined through LDS in fixed order.  The block writes b[j] -- for the gradient product's epilogue, a
-//     later launch -- and colsum(G)[j] = -sum_k s[k] M[k][j] - n b[j] from its own b[j]: no block reads another's;
-//   the next nb_s: s itself, one thread per column (the gradient product's epilogue reads it);
+// of column sums of E per slab.  fr_fold_msum_kernel, ONE launch behind it, runs four kinds of workgroups that do not
+// depend on each other, in this order:
+//   [0, nb_m): the M = L' P product on paired row blocks (gemm_f64_dma_pair_tiles: 64 x 32 tiles, three LDS stages, row
+//     blocks b and T - 1 - b of a column tile, each over its whole k range).  They follow the parameter alone, are the
+//     longest pieces of the launch and bound by their operands' latency with one wave per SIMD, so they are dispatched first
+//     (D = 1024: 256 of them, one per CU) and the memory-bound blocks behind them take the wave slots they leave free;
+//   the next nb_b, 8 columns each: b[j] = sum_k P[k][j] c[k] (P is symmetric: its column j).  Thread (pair p = t & 3, k
+//     group t >> 2) sums its 64th of the k range, sixteen rows per pass, and the groups are combined through LDS in fixed
+//     order;
+//   the next nb_s: s itself, one thread per column (the gradient product's epilogue reads b and s);
 //   the rest, one per 32 x 32 tile (bi, bj <= bi) of S: the slabs added in slab order,
 //     the sum written to S[i][j] and, through LDS, to S[j][i] -- both halves from the same sum, so S is exactly
 //     symmetric, and both stores are contiguous runs.  Of a diagonal tile only the entries j <= i are read (the product's
 //     waves that lie above the diagonal store zeros there).  Only the lower tiles are dispatched; the tile comes from the
 //     block index by arithmetic that is uniform over the block, and no thread divides.
+// The launch's LDS is the M tiles' three stages, dynamic (36.9 KB); the other kinds carve their arrays out of the same
+// allocation, so that four workgroups fit a CU -- an M tile and three of the others.  No launch bound beyond the block size:
+// bounded to four waves per SIMD the sum code spills; it stays below 128 registers by itself.
+// colsum(G), which needs M and s and b, is formed by fr_fold_csg_blocks in a later launch; nobody reads it before the reduction.
 // Everything is added in a fixed order: the same inputs give the same bits.
-__global__ void __launch_bounds__(256) fr_fold_ssum_kernel(const double* __restrict__ Spart, int gsplits, int64_t slab, int d,
+struct FoldMsumNoDep : GemmNoDep {};      // (a Dep type of this kernel's own: see gemm_f64_dma_pair_tiles)
+
+__global__ void __launch_bounds__(256) fr_fold_msum_kernel(const GemmArgs gm, const EpiSplitSlab em, int nb_m,
+                                                           const double* __restrict__ Spart, int gsplits, int64_t slab, int d,
                                                            int64_t ldl, const double* __restrict__ colpart, int64_t ldz,
-                                                           const double* __restrict__ M, const double* __restrict__ P,
-                                                           int64_t ldp, const double* __restrict__ mu,
-                                                           const double* __restrict__ mean, double n_rows, int nb_cs,
-                                                           int nb_s, double* __restrict__ S, double* __restrict__ svec,
-                                                           double* __restrict__ b, double* __restrict__ csg) {
-  if ((int)blockIdx.x < nb_cs) {
-    __shared__ fr_d2 part[2][64][4];
+                                                           const double* __restrict__ P, int64_t ldp,
+                                                           const double* __restrict__ mu, const double* __restrict__ mean,
+                                                           int nb_b, int nb_s, double* __restrict__ S,
+                                                           double* __restrict__ svec, double* __restrict__ b) {
+  extern __shared__ double fold_lds[];      // (the dynamic allocation the tile body calls gemm_lds)
+  if ((int)blockIdx.x < nb_m) {
+    gemm_f64_dma_pair_tiles<2, 4, 3, EpiSplitSlab, FoldMsumNoDep>(gm, em, FoldMsumNoDep{}, (int)blockIdx.x, nb_m);
+    return;
+  }
+  const int blk = (int)blockIdx.x - nb_m;
+  if (blk < nb_b) {
+    fr_d2(*part)[4] = reinterpret_cast<fr_d2(*)[4]>(fold_lds);      // [64][4]
     const int p = threadIdx.x & 3, kg = threadIdx.x >> 2;
-    const int col = (int)blockIdx.x * 8 + 2 * p;
-    const int colc = col < d ? col : 0;                        // (rows of M and P have an even stride >= d)
+    const int col = blk * 8 + 2 * p;
+    const int colc = col < d ? col : 0;                        // (rows of P have an even stride >= d)
     const int kper = (d + 63) / 64;
     const int k0 = kg * kper, k1 = k0 + kper < d ? k0 + kper : d;
-    fr_d2 acc = (fr_d2){0.0, 0.0}, bacc = (fr_d2){0.0, 0.0};
-    // (one dot product after the other: sixteen rows of one operand in flight at a time)
-    for (int kb = k0; kb < k1; kb += 16) {
+    fr_d2 bacc = (fr_d2){0.0, 0.0};
+    for (int kb = k0; kb < k1; kb += 16) {      // sixteen rows in flight
       fr_d2 v[16];
       double c[16];
 #pragma unroll
@@ -443,36 +456,19 @@ __global__ void __launch_bounds__(256) fr_fold_ssum_kernel(const double* __restr
       for (int u = 0; u < 16; ++u)
         if (kb + u < k1) bacc += v[u] * c[u];
     }
-    for (int kb = k0; kb < k1; kb += 16) {
-      fr_d2 v[16];
-      double c[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const int k = kb + u < k1 ? kb + u : k1 - 1;
-        v[u] = *reinterpret_cast<const fr_d2*>(M + (int64_t)k * ldz + colc);
-        c[u] = colpart[k];
-      }
-      for (int z = 1; z < gsplits; ++z)
-#pragma unroll
-        for (int u = 0; u < 16; ++u) c[u] += colpart[(int64_t)z * ldz + (kb + u < k1 ? kb + u : k1 - 1)];
-#pragma unroll
-      for (int u = 0; u < 16; ++u)
-        if (kb + u < k1) acc += v[u] * c[u];
-    }
-    part[0][kg][p] = acc;
-    part[1][kg][p] = bacc;
+    part[kg][p] = bacc;
     __syncthreads();
     if (kg == 0) {
-      fr_d2 tot = part[0][0][p], btot = part[1][0][p];
+      fr_d2 btot = part[0][p];
 #pragma unroll 16
-      for (int q = 1; q < 64; ++q) tot += part[0][q][p], btot += part[1][q][p];
-      if (col < d) b[col] = btot.x, csg[col] = -tot.x - n_rows * btot.x;
-      if (col + 1 < d) b[col + 1] = btot.y, csg[col + 1] = -tot.y - n_rows * btot.y;
+      for (int q = 1; q < 64; ++q) btot += part[q][p];
+      if (col < d) b[col] = btot.x;
+      if (col + 1 < d) b[col + 1] = btot.y;
     }
     return;
   }
-  if ((int)blockIdx.x < nb_cs + nb_s) {
-    const int k = ((int)blockIdx.x - nb_cs) * 256 + (int)threadIdx.x;
+  if (blk < nb_b + nb_s) {
+    const int k = (blk - nb_b) * 256 + (int)threadIdx.x;
     if (k >= ldz) return;
     double s = 0.0;
     if (k < d) {
@@ -482,9 +478,9 @@ __global__ void __launch_bounds__(256) fr_fold_ssum_kernel(const double* __restr
     svec[k] = s;
     return;
   }
-  int bi = 0, bj = (int)blockIdx.x - nb_cs - nb_s;      // lower tiles only, row by row: tile row bi has bi + 1 of them
+  int bi = 0, bj = blk - nb_b - nb_s;                    // lower tiles only, row by row: tile row bi has bi + 1 of them
   while (bj > bi) bj -= ++bi;                            // (uniform over the block: scalar arithmetic)
-  __shared__ double tile[32][33];
+  double(*tile)[33] = reinterpret_cast<double(*)[33]>(fold_lds);      // [32][33]
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const int i0 = bi * 32, j0 = bj * 32;
   double v[4];
@@ -524,6 +520,76 @@ __global__ void __launch_bounds__(256) fr_fold_ssum_kernel(const double* __restr
       if (it < d && jt < d) S[(int64_t)it * ldl + jt] = tile[tx][r];
     }
   }
+}
+
+// colsum(G)[j] = -sum_k s[k] M[k][j] - n b[j], eight columns per block `blk`: the arithmetic the b blocks above use, with
+// s[k] added up from the rows of `colpart` in row order by the thread that needs it and b[j] read from the vector an
+// earlier launch wrote.  `part`: 64 x 4 pairs of LDS.  M, s and b are complete when this runs (earlier launches), and only
+// the reduction reads the result.
+template <int U>
+__device__ __forceinline__ void fr_fold_csg_blocks(const int blk, fr_d2 (*part)[4], const double* __restrict__ colpart,
+                                                   int gsplits, int64_t ldz, int d, const double* __restrict__ M,
+                                                   const double* __restrict__ b, double n_rows, double* __restrict__ csg) {
+  const int p = threadIdx.x & 3, kg = threadIdx.x >> 2;
+  const int col = blk * 8 + 2 * p;
+  const int colc = col < d ? col : 0;                        // (rows of M have an even stride >= d)
+  const int kper = (d + 63) / 64;
+  const int k0 = kg * kper, k1 = k0 + kper < d ? k0 + kper : d;
+  fr_d2 acc = (fr_d2){0.0, 0.0};
+  for (int kb = k0; kb < k1; kb += U) {      // U rows in flight (the sums do not depend on U: every thread adds in k order)
+    fr_d2 v[U];
+    double c[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int k = kb + u < k1 ? kb + u : k1 - 1;
+      v[u] = *reinterpret_cast<const fr_d2*>(M + (int64_t)k * ldz + colc);
+      c[u] = colpart[k];
+    }
+    for (int z = 1; z < gsplits; ++z)
+#pragma unroll
+      for (int u = 0; u < U; ++u) c[u] += colpart[(int64_t)z * ldz + (kb + u < k1 ? kb + u : k1 - 1)];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (kb + u < k1) acc += v[u] * c[u];
+  }
+  part[kg][p] = acc;
+  __syncthreads();
+  if (kg == 0) {
+    fr_d2 tot = part[0][p];
+#pragma unroll 16
+    for (int q = 1; q < 64; ++q) tot += part[q][p];
+    if (col < d) csg[col] = -tot.x - n_rows * b[col];
+    if (col + 1 < d) csg[col + 1] = -tot.y - n_rows * b[col + 1];
+  }
+}
+
+__global__ void __launch_bounds__(256) fr_fold_csg_kernel(const double* __restrict__ colpart, int gsplits, int64_t ldz, int d,
+                                                          const double* __restrict__ M, const double* __restrict__ b,
+                                                          double n_rows, double* __restrict__ csg) {
+  __shared__ fr_d2 part[64][4];
+  fr_fold_csg_blocks<16>((int)blockIdx.x, part, colpart, gsplits, ldz, d, M, b, n_rows, csg);
+}
+
+// The same blocks behind the tiles of the C product in ONE launch, for the tile the route takes while the product fits the
+// chip at once (cfgc 4: 64 x 64, two LDS stages; D = 1024: 544 of 1 024 slots): block x < nb_tiles is tile x % gx of split
+// x / gx -- the linear order of the launcher's (gx, 1, splits) grid -- and the blocks behind take the free slots.  Neither
+// kind reads what the other writes.  `part` is carved out of the tiles' dynamic LDS, and a thread keeps eight rows in flight:
+// with sixteen the kernel needs scratch under the tile's bound of four workgroups per CU.
+struct FoldCsgNoDep : GemmNoDep {};      // (a Dep type of this kernel's own: see gemm_f64_dma_pair_tiles)
+
+__global__ void __launch_bounds__(256, 4) fr_fold_ctile_csg_kernel(const GemmArgs g, const EpiFoldSlabF epi, int gx, int nb_tiles,
+                                                                   const double* __restrict__ colpart, int gsplits, int64_t ldz,
+                                                                   int d, const double* __restrict__ M,
+                                                                   const double* __restrict__ b, double n_rows,
+                                                                   double* __restrict__ csg) {
+  if ((int)blockIdx.x < nb_tiles) {
+    const int bz = (int)blockIdx.x / gx, bx = (int)blockIdx.x - bz * gx;
+    gemm_f64_dma_tile<false, 2, 8, 2, EpiFoldSlabF, FoldCsgNoDep>(g, epi, FoldCsgNoDep{}, bx, bz, gx);
+    return;
+  }
+  extern __shared__ double fold_lds[];
+  fr_fold_csg_blocks<8>((int)blockIdx.x - nb_tiles, reinterpret_cast<fr_d2(*)[4]>(fold_lds), colpart, gsplits, ldz, d, M, b,
+                        n_rows, csg);
 }
 
 // k splits of the folded gradient product C = -tril(M' S) - b s' (K = D, lower 64 x 64 tiles): pieces of about sixteen
@@ -1516,11 +1582,12 @@ static FrRoute fr_route(const vb_ctx* ctx, const ModelDev& m, int64_t n, int64_t
   // Nothing the evaluation returns needs G itself: with S = E' E, s = colsum(E) and n the rows of this rank,
   //   C = G' E = -M' S - b s'        colsum(G) = -s' M - n b'
   // so neither N x D x D product is formed and neither Z nor G is stored.  The chain:
-  //   M = L' P (tri_mode 4, row blocks in pairs: one launch writes M itself)
   //   Gram product of the noise: the gradient product's own shape, kernel and tile map with A = B = E, `splits` slabs of
   //     the lower tiles of S, one row of column sums of E per slab out of its LDS tiles (EpiSplitSlabCs)
-  //   fr_fold_ssum_kernel: b, S in full (mirrored), s, colsum(G)
+  //   fr_fold_msum_kernel: M = L' P (tri_mode 4, row blocks in pairs: M itself, no slabs) and, in the wave slots its
+  //     workgroups leave free, b, S in full (mirrored), s
   //   C slabs = -(M' S) - b s' (lower tiles, K = D in csplits pieces, EpiFoldSlabF: sum L o tril(C) per tile and split)
+  //   colsum(G) = -s' M - n b' (fr_fold_csg_blocks), which nobody reads before
   //   fr_reduce_packed_kernel, as for every route: the slabs of C, ONE row of column sums, the f partials.
   // M and S are formed anew in EVERY evaluation: M follows the parameter, which an optimiser steps every time, and S the
   // noise, which every iteration of a fit draws afresh -- nothing is kept per slot, per parameter or per engine.
@@ -1760,23 +1827,10 @@ static int fr_model_glm(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const Mo
   return glm_grad_enqueue(ctx, st, m, b.Rm, r.ldr, Z, b.G, r.ldz, r.n, r.D);   // G = R X - Z / sd^2
 }
 
-// the folded evaluation (fr_route), its product that follows the parameter alone: M = L' P
-static int fr_model_folded(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelDev& m) {
-  hipStream_t st = ctx->stream;
-  const int D = r.D;
-  // M[r][j] = sum_{k >= r} Lt[r][k] P[k][j]: 64 x 32 tiles, row blocks b and T - 1 - b by one workgroup -- equal work per
-  // workgroup with the k range unsplit, so the launch writes M itself (D = 1024: 256 workgroups, one per CU).  Three LDS
-  // stages: a workgroup alone on its CU has nothing but its own prefetch to cover the operands' latency (two stages:
-  // 4 us more per evaluation)
-  const GemmArgs gm = gemm_product(b.Lt, r.ldl, m.p1, m.ldp, D, D, D, 4);
-  gemm_f64_launch<true, true>(st, gm, 1, r.n_cu, EpiSplitSlab{b.Mf, r.ldz, r.slab});
-  VB_HIP(ctx, hipGetLastError());
-  return VB_OK;
-}
-
-// ... and its part that follows the noise: S = E' E and s = colsum(E) (the Gram product, timed as VB_PROF_FR_GRAD_GEMM:
-// the gradient product's shape), b = P (mu - m) and colsum(G) = -s' M - n b', then the slabs of C = -tril(M' S) - b s' with
-// one partial of sum L o tril(C) per tile and split.  Returns in *tiles3 the number of output tiles of the C product.
+// The folded evaluation (fr_route).  The Gram product S = E' E with s = colsum(E) per slab (timed as VB_PROF_FR_GRAD_GEMM:
+// the gradient product's shape); fr_fold_msum_kernel: M = L' P beside b = P (mu - m), s and the slabs of S added up; the
+// slabs of C = -tril(M' S) - b s' with one partial of sum L o tril(C) per tile and split; colsum(G) = -s' M - n b', which
+// only the reduction reads.  Returns in *tiles3 the number of output tiles of the C product.
 static int fr_grad_folded(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const ModelDev& m, unsigned* tiles3) {
   hipStream_t st = ctx->stream;
   const int D = r.D;
@@ -1786,16 +1840,52 @@ static int fr_grad_folded(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const 
   if (r.cfg3 == 2) VB_TRY(tri2_tile_map(ctx, D, 128, 64, &gs.tile_map, &gs.tile_blocks));
   gemm_f64_launch<false>(st, gs, r.splits, r.n_cu, EpiSplitSlabCs{b.Cpart, r.ldl, r.slab, b.colpart, r.ldz}, r.cfg3);
   VB_HIP(ctx, hipGetLastError());
+  // M[r][j] = sum_{k >= r} Lt[r][k] P[k][j]: 64 x 32 tiles, row blocks b and T - 1 - b by one workgroup -- equal work per
+  // workgroup with the k range unsplit, so the launch writes M itself (D = 1024: 256 workgroups, one per CU).  Three LDS
+  // stages: a workgroup has little but its own prefetch to cover the operands' latency (two stages: 4 us more per
+  // evaluation when it was a launch of its own)
+  GemmArgs gm = gemm_product(b.Lt, r.ldl, m.p1, m.ldp, D, D, D, 4);
+  const unsigned nb_m = gemm_f64_pair_plan(&gm);
+  if (nb_m == 0) return fail(ctx, VB_ERR_STATE, "folded evaluation: D = %d does not go to the LDS-DMA product", D);
   const int nb_cs = (D + 7) / 8, nb_s = (int)((r.ldz + 255) / 256), tiles = (D + 31) / 32;
-  hipLaunchKernelGGL(fr_fold_ssum_kernel, dim3((unsigned)(nb_cs + nb_s + tiles * (tiles + 1) / 2)), dim3(256), 0, st,
-                     (const double*)b.Cpart, r.splits, r.slab, D, r.ldl, (const double*)b.colpart, r.ldz, M, m.p1,
-                     (int64_t)m.ldp, (const double*)b.mu, m.p0, (double)r.n, nb_cs, nb_s, b.Sg, b.svec, b.bvec, b.csg);
+  constexpr size_t msum_lds = gemm_f64_dma_pair_lds<2, 4, 3>();
+  static_assert(msum_lds >= 64 * 4 * sizeof(fr_d2) && msum_lds >= 32 * 33 * sizeof(double), "the sum blocks' LDS is the tiles'");
+  static bool configured = false;
+  if (!configured) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fr_fold_msum_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)msum_lds);
+    configured = true;
+  }
+  hipLaunchKernelGGL(fr_fold_msum_kernel, dim3(nb_m + (unsigned)(nb_cs + nb_s + tiles * (tiles + 1) / 2)), dim3(256), msum_lds, st,
+                     gm, EpiSplitSlab{b.Mf, r.ldz, r.slab}, (int)nb_m, (const double*)b.Cpart, r.splits, r.slab, D, r.ldl,
+                     (const double*)b.colpart, r.ldz, m.p1, (int64_t)m.ldp, (const double*)b.mu, m.p0, nb_cs, nb_s, b.Sg, b.svec,
+                     b.bvec);
   VB_HIP(ctx, hipGetLastError());
   // C[i][j] = sum_k M[k][i] S[k][j]: the gradient product's form, lower tiles, split over k
   GemmArgs gc = gemm_product(M, r.ldz, b.Sg, r.ldl, D, D, D, 2);
+  const EpiFoldSlabF ec{b.Cpart, r.ldl, r.slab, b.bvec, b.svec, b.Lt, r.ldl, b.fpart};
+  if (r.cfgc == 4) {      // the blocks of colsum(G) behind the tiles, in the same launch
+    const int gx = (int)gemm_f64_tri2_small_plan(&gc, r.csplits, r.n_cu), nb_tiles = gx * r.csplits;
+    if (gx == 0) return fail(ctx, VB_ERR_STATE, "folded evaluation: D = %d does not go to the LDS-DMA product", D);
+    constexpr size_t lds = (size_t)2 * (64 * kGemmBK + kGemmBK * 64) * sizeof(double);
+    static_assert(lds >= 64 * 4 * sizeof(fr_d2), "the colsum(G) blocks' LDS is the tiles'");
+    static bool configured_c = false;
+    if (!configured_c) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fr_fold_ctile_csg_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds);
+      configured_c = true;
+    }
+    hipLaunchKernelGGL(fr_fold_ctile_csg_kernel, dim3((unsigned)(nb_tiles + nb_cs)), dim3(256), lds, st, gc, ec, gx, nb_tiles,
+                       (const double*)b.colpart, r.splits, r.ldz, D, M, (const double*)b.bvec, (double)r.n, b.csg);
+    VB_HIP(ctx, hipGetLastError());
+    *tiles3 = (unsigned)gx;
+    return VB_OK;
+  }
   if (r.cfgc == 2) VB_TRY(tri2_tile_map(ctx, D, 128, 64, &gc.tile_map, &gc.tile_blocks));
-  *tiles3 = gemm_f64_launch<false>(st, gc, r.csplits, r.n_cu,
-                                   EpiFoldSlabF{b.Cpart, r.ldl, r.slab, b.bvec, b.svec, b.Lt, r.ldl, b.fpart}, r.cfgc);
+  *tiles3 = gemm_f64_launch<false>(st, gc, r.csplits, r.n_cu, ec, r.cfgc);
+  VB_HIP(ctx, hipGetLastError());
+  hipLaunchKernelGGL(fr_fold_csg_kernel, dim3((unsigned)nb_cs), dim3(256), 0, st, (const double*)b.colpart, r.splits, r.ldz, D, M,
+                     (const double*)b.bvec, (double)r.n, b.csg);
   VB_HIP(ctx, hipGetLastError());
   return VB_OK;
 }
@@ -1809,8 +1899,8 @@ static int fr_model_gauss_full(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, c
   *G = b.G;
   GemmArgs g2 = gemm_product(b.Z, r.ldz, m.p1, m.ldp, (int)r.n, D, D, 0);
   switch (r.dense) {
-    case kDenseNoG:
-      return fr_model_folded(ctx, r, b, m);
+    case kDenseNoG:      // (nothing to do here: M = L' P rides in the slab-sum launch behind the Gram product, fr_grad_folded)
+      return VB_OK;
     case kDenseCallerG:
       *G = const_cast<double*>(g_ready);
       return VB_OK;

@@ -53,9 +53,9 @@ struct GemmArgs {
                     // 3: B[k][j] == 0 for k < j (the mirror image of 1; LDS-DMA kernel, otherwise computed densely)
                     // 4: A[m][k] == 0 for k < m, A given as A[m][k] (an upper-triangular left factor: M = L' P of the
                     //    folded full-rank evaluation): the k range of row block bm starts at its first row rounded down
-                    //    to a slab, row block 0 -- the longest range -- is dispatched first.  The launcher's TRI4_PAIRS
+                    //    to a slab, row block 0 -- the longest range -- is dispatched first.  gemm_f64_dma_pair_tiles
                     //    gives one workgroup row blocks b and tiles_m - 1 - b of a column tile, whose k ranges add up to
-                    //    the same length for every b (gemm_f64_dma_pair_kernel).  (LDS-DMA kernel, otherwise computed
+                    //    the same length for every b (gemm_f64_pair_plan).  (LDS-DMA kernel, otherwise computed
                     //    densely)
   int k_split = 0;  // K range per blockIdx.z (multiple of kGemmBK); splits = gridDim.z
   // batch mode (batch != 0): blockIdx.z selects one of gridDim.z independent products of the same shape -- operand
@@ -414,11 +414,37 @@ inline bool gemm_uses_dma(const GemmArgs& g) {
   return g.K % kGemmBK == 0 && g.M > 0 && g.N > 0;
 }
 
-// TRI4_PAIRS (an unsplit tri_mode 4 product, plain-store epilogue): 64 x 32 tiles with three LDS stages whatever `cfg` says,
-// row blocks b and tiles_m - 1 - b of a column tile by one workgroup (gemm_f64_dma_pair_kernel; with two stages the
-// M = L' P product of the folded full-rank evaluation took 39.5 instead of 35.7 us)
+// An unsplit tri_mode 4 product with a plain-store epilogue on paired row blocks (gemm_f64_dma_pair_tiles<2, 4, 3, ...>: 64 x 32
+// tiles with three LDS stages, row blocks b and tiles_m - 1 - b of a column tile by one workgroup; with two stages the
+// M = L' P product of the folded full-rank evaluation took 39.5 instead of 35.7 us).  The caller's own kernel runs the
+// workgroups (the folded evaluation's fr_fold_msum_kernel, beside its slab sums): this fills in what the launcher would
+// and returns their number, 0 if the shape does not go to the LDS-DMA kernel.
+inline unsigned gemm_f64_pair_plan(GemmArgs* g) {
+  if (g->tri_mode != 4 || g->batch || !gemm_uses_dma(*g)) return 0;
+  g->k_split = gemm_tiles(g->K, kGemmBK) * kGemmBK;
+  g->tiles_m = gemm_tiles(g->M, 64);
+  g->tiles_n = gemm_tiles(g->N, 32);
+  g->xcd_group = 0;
+  g->prio_div = 0;      // (triangular k ranges: no priority alternation, as the launcher below)
+  return (unsigned)((g->tiles_m + 1) / 2 * g->tiles_n);
+}
+
+// A tri_mode 2 product in `splits` k pieces on the launcher's cfg 4 (gemm_f64_dma_tile<false, 2, 8, 2, ...>: 64 x 64 tiles, two
+// LDS stages), likewise for a caller whose own kernel runs the tiles (the folded evaluation's fr_fold_ctile_csg_kernel):
+// what the launcher below would fill in.  Returns the tiles per split -- the launcher's gridDim.x, with gridDim.z = splits,
+// dispatched x fastest -- or 0 if the shape does not go to the LDS-DMA kernel.
+inline unsigned gemm_f64_tri2_small_plan(GemmArgs* g, int splits, int n_cu) {
+  if (g->tri_mode != 2 || g->batch || g->tile_map || splits < 1 || !gemm_uses_dma(*g)) return 0;
+  g->k_split = gemm_tiles(gemm_tiles(g->K, splits), kGemmBK) * kGemmBK;
+  g->tiles_m = gemm_tiles(g->M, 64);
+  g->tiles_n = gemm_tiles(g->N, 64);
+  g->xcd_group = 0;
+  g->prio_div = n_cu;
+  return (unsigned)gemm_count_blocks(*g, 64, 64);
+}
+
 // returns gridDim.x of the launch (the number of output tiles; reducing epilogues write one partial per tile and split)
-template <bool A_KCONTIG, bool TRI4_PAIRS = false, class Epi>
+template <bool A_KCONTIG, class Epi>
 inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu, const Epi& epi, int cfg = 0,
                                 int flags = 0) {
   // 64 x 32 tiles: only where the result cannot depend on the tiling (no per-tile partial sums, no column sums)
@@ -466,9 +492,6 @@ inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu
       if (kNarrowAuto && dma && g.tri_mode == 0 && !g.batch && gemm_count_blocks(g, 64, 64) * splits <= (long)n_cu) cfg = 7;
     }
   }
-  static_assert(!TRI4_PAIRS || kNarrowAuto, "paired row blocks: A[m][k], an epilogue that only stores");
-  const bool pairs = TRI4_PAIRS && g.tri_mode == 4 && splits == 1;      // (tri_mode 4 withdrawn above: the dense launch)
-  if (pairs) cfg = 7;
   if (!kNarrowOk && cfg >= 7) cfg = 4;
   if (!dma && cfg > 3) cfg = (cfg == 4 || cfg >= 7) ? 3 : cfg == 6 ? 1 : 2;
   const int bm_rows = (cfg == 3 || cfg == 4 || cfg >= 7) ? 64 : 128, bn_cols = cfg >= 7 ? 32 : (cfg == 1 || cfg == 6) ? 128 : 64;
@@ -476,7 +499,6 @@ inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu
   g.tiles_n = gemm_tiles(g.N, bn_cols);
   if (splits % 8 != 0 || g.batch) g.xcd_group = 0;
   dim3 grid(g.tile_map ? (unsigned)g.tile_blocks : (unsigned)gemm_count_blocks(g, bm_rows, bn_cols), 1, (unsigned)splits);
-  if (pairs) grid = dim3((unsigned)((g.tiles_m + 1) / 2 * g.tiles_n), 1, 1);      // one workgroup per (pair of row blocks, column tile)
   // (triangular k ranges: the tiles of a CU differ in length anyway, and the alternation costs 1 - 3 us there --
   // 4096 x 768 x 768: 55.5 -> 52.7 us, 512: 30.1 -> 29.1 us, 1024: unchanged, tools/gemm_bench.hip with it switched off)
   g.prio_div = (g.tri_mode != 1 && g.tri_mode != 3 && g.tri_mode != 4) ? n_cu : 0;
@@ -487,12 +509,6 @@ inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu
     else if (cfg == 4) gemm_f64_dma_launch<A_KCONTIG, 2, 8, 2, Epi>(st, g, grid, epi);
     else if (cfg == 6) gemm_f64_dma_launch<A_KCONTIG, 4, 16, 2, Epi>(st, g, grid, epi);
     else if (cfg >= 7) {
-      if constexpr (TRI4_PAIRS) {
-        if (pairs) {
-          gemm_f64_dma_pair_launch<2, 4, 3, Epi>(st, g, grid, epi);
-          return grid.x;
-        }
-      }
       if constexpr (kNarrowOk) {
         if (cfg == 7) gemm_f64_dma_launch<A_KCONTIG, 2, 4, 3, Epi>(st, g, grid, epi);
         else gemm_f64_dma_launch<A_KCONTIG, 2, 4, 2, Epi>(st, g, grid, epi);

@@ -542,7 +542,7 @@ inline void gemm_f64_dma_launch(hipStream_t st, const GemmArgs& g, dim3 grid, co
 // runs the tile of row block `pair` and then, for the same column tile, the tile of row block tiles_m - 1 - pair, each
 // over its whole k range: every workgroup carries the same work (the middle block of an odd tiles_m, run once, carries
 // about half), every entry of C is written once by the one accumulator that summed it, and there are no split slabs to
-// add.  gridDim.x = ((tiles_m + 1) / 2) * tiles_n, set by the launcher.
+// add.  There are ((tiles_m + 1) / 2) * tiles_n such workgroups (gemm_f64_pair_plan, vb_gemm_f64.h).
 // The two passes share the LDS stages.  A pass ends with s_waitcnt(0) and a barrier in front of its epilogue: once a wave
 // is past that barrier, every wave's fragment reads have returned and every wave's LDS-DMA has landed, and the plain
 // epilogues admitted here do not touch LDS -- so no DMA of pass two can land in a stage that a wave of pass one still
@@ -550,39 +550,32 @@ inline void gemm_f64_dma_launch(hipStream_t st, const GemmArgs& g, dim3 grid, co
 // its epilogue's global stores: they sit on the same counter as the DMAs, and pass two's counted waits (vmcnt(UPW): "only
 // my newest slab is outstanding") must count DMAs only, so each wave waits for its stores between the passes.
 //
-// (GemmNoDep under a name of its own: hipcc accepts one specialisation of the tile body in one kernel only -- called from a
-// second kernel, the same template arguments are rejected as a substitution failure)
-struct GemmPairNoDep : GemmNoDep {};
-
-template <int AF, int NB, int STAGES, class Epi>
-__global__ void __launch_bounds__(256, AF * NB > 32 ? (STAGES > 2 ? 1 : 2) : (AF * NB > 16 || STAGES > 2 ? 2 : 4))
-    gemm_f64_dma_pair_kernel(const GemmArgs g, const Epi epi) {
+// (A caller gives `Dep` a type of its own, derived from GemmNoDep: hipcc accepts one specialisation of the tile body in one
+// kernel only -- called from a second kernel, the same template arguments are rejected as a substitution failure.)
+// `block` = pair * tiles_n + column tile, uniform over the workgroup; `gx` as for gemm_f64_dma_tile.  The caller's kernel
+// provides the dynamic LDS of the tile, STAGES * (32 AF + 8 NB) * kGemmBK doubles (gemm_f64_dma_pair_lds).
+template <int AF, int NB, int STAGES, class Epi, class Dep>
+__device__ __forceinline__ void gemm_f64_dma_pair_tiles(const GemmArgs& g, const Epi& epi, const Dep& dep, const int block,
+                                                        const int gx) {
   static_assert(!EpiReduces<Epi>::value && !EpiColsum<Epi>::value && !EpiRowSums<Epi>::value,
                 "the epilogue between the passes must leave LDS alone");
-  const int pair = (int)blockIdx.x / g.tiles_n, bn = (int)blockIdx.x % g.tiles_n;
+  const int pair = block / g.tiles_n, bn = block % g.tiles_n;
   const int mirror = g.tiles_m - 1 - pair;
   const int passes = mirror > pair ? 2 : 1;
 #pragma unroll 1
   for (int pass = 0; pass < passes; ++pass) {
     const int bm = pass == 0 ? pair : mirror;
     const int bx = bm * g.tiles_n + bn, bz = 0;      // (tri_mode 4 reads the row block and the column tile back from bx)
-    gemm_f64_dma_tile<true, AF, NB, STAGES, Epi, GemmPairNoDep>(g, epi, GemmPairNoDep{}, bx, bz, (int)gridDim.x);
+    gemm_f64_dma_tile<true, AF, NB, STAGES, Epi, Dep>(g, epi, dep, bx, bz, gx);
     __asm__ volatile("" ::: "memory");
     __builtin_amdgcn_s_waitcnt(0);
     __asm__ volatile("" ::: "memory");
   }
 }
 
-template <int AF, int NB, int STAGES, class Epi>
-inline void gemm_f64_dma_pair_launch(hipStream_t st, const GemmArgs& g, dim3 grid, const Epi& epi) {
-  constexpr size_t lds = (size_t)STAGES * (32 * AF * kGemmBK + kGemmBK * 8 * NB) * sizeof(double);
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f64_dma_pair_kernel<AF, NB, STAGES, Epi>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    configured = true;
-  }
-  hipExtLaunchKernelGGL((gemm_f64_dma_pair_kernel<AF, NB, STAGES, Epi>), grid, dim3(256), lds, st, g.ev0, g.ev1, 0, g, epi);
+template <int AF, int NB, int STAGES>
+constexpr size_t gemm_f64_dma_pair_lds() {
+  return (size_t)STAGES * (32 * AF * kGemmBK + kGemmBK * 8 * NB) * sizeof(double);
 }
 
 }  // namespace vb
