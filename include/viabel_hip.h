@@ -99,6 +99,13 @@ typedef struct vb_ctx vb_ctx;
                                   1 <= B <= n_data < 2^31.  t is the context's batch counter (vb_minibatch_set_batch; 0
                                   after vb_set_model), which the device-resident fits advance by one per iteration.
                                   ExclusiveKL routes only take it meaningfully: the density changes with t */
+#define VB_MODEL_NEURALNET 10  /* one-hidden-layer Bayesian neural network regression, tanh units: D = n_hidden * (p + 2) + 1,
+                                  theta = [w_0 | ... | w_{h-1} | a (h) | v (h) | c] (unit-major, w_k of length p),
+                                  t_ik = tanh(x_i' w_k + a_k), eta_i = c + sum_k v_k t_ik, any VB_GLM_* likelihood of eta_i,
+                                  N(0, prior_sd) prior on every coordinate; the density is normalised as VB_MODEL_LOGISTIC's.
+                                  dparams=[X(n_data x p)|y(n_data)|prior_sd|noise_sd], iparams=[n_data, n_hidden, link];
+                                  noise_sd is read by VB_GLM_GAUSSIAN only.  Taken by every route that takes a
+                                  VB_MODEL_SOURCE target, like VB_MODEL_SOFTMAX */
 /* likelihoods of VB_MODEL_LOCSCALE */
 #define VB_LOCSCALE_GAUSSIAN 0
 #define VB_LOCSCALE_STUDENT_T 1
@@ -567,6 +574,20 @@ int vb_glm_psis_loo(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const do
 int vb_glm_predict(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const double* log_w, const double* x_new,
                    int64_t m, const double* y_new, double* mean, double* var, double* eta_mean, double* eta_var,
                    double* lpd);
+/* vb_nn_pointwise: vb_glm_pointwise for the bound VB_MODEL_NEURALNET target: ll_out[s * n_data + i] = log p(y_i | eta_i) at
+ * the network output eta_i = c + sum_k v_k tanh(x_i' w_k + a_k) of draw s (s x d row-major, d = n_hidden (p + 2) + 1) as a
+ * NORMALISED density (the Poisson -log y_i!, the Gaussian -log noise_sd - log(2 pi) / 2 included), the prior not.
+ * VB_ERR_STATE without a bound model, VB_ERR_UNSUPPORTED for any other model.
+ * vb_nn_predict: vb_glm_predict for that target -- the same argument rules, weight normalisation, outputs and error codes,
+ * with eta_is the network output of draw s at row i of x_new.  x_new is m x p (p = the model's features), row-major; NULL
+ * predicts the bound design.  The draws' unit weights are packed with the draw index fastest (p x n_hidden round_up(s, 16)),
+ * ONE fp64 MFMA product per chunk of observations forms all hidden pre-activations against the design's rows, a forward
+ * kernel (lanes over draws) writes eta observation-major and vb_glm_predict's reduction kernel follows.  The observations go
+ * in chunks that keep n_hidden * chunk * round_up(s, 16) doubles within 16 Mi doubles (128 MiB); only the five m-vectors
+ * come back.  Bit-reproducible.  Additionally VB_ERR_INVALID when n_hidden * round_up(s, 16) exceeds 2^31 - 1.        */
+int vb_nn_pointwise(vb_ctx* ctx, const double* x, int64_t s, int64_t d, double* ll_out);
+int vb_nn_predict(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const double* log_w, const double* x_new, int64_t m,
+                  const double* y_new, double* mean, double* var, double* eta_mean, double* eta_var, double* lpd);
 /* vb_glm_value_grad_hessian: log density, gradient and Hessian of the bound regression target (VB_MODEL_LOGISTIC, any
  * VB_GLM_* likelihood) at the ONE host point x[d] -- what a Newton step and the Laplace approximation need.
  *   *f      the log density as vb_model_logp gives it: likelihood, prior and all constants

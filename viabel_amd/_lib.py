@@ -29,7 +29,9 @@ MODEL_MINIBATCH_GLM = 9
 # targets that hand every pipeline finished rows (f, grad f): a softmax, multilevel, location-scale or sparse regression
 # target goes wherever a source model goes; the minibatch target forms its rows the same way (the objectives decide what
 # may take a density that changes from batch to batch)
-MODELS_WITH_ROWS = (MODEL_SOURCE, MODEL_SOFTMAX, MODEL_MULTILEVEL, MODEL_LOCSCALE, MODEL_SPARSE_GLM, MODEL_MINIBATCH_GLM)
+MODEL_NEURALNET = 10
+MODELS_WITH_ROWS = (MODEL_SOURCE, MODEL_SOFTMAX, MODEL_MULTILEVEL, MODEL_LOCSCALE, MODEL_SPARSE_GLM, MODEL_MINIBATCH_GLM,
+                    MODEL_NEURALNET)
 # doubles of predictor matrix one row chunk of the softmax pipeline may hold (csrc/vb_common.h: kSoftmaxChunkDoubles);
 # a chunk is max(8, SOFTMAX_CHUNK_DOUBLES // (n_classes * round_up(n_data, 16))) rows
 SOFTMAX_CHUNK_DOUBLES = 16 << 20
@@ -61,6 +63,24 @@ def minibatch_chunk_rows(batch_size):
     """Samples per chunk of the minibatch regression pipeline for batches of ``batch_size`` observations: the arithmetic of
     ``minibatch_chunk_rows`` in ``csrc/vb_common.h``."""
     return max(8, MINIBATCH_CHUNK_DOUBLES // (2 * ((int(batch_size) + 15) // 16 * 16)))
+
+
+# doubles of the hidden-unit matrix per chunk of samples of the neural-network pipeline (kNeuralNetChunkDoubles), and of the
+# matrix of hidden pre-activations per chunk of OBSERVATIONS of vb_nn_predict (kNeuralNetPredictDoubles)
+NN_CHUNK_DOUBLES = 16 << 20
+NN_PREDICT_DOUBLES = 16 << 20
+
+
+def nn_chunk_rows(n_hidden, n_data):
+    """Samples per chunk of the neural-network pipeline: a sample holds ``n_hidden * round_up(n_data, 16)`` doubles of the
+    hidden-unit matrix (``csrc/vb_common.h``: kNeuralNetChunkDoubles; a call of fewer samples is one chunk)."""
+    return max(8, NN_CHUNK_DOUBLES // (int(n_hidden) * ((int(n_data) + 15) // 16 * 16)))
+
+
+def nn_predict_chunk(n_hidden, n_draws):
+    """Observations per chunk of ``vb_nn_predict``: an observation holds ``n_hidden * round_up(n_draws, 16)`` doubles
+    (``csrc/vb_common.h``: kNeuralNetPredictDoubles)."""
+    return max(1, NN_PREDICT_DOUBLES // (int(n_hidden) * ((int(n_draws) + 15) // 16 * 16)))
 
 
 GLM_BERNOULLI_LOGIT, GLM_POISSON, GLM_GAUSSIAN = range(3)
@@ -193,6 +213,10 @@ SIGNATURES = {
     'vb_glm_predict': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p,
                                       ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
                                       _c_double_p]),
+    'vb_nn_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
+    'vb_nn_predict': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p,
+                                     ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                     _c_double_p]),
     'vb_glm_value_grad_hessian': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p]),
     'vb_hmc_run': (ctypes.c_int, [_ctx_p, _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                   ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_double,
@@ -816,6 +840,11 @@ class Engine:
         ``x`` (S x D)."""
         return self._pointwise('vb_sparse_glm_pointwise', x, n_data)
 
+    def nn_pointwise(self, x, n_data):
+        """``(S, n_data)`` normalised terms ``log p(y_i | eta_i)`` of the bound neural-network regression target at the
+        draws ``x`` (S x D), ``eta_i`` the network's output at observation ``i``."""
+        return self._pointwise('vb_nn_pointwise', x, n_data)
+
     def minibatch_pointwise(self, x, batch_size):
         """``(S, batch_size)`` normalised, unscaled terms ``log p(y_j | x_j' theta)`` of the current batch of the bound
         minibatch regression target at the draws ``x`` (S x D), in batch order."""
@@ -859,6 +888,15 @@ class Engine:
         predict at, ``y_new`` (m,) its responses; ``X_new=None`` predicts the bound design and ``y_new=None`` then means
         the bound responses.  Returns a dict of ``(m,)`` arrays: ``mean``, ``var``, ``eta_mean``, ``eta_var`` and -- with
         a response -- ``lpd``.  The (m x S) matrix of linear predictors stays on the device."""
+        return self._predict('vb_glm_predict', x, None, log_w, X_new, y_new)
+
+    def nn_predict(self, x, n_features, log_w=None, X_new=None, y_new=None):
+        """:meth:`glm_predict` for the bound neural-network regression target (``vb_nn_predict``): the same arguments and
+        the same dict, with ``X_new`` (m x ``n_features``) and ``eta`` the network's output."""
+        return self._predict('vb_nn_predict', x, int(n_features), log_w, X_new, y_new)
+
+    def _predict(self, symbol, x, n_cols, log_w, X_new, y_new):
+        """The argument checks and the call shared by the prediction entries; ``n_cols``: columns of ``X_new`` (None: D)."""
         x = _f64(x)
         if x.ndim != 2:
             raise ValueError('x must be (S, D)')
@@ -876,8 +914,9 @@ class Engine:
             m = int(iparams[0]) if len(iparams) else 0
         else:
             X_new = _f64(X_new)
-            if X_new.ndim != 2 or X_new.shape[1] != d:
-                raise ValueError('X_new must be (m, {}); got {}'.format(d, X_new.shape))
+            n_cols = d if n_cols is None else n_cols
+            if X_new.ndim != 2 or X_new.shape[1] != n_cols:
+                raise ValueError('X_new must be (m, {}); got {}'.format(n_cols, X_new.shape))
             m = X_new.shape[0]
         if y_new is not None:
             if np.shape(y_new) != (m,):
@@ -885,10 +924,10 @@ class Engine:
             y_new = _f64(y_new)
         mean, var, eta_mean, eta_var = (np.empty(m, dtype=np.float64) for _ in range(4))
         lpd = np.empty(m, dtype=np.float64) if X_new is None or y_new is not None else None
-        self._check(self._lib.vb_glm_predict(self._ctx, _dptr(x), s, d, None if log_w is None else _dptr(log_w),
-                                             None if X_new is None else _dptr(X_new), m,
-                                             None if y_new is None else _dptr(y_new), _dptr(mean), _dptr(var),
-                                             _dptr(eta_mean), _dptr(eta_var), None if lpd is None else _dptr(lpd)))
+        self._check(getattr(self._lib, symbol)(self._ctx, _dptr(x), s, d, None if log_w is None else _dptr(log_w),
+                                               None if X_new is None else _dptr(X_new), m,
+                                               None if y_new is None else _dptr(y_new), _dptr(mean), _dptr(var),
+                                               _dptr(eta_mean), _dptr(eta_var), None if lpd is None else _dptr(lpd)))
         out = dict(mean=mean, var=var, eta_mean=eta_mean, eta_var=eta_var)
         if lpd is not None:
             out['lpd'] = lpd

@@ -241,7 +241,9 @@ def predict(var_param, *, objective=None, model=None, approx=None, X_new=None, y
     (:func:`samples_and_log_weights`).  ``weights='psis'`` corrects the draws towards the posterior with the
     Pareto-smoothed, normalised ratios (``psislw``); ``weights=None`` takes the draws as they are.  The
     ``m x n_samples`` matrix of linear predictors is formed and reduced on the device (``vb_glm_predict``,
-    :meth:`LogisticRegressionModel.predict_from_draws`); five ``m``-vectors come back.  Returns a dict: ``mean`` and ``sd``
+    :meth:`LogisticRegressionModel.predict_from_draws`; any model that has a ``predict_from_draws`` is taken -- a
+    ``NeuralNetRegressionModel`` predicts its network output, ``vb_nn_predict``); five ``m``-vectors come back.
+    Returns a dict: ``mean`` and ``sd``
     of the response, ``eta_mean`` and ``eta_sd`` of the linear predictor, ``khat`` (of the ratios; None with
     ``weights=None``), ``n_samples`` and, with a response, ``lpd`` (``log p(y_i | y)`` per observation), ``elpd``
     (their sum: on held-out rows the number ``loo()``'s ``elpd_loo`` estimates) and ``se_elpd = sqrt(m var(lpd))``.
@@ -262,7 +264,7 @@ def predict(var_param, *, objective=None, model=None, approx=None, X_new=None, y
     if not (Reff > 0):
         raise ValueError('Reff must be positive')
     refuse_minibatch(model, 'predict')
-    if not isinstance(model, LogisticRegressionModel):
+    if not callable(getattr(model, 'predict_from_draws', None)):
         raise NotImplementedError(
             'predict covers LogisticRegressionModel, PoissonRegressionModel and LinearRegressionModel; {} has no '
             'predict_from_draws. What exists for it: pointwise_log_likelihood(draws) where the model defines it, to be '

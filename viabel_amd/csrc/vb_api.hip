@@ -446,7 +446,7 @@ static int ticket(vb_ctx* ctx, ResultSlot** rs, int count) {
 }
 
 // ---- vb_set_model by model id (the rows targets': vb_softmax.hip, vb_multilevel.hip, vb_locscale.hip, vb_sparse.hip,
-// vb_minibatch.hip) ------
+// vb_minibatch.hip, vb_neuralnet.hip) ------
 int upload_model_params(vb_ctx* ctx, const std::vector<double>& dev, const double** base) {
   VB_TRY(ensure(ctx, ctx->model_params, dev.size() * sizeof(double)));
   VB_HIP(ctx, hipMemcpyAsync(ctx->model_params.ptr, dev.data(), dev.size() * sizeof(double), hipMemcpyHostToDevice,
@@ -778,6 +778,7 @@ int vb_set_model(vb_ctx* ctx, int model_id, int64_t dim, const double* dparams, 
     case VB_MODEL_LOCSCALE: return locscale_set_model(ctx, dim, dparams, n_dparams, iparams, n_iparams);
     case VB_MODEL_SPARSE_GLM: return sparse_set_model(ctx, dim, dparams, n_dparams, iparams, n_iparams);
     case VB_MODEL_MINIBATCH_GLM: return minibatch_set_model(ctx, dim, dparams, n_dparams, iparams, n_iparams);
+    case VB_MODEL_NEURALNET: return neuralnet_set_model(ctx, dim, dparams, n_dparams, iparams, n_iparams);
   }
   return fail(ctx, VB_ERR_INVALID, "unknown model id %d", model_id);
 }

@@ -119,12 +119,16 @@ struct ModelDev {
   int mb_shuffle = 0;           // 1: slot -> observation through the epoch's permutation; 0: the slot itself
   int mb_half_bits = 0;         // w: the permutation's Feistel network works on 2 w bits
   uint64_t mb_seed = 0;         // its Philox key
+  // VB_MODEL_NEURALNET (vb_neuralnet.hip): theta = [w_0 | ... | w_{h-1} | a (h) | v (h) | c], n_feat = p, dim = h (p + 2) + 1;
+  // p0 = X, p1 = X', p2 = y as for the softmax target, tau = prior_sd of every coordinate, link / aux as for the regression
+  // target.  A rows target as well: c0 stays 0, f0 holds the likelihood's and the prior's constants.
+  int n_hidden = 0;             // neural net: h
 };
 
 // targets whose rows (f, grad f) are formed before a pipeline's streaming pass and loaded by it (model_rows_enqueue)
 __host__ __device__ __forceinline__ bool model_has_rows(int id) {
   return id == VB_MODEL_SOURCE || id == VB_MODEL_SOFTMAX || id == VB_MODEL_MULTILEVEL || id == VB_MODEL_LOCSCALE ||
-         id == VB_MODEL_SPARSE_GLM || id == VB_MODEL_MINIBATCH_GLM;
+         id == VB_MODEL_SPARSE_GLM || id == VB_MODEL_MINIBATCH_GLM || id == VB_MODEL_NEURALNET;
 }
 
 // per-observation log-likelihood term (without constants) and its derivative with respect to eta = x' b
@@ -524,7 +528,7 @@ void user_model_release(vb_ctx* ctx);
 int softmax_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
                          int64_t ldg, double* f);
 // rows of the bound target by whichever forms them: a source model's kernel, the softmax, the multilevel, the
-// location-scale, the sparse or the minibatch regression pipeline (vb_rows.hip)
+// location-scale, the sparse, the minibatch or the neural-network regression pipeline (vb_rows.hip)
 int model_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G,
                        int64_t ldg, double* f);
 // doubles of predictor matrix H one row chunk of the softmax pipeline may hold (mirrored by _lib.SOFTMAX_CHUNK_DOUBLES)
@@ -570,6 +574,33 @@ inline int64_t minibatch_chunk_rows(int64_t batch_size) {
   const int64_t rows = kMinibatchChunkDoubles / (2 * ((batch_size + 15) / 16 * 16));
   return rows < 8 ? 8 : rows;
 }
+// neural-network regression target (vb_neuralnet.hip), the same contract and the same alignment rules as the multilevel one
+int neuralnet_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz, int64_t n, int d, double* G, int64_t ldg,
+                           double* f);
+// doubles of the hidden-unit matrix H one row chunk of the neural-network pipeline may hold (mirrored by
+// _lib.NN_CHUNK_DOUBLES): a sample holds n_hidden * round_up(n_data, 16) doubles of it, so a chunk is
+// max(8, kNeuralNetChunkDoubles / (n_hidden * round_up(n_data, 16))) rows (mirrored by _lib.nn_chunk_rows)
+constexpr int64_t kNeuralNetChunkDoubles = (int64_t)16 << 20;
+// ... and of the matrix H = X_new Wt one chunk of OBSERVATIONS of vb_nn_predict may hold (mirrored by
+// _lib.NN_PREDICT_DOUBLES): an observation holds n_hidden * round_up(s, 16) doubles of it, so a chunk is
+// max(1, kNeuralNetPredictDoubles / (n_hidden * round_up(s, 16))) observations (mirrored by _lib.nn_predict_chunk)
+constexpr int64_t kNeuralNetPredictDoubles = (int64_t)16 << 20;
+// The reduction of a prediction (vb_psis_batch.hip), shared by vb_glm_predict and vb_nn_predict: glm_predict_kernel over
+// `rows` observations whose linear predictors lie observation-major in a.eta
+struct PredictArgs {
+  const double* eta;          // rows observations of n draws, observation j at eta + j * ld
+  int64_t ld;
+  int n;
+  const double* w;            // [n] normalised weights (sum 1) and ...
+  const double* log_w;        // [n] ... their logarithms (-inf where the weight is 0)
+  const double* y;            // [rows] responses, or nullptr: no lpd
+  double aux;
+  double *mean, *var, *eta_mean, *eta_var, *lpd;      // [rows]
+};
+int glm_predict_enqueue(vb_ctx* ctx, hipStream_t st, int link, const PredictArgs& a, int64_t rows);
+// w | log w (2 s doubles) of the s log weights, normalised in a fixed order on the host; uniform without them.  False when
+// no weight is finite (or one is NaN / +inf: the sum is then not a number).
+bool predict_weights(const double* log_w, int64_t s, std::vector<double>& out);
 // The pointwise entry of a rows target (vb_rows.hip): the argument checks of `api_name` against the bound model, then the
 // draws x [s x d] in chunks -- each uploaded into ctx->target_work with row stride round_up(d, 16), evaluated by `body` into
 // a term matrix there and downloaded to ll_out [s x n_data].  `plan` lays the workspace out for s draws and makes the
@@ -589,7 +620,8 @@ int rows_pointwise(vb_ctx* ctx, const char* api_name, int model_id, const char* 
 int upload_model_params(vb_ctx* ctx, const std::vector<double>& dev, const double** base);      // vb_api.hip
 using SetModelFn = int(vb_ctx* ctx, int64_t dim, const double* dparams, size_t n_dparams, const int64_t* iparams,
                        size_t n_iparams);
-SetModelFn softmax_set_model, multilevel_set_model, locscale_set_model, sparse_set_model, minibatch_set_model;
+SetModelFn softmax_set_model, multilevel_set_model, locscale_set_model, sparse_set_model, minibatch_set_model,
+    neuralnet_set_model;
 struct LegacyFinish;
 // (defer != nullptr: the kernels are enqueued, the state is left untouched and *defer describes the finish -- exact path only,
 // VB_ERR_UNSUPPORTED otherwise)

@@ -611,16 +611,7 @@ static int glm_pointwise_enqueue(vb_ctx* ctx, hipStream_t st, const GlmLayout& L
 // ---- posterior prediction of the regression targets (vb_glm_predict) ------------------------------------------------
 // ETA[observation][draw] = x_obs' theta_draw: the product of glm_pointwise_enqueue with a plain store, against the bound
 // design or a chunk of an uploaded one (EpiStorePlain)
-struct PredictArgs {
-  const double* eta;          // rows observations of n draws, observation j at eta + j * ld
-  int64_t ld;
-  int n;
-  const double* w;            // [n] normalised weights (sum 1) and ...
-  const double* log_w;        // [n] ... their logarithms (-inf where the weight is 0)
-  const double* y;            // [rows] responses, or nullptr: no lpd
-  double aux;
-  double *mean, *var, *eta_mean, *eta_var, *lpd;      // [rows]
-};
+// (PredictArgs: vb_common.h)
 
 // One 256-thread workgroup per observation, two passes over its n linear predictors (8 n bytes the workgroup has just
 // read: the second pass comes from the cache).  Pass 1: the weighted sums of eta, mu(eta), V(eta) and the running
@@ -703,7 +694,7 @@ __global__ void __launch_bounds__(kPbThreads) glm_predict_kernel(const PredictAr
   }
 }
 
-static int glm_predict_enqueue(vb_ctx* ctx, hipStream_t st, int link, const PredictArgs& a, int64_t rows) {
+int glm_predict_enqueue(vb_ctx* ctx, hipStream_t st, int link, const PredictArgs& a, int64_t rows) {
   const dim3 grid((unsigned)rows), block(kPbThreads);
   if (link == VB_GLM_POISSON) hipLaunchKernelGGL(glm_predict_kernel<VB_GLM_POISSON>, grid, block, 0, st, a);
   else if (link == VB_GLM_GAUSSIAN) hipLaunchKernelGGL(glm_predict_kernel<VB_GLM_GAUSSIAN>, grid, block, 0, st, a);
@@ -737,9 +728,8 @@ static PredictLayout predict_layout(int64_t s, int64_t d, int64_t m, bool own_de
   return L;
 }
 
-// w | log w (2 s doubles) of the s log weights, normalised in a fixed order on the host; uniform without them.  False when
-// no weight is finite (or one is NaN / +inf: the sum is then not a number).
-static bool predict_weights(const double* log_w, int64_t s, std::vector<double>& out) {
+// (contract: vb_common.h)
+bool predict_weights(const double* log_w, int64_t s, std::vector<double>& out) {
   out.resize((size_t)(2 * s));
   double *w = out.data(), *lw = w + s;
   if (!log_w) {

@@ -334,6 +334,7 @@ int model_rows_enqueue(vb_ctx* ctx, hipStream_t st, const double* Z, int64_t ldz
   if (ctx->model.id == VB_MODEL_LOCSCALE) return locscale_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
   if (ctx->model.id == VB_MODEL_SPARSE_GLM) return sparse_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
   if (ctx->model.id == VB_MODEL_MINIBATCH_GLM) return minibatch_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
+  if (ctx->model.id == VB_MODEL_NEURALNET) return neuralnet_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
   return user_rows_enqueue(ctx, st, Z, ldz, n, d, G, ldg, f);
 }
 

@@ -1,6 +1,6 @@
-// What the rows targets share (vb_softmax.hip, vb_multilevel.hip, vb_locscale.hip, vb_sparse.hip): the plain-store GEMM
-// epilogue, the wave and workgroup sums in their fixed order, the per-observation constant of a GLM likelihood, and the host
-// pieces of a layout, of the argument checks and of vb_set_model.  Not part of the C ABI.
+// What the rows targets share (vb_softmax.hip, vb_multilevel.hip, vb_locscale.hip, vb_sparse.hip, vb_neuralnet.hip): the
+// plain-store GEMM epilogue, the wave and workgroup sums in their fixed order, the per-observation constant of a GLM
+// likelihood, and the host pieces of a layout, of the argument checks and of vb_set_model.  Not part of the C ABI.
 #pragma once
 
 #include "vb_common.h"

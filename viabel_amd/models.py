@@ -15,7 +15,7 @@ from . import _lib
 __all__ = ['Model', 'DeviceModel', 'GaussianModel', 'FunnelModel', 'CorrelatedGaussianModel',
            'LogisticRegressionModel', 'PoissonRegressionModel', 'LinearRegressionModel', 'SoftmaxRegressionModel',
            'MultilevelRegressionModel', 'LocationScaleRegressionModel', 'SparseRegressionModel',
-           'MinibatchRegressionModel', 'SourceModel', 'CallableModel']
+           'NeuralNetRegressionModel', 'MinibatchRegressionModel', 'SourceModel', 'CallableModel']
 
 
 class Model(object):
@@ -947,6 +947,126 @@ class SparseRegressionModel(DeviceModel):
         argument of :func:`psisloo` (``psisloo(log_lik, log_ratios)`` is this model's route to LOO).  Normalised densities,
         without the prior (``vb_sparse_glm_pointwise``).  ``x``: (S, D), or (D,) for one draw."""
         return self._pointwise(x)
+
+
+class NeuralNetRegressionModel(DeviceModel):
+    """A Bayesian neural network with one hidden layer of ``tanh`` units: a regression that is not linear in its
+    predictor, and the large-dimension target for the mean-field, ``LRGaussian`` and ``NVPFlow`` families.
+
+    ``X`` is ``(n_data, p)``, ``n_hidden = h >= 1``, ``likelihood`` is ``'gaussian'`` (known ``noise_sd``, read by this
+    likelihood only), ``'logistic'`` (``y`` in ``{0, 1}``) or ``'poisson'`` (``y >= 0``).  The parameter is
+    **unit-major**, ``dim = h (p + 2) + 1``, every coordinate under a ``N(0, prior_sd)`` prior::
+
+        theta    = [ w_0 | ... | w_{h-1} | a (h) | v (h) | c ]      w_k of length p
+        t_ik     = tanh(x_i' w_k + a_k)
+        eta_i    = c + sum_k v_k t_ik
+        f(theta) = sum_i log p(y_i | eta_i) - |theta|^2 / (2 sd^2) - dim (log sd + log(2 pi) / 2)
+        r_i      = d log p(y_i | eta_i) / d eta,      delta_ik = r_i v_k (1 - t_ik^2)
+        df/dc    = sum_i r_i          - c   / sd^2
+        df/dv_k  = sum_i r_i t_ik     - v_k / sd^2
+        df/da_k  = sum_i delta_ik     - a_k / sd^2
+        df/dw_k  = sum_i delta_ik x_i - w_k / sd^2
+
+    ``log p(y | eta)`` is a normalised density, as the flat regression targets have it.  The inputs are taken as they
+    are: no standardisation and no intercept column (``a`` and ``c`` are the network's own biases); standardise ``X``
+    yourself.  The posterior is invariant under permuting the hidden units and under flipping the sign of a unit's
+    ``(w_k, a_k, v_k)``: compare fits through predictions, not coordinates.
+
+    The engine takes the units of a sample as ``h`` rows of a packed matrix, forms all pre-activations with one fp64 MFMA
+    product, runs a forward kernel (``tanh``, the output, the likelihood and its residual) and a backward kernel (the
+    ``a`` and ``v`` sums, ``delta`` in place) and takes the weight gradient with the regression targets' second product
+    (``csrc/vb_neuralnet.hip``, ``DESIGN.md`` 4.24).  To every objective it looks like a :class:`SourceModel` and is
+    accepted wherever one is: ``ExclusiveKL`` (both estimator forms, the RGE control variates, ``NVPFlow``),
+    ``AlphaDivergence`` and ``DISInclusiveKL`` with every family, ``bbvi``, ``vi_diagnostics``, the device-resident fit,
+    ``hmc`` and the difference route of ``hessian()``.  :func:`predict` takes it (:meth:`predict_from_draws`).  ``loo()``
+    takes the one-predictor regression targets only: this model's route to LOO is
+    ``psisloo(model.pointwise_log_likelihood(draws), log_ratios)``.  Not in the reference."""
+
+    _LINKS = _GLM_LINKS
+    _pointwise_entry = 'nn_pointwise'
+
+    def __init__(self, X, y, n_hidden, likelihood='gaussian', prior_sd=1.0, noise_sd=1.0):
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1 or y.shape != (X.shape[0],):
+            raise ValueError('X must be (n_data, p) with p >= 1 and y (n_data,)')
+        if isinstance(n_hidden, bool) or int(n_hidden) != n_hidden or int(n_hidden) < 1:
+            raise ValueError('n_hidden must be an integer >= 1')
+        if likelihood not in self._LINKS:
+            raise ValueError("likelihood must be 'gaussian', 'logistic' or 'poisson'")
+        if not prior_sd > 0 or not noise_sd > 0:
+            raise ValueError('prior_sd and noise_sd must be positive')
+        if not np.all(np.isfinite(X)):
+            raise ValueError('X must be finite')
+        _check_glm_response(likelihood, y)
+        self.X, self.y = X, y
+        self.likelihood = likelihood
+        self.prior_sd, self.noise_sd = float(prior_sd), float(noise_sd)
+        self._n_hidden = int(n_hidden)
+        super().__init__(self._n_hidden * (X.shape[1] + 2) + 1)
+
+    def _build_spec(self):
+        return (_lib.MODEL_NEURALNET, self._dim,
+                np.concatenate([self.X.ravel(), self.y, [self.prior_sd, self.noise_sd]]),
+                np.array([self.n_data, self._n_hidden, self._LINKS[self.likelihood]], dtype=np.int64))
+
+    @property
+    def n_data(self):
+        return self.X.shape[0]
+
+    @property
+    def n_hidden(self):
+        return self._n_hidden
+
+    @property
+    def n_features(self):
+        return self.X.shape[1]
+
+    def unpack(self, theta):
+        """``(W, a, v, c)`` of ``theta`` ``(D,)`` or ``(N, D)``: the hidden weights ``W`` ``(..., h, p)`` (row ``k`` is
+        ``w_k``), the hidden biases ``a`` and the output weights ``v`` ``(..., h)``, the output bias ``c`` ``(...)``."""
+        theta = np.asarray(theta, dtype=np.float64)
+        if theta.ndim not in (1, 2) or theta.shape[-1] != self._dim:
+            raise ValueError('theta must have shape (N, {0}) or ({0},)'.format(self._dim))
+        h, p = self._n_hidden, self.n_features
+        return (theta[..., :h * p].reshape(theta.shape[:-1] + (h, p)), theta[..., h * p:h * p + h],
+                theta[..., h * p + h:h * p + 2 * h], theta[..., -1])
+
+    def pointwise_log_likelihood(self, x):
+        """``log p(y_i | eta_i(theta_s))`` for every draw (row of ``x``) and observation: ``(S, n_data)``, the ``log_lik``
+        argument of :func:`psisloo` (``psisloo(log_lik, log_ratios)`` is this model's route to LOO).  Normalised
+        densities, without the prior (``vb_nn_pointwise``).  ``x``: (S, D), or (D,) for one draw."""
+        return self._pointwise(x)
+
+    def predict_from_draws(self, x, X_new=None, y_new=None, log_weights=None):
+        """Posterior prediction from the draws ``x`` (S, D) -- or (D,) for one -- and their log weights ``log_weights``
+        (S,; None: equal weights; normalised on the way, ``-inf`` drops a draw): the arguments and the returned dict of
+        :meth:`LogisticRegressionModel.predict_from_draws`, with ``X_new`` ``(m, p)`` and ``eta_is`` the network's output
+        of draw ``s`` at row ``i``.  One fp64 MFMA product per chunk of observations, a forward kernel and the regression
+        targets' reduction kernel (``vb_nn_predict``): the (m, S) matrix stays on the device, five m-vectors come back."""
+        x, _ = self._rows(x)
+        p = self.n_features
+        if X_new is not None:
+            X_new = np.ascontiguousarray(X_new, dtype=np.float64)
+            if X_new.ndim != 2 or X_new.shape[1] != p:
+                raise ValueError('X_new must have shape (m, {}); got {}'.format(p, X_new.shape))
+            if X_new.shape[0] < 1:
+                raise ValueError('X_new must have at least one row')
+        m = self.n_data if X_new is None else X_new.shape[0]
+        if y_new is not None:
+            y_new = np.asarray(y_new, dtype=np.float64)
+            if y_new.shape != (m,):
+                raise ValueError('y_new must have shape ({},); got {}'.format(m, y_new.shape))
+            _check_glm_response(self.likelihood, y_new)
+        if log_weights is not None:
+            log_weights = np.asarray(log_weights, dtype=np.float64)
+            if log_weights.shape != (x.shape[0],):
+                raise ValueError('log_weights must have shape ({},)'.format(x.shape[0]))
+            if not np.any(np.isfinite(log_weights)):
+                raise ValueError('no log weight is finite')
+        eng = _lib.default_engine()
+        eng.set_model(self.device_spec())
+        return eng.nn_predict(x, p, log_w=log_weights, X_new=X_new, y_new=y_new)
 
 
 _M32 = np.uint64(0xFFFFFFFF)
