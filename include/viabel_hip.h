@@ -640,6 +640,37 @@ int vb_hmc_run(vb_ctx* ctx, const double* x0, const double* inv_mass, int64_t n_
                double* chain_m2, double* accept_rate, double* step_hist, double* accept_hist, double* final_step,
                int64_t* n_divergent);
 
+/* vb_hmc_run_metric: vb_hmc_run with a choice of metric, warm-up-only segments and window moments.  Arguments, outputs,
+ * random numbers, refusals and error codes are vb_hmc_run's except as stated here.
+ *   metric_kind, metric
+ *     VB_HMC_METRIC_DIAG   metric = inv_mass[d].  Without moments the call enqueues what vb_hmc_run enqueues and returns
+ *                          the same bits.
+ *     VB_HMC_METRIC_DENSE  metric = L (d x d, row-major), the lower Cholesky factor of the estimated posterior covariance
+ *                          Sigma = L L' (the inverse mass).  Entries above the diagonal are ignored; the diagonal must be
+ *                          positive and finite and the entries below it finite, else VB_ERR_INVALID.  HMC in whitened
+ *                          momenta r (p = L^-T r): r = z, the stream's normals unscaled, H = -f + 1/2 sum r^2, kicks
+ *                          r += c eps (g L), drifts x += eps (r L'); with L = diag(sqrt(inv_mass)) this is the diagonal
+ *                          algorithm.  Both products are fp64 MFMA GEMMs (chains x d x d, triangular) that read the step
+ *                          size from device memory: still no host synchronisation inside a call.  Capacity: d <= 4096
+ *                          (two padded copies of L on the device), VB_ERR_UNSUPPORTED beyond it.
+ *   n_draws >= 0 with n_warmup + n_draws >= 1.  A warm-up-only segment (n_draws = 0) returns last_x, step_hist,
+ *     accept_hist and *final_step (the averaged step of its dual averaging); draws, logp, chain_mean, chain_m2, accept_rate
+ *     and n_divergent may then be NULL (with n_draws > 0 the last four are required).  A run is continued by passing
+ *     last_x as x0, *final_step as step_size and stream_offset + n_warmup + n_draws as stream_offset.
+ *   moment_shift[d], moment_sum[d], moment_m2 (d for the diagonal kind, d x d for the dense kind): all three or none
+ *     (VB_ERR_INVALID otherwise).  With X_t the states after iteration t's accept step, over ALL iterations of the call:
+ *     moment_sum = sum_t sum_c (x - shift), moment_m2 = sum_t sum_c (x - shift)^2 (diagonal kind) or
+ *     sum_t sum_c (x - shift)(x - shift)' (dense kind; exactly symmetric).  The chains of an iteration are summed in a
+ *     fixed order (the dense kind's Gram product split over the chains, its slabs summed in order), the iterations in
+ *     order; no atomics: bit-reproducible.                                                                             */
+#define VB_HMC_METRIC_DIAG 0
+#define VB_HMC_METRIC_DENSE 1
+int vb_hmc_run_metric(vb_ctx* ctx, const double* x0, int metric_kind, const double* metric, int64_t n_chains, int64_t d,
+                      int64_t n_warmup, int64_t n_draws, int64_t thin, int n_leapfrog, double step_size, double target_accept,
+                      double jitter, uint64_t seed, uint64_t stream_offset, const double* moment_shift, double* moment_sum,
+                      double* moment_m2, double* draws, double* logp, double* last_x, double* chain_mean, double* chain_m2,
+                      double* accept_rate, double* step_hist, double* accept_hist, double* final_step, int64_t* n_divergent);
+
 /* ---- ExclusiveKL, multivariate t family ------------------------------------------------
  * ExclusiveKL closure (objectives.py:154-164, entropy form) for MultivariateT
  * (approximations.py:322-382): x_n = mu + (z_n Sigma^{1/2}) / s_n with the normals z (n x D) in

@@ -92,6 +92,7 @@ MAX_SLOTS = 64
 PSIS_BATCH_MAX_N, PSIS_BATCH_MAX_TAIL = 16384, 1024
 OPT_SGD, OPT_RMSPROP, OPT_ADAM, OPT_ADAGRAD = range(4)
 PRIOR_DIAG_GAUSSIAN, PRIOR_DIAG_STUDENT_T, PRIOR_DENSE = range(3)
+HMC_METRIC_DIAG, HMC_METRIC_DENSE = range(2)      # VB_HMC_METRIC_* (vb_hmc_run_metric)
 # int fn(void* user, const double* z, int64 n, int64 d, double* f, double* grad)   (include/viabel_hip.h: vb_model_callback)
 MODEL_CALLBACK_TYPE = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_int64,
                                        ctypes.c_int64, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double))
@@ -222,6 +223,11 @@ SIGNATURES = {
                                   ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                   ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64, _c_double_p, _c_double_p, _c_double_p,
                                   _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int64_p]),
+    'vb_hmc_run_metric': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int64, ctypes.c_int64,
+                                         ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64, _c_double_p,
+                                         _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                         _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int64_p]),
     'vb_alpha_grad_meanfield': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                ctypes.c_int, ctypes.c_double, _c_double_p, ctypes.c_double,
                                                _c_double_p, _c_double_p]),
@@ -981,6 +987,49 @@ class Engine:
         return dict(draws=draws, logp=logp, last=last, chain_mean=mean, chain_m2=m2, accept_rate=rate,
                     step_size_history=step_hist, accept_prob=accept_hist, step_size=final.value,
                     n_divergent=int(n_div.value))
+
+    def hmc_run_metric(self, x0, metric, n_warmup, n_draws, n_leapfrog, step_size, target_accept=0.8, jitter=0.2, seed=1,
+                       stream_offset=0, thin=1, keep_draws=True, moment_shift=None):
+        """``hmc_run`` with a choice of metric (``vb_hmc_run_metric``): ``metric`` (D,) is the diagonal metric
+        ``inv_mass``, ``metric`` (D, D) the lower Cholesky factor ``L`` of the dense one (``Sigma = L L'``).  ``n_draws``
+        may be 0 (a warm-up-only segment: the sampling outputs come back as None).  With ``moment_shift`` (D,) the dict
+        also has ``moment_sum`` (D,) and ``moment_m2`` ((D,) or (D, D)): the sums of ``x - shift`` and of its squares /
+        outer products over the chains and all iterations of the call."""
+        x0 = _f64(x0)
+        metric = _f64(metric)
+        if x0.ndim != 2:
+            raise ValueError('x0 must be (n_chains, D)')
+        c, d = x0.shape
+        if metric.shape not in ((d,), (d, d)):
+            raise ValueError('metric must have shape ({0},) or ({0}, {0})'.format(d))
+        dense = metric.ndim == 2
+        n_warmup, n_draws, thin = int(n_warmup), int(n_draws), int(thin)
+        n_iter = max(n_warmup, 0) + max(n_draws, 0)
+        n_kept = -(-max(n_draws, 0) // thin) if thin >= 1 else 0
+        sampling = n_draws > 0
+        draws = np.empty((n_kept, c, d), dtype=np.float64) if keep_draws and sampling else None
+        logp = np.empty((n_kept, c), dtype=np.float64) if sampling else None
+        last = np.empty((c, d), dtype=np.float64)
+        mean, m2 = (np.empty((c, d), dtype=np.float64) if sampling else None for _ in range(2))
+        rate = np.empty(c, dtype=np.float64) if sampling else None
+        step_hist, accept_hist = np.empty(n_iter, dtype=np.float64), np.empty(n_iter, dtype=np.float64)
+        shift = s1 = s2 = None
+        if moment_shift is not None:
+            shift = _f64(moment_shift)
+            if shift.shape != (d,):
+                raise ValueError('moment_shift must have shape ({},)'.format(d))
+            s1, s2 = np.empty(d, dtype=np.float64), np.empty((d, d) if dense else d, dtype=np.float64)
+        final = ctypes.c_double(0.0)
+        n_div = ctypes.c_int64(0)
+        opt = lambda a: None if a is None else _dptr(a)                                                       # noqa: E731
+        self._check(self._lib.vb_hmc_run_metric(
+            self._ctx, _dptr(x0), HMC_METRIC_DENSE if dense else HMC_METRIC_DIAG, _dptr(metric), c, d, n_warmup, n_draws,
+            thin, int(n_leapfrog), float(step_size), float(target_accept), float(jitter), int(seed), int(stream_offset),
+            opt(shift), opt(s1), opt(s2), opt(draws), opt(logp), _dptr(last), opt(mean), opt(m2), opt(rate),
+            _dptr(step_hist), _dptr(accept_hist), ctypes.addressof(final), ctypes.byref(n_div)))
+        return dict(draws=draws, logp=logp, last=last, chain_mean=mean, chain_m2=m2, accept_rate=rate,
+                    step_size_history=step_hist, accept_prob=accept_hist, step_size=final.value,
+                    n_divergent=int(n_div.value), moment_sum=s1, moment_m2=s2)
 
     # ------------------------------------------------------------------ AlphaDivergence, mean field
     def alpha_grad_meanfield(self, slot, n, d, theta, family, alpha, df=0.0, n_total=None):

@@ -2,7 +2,7 @@
 
 The reference's documentation compares its fits with MCMC draws (``docs/source/robust-regression.ipynb``:
 ``check_accuracy(true_mean, true_cov, var_param, approx)``); :func:`hmc` produces those draws here, from the gradient
-pipeline the objectives use (``vb_hmc_run``, ``csrc/vb_hmc.hip``; ``DESIGN.md`` 4.22)."""
+pipeline the objectives use (``vb_hmc_run`` / ``vb_hmc_run_metric``, ``csrc/vb_hmc.hip``; ``DESIGN.md`` 4.22)."""
 import numpy as np
 
 from viabel_amd import _lib
@@ -24,9 +24,70 @@ def _combine_chains(chain_mean, chain_var, n):
     return chain_mean.mean(axis=0), np.sqrt(var_plus), rhat
 
 
+MIN_ADAPT_WARMUP = 20          # the shortest warm-up the window schedule divides
+ADAPT_REG_WEIGHT, ADAPT_REG_VAR = 5.0, 1e-3
+
+
+def _adaptation_windows(n_warmup):
+    """The slow-phase windows ``[(start, end), ...]`` of an ``n_warmup``-iteration warm-up (Stan's schedule): an initial
+    buffer of 75, a terminal buffer of 50 and a first window of 25 iterations -- or 15 % / 10 % / the rest when those do not
+    fit --, each window twice as long as the last, the last one stretched to the terminal buffer when the next would not
+    fit in front of it."""
+    n = int(n_warmup)
+    if n < MIN_ADAPT_WARMUP:
+        raise ValueError('adapt_metric needs n_warmup >= {}'.format(MIN_ADAPT_WARMUP))
+    init, term, base = 75, 50, 25
+    if init + base + term > n:
+        init, term = int(0.15 * n), int(0.10 * n)
+        base = n - init - term
+    end_slow = n - term
+    windows, start, size = [], init, base
+    while True:
+        end = start + size
+        if end + 2 * size > end_slow:
+            windows.append((start, end_slow))
+            return windows
+        windows.append((start, end))
+        start, size = end, 2 * size
+
+
+def _window_metric(s1, s2, n, dense, window):
+    """The regularised metric of one window from the moments of its ``n`` states about a shift (which only conditions the
+    sums): ``cov = (S2 - S1 S1' / n) / (n - 1)`` shrunk as Stan does, ``n / (n + 5) cov + 1e-3 * 5 / (n + 5) I`` -- the
+    matrix and its lower Cholesky factor (dense), or the variances twice (diagonal)."""
+    n = float(n)
+    w = n / (n + ADAPT_REG_WEIGHT)
+    floor = ADAPT_REG_VAR * ADAPT_REG_WEIGHT / (n + ADAPT_REG_WEIGHT)
+    if not dense:
+        var = w * ((s2 - s1 * s1 / n) / (n - 1.0)) + floor
+        if not (np.all(var > 0.0) and np.all(np.isfinite(var))):
+            raise ValueError('adaptation window {}: the chains\' variances are not finite and positive'.format(window))
+        return var, var
+    cov = w * ((s2 - np.outer(s1, s1) / n) / (n - 1.0)) + floor * np.eye(s1.size)
+    try:
+        return cov, np.linalg.cholesky(cov)
+    except np.linalg.LinAlgError as err:
+        raise np.linalg.LinAlgError('adaptation window {}: the chains\' covariance has no Cholesky factor ({})'.format(
+            window, err)) from err
+
+
+def _dense_factor(cov, what):
+    """Lower Cholesky factor of a symmetric (to rounding), finite, positive definite matrix, else ``ValueError``."""
+    if not np.all(np.isfinite(cov)):
+        raise ValueError('{} must be finite'.format(what))
+    if np.max(np.abs(cov - cov.T)) > 1e-8 * np.max(np.abs(cov)):
+        raise ValueError('{} must be symmetric'.format(what))
+    try:
+        return np.linalg.cholesky(cov)
+    except np.linalg.LinAlgError:
+        raise ValueError('{} must be positive definite'.format(what))
+
+
 def _check_arguments(model, n_chains, n_warmup, n_draws, n_leapfrog, step_size, target_accept, jitter, init, inv_mass,
-                     var_param, approx, thin):
+                     var_param, approx, thin, metric='diag', adapt_metric=False):
     """Everything that can be refused without an engine; returns ``(init, inv_mass, step_size)`` as arrays / float."""
+    if metric not in ('diag', 'dense'):
+        raise ValueError('metric must be \'diag\' or \'dense\'; got {!r}'.format(metric))
     if not isinstance(model, DeviceModel):
         raise TypeError('hmc needs a viabel_amd device model (its gradient is device code); got {}'.format(
             type(model).__name__))
@@ -45,6 +106,8 @@ def _check_arguments(model, n_chains, n_warmup, n_draws, n_leapfrog, step_size, 
         raise ValueError('var_param and approx must be given together')
     if var_param is None and init is None:
         raise ValueError('either init or both var_param and approx must be given')
+    if adapt_metric and n_warmup < MIN_ADAPT_WARMUP:
+        raise ValueError('adapt_metric needs n_warmup >= {}'.format(MIN_ADAPT_WARMUP))
     d = model.dim
     step_size = d ** -0.25 if step_size is None else float(step_size)
     if not (step_size > 0.0 and np.isfinite(step_size)):
@@ -57,19 +120,42 @@ def _check_arguments(model, n_chains, n_warmup, n_draws, n_leapfrog, step_size, 
             raise ValueError('init must be finite')
     if inv_mass is not None:
         inv_mass = np.ascontiguousarray(inv_mass, dtype=np.float64)
+        if metric == 'dense' and inv_mass.shape == (d, d):
+            _dense_factor(inv_mass, 'inv_mass')
+            return init, inv_mass, step_size
         if inv_mass.shape != (d,):
-            raise ValueError('inv_mass must have shape ({},); got {}'.format(d, inv_mass.shape))
+            raise ValueError('inv_mass must have shape ({0},){1}; got {2}'.format(
+                d, ' or ({0}, {0})'.format(d) if metric == 'dense' else '', inv_mass.shape))
         if not (np.all(inv_mass > 0.0) and np.all(np.isfinite(inv_mass))):
             raise ValueError('inv_mass must be positive and finite')
+        if metric == 'dense':
+            inv_mass = np.diag(inv_mass)
     return init, inv_mass, step_size
 
 
+def _segments(n_warmup, n_draws, windows):
+    """``[(n_warmup, n_draws, window or None), ...]``: the engine calls of an adaptive run -- the initial buffer, every
+    window, the terminal buffer together with the sampling phase."""
+    out = [(windows[0][0], 0, None)] if windows[0][0] > 0 else []
+    out += [(end - start, 0, (start, end)) for start, end in windows]
+    return out + [(n_warmup - windows[-1][1], n_draws, None)]
+
+
 def hmc(model, *, n_chains=256, n_warmup=300, n_draws=300, n_leapfrog=16, step_size=None, target_accept=0.8, jitter=0.2,
-        init=None, inv_mass=None, var_param=None, approx=None, seed=1, stream_offset=0, thin=1, keep_draws=True):
+        init=None, inv_mass=None, var_param=None, approx=None, seed=1, stream_offset=0, thin=1, keep_draws=True,
+        metric='diag', adapt_metric=False):
     """Hamiltonian Monte Carlo draws from a device model: ``n_chains`` chains advanced in lock-step on the GPU, each
-    iteration one trajectory of ``n_leapfrog`` leapfrog steps under a diagonal metric and an accept test; the step size is
-    adapted by dual averaging on the chains' mean acceptance during ``n_warmup`` iterations (target ``target_accept``)
-    and jittered by ``+- jitter`` per iteration.  No NUTS, no mass-matrix adaptation: the metric comes from a fit.
+    iteration one trajectory of ``n_leapfrog`` leapfrog steps under a diagonal or dense metric and an accept test; the step
+    size is adapted by dual averaging on the chains' mean acceptance during ``n_warmup`` iterations (target
+    ``target_accept``) and jittered by ``+- jitter`` per iteration.  No NUTS.  The metric comes from a fit, or, with
+    ``adapt_metric=True``, from the chains themselves.
+
+    ``metric='dense'`` takes the whole covariance as the inverse mass (two triangular ``n_chains x D x D`` products per
+    leapfrog step): ``inv_mass`` may then be (D, D) -- symmetric, positive definite -- or (D,), and defaults to the full
+    ``approx.mean_and_cov(var_param)[1]`` with a fit and to the identity without one.  ``adapt_metric=True``
+    (``n_warmup >= 20``) re-estimates the metric during warm-up from the cross-chain moments of doubling windows (Stan's
+    schedule and regularisation; ``_adaptation_windows``): each window end costs one host round trip, and the step-size
+    adaptation restarts there from the step it had reached.  With neither keyword the run is ``vb_hmc_run``'s, as ever.
 
     With ``var_param`` and ``approx`` (as ``bbvi`` or ``laplace_approximation`` return them) the chains start at
     ``approx.sample(var_param, n_chains)`` unless ``init`` (n_chains x D) is given, and the metric is the diagonal of
@@ -81,16 +167,24 @@ def hmc(model, *, n_chains=256, n_warmup=300, n_draws=300, n_leapfrog=16, step_s
     (C x D; ``ddof=1`` over all ``n_draws`` sampling iterations, thinned or not); ``mean``, ``sd`` and ``rhat`` (D,) from
     them (``W`` the mean chain variance, ``B = n var(chain means)``, ``var+ = (n - 1) / n W + B / n``, ``sd = sqrt(var+)``,
     ``rhat = sqrt(var+ / W)``); ``accept_rate`` (C,); ``accept_prob`` and ``step_size_history`` (n_warmup + n_draws,);
-    ``step_size`` (the sampling phase's); ``n_divergent``; ``inv_mass``; ``seed`` and ``next_stream``.  A continuation
+    ``step_size`` (the sampling phase's); ``n_divergent``; ``inv_mass`` (the metric the sampling phase used: (D,), or
+    (D, D) for the dense metric); ``metric``; ``adapt_windows`` (the windows ``[(start, end), ...]``, empty without
+    adaptation); ``seed`` and ``next_stream``.  A continuation
     passes ``init=res['last']``, ``step_size=res['step_size']``, ``n_warmup=0`` and ``stream_offset=res['next_stream']``.
     Runs on the calling process's engine; raises ``NotImplementedError`` for a ``CallableModel`` and for a sharded
     engine."""
     refuse_minibatch(model, 'hmc')
     init, inv_mass, step_size = _check_arguments(model, n_chains, n_warmup, n_draws, n_leapfrog, step_size, target_accept,
-                                                 jitter, init, inv_mass, var_param, approx, thin)
+                                                 jitter, init, inv_mass, var_param, approx, thin, metric, adapt_metric)
+    dense = metric == 'dense'
     if var_param is not None:
         var_param = np.asarray(var_param, dtype=np.float64)
-        if inv_mass is None:
+        if inv_mass is None and dense:
+            inv_mass = np.ascontiguousarray(approx.mean_and_cov(var_param)[1], dtype=np.float64)
+            if inv_mass.shape != (model.dim, model.dim):
+                raise ValueError('approx.mean_and_cov returned a covariance of shape {}'.format(inv_mass.shape))
+            _dense_factor(inv_mass, 'the approximation\'s covariance')
+        elif inv_mass is None:
             inv_mass = np.ascontiguousarray(np.diag(approx.mean_and_cov(var_param)[1]), dtype=np.float64)
             if not (np.all(inv_mass > 0.0) and np.all(np.isfinite(inv_mass))):
                 raise ValueError('the approximation has no finite positive variances to take the metric from; pass inv_mass')
@@ -99,14 +193,32 @@ def hmc(model, *, n_chains=256, n_warmup=300, n_draws=300, n_leapfrog=16, step_s
             if init.shape != (n_chains, model.dim):
                 raise ValueError('approx.sample returned shape {}, expected ({}, {})'.format(init.shape, n_chains, model.dim))
     if inv_mass is None:
-        inv_mass = np.ones(model.dim)
+        inv_mass = np.eye(model.dim) if dense else np.ones(model.dim)
+    windows = _adaptation_windows(n_warmup) if adapt_metric else []
     eng = _lib.default_engine()
     if eng.n_ranks > 1:
         raise NotImplementedError('hmc runs on one process\'s engine; a sharded engine ({} ranks) is not supported'.format(
             eng.n_ranks))
     eng.set_model(model.device_spec())
-    out = eng.hmc_run(init, inv_mass, n_warmup, n_draws, n_leapfrog, step_size, target_accept=target_accept, jitter=jitter,
-                      seed=seed, stream_offset=stream_offset, thin=thin, keep_draws=keep_draws)
+    if not dense and not adapt_metric:
+        out = eng.hmc_run(init, inv_mass, n_warmup, n_draws, n_leapfrog, step_size, target_accept=target_accept,
+                          jitter=jitter, seed=seed, stream_offset=stream_offset, thin=thin, keep_draws=keep_draws)
+    else:
+        # one engine call per segment, each continuing from the last one's states, final step and stream
+        factor = np.linalg.cholesky(inv_mass) if dense else inv_mass
+        segments = _segments(int(n_warmup), int(n_draws), windows) if adapt_metric else [(int(n_warmup), int(n_draws), None)]
+        x, step, stream, hist = init, step_size, int(stream_offset), []
+        for seg_warmup, seg_draws, window in segments:
+            out = eng.hmc_run_metric(x, factor, seg_warmup, seg_draws, n_leapfrog, step, target_accept=target_accept,
+                                     jitter=jitter, seed=seed, stream_offset=stream, thin=thin, keep_draws=keep_draws,
+                                     moment_shift=None if window is None else x.mean(axis=0))
+            hist.append((out['step_size_history'], out['accept_prob']))
+            if window is not None:
+                inv_mass, factor = _window_metric(out['moment_sum'], out['moment_m2'], int(n_chains) * seg_warmup, dense,
+                                                  window)
+            x, step, stream = out['last'], out['step_size'], stream + seg_warmup + seg_draws
+        out['step_size_history'] = np.concatenate([h[0] for h in hist])
+        out['accept_prob'] = np.concatenate([h[1] for h in hist])
     n = int(n_draws)
     with np.errstate(divide='ignore', invalid='ignore'):
         chain_var = out['chain_m2'] / (n - 1.0) if n > 1 else np.full_like(out['chain_m2'], np.nan)
@@ -114,7 +226,7 @@ def hmc(model, *, n_chains=256, n_warmup=300, n_draws=300, n_leapfrog=16, step_s
     results = dict(draws=out['draws'], logp=out['logp'], last=out['last'], chain_mean=out['chain_mean'],
                    chain_var=chain_var, mean=mean, sd=sd, rhat=rhat, accept_rate=out['accept_rate'],
                    accept_prob=out['accept_prob'], step_size_history=out['step_size_history'], step_size=out['step_size'],
-                   n_divergent=out['n_divergent'], inv_mass=inv_mass, seed=int(seed),
+                   n_divergent=out['n_divergent'], inv_mass=inv_mass, metric=metric, adapt_windows=windows, seed=int(seed),
                    next_stream=int(stream_offset) + int(n_warmup) + int(n_draws))
     max_rhat = float(np.max(rhat[~np.isnan(rhat)])) if not np.all(np.isnan(rhat)) else float('nan')
     print('hmc: step size = {:.4g}, mean acceptance = {:.3f}, max rhat = {:.3f}, {} divergent of {} proposals'.format(
