@@ -671,6 +671,36 @@ int vb_hmc_run_metric(vb_ctx* ctx, const double* x0, int metric_kind, const doub
                       double* moment_m2, double* draws, double* logp, double* last_x, double* chain_mean, double* chain_m2,
                       double* accept_rate, double* step_hist, double* accept_hist, double* final_step, int64_t* n_divergent);
 
+/* vb_hmc_run_chees: vb_hmc_run_metric with the trajectory length adapted across the chains (ChEES-HMC; Hoffman, Radul &
+ * Sountsov 2021) instead of a fixed n_leapfrog.  Arguments, outputs, random numbers, refusals and error
+ * codes are vb_hmc_run_metric's except as stated here.
+ *   One trajectory length T, shared by all chains.  Iteration t (Philox stream s = stream_offset + t) takes
+ *   L_t = clamp(ceil(h_s T_t / eps_t), 1, max_leapfrog) leapfrog steps, h_s = (bitreverse32(low32(s + 1)) + 0.5) 2^-32 the
+ *   base-2 radical inverse and eps_t the iteration's jittered step size: the mean trajectory is T / 2.  During warm-up T_t
+ *   is the iterate of a stochastic gradient ascent (Adam without first moment, beta_2 = 0.95, learning rate trajectory_lr,
+ *   on log T) on the ChEES criterion, formed from the chains' states, proposals, final velocities and acceptance
+ *   probabilities; chains whose proposal has a non-finite log density are left out, and an iteration whose estimate is not
+ *   finite (or whose acceptance probabilities are all zero) leaves T alone.  log T is kept in
+ *   [log eps_base, log(max_leapfrog eps_base)].  During sampling T_t = exp(log T_bar), the m^-0.75-weighted average.
+ *   traj_state[4], in and out: log T, Adam's second moment v, log T_bar, the count m of adapted warm-up iterations.  A
+ *     first call passes (log T_0, 0, log T_0, 0); a continuation passes what the last call returned.  A call with
+ *     n_warmup = 0 uses exp(traj_state[2]) throughout and returns the state unchanged.
+ *   traj_hist[n_warmup + n_draws]   T_t of every iteration;  leap_hist[n_warmup + n_draws] (int64): L_t
+ *   step_hist is what the transitions used, bit for bit.
+ *   Warm-up iterations fetch L_{t+1} (8 bytes) before the next transition is enqueued: one host synchronisation per warm-up
+ *   iteration.  The sampling phase's step sizes and step counts are planned by one kernel and fetched once: from there on
+ *   the call synchronises only for the download, as vb_hmc_run does.  The dense kind runs one more triangular product per
+ *   warm-up transition (the velocities r L').  Every sum has a fixed order: bit-reproducible.
+ *   VB_ERR_INVALID also for: a NULL traj_state / traj_hist / leap_hist, max_leapfrog < 1, trajectory_lr negative or not
+ *   finite, a non-finite traj_state entry (or m < 0), n_chains < 2 with n_warmup > 0 (the criterion is a cross-chain
+ *   statistic) -- all before any device work.                                                                         */
+int vb_hmc_run_chees(vb_ctx* ctx, const double* x0, int metric_kind, const double* metric, int64_t n_chains, int64_t d,
+                     int64_t n_warmup, int64_t n_draws, int64_t thin, int max_leapfrog, double trajectory_lr, double step_size,
+                     double target_accept, double jitter, uint64_t seed, uint64_t stream_offset, const double* moment_shift,
+                     double* moment_sum, double* moment_m2, double* draws, double* logp, double* last_x, double* chain_mean,
+                     double* chain_m2, double* accept_rate, double* step_hist, double* accept_hist, double* final_step,
+                     int64_t* n_divergent, double* traj_state, double* traj_hist, int64_t* leap_hist);
+
 /* ---- ExclusiveKL, multivariate t family ------------------------------------------------
  * ExclusiveKL closure (objectives.py:154-164, entropy form) for MultivariateT
  * (approximations.py:322-382): x_n = mu + (z_n Sigma^{1/2}) / s_n with the normals z (n x D) in

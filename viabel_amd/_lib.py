@@ -228,6 +228,12 @@ SIGNATURES = {
                                          ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64, _c_double_p,
                                          _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
                                          _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int64_p]),
+    'vb_hmc_run_chees': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int64, ctypes.c_int64,
+                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
+                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64,
+                                        _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                        _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                        _c_int64_p, _c_double_p, _c_double_p, _c_int64_p]),
     'vb_alpha_grad_meanfield': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                ctypes.c_int, ctypes.c_double, _c_double_p, ctypes.c_double,
                                                _c_double_p, _c_double_p]),
@@ -1030,6 +1036,55 @@ class Engine:
         return dict(draws=draws, logp=logp, last=last, chain_mean=mean, chain_m2=m2, accept_rate=rate,
                     step_size_history=step_hist, accept_prob=accept_hist, step_size=final.value,
                     n_divergent=int(n_div.value), moment_sum=s1, moment_m2=s2)
+
+    def hmc_run_chees(self, x0, metric, n_warmup, n_draws, max_leapfrog, step_size, traj_state, trajectory_lr=0.025,
+                      target_accept=0.8, jitter=0.2, seed=1, stream_offset=0, thin=1, keep_draws=True, moment_shift=None):
+        """``hmc_run_metric`` with the trajectory length adapted across the chains (``vb_hmc_run_chees``; ChEES-HMC) in
+        place of ``n_leapfrog``: at most ``max_leapfrog`` steps per iteration.  ``traj_state`` is ``(log T, v, log T_bar,
+        m)`` -- ``(log T0, 0, log T0, 0)`` for a first call, the last call's ``traj_state`` for a continuation.  The dict
+        has ``hmc_run_metric``'s entries plus ``traj_state`` (the state after the call), ``trajectory_history`` (float64)
+        and ``n_leapfrog_history`` (int64), both of length ``n_warmup + n_draws``."""
+        x0 = _f64(x0)
+        metric = _f64(metric)
+        if x0.ndim != 2:
+            raise ValueError('x0 must be (n_chains, D)')
+        c, d = x0.shape
+        if metric.shape not in ((d,), (d, d)):
+            raise ValueError('metric must have shape ({0},) or ({0}, {0})'.format(d))
+        state = np.array(traj_state, dtype=np.float64)
+        if state.shape != (4,):
+            raise ValueError('traj_state must have four entries (log T, v, log T_bar, m)')
+        dense = metric.ndim == 2
+        n_warmup, n_draws, thin = int(n_warmup), int(n_draws), int(thin)
+        n_iter = max(n_warmup, 0) + max(n_draws, 0)
+        n_kept = -(-max(n_draws, 0) // thin) if thin >= 1 else 0
+        sampling = n_draws > 0
+        draws = np.empty((n_kept, c, d), dtype=np.float64) if keep_draws and sampling else None
+        logp = np.empty((n_kept, c), dtype=np.float64) if sampling else None
+        last = np.empty((c, d), dtype=np.float64)
+        mean, m2 = (np.empty((c, d), dtype=np.float64) if sampling else None for _ in range(2))
+        rate = np.empty(c, dtype=np.float64) if sampling else None
+        step_hist, accept_hist = np.empty(n_iter, dtype=np.float64), np.empty(n_iter, dtype=np.float64)
+        traj_hist, leap_hist = np.empty(n_iter, dtype=np.float64), np.zeros(n_iter, dtype=np.int64)
+        shift = s1 = s2 = None
+        if moment_shift is not None:
+            shift = _f64(moment_shift)
+            if shift.shape != (d,):
+                raise ValueError('moment_shift must have shape ({},)'.format(d))
+            s1, s2 = np.empty(d, dtype=np.float64), np.empty((d, d) if dense else d, dtype=np.float64)
+        final = ctypes.c_double(0.0)
+        n_div = ctypes.c_int64(0)
+        opt = lambda a: None if a is None else _dptr(a)                                                       # noqa: E731
+        self._check(self._lib.vb_hmc_run_chees(
+            self._ctx, _dptr(x0), HMC_METRIC_DENSE if dense else HMC_METRIC_DIAG, _dptr(metric), c, d, n_warmup, n_draws,
+            thin, int(max_leapfrog), float(trajectory_lr), float(step_size), float(target_accept), float(jitter), int(seed),
+            int(stream_offset), opt(shift), opt(s1), opt(s2), opt(draws), opt(logp), _dptr(last), opt(mean), opt(m2),
+            opt(rate), _dptr(step_hist), _dptr(accept_hist), ctypes.addressof(final), ctypes.byref(n_div), _dptr(state),
+            _dptr(traj_hist), leap_hist.ctypes.data_as(_c_int64_p)))
+        return dict(draws=draws, logp=logp, last=last, chain_mean=mean, chain_m2=m2, accept_rate=rate,
+                    step_size_history=step_hist, accept_prob=accept_hist, step_size=final.value,
+                    n_divergent=int(n_div.value), moment_sum=s1, moment_m2=s2, traj_state=state,
+                    trajectory_history=traj_hist, n_leapfrog_history=leap_hist)
 
     # ------------------------------------------------------------------ AlphaDivergence, mean field
     def alpha_grad_meanfield(self, slot, n, d, theta, family, alpha, df=0.0, n_total=None):

@@ -83,6 +83,43 @@
 // drift 38.9 us for 1024 x 1024 x 1025 multiply-adds: 27.5 TFLOP/s counting the triangle only, against 44.7 TFLOP/s of the
 // same run's dense 1024^3 gradient product and the 52 TFLOP/s the triangular product reaches at 4096 rows -- 512 tiles of
 // unequal k range on 256 CUs).
+//
+// ---- vb_hmc_run_chees: the trajectory length adapted across the chains (ChEES-HMC) ---------------------------
+// One length T for all chains; iteration t takes L_t = clamp(ceil(h_s T_t / eps_t), 1, max_leapfrog) steps, h_s the base-2
+// radical inverse of low32(s + 1); warm-up adapts log T by Adam (no first moment) on the cross-chain criterion.  The fixed
+// route's kernels and launches are untouched.  A warm-up transition adds, between the last gradient and the end kernel:
+//   velocity GEMM (dense)       A = r, B = L' (the drift's operands), EpiHmcVelocity: v' = acc stored to a C x ld buffer of
+//                               the zeroed region (N = d: the pads are never written)
+//   hmc_chees_mean_kernel       hmc_moment_kernel's layout and order (64 columns per workgroup, wave w: chains w, w + 4, ...;
+//                               (w0 + w1) + (w2 + w3)): column sums of x over all chains and of xp over the usable ones
+//                               (finite fp), and the usable count; sixteen chains' loads in flight per wave
+//   hmc_chees_chain_kernel<D>   one wave per chain: |xp - mean xp|^2, |x - mean x|^2 and (xp - mean xp) . v' by lane-strided
+//                               fma and wave_sum; crit[c] = their product form, 0 and flag[c] = 1 for an unusable chain
+// and every transition runs, in place of hmc_adapt_kernel,
+//   hmc_chees_adapt_kernel      one workgroup: the mean of a and (warm-up) sum a_c, sum a_c crit_c over the unflagged chains,
+//                               all in the a-mean's order (thread i: i, i + 256, ...; shuffle tree; (w0 + w1) + (w2 + w3));
+//                               dual averaging as above; the Adam step, the clamp to [log base, log(max_leapfrog base)], the
+//                               m^-0.75 average; while the next iteration is a warm-up one its eps, T and L into the state
+//                               (slots 4 .. 7: log T, v, log T_bar, L_next) and the histories; in the sampling phase it
+//                               moves the planned eps of the next iteration from step_hist into the state
+//   hmc_chees_plan_kernel       once, when the warm-up has ended: eps_t, T_t = exp(log T_bar), L_t of every sampling iteration
+// The host reads L_{t+1} back (8 bytes, fetch_blocking) after every warm-up iteration but the last, and all sampling step
+// counts at once after the plan kernel: the sampling phase synchronises only for the download, as above.
+// Workspace, in the zeroed region before the draws: [colsum (2 ld) | n_usable | crit (C) | flag (C, int) | v' (C x ld, dense
+// with a warm-up) | traj_hist | leap_hist (n_iter each)].
+// Resources (same command; scratch 0 and no AGPRs in all; hmc_adapt_kernel and the other kernels above unchanged):
+//     hmc_chees_mean_kernel:        112 VGPRs, 106 SGPRs, 4128 B LDS -> 4 waves per SIMD (one workgroup per 64 columns)
+//     hmc_chees_chain_kernel<false>: 52 VGPRs,  36 SGPRs, no LDS     -> 8 waves per SIMD
+//     hmc_chees_chain_kernel<true>:  46 VGPRs,  32 SGPRs, no LDS     -> 8 waves per SIMD
+//     hmc_chees_adapt_kernel:        49 VGPRs,  64 SGPRs, 96 B LDS   -> one workgroup
+//     hmc_chees_plan_kernel:         18 VGPRs,  26 SGPRs, no LDS     -> 8 waves per SIMD
+//     EpiHmcVelocity's GEMM instances: 59 VGPRs for the 64 x 32 tile the launcher picks here, at most 249, scratch 0
+// Measured (tools/hmc_chees_bench.py, profiles/hmc_chees_kernel_stats.txt; one MI355X, 1024 chains): a sampling transition of
+// 16.1 steps on average 5.48 ms against 5.44 for n_leapfrog = 16 at the logistic shape (0.3405 / 0.3397 ms per step),
+// 1.253 / 1.243 at the multilevel one; a warm-up transition 0.05 - 0.08 ms beyond its own steps; mean kernel 51.4 us at
+// D = 64 (one workgroup) and 37.4 us at D = 117 (213 us with one load in flight), chain kernel 4.9 us, velocity product
+// 6.0 / 7.4 us, adapt 6.3 us, plan 4.8 us.  Smallest ESS per gradient evaluation against n_leapfrog = 16: 2.5, 2.2 and 1.8
+// times at the logistic, multilevel and correlated-logistic shapes; at the logistic shape n_leapfrog = 4 beats it five times.
 #include "vb_rows_target.h"
 #include "vb_rng.h"
 
@@ -352,6 +389,225 @@ __global__ void __launch_bounds__(256) hmc_gram_add_kernel(const HmcMomentArgs q
   q.s2[e] += acc;
 }
 
+// ---- ChEES: the trajectory length adapted across the chains (vb_hmc_run_chees) --------------------------------
+constexpr double kCheesBeta2 = 0.95, kCheesAdamEps = 1e-8;
+enum HmcCheesState { HS_LOG_T = 4, HS_V, HS_LOG_TBAR, HS_LNEXT };      // the four slots of state[] the fixed route leaves free
+
+struct HmcCheesBuf {
+  double* colsum;          // 2 ld: column sums of x over all chains | of xp over the usable chains
+  double* n_usable;        // 1: chains whose proposal has a finite log density
+  double* crit;            // C: the criterion's per-chain factor product (0 for an unusable chain)
+  int* flag;               // C: 1 for an unusable chain
+  const double* vel;       // dense kind: C x ld, v' = r L' (pad columns zero); else nullptr
+};
+
+// h_s of the iteration whose stream has low32(s + 1) = n: the base-2 radical inverse, in (0, 1), exact in fp64
+__device__ __forceinline__ double chees_halton(uint32_t n) { return ((double)__brev(n) + 0.5) * 0x1p-32; }
+
+// L = clamp(ceil(tau / eps), 1, max_leapfrog); a NaN quotient gives 1
+__device__ __forceinline__ long long chees_steps(double tau, double eps, int max_leapfrog) {
+  const double r = ceil(tau / eps);
+  return r >= (double)max_leapfrog ? (long long)max_leapfrog : (r >= 1.0 ? (long long)r : 1ll);
+}
+
+// 64 columns per workgroup, the chains dealt to its four waves (wave w: chains w, w + 4, ...; then (w0 + w1) + (w2 + w3)):
+// the column sums of x over all chains and of xp over the usable ones; workgroup 0 also stores the usable count
+__global__ void __launch_bounds__(256) hmc_chees_mean_kernel(const HmcArgs a, const HmcCheesBuf b) {
+  __shared__ double sh[2][4][64];
+  __shared__ double cnt[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int col = blockIdx.x * 64 + lane;
+  double s = 0.0, sp = 0.0, n = 0.0;
+  // kMeanAhead chains' loads in flight per wave (one at a time, the loop is a chain of memory latencies: 213 us at 1024
+  // chains), added in chain order.  The loads are unconditional, at indices clamped into the matrices, and selected
+  // afterwards: a chain that is left out, or beyond the last one, adds +0.0, which changes no bit
+  constexpr int kMeanAhead = 16;
+  const int lc = col < a.d ? col : a.d - 1;
+  for (int64_t c0 = w; c0 < a.n_chains; c0 += 4 * kMeanAhead) {
+    double xv[kMeanAhead], pv[kMeanAhead], uv[kMeanAhead];
+#pragma unroll
+    for (int u = 0; u < kMeanAhead; ++u) {
+      const int64_t c = c0 + 4 * u, cc = c < a.n_chains ? c : a.n_chains - 1;
+      xv[u] = a.x[cc * a.ld + lc], pv[u] = a.xp[cc * a.ld + lc], uv[u] = a.fp[cc];
+    }
+#pragma unroll
+    for (int u = 0; u < kMeanAhead; ++u) {
+      const bool in = c0 + 4 * u < a.n_chains, usable = in && isfinite(uv[u]);
+      xv[u] = in && col < a.d ? xv[u] : 0.0, pv[u] = usable && col < a.d ? pv[u] : 0.0, uv[u] = usable ? 1.0 : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < kMeanAhead; ++u) s += xv[u], sp += pv[u], n += uv[u];
+  }
+  sh[0][w][lane] = s;
+  sh[1][w][lane] = sp;
+  if (lane == 0) cnt[w] = n;
+  __syncthreads();
+  if (w != 0) return;
+  if (col < a.d) {
+    b.colsum[col] = (sh[0][0][lane] + sh[0][1][lane]) + (sh[0][2][lane] + sh[0][3][lane]);
+    b.colsum[a.ld + col] = (sh[1][0][lane] + sh[1][1][lane]) + (sh[1][2][lane] + sh[1][3][lane]);
+  }
+  if (blockIdx.x == 0 && lane == 0) b.n_usable[0] = (cnt[0] + cnt[1]) + (cnt[2] + cnt[3]);
+}
+
+// one wave per chain, four chains per workgroup: crit_c = (|x' - mean x'|^2 - |x - mean x|^2) ((x' - mean x') . v'), the three
+// sums lane-strided fma and wave_sum; v' = inv_mass (p + 1/2 eps gp) (the end kernel's last half kick), or the row of r L'
+template <bool DENSE>
+__global__ void __launch_bounds__(256) hmc_chees_chain_kernel(const HmcArgs a, const HmcCheesBuf b) {
+  const int lane = threadIdx.x & 63;
+  const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= a.n_chains) return;
+  [[maybe_unused]] const double half = 0.5 * a.state[HS_EPS];
+  const double n_all = (double)a.n_chains, n_usable = b.n_usable[0];
+  const int64_t row = c * a.ld;
+  double n0 = 0.0, n1 = 0.0, dot = 0.0;
+  for (int col = lane; col < a.d; col += 64) {
+    const double dx = a.x[row + col] - b.colsum[col] / n_all;
+    const double dxp = a.xp[row + col] - b.colsum[a.ld + col] / n_usable;
+    double vel;
+    if constexpr (DENSE) vel = b.vel[row + col];
+    else vel = a.inv_mass[col] * (a.p[row + col] + half * a.gp[row + col]);
+    n0 = fma(dx, dx, n0);
+    n1 = fma(dxp, dxp, n1);
+    dot = fma(dxp, vel, dot);
+  }
+  n0 = wave_sum(n0), n1 = wave_sum(n1), dot = wave_sum(dot);
+  if (lane != 0) return;
+  const bool usable = isfinite(a.fp[c]);
+  b.crit[c] = usable ? (n1 - n0) * dot : 0.0;
+  b.flag[c] = usable ? 0 : 1;
+}
+
+struct EpiHmcVelocity {      // v' = acc, acc = (r L')[row][col]: the velocity at the proposal (dense kind)
+  double* v;
+  int64_t ld;
+  __device__ void operator()(int, int row, int col, double acc) const { v[(int64_t)row * ld + col] = acc; }
+};
+
+struct HmcCheesAdaptArgs {
+  const double* crit;      // C
+  const int* flag;         // C
+  double* traj_hist;       // T: the trajectory length T_t of every iteration
+  long long* leap_hist;    // T: its number of leapfrog steps
+  double log_t0, v0, log_tbar0, m0;      // t = -1: the state the call starts from
+  double lr;
+  int max_leapfrog;
+};
+
+// hmc_adapt_kernel's sibling for the ChEES route, launched in its place: the same mean of a and dual-averaging update, then
+// (warm-up) the two weighted sums over the usable chains in the a-mean's order, the Adam step on log T, its clamp and its
+// running average, and -- while the next iteration is a warm-up one -- that iteration's eps, T and L.  The sampling
+// iterations' eps, T and L come from hmc_chees_plan_kernel; there this kernel only moves the planned eps into the state.
+__global__ void __launch_bounds__(256) hmc_chees_adapt_kernel(const HmcAdaptArgs q, const HmcCheesAdaptArgs z) {
+  __shared__ double sh[3][4];
+  const int t = threadIdx.x;
+  const bool warm = q.t >= 0 && q.t < q.n_warmup;
+  double s = 0.0, sa = 0.0, sc = 0.0;
+  if (q.t >= 0)
+    for (int64_t c = t; c < q.n_chains; c += 256) {
+      const double ac = q.a[c];
+      s += ac;
+      if (warm && !z.flag[c]) {
+        sa += ac;
+        sc += ac * z.crit[c];
+      }
+    }
+  s = wave_sum(s), sa = wave_sum(sa), sc = wave_sum(sc);
+  if ((t & 63) == 0) sh[0][t >> 6] = s, sh[1][t >> 6] = sa, sh[2][t >> 6] = sc;
+  __syncthreads();
+  if (t != 0) return;
+  double base = q.step_size;
+  if (q.t >= 0) {
+    const double abar = ((sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3])) / (double)q.n_chains;
+    q.accept_hist[q.t] = abar;
+    base = q.state[HS_BASE];
+    if (warm) {
+      const double m = (double)(q.t + 1), w = 1.0 / (m + kHmcT0);
+      const double hbar = (1.0 - w) * q.state[HS_HBAR] + (q.target - abar) * w;
+      const double log_eps = q.mu - sqrt(m) / kHmcGamma * hbar;
+      const double eta = pow(m, -kHmcKappa);
+      const double log_eps_bar = eta * log_eps + (1.0 - eta) * q.state[HS_LOG_EPS_BAR];
+      q.state[HS_HBAR] = hbar;
+      q.state[HS_LOG_EPS_BAR] = log_eps_bar;
+      base = q.t + 1 < q.n_warmup ? exp(log_eps) : exp(log_eps_bar);
+    }
+  } else {
+    q.state[HS_HBAR] = 0.0;
+    q.state[HS_LOG_EPS_BAR] = 0.0;
+    q.state[HS_LOG_T] = z.log_t0;
+    q.state[HS_V] = z.v0;
+    q.state[HS_LOG_TBAR] = z.log_tbar0;
+  }
+  q.state[HS_BASE] = base;
+  if (warm) {
+    // low32(s_t + 1) is the low word of the next iteration's stream
+    const double tau = chees_halton(q.w_next) * z.traj_hist[q.t];
+    const double wsum = (sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3]), csum = (sh[2][0] + sh[2][1]) + (sh[2][2] + sh[2][3]);
+    const double ghat = tau * csum / wsum;
+    const double m = z.m0 + (double)(q.t + 1);
+    double log_t = q.state[HS_LOG_T];
+    if (wsum != 0.0 && isfinite(ghat)) {
+      const double v = kCheesBeta2 * q.state[HS_V] + (1.0 - kCheesBeta2) * ghat * ghat;
+      q.state[HS_V] = v;
+      log_t += z.lr * ghat / (sqrt(v / (1.0 - pow(kCheesBeta2, m))) + kCheesAdamEps);
+    }
+    log_t = fmin(fmax(log_t, log(base)), log((double)z.max_leapfrog * base));
+    const double eta = pow(m, -kHmcKappa);
+    q.state[HS_LOG_T] = log_t;
+    q.state[HS_LOG_TBAR] = eta * log_t + (1.0 - eta) * q.state[HS_LOG_TBAR];
+  }
+  if (q.t + 1 >= q.n_iter) return;
+  if (q.t + 1 < q.n_warmup) {
+    const Philox4 o = philox_sub(~(uint64_t)0, kHmcUniformCol, q.w_next, 0, q.k0, q.k1_next);
+    const double eps = base * (1.0 + q.jitter * (2.0 * u01(o.z, o.w) - 1.0));
+    const double traj = exp(q.state[HS_LOG_T]);
+    const long long n_leap = chees_steps(chees_halton(q.w_next + 1u) * traj, eps, z.max_leapfrog);
+    q.state[HS_EPS] = eps;
+    q.step_hist[q.t + 1] = eps;
+    z.traj_hist[q.t + 1] = traj;
+    z.leap_hist[q.t + 1] = n_leap;
+    q.state[HS_LNEXT] = (double)n_leap;
+  } else if (q.t >= q.n_warmup) {
+    q.state[HS_EPS] = q.step_hist[q.t + 1];
+  }
+}
+
+struct HmcCheesPlanArgs {
+  double* state;
+  double* step_hist;
+  double* traj_hist;
+  long long* leap_hist;
+  int64_t n_warmup, n_iter;
+  double jitter;
+  uint32_t k0, seed_hi;
+  uint64_t stream_offset;
+  int max_leapfrog;
+};
+
+// launched once, when the warm-up has ended: eps_t, T_t = exp(log T_bar) and L_t of every sampling iteration, one thread
+// each, from hmc_chees_adapt_kernel's expressions; the first one's eps goes into the state
+__global__ void __launch_bounds__(256) hmc_chees_plan_kernel(const HmcCheesPlanArgs q) {
+  const int64_t t = q.n_warmup + (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= q.n_iter) return;
+  const uint64_t s = q.stream_offset + (uint64_t)t;
+  const double base = q.state[HS_BASE];
+  const Philox4 o = philox_sub(~(uint64_t)0, kHmcUniformCol, (uint32_t)s, 0, q.k0, q.seed_hi ^ (uint32_t)(s >> 32));
+  const double eps = base * (1.0 + q.jitter * (2.0 * u01(o.z, o.w) - 1.0));
+  const double traj = exp(q.state[HS_LOG_TBAR]);
+  q.step_hist[t] = eps;
+  q.traj_hist[t] = traj;
+  q.leap_hist[t] = chees_steps(chees_halton((uint32_t)s + 1u) * traj, eps, q.max_leapfrog);
+  if (t == q.n_warmup) q.state[HS_EPS] = eps;
+}
+
+struct HmcChees {            // vb_hmc_run_chees's own arguments
+  int max_leapfrog;
+  double lr;
+  double* traj_state;      // in / out: log T, v, log T_bar, m
+  double* traj_hist;       // n_iter
+  int64_t* leap_hist;      // n_iter
+};
+
 constexpr int kHmcDenseMaxDim = 4096;                           // dense metric: two padded d x d factors on the device
 constexpr int kHmcMaxSplits = 32;
 constexpr int64_t kHmcSlabBudgetDoubles = (int64_t)1 << 25;     // 256 MiB of Gram slabs
@@ -373,14 +629,17 @@ struct HmcCall {
   const double* moment_shift;
   double* moment_sum;
   double* moment_m2;
+  const HmcChees* chees;   // vb_hmc_run_chees: n_leapfrog is then the largest step count; else nullptr
 };
 
-// vb_hmc_run and vb_hmc_run_metric: the diagonal kind without moments enqueues exactly what vb_hmc_run always did
+// vb_hmc_run, vb_hmc_run_metric and vb_hmc_run_chees: the diagonal kind without moments and without ChEES enqueues exactly
+// what vb_hmc_run always did
 int hmc_run(vb_ctx* ctx, const HmcCall& hc, const double* x0, int64_t n_chains, int64_t d, int64_t n_warmup, int64_t n_draws,
             int64_t thin, int n_leapfrog, double step_size, double target_accept, double jitter, uint64_t seed,
             uint64_t stream_offset, double* draws, double* logp, double* last_x, double* chain_mean, double* chain_m2,
             double* accept_rate, double* step_hist, double* accept_hist, double* final_step, int64_t* n_divergent) {
   const bool dense = hc.kind == VB_HMC_METRIC_DENSE, moments = hc.moment_shift != nullptr;
+  const HmcChees* ch = hc.chees;
   if (thin < 1) return fail(ctx, VB_ERR_INVALID, "thin must be at least 1");
   if (n_leapfrog < 1) return fail(ctx, VB_ERR_INVALID, "n_leapfrog must be at least 1");
   if (!(step_size > 0.0) || !std::isfinite(step_size)) return fail(ctx, VB_ERR_INVALID, "step_size must be positive and finite");
@@ -430,6 +689,9 @@ int hmc_run(vb_ctx* ctx, const HmcCall& hc, const double* x0, int64_t n_chains, 
                 o_div = carve(C), o_l = carve(dense ? ld * ld : 0), o_lt = carve(dense ? ld * ld : 0),
                 o_shift = carve(moments ? ld : 0), o_s1 = carve(moments ? ld : 0),
                 o_s2 = carve(moments ? (dense ? d * d : ld) : 0), o_xc = carve(splits ? mat : 0),
+                o_cs = carve(ch ? 2 * ld : 0), o_nu = carve(ch ? 1 : 0), o_crit = carve(ch ? C : 0),
+                o_flag = carve(ch ? (C + 1) / 2 : 0), o_vel = carve(ch && dense && n_warmup > 0 ? mat : 0),
+                o_th = carve(ch ? n_iter : 0), o_lh = carve(ch ? n_iter : 0),
                 o_draws = carve(draws ? n_kept * C * d : 0), o_logp = carve(logp ? n_kept * C : 0),
                 o_slab = carve((int64_t)splits * slab_stride);
   VB_TRY(ensure(ctx, ctx->hmc_work, (size_t)carve.off * sizeof(double)));
@@ -474,8 +736,26 @@ int hmc_run(vb_ctx* ctx, const HmcCall& hc, const double* x0, int64_t n_chains, 
                           EpiHmcDrift{a.xp, ld, a.state});
     return hipGetLastError();
   };
+  auto velocity = [&](double* vel) {                   // v' = r L' (ChEES, warm-up): the drift's operands, stored
+    gemm_f64_launch<true>(st, gemm_product(a.p, ld, base + o_lt, ld, (int)C, (int)d, (int)ld, 1), 1, n_cu,
+                          EpiHmcVelocity{vel, ld});
+    return hipGetLastError();
+  };
 
   const uint32_t k0 = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32);
+  HmcCheesBuf cb{};
+  HmcCheesAdaptArgs cz{};
+  if (ch) {
+    cb.colsum = base + o_cs, cb.n_usable = base + o_nu, cb.crit = base + o_crit, cb.flag = (int*)(base + o_flag);
+    cb.vel = dense && n_warmup > 0 ? base + o_vel : nullptr;
+    cz.crit = cb.crit, cz.flag = cb.flag, cz.traj_hist = base + o_th, cz.leap_hist = (long long*)(base + o_lh);
+    cz.log_t0 = ch->traj_state[0], cz.v0 = ch->traj_state[1], cz.log_tbar0 = ch->traj_state[2], cz.m0 = ch->traj_state[3];
+    cz.lr = ch->lr, cz.max_leapfrog = ch->max_leapfrog;
+  }
+  // ChEES: the step count of the iteration about to be enqueued -- fetched after every warm-up iteration (8 bytes), and for
+  // all sampling iterations at once when the warm-up has ended
+  int steps = n_leapfrog;
+  auto steps_ok = [&](double l) { return l >= 1.0 && l <= (double)n_leapfrog; };
   HmcAdaptArgs q;
   q.a = a.a, q.n_chains = C, q.state = a.state, q.step_hist = base + o_sh, q.accept_hist = base + o_ah;
   q.n_warmup = n_warmup, q.n_iter = n_iter, q.step_size = step_size, q.target = target_accept, q.jitter = jitter;
@@ -489,20 +769,28 @@ int hmc_run(vb_ctx* ctx, const HmcCall& hc, const double* x0, int64_t n_chains, 
         hipLaunchKernelGGL(hmc_begin_kernel<true>, chain_grid, block, 0, st, a, k0, k1, w);
         VB_HIP(ctx, hipGetLastError());
         VB_HIP(ctx, kick(a.g, 0.5));
-        for (int l = 0; l < n_leapfrog; ++l) {
+        for (int l = 0; l < steps; ++l) {
           VB_HIP(ctx, drift());
           VB_TRY(model_grad_rows(ctx, a.xp, ld, C, d, a.gp, a.fp));
-          VB_HIP(ctx, kick(a.gp, l + 1 == n_leapfrog ? 0.5 : 1.0));
+          VB_HIP(ctx, kick(a.gp, l + 1 == steps ? 0.5 : 1.0));
         }
       } else {
         hipLaunchKernelGGL(hmc_begin_kernel<false>, chain_grid, block, 0, st, a, k0, k1, w);
         VB_HIP(ctx, hipGetLastError());
-        for (int l = 0; l < n_leapfrog; ++l) {
+        for (int l = 0; l < steps; ++l) {
           VB_TRY(model_grad_rows(ctx, a.xp, ld, C, d, a.gp, a.fp));
-          if (l + 1 == n_leapfrog) break;
+          if (l + 1 == steps) break;
           hipLaunchKernelGGL(hmc_leap_kernel, leap_grid, block, 0, st, a);
           VB_HIP(ctx, hipGetLastError());
         }
+      }
+      if (ch && t < n_warmup) {      // the criterion, before the accept step overwrites x
+        if (dense) VB_HIP(ctx, velocity(base + o_vel));
+        hipLaunchKernelGGL(hmc_chees_mean_kernel, dim3((unsigned)((d + 63) / 64)), block, 0, st, a, cb);
+        VB_HIP(ctx, hipGetLastError());
+        if (dense) hipLaunchKernelGGL(hmc_chees_chain_kernel<true>, chain_grid, block, 0, st, a, cb);
+        else hipLaunchKernelGGL(hmc_chees_chain_kernel<false>, chain_grid, block, 0, st, a, cb);
+        VB_HIP(ctx, hipGetLastError());
       }
       HmcEndArgs e;
       e.k0 = k0, e.k1 = k1, e.w = w;
@@ -531,8 +819,33 @@ int hmc_run(vb_ctx* ctx, const HmcCall& hc, const double* x0, int64_t n_chains, 
     }
     const uint64_t sn = stream_offset + (uint64_t)(t + 1);
     q.t = t, q.k1_next = seed_hi ^ (uint32_t)(sn >> 32), q.w_next = (uint32_t)sn;
-    hipLaunchKernelGGL(hmc_adapt_kernel, dim3(1), block, 0, st, q);
+    if (!ch) {
+      hipLaunchKernelGGL(hmc_adapt_kernel, dim3(1), block, 0, st, q);
+      VB_HIP(ctx, hipGetLastError());
+      continue;
+    }
+    hipLaunchKernelGGL(hmc_chees_adapt_kernel, dim3(1), block, 0, st, q, cz);
     VB_HIP(ctx, hipGetLastError());
+    if (t + 1 < n_warmup) {
+      double l_next = 0.0;
+      const FetchSeg seg{a.state + HS_LNEXT, sizeof(double), &l_next};
+      VB_TRY(fetch_blocking(ctx, st, &seg, 1));
+      if (!steps_ok(l_next)) return fail(ctx, VB_ERR_NUMERIC, "%s: the device planned %g leapfrog steps", hc.name, l_next);
+      steps = (int)l_next;
+    } else if (t + 1 == n_warmup && n_draws > 0) {
+      HmcCheesPlanArgs pq;
+      pq.state = a.state, pq.step_hist = q.step_hist, pq.traj_hist = cz.traj_hist, pq.leap_hist = cz.leap_hist;
+      pq.n_warmup = n_warmup, pq.n_iter = n_iter, pq.jitter = jitter, pq.k0 = k0, pq.seed_hi = seed_hi;
+      pq.stream_offset = stream_offset, pq.max_leapfrog = ch->max_leapfrog;
+      hipLaunchKernelGGL(hmc_chees_plan_kernel, dim3((unsigned)((n_draws + 255) / 256)), block, 0, st, pq);
+      VB_HIP(ctx, hipGetLastError());
+      const FetchSeg seg{cz.leap_hist + n_warmup, (size_t)n_draws * sizeof(long long), ch->leap_hist + n_warmup};
+      VB_TRY(fetch_blocking(ctx, st, &seg, 1));
+      for (int64_t i = n_warmup; i < n_iter; ++i)
+        if (!steps_ok((double)ch->leap_hist[i]))
+          return fail(ctx, VB_ERR_NUMERIC, "%s: the device planned %lld leapfrog steps", hc.name, (long long)ch->leap_hist[i]);
+    }
+    if (t + 1 >= n_warmup && t + 1 < n_iter) steps = (int)ch->leap_hist[t + 1];
   }
 
   // the one synchronisation: download
@@ -554,6 +867,11 @@ int hmc_run(vb_ctx* ctx, const HmcCall& hc, const double* x0, int64_t n_chains, 
     VB_HIP(ctx, hipMemcpyAsync(hc.moment_sum, mq.s1, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, st));
     VB_HIP(ctx, hipMemcpyAsync(hc.moment_m2, mq.s2, (size_t)(dense ? d * d : d) * sizeof(double), hipMemcpyDeviceToHost, st));
   }
+  if (ch) {
+    VB_HIP(ctx, hipMemcpyAsync(ch->traj_hist, cz.traj_hist, (size_t)n_iter * sizeof(double), hipMemcpyDeviceToHost, st));
+    VB_HIP(ctx, hipMemcpyAsync(ch->leap_hist, cz.leap_hist, (size_t)n_iter * sizeof(long long), hipMemcpyDeviceToHost, st));
+    VB_HIP(ctx, hipMemcpyAsync(ch->traj_state, a.state + HS_LOG_T, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
   std::vector<long long> div((size_t)C);
   VB_HIP(ctx, hipMemcpyAsync(div.data(), a.n_div, (size_t)C * sizeof(long long), hipMemcpyDeviceToHost, st));
   VB_HIP(ctx, hipStreamSynchronize(st));
@@ -563,6 +881,7 @@ int hmc_run(vb_ctx* ctx, const HmcCall& hc, const double* x0, int64_t n_chains, 
     if (accept_rate && n_draws > 0) accept_rate[c] /= (double)n_draws;
   }
   if (n_divergent) *n_divergent = total;
+  if (ch) ch->traj_state[3] += (double)n_warmup;
   return VB_OK;
 }
 
@@ -582,7 +901,7 @@ int vb_hmc_run(vb_ctx* ctx, const double* x0, const double* inv_mass, int64_t n_
     return fail(ctx, VB_ERR_INVALID, "NULL argument");
   if (n_chains <= 0 || d <= 0 || n_draws <= 0 || n_warmup < 0)
     return fail(ctx, VB_ERR_INVALID, "n_chains, d and n_draws must be positive and n_warmup non-negative");
-  const HmcCall hc{"vb_hmc_run", VB_HMC_METRIC_DIAG, inv_mass, nullptr, nullptr, nullptr};
+  const HmcCall hc{"vb_hmc_run", VB_HMC_METRIC_DIAG, inv_mass, nullptr, nullptr, nullptr, nullptr};
   return hmc_run(ctx, hc, x0, n_chains, d, n_warmup, n_draws, thin, n_leapfrog, step_size, target_accept, jitter, seed,
                  stream_offset, draws, logp, last_x, chain_mean, chain_m2, accept_rate, step_hist, accept_hist, final_step,
                  n_divergent);
@@ -605,8 +924,42 @@ int vb_hmc_run_metric(vb_ctx* ctx, const double* x0, int metric_kind, const doub
   const int given = (moment_shift != nullptr) + (moment_sum != nullptr) + (moment_m2 != nullptr);
   if (given != 0 && given != 3)
     return fail(ctx, VB_ERR_INVALID, "moment_shift, moment_sum and moment_m2 go together: pass all three or none");
-  const HmcCall hc{"vb_hmc_run_metric", metric_kind, metric, moment_shift, moment_sum, moment_m2};
+  const HmcCall hc{"vb_hmc_run_metric", metric_kind, metric, moment_shift, moment_sum, moment_m2, nullptr};
   return hmc_run(ctx, hc, x0, n_chains, d, n_warmup, n_draws, thin, n_leapfrog, step_size, target_accept, jitter, seed,
+                 stream_offset, draws, logp, last_x, chain_mean, chain_m2, accept_rate, step_hist, accept_hist, final_step,
+                 n_divergent);
+}
+
+int vb_hmc_run_chees(vb_ctx* ctx, const double* x0, int metric_kind, const double* metric, int64_t n_chains, int64_t d,
+                     int64_t n_warmup, int64_t n_draws, int64_t thin, int max_leapfrog, double trajectory_lr, double step_size,
+                     double target_accept, double jitter, uint64_t seed, uint64_t stream_offset, const double* moment_shift,
+                     double* moment_sum, double* moment_m2, double* draws, double* logp, double* last_x, double* chain_mean,
+                     double* chain_m2, double* accept_rate, double* step_hist, double* accept_hist, double* final_step,
+                     int64_t* n_divergent, double* traj_state, double* traj_hist, int64_t* leap_hist) {
+  if (!ctx || !x0 || !metric || !last_x || !step_hist || !accept_hist || !final_step || !traj_state || !traj_hist || !leap_hist)
+    return fail(ctx, VB_ERR_INVALID, "NULL argument");
+  if (metric_kind != VB_HMC_METRIC_DIAG && metric_kind != VB_HMC_METRIC_DENSE)
+    return fail(ctx, VB_ERR_INVALID, "metric_kind must be VB_HMC_METRIC_DIAG or VB_HMC_METRIC_DENSE");
+  if (n_chains <= 0 || d <= 0 || n_draws < 0 || n_warmup < 0 || n_warmup + n_draws < 1)
+    return fail(ctx, VB_ERR_INVALID, "n_chains and d must be positive, n_warmup and n_draws non-negative with at least one "
+                                     "iteration between them");
+  if (n_draws > 0 && (!chain_mean || !chain_m2 || !accept_rate || !n_divergent))
+    return fail(ctx, VB_ERR_INVALID, "NULL sampling output with n_draws > 0");
+  const int given = (moment_shift != nullptr) + (moment_sum != nullptr) + (moment_m2 != nullptr);
+  if (given != 0 && given != 3)
+    return fail(ctx, VB_ERR_INVALID, "moment_shift, moment_sum and moment_m2 go together: pass all three or none");
+  if (max_leapfrog < 1) return fail(ctx, VB_ERR_INVALID, "max_leapfrog must be at least 1");
+  if (!(trajectory_lr >= 0.0) || !std::isfinite(trajectory_lr))
+    return fail(ctx, VB_ERR_INVALID, "trajectory_lr must be non-negative and finite");
+  for (int k = 0; k < 4; ++k)
+    if (!std::isfinite(traj_state[k])) return fail(ctx, VB_ERR_INVALID, "traj_state[%d] must be finite", k);
+  if (traj_state[1] < 0.0 || traj_state[3] < 0.0)
+    return fail(ctx, VB_ERR_INVALID, "traj_state: the second moment and the iteration count must be non-negative");
+  if (n_chains < 2 && n_warmup > 0)
+    return fail(ctx, VB_ERR_INVALID, "the trajectory length is adapted across the chains: n_chains >= 2 with n_warmup > 0");
+  const HmcChees ch{max_leapfrog, trajectory_lr, traj_state, traj_hist, leap_hist};
+  const HmcCall hc{"vb_hmc_run_chees", metric_kind, metric, moment_shift, moment_sum, moment_m2, &ch};
+  return hmc_run(ctx, hc, x0, n_chains, d, n_warmup, n_draws, thin, max_leapfrog, step_size, target_accept, jitter, seed,
                  stream_offset, draws, logp, last_x, chain_mean, chain_m2, accept_rate, step_hist, accept_hist, final_step,
                  n_divergent);
 }

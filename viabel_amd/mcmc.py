@@ -2,7 +2,8 @@
 
 The reference's documentation compares its fits with MCMC draws (``docs/source/robust-regression.ipynb``:
 ``check_accuracy(true_mean, true_cov, var_param, approx)``); :func:`hmc` produces those draws here, from the gradient
-pipeline the objectives use (``vb_hmc_run`` / ``vb_hmc_run_metric``, ``csrc/vb_hmc.hip``; ``DESIGN.md`` 4.22)."""
+pipeline the objectives use (``vb_hmc_run`` / ``vb_hmc_run_metric`` / ``vb_hmc_run_chees``, ``csrc/vb_hmc.hip``;
+``DESIGN.md`` 4.22 and 4.25)."""
 import numpy as np
 
 from viabel_amd import _lib
@@ -84,10 +85,19 @@ def _dense_factor(cov, what):
 
 
 def _check_arguments(model, n_chains, n_warmup, n_draws, n_leapfrog, step_size, target_accept, jitter, init, inv_mass,
-                     var_param, approx, thin, metric='diag', adapt_metric=False):
+                     var_param, approx, thin, metric='diag', adapt_metric=False, trajectory='fixed', max_leapfrog=256,
+                     trajectory_length=None, trajectory_lr=0.025):
     """Everything that can be refused without an engine; returns ``(init, inv_mass, step_size)`` as arrays / float."""
     if metric not in ('diag', 'dense'):
         raise ValueError('metric must be \'diag\' or \'dense\'; got {!r}'.format(metric))
+    if trajectory not in ('fixed', 'chees'):
+        raise ValueError('trajectory must be \'fixed\' or \'chees\'; got {!r}'.format(trajectory))
+    if isinstance(max_leapfrog, bool) or int(max_leapfrog) != max_leapfrog or not (1 <= max_leapfrog < 2 ** 31):
+        raise ValueError('max_leapfrog must be an integer >= 1')
+    if trajectory_length is not None and not (trajectory_length > 0.0 and np.isfinite(trajectory_length)):
+        raise ValueError('trajectory_length must be positive and finite')
+    if not (trajectory_lr >= 0.0 and np.isfinite(trajectory_lr)):
+        raise ValueError('trajectory_lr must be non-negative and finite')
     if not isinstance(model, DeviceModel):
         raise TypeError('hmc needs a viabel_amd device model (its gradient is device code); got {}'.format(
             type(model).__name__))
@@ -98,6 +108,9 @@ def _check_arguments(model, n_chains, n_warmup, n_draws, n_leapfrog, step_size, 
                          ('n_leapfrog', n_leapfrog, 1), ('thin', thin, 1)):
         if isinstance(v, bool) or int(v) != v or v < low:
             raise ValueError('{} must be an integer >= {}'.format(name, low))
+    if trajectory == 'chees' and n_chains < 2 and n_warmup > 0:
+        raise ValueError('trajectory=\'chees\' adapts the trajectory length across the chains: it needs n_chains >= 2 '
+                         '(or n_warmup = 0)')
     if not (0.0 < target_accept < 1.0):
         raise ValueError('target_accept must lie in (0, 1)')
     if not (0.0 <= jitter < 1.0):
@@ -143,12 +156,24 @@ def _segments(n_warmup, n_draws, windows):
 
 def hmc(model, *, n_chains=256, n_warmup=300, n_draws=300, n_leapfrog=16, step_size=None, target_accept=0.8, jitter=0.2,
         init=None, inv_mass=None, var_param=None, approx=None, seed=1, stream_offset=0, thin=1, keep_draws=True,
-        metric='diag', adapt_metric=False):
+        metric='diag', adapt_metric=False, trajectory='fixed', max_leapfrog=256, trajectory_length=None,
+        trajectory_lr=0.025):
     """Hamiltonian Monte Carlo draws from a device model: ``n_chains`` chains advanced in lock-step on the GPU, each
     iteration one trajectory of ``n_leapfrog`` leapfrog steps under a diagonal or dense metric and an accept test; the step
     size is adapted by dual averaging on the chains' mean acceptance during ``n_warmup`` iterations (target
-    ``target_accept``) and jittered by ``+- jitter`` per iteration.  No NUTS.  The metric comes from a fit, or, with
-    ``adapt_metric=True``, from the chains themselves.
+    ``target_accept``) and jittered by ``+- jitter`` per iteration.  The metric comes from a fit, or, with
+    ``adapt_metric=True``, from the chains themselves.  The trajectory length is ``n_leapfrog`` steps, or, with
+    ``trajectory='chees'``, adapted across the chains.
+
+    ``trajectory='chees'`` (ChEES-HMC; Hoffman, Radul & Sountsov 2021; no NUTS: per-chain tree depths would break the
+    lock-step batch) keeps one trajectory length ``T`` shared by all chains: iteration ``t`` takes
+    ``clamp(ceil(h_t T / step size), 1, max_leapfrog)`` leapfrog steps with ``h_t`` in (0, 1) the base-2 radical inverse of
+    its stream index plus one, so the mean trajectory is ``T / 2``.  During warm-up ``T`` follows a stochastic gradient
+    ascent (Adam without first moment, learning rate ``trajectory_lr``) on the "change in the estimator of the expected
+    square" across the chains, from ``trajectory_length`` (default: the initial step size, one leapfrog step); sampling
+    uses the average of its iterates.  ``n_leapfrog`` is ignored then.  It needs ``n_chains >= 2`` when there is a warm-up,
+    works with both metrics and with ``adapt_metric`` (the trajectory state is carried across the windows, as the step
+    size is), and costs one 8-byte host round trip per warm-up iteration; the sampling phase still runs without one.
 
     ``metric='dense'`` takes the whole covariance as the inverse mass (two triangular ``n_chains x D x D`` products per
     leapfrog step): ``inv_mass`` may then be (D, D) -- symmetric, positive definite -- or (D,), and defaults to the full
@@ -169,14 +194,19 @@ def hmc(model, *, n_chains=256, n_warmup=300, n_draws=300, n_leapfrog=16, step_s
     ``rhat = sqrt(var+ / W)``); ``accept_rate`` (C,); ``accept_prob`` and ``step_size_history`` (n_warmup + n_draws,);
     ``step_size`` (the sampling phase's); ``n_divergent``; ``inv_mass`` (the metric the sampling phase used: (D,), or
     (D, D) for the dense metric); ``metric``; ``adapt_windows`` (the windows ``[(start, end), ...]``, empty without
-    adaptation); ``seed`` and ``next_stream``.  A continuation
-    passes ``init=res['last']``, ``step_size=res['step_size']``, ``n_warmup=0`` and ``stream_offset=res['next_stream']``.
+    adaptation); ``trajectory_length`` (the sampling phase's ``T``; for ``'fixed'``, ``n_leapfrog`` times the sampling
+    phase's step size), ``trajectory_history`` and ``n_leapfrog_history`` (n_warmup + n_draws,; for ``'fixed'`` the
+    constants ``trajectory_length`` and ``n_leapfrog``); ``n_grad_evals`` (gradient evaluations per chain: the leapfrog
+    steps of all iterations plus one for the start of every engine call); ``seed`` and ``next_stream``.  A continuation
+    passes ``init=res['last']``, ``step_size=res['step_size']``, ``n_warmup=0`` and ``stream_offset=res['next_stream']``,
+    and, for ``'chees'``, ``trajectory='chees'`` and ``trajectory_length=res['trajectory_length']``.
     Runs on the calling process's engine; raises ``NotImplementedError`` for a ``CallableModel`` and for a sharded
     engine."""
     refuse_minibatch(model, 'hmc')
     init, inv_mass, step_size = _check_arguments(model, n_chains, n_warmup, n_draws, n_leapfrog, step_size, target_accept,
-                                                 jitter, init, inv_mass, var_param, approx, thin, metric, adapt_metric)
-    dense = metric == 'dense'
+                                                 jitter, init, inv_mass, var_param, approx, thin, metric, adapt_metric,
+                                                 trajectory, max_leapfrog, trajectory_length, trajectory_lr)
+    dense, chees = metric == 'dense', trajectory == 'chees'
     if var_param is not None:
         var_param = np.asarray(var_param, dtype=np.float64)
         if inv_mass is None and dense:
@@ -200,25 +230,45 @@ def hmc(model, *, n_chains=256, n_warmup=300, n_draws=300, n_leapfrog=16, step_s
         raise NotImplementedError('hmc runs on one process\'s engine; a sharded engine ({} ranks) is not supported'.format(
             eng.n_ranks))
     eng.set_model(model.device_spec())
-    if not dense and not adapt_metric:
+    n_calls = 1
+    if not dense and not adapt_metric and not chees:
         out = eng.hmc_run(init, inv_mass, n_warmup, n_draws, n_leapfrog, step_size, target_accept=target_accept,
                           jitter=jitter, seed=seed, stream_offset=stream_offset, thin=thin, keep_draws=keep_draws)
     else:
         # one engine call per segment, each continuing from the last one's states, final step and stream
         factor = np.linalg.cholesky(inv_mass) if dense else inv_mass
         segments = _segments(int(n_warmup), int(n_draws), windows) if adapt_metric else [(int(n_warmup), int(n_draws), None)]
-        x, step, stream, hist = init, step_size, int(stream_offset), []
+        x, step, stream, hist, n_calls = init, step_size, int(stream_offset), [], len(segments)
+        log_t0 = np.log(step_size if trajectory_length is None else float(trajectory_length))
+        traj_state = np.array([log_t0, 0.0, log_t0, 0.0])
         for seg_warmup, seg_draws, window in segments:
-            out = eng.hmc_run_metric(x, factor, seg_warmup, seg_draws, n_leapfrog, step, target_accept=target_accept,
-                                     jitter=jitter, seed=seed, stream_offset=stream, thin=thin, keep_draws=keep_draws,
-                                     moment_shift=None if window is None else x.mean(axis=0))
-            hist.append((out['step_size_history'], out['accept_prob']))
+            kw = dict(target_accept=target_accept, jitter=jitter, seed=seed, stream_offset=stream, thin=thin,
+                      keep_draws=keep_draws, moment_shift=None if window is None else x.mean(axis=0))
+            if chees:
+                out = eng.hmc_run_chees(x, factor, seg_warmup, seg_draws, max_leapfrog, step, traj_state,
+                                        trajectory_lr=trajectory_lr, **kw)
+                traj_state = out['traj_state']
+                hist.append((out['step_size_history'], out['accept_prob'], out['trajectory_history'],
+                             out['n_leapfrog_history']))
+            else:
+                out = eng.hmc_run_metric(x, factor, seg_warmup, seg_draws, n_leapfrog, step, **kw)
+                hist.append((out['step_size_history'], out['accept_prob']))
             if window is not None:
                 inv_mass, factor = _window_metric(out['moment_sum'], out['moment_m2'], int(n_chains) * seg_warmup, dense,
                                                   window)
             x, step, stream = out['last'], out['step_size'], stream + seg_warmup + seg_draws
         out['step_size_history'] = np.concatenate([h[0] for h in hist])
         out['accept_prob'] = np.concatenate([h[1] for h in hist])
+        if chees:
+            out['trajectory_history'] = np.concatenate([h[2] for h in hist])
+            out['n_leapfrog_history'] = np.concatenate([h[3] for h in hist])
+    n_iter = int(n_warmup) + int(n_draws)
+    if chees:          # (without a warm-up the length is the one given: a continuation passes it on unchanged)
+        traj_hist, leap_hist = out['trajectory_history'], out['n_leapfrog_history']
+        traj = float(traj_hist[int(n_warmup)]) if n_warmup > 0 or trajectory_length is None else float(trajectory_length)
+    else:
+        traj = int(n_leapfrog) * out['step_size']
+        traj_hist, leap_hist = np.full(n_iter, traj), np.full(n_iter, int(n_leapfrog), dtype=np.int64)
     n = int(n_draws)
     with np.errstate(divide='ignore', invalid='ignore'):
         chain_var = out['chain_m2'] / (n - 1.0) if n > 1 else np.full_like(out['chain_m2'], np.nan)
@@ -226,11 +276,14 @@ def hmc(model, *, n_chains=256, n_warmup=300, n_draws=300, n_leapfrog=16, step_s
     results = dict(draws=out['draws'], logp=out['logp'], last=out['last'], chain_mean=out['chain_mean'],
                    chain_var=chain_var, mean=mean, sd=sd, rhat=rhat, accept_rate=out['accept_rate'],
                    accept_prob=out['accept_prob'], step_size_history=out['step_size_history'], step_size=out['step_size'],
-                   n_divergent=out['n_divergent'], inv_mass=inv_mass, metric=metric, adapt_windows=windows, seed=int(seed),
+                   n_divergent=out['n_divergent'], inv_mass=inv_mass, metric=metric, adapt_windows=windows, trajectory_length=traj,
+                   trajectory_history=traj_hist, n_leapfrog_history=leap_hist,
+                   n_grad_evals=int(leap_hist.sum()) + n_calls, seed=int(seed),
                    next_stream=int(stream_offset) + int(n_warmup) + int(n_draws))
     max_rhat = float(np.max(rhat[~np.isnan(rhat)])) if not np.all(np.isnan(rhat)) else float('nan')
-    print('hmc: step size = {:.4g}, mean acceptance = {:.3f}, max rhat = {:.3f}, {} divergent of {} proposals'.format(
-        results['step_size'], float(out['accept_rate'].mean()), max_rhat, results['n_divergent'], n * int(n_chains)))
+    print('hmc: step size = {:.4g}, T = {:.4g}, mean L = {:.1f}, mean acceptance = {:.3f}, max rhat = {:.3f}, {} divergent of '
+          '{} proposals'.format(results['step_size'], traj, float(leap_hist.mean()), float(out['accept_rate'].mean()),
+                                max_rhat, results['n_divergent'], n * int(n_chains)))
     if max_rhat > 1.05 or results['n_divergent'] > 0:
         print('WARNING: rhat > 1.05 means the chains have not mixed; divergences mean the step size is too large for '
               'parts of the posterior. Run longer, start from a better fit, or lower step_size.')
