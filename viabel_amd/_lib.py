@@ -107,6 +107,13 @@ _c_double_p = ctypes.c_void_p
 _c_int64_p = ctypes.POINTER(ctypes.c_int64)
 _ctx_p = ctypes.c_void_p
 
+# the parts the three vb_hmc_run* argument lists are made of
+_HMC_METRIC = [_ctx_p, _c_double_p, ctypes.c_int, _c_double_p]        # ctx, x0, metric_kind, metric
+_HMC_SIZES = [ctypes.c_int64] * 5 + [ctypes.c_int]                    # n_chains, d, n_warmup, n_draws, thin, n_leapfrog
+_HMC_SCALARS = [ctypes.c_double] * 3 + [ctypes.c_uint64] * 2          # step_size, target_accept, jitter, seed, stream_offset
+_HMC_MOMENTS = [_c_double_p] * 3                                      # moment_shift, moment_sum, moment_m2
+_HMC_OUTPUTS = [_c_double_p] * 9 + [_c_int64_p]                       # draws ... final_step, n_divergent
+
 # name -> (restype, argtypes); every symbol declared in include/viabel_hip.h
 SIGNATURES = {
     'vb_version': (ctypes.c_char_p, []),
@@ -219,21 +226,11 @@ SIGNATURES = {
                                      ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
                                      _c_double_p]),
     'vb_glm_value_grad_hessian': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p]),
-    'vb_hmc_run': (ctypes.c_int, [_ctx_p, _c_double_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                  ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_double,
-                                  ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64, _c_double_p, _c_double_p, _c_double_p,
-                                  _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int64_p]),
-    'vb_hmc_run_metric': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int64, ctypes.c_int64,
-                                         ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
-                                         ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64, _c_double_p,
-                                         _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
-                                         _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int64_p]),
-    'vb_hmc_run_chees': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int64, ctypes.c_int64,
-                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
-                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64,
-                                        _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
-                                        _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
-                                        _c_int64_p, _c_double_p, _c_double_p, _c_int64_p]),
+    'vb_hmc_run': (ctypes.c_int, [_ctx_p, _c_double_p, _c_double_p] + _HMC_SIZES + _HMC_SCALARS + _HMC_OUTPUTS),
+    'vb_hmc_run_metric': (ctypes.c_int, _HMC_METRIC + _HMC_SIZES + _HMC_SCALARS + _HMC_MOMENTS + _HMC_OUTPUTS),
+    # (max_leapfrog in n_leapfrog's place, trajectory_lr after it; traj_state, traj_hist, leap_hist at the end)
+    'vb_hmc_run_chees': (ctypes.c_int, _HMC_METRIC + _HMC_SIZES + [ctypes.c_double] + _HMC_SCALARS + _HMC_MOMENTS +
+                         _HMC_OUTPUTS + [_c_double_p, _c_double_p, _c_int64_p]),
     'vb_alpha_grad_meanfield': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                ctypes.c_int, ctypes.c_double, _c_double_p, ctypes.c_double,
                                                _c_double_p, _c_double_p]),
@@ -968,31 +965,63 @@ class Engine:
         None with ``keep_draws=False``), ``logp`` (n_kept x C), ``last`` (C x D), ``chain_mean`` and ``chain_m2`` (C x D),
         ``accept_rate`` (C,), ``step_size_history`` and ``accept_prob`` (n_warmup + n_draws,), ``step_size`` (the
         sampling phase's) and ``n_divergent``."""
-        x0 = _f64(x0)
-        inv_mass = _f64(inv_mass)
+        run = [int(n_warmup), int(n_draws), int(thin), int(n_leapfrog), float(step_size), float(target_accept), float(jitter),
+               int(seed), int(stream_offset)]
+        return self._hmc_call('vb_hmc_run', x0, inv_mass, run, keep_draws)
+
+    def _hmc_call(self, entry, x0, metric, run, keep_draws, moment_shift=None, traj_state=None):
+        """What ``hmc_run``, ``hmc_run_metric`` and ``hmc_run_chees`` share: the arrays coerced and checked, the outputs
+        allocated, the entry's argument list, the result dict.  ``run`` holds the entry's scalars from ``n_warmup`` to
+        ``stream_offset`` as the C entry takes them; ``vb_hmc_run`` takes a diagonal metric only, no metric kind and no
+        moments, and always samples; ``traj_state`` is ``vb_hmc_run_chees``'s."""
+        plain, chees = entry == 'vb_hmc_run', entry == 'vb_hmc_run_chees'
+        x0, metric = _f64(x0), _f64(metric)
         if x0.ndim != 2:
             raise ValueError('x0 must be (n_chains, D)')
         c, d = x0.shape
-        if inv_mass.shape != (d,):
+        if plain and metric.shape != (d,):
             raise ValueError('inv_mass must have shape ({},)'.format(d))
-        n_warmup, n_draws, thin = int(n_warmup), int(n_draws), int(thin)
+        if metric.shape not in ((d,), (d, d)):
+            raise ValueError('metric must have shape ({0},) or ({0}, {0})'.format(d))
+        if chees:
+            state = np.array(traj_state, dtype=np.float64)
+            if state.shape != (4,):
+                raise ValueError('traj_state must have four entries (log T, v, log T_bar, m)')
+        dense = metric.ndim == 2
+        n_warmup, n_draws, thin = run[:3]
         n_iter = max(n_warmup, 0) + max(n_draws, 0)
         n_kept = -(-max(n_draws, 0) // thin) if thin >= 1 else 0
-        draws = np.empty((n_kept, c, d), dtype=np.float64) if keep_draws else None
-        logp = np.empty((n_kept, c), dtype=np.float64)
-        last, mean, m2 = (np.empty((c, d), dtype=np.float64) for _ in range(3))
-        rate = np.empty(c, dtype=np.float64)
+        sampling = plain or n_draws > 0
+        draws = np.empty((n_kept, c, d), dtype=np.float64) if keep_draws and sampling else None
+        logp = np.empty((n_kept, c), dtype=np.float64) if sampling else None
+        last = np.empty((c, d), dtype=np.float64)
+        mean, m2 = (np.empty((c, d), dtype=np.float64) if sampling else None for _ in range(2))
+        rate = np.empty(c, dtype=np.float64) if sampling else None
         step_hist, accept_hist = np.empty(n_iter, dtype=np.float64), np.empty(n_iter, dtype=np.float64)
-        final = ctypes.c_double(0.0)
-        n_div = ctypes.c_int64(0)
-        self._check(self._lib.vb_hmc_run(self._ctx, _dptr(x0), _dptr(inv_mass), c, d, n_warmup, n_draws, thin,
-                                         int(n_leapfrog), float(step_size), float(target_accept), float(jitter),
-                                         int(seed), int(stream_offset), None if draws is None else _dptr(draws),
-                                         _dptr(logp), _dptr(last), _dptr(mean), _dptr(m2), _dptr(rate), _dptr(step_hist),
-                                         _dptr(accept_hist), ctypes.addressof(final), ctypes.byref(n_div)))
-        return dict(draws=draws, logp=logp, last=last, chain_mean=mean, chain_m2=m2, accept_rate=rate,
-                    step_size_history=step_hist, accept_prob=accept_hist, step_size=final.value,
-                    n_divergent=int(n_div.value))
+        shift = s1 = s2 = None
+        if moment_shift is not None:
+            shift = _f64(moment_shift)
+            if shift.shape != (d,):
+                raise ValueError('moment_shift must have shape ({},)'.format(d))
+            s1, s2 = np.empty(d, dtype=np.float64), np.empty((d, d) if dense else d, dtype=np.float64)
+        final, n_div = ctypes.c_double(0.0), ctypes.c_int64(0)
+        opt = lambda a: None if a is None else _dptr(a)                                                       # noqa: E731
+        args = [self._ctx, _dptr(x0)] + ([] if plain else [HMC_METRIC_DENSE if dense else HMC_METRIC_DIAG])
+        args += [_dptr(metric), c, d] + run + ([] if plain else [opt(shift), opt(s1), opt(s2)])
+        args += [opt(draws), opt(logp), _dptr(last), opt(mean), opt(m2), opt(rate), _dptr(step_hist), _dptr(accept_hist),
+                 ctypes.addressof(final), ctypes.byref(n_div)]
+        if chees:
+            traj_hist, leap_hist = np.empty(n_iter, dtype=np.float64), np.zeros(n_iter, dtype=np.int64)
+            args += [_dptr(state), _dptr(traj_hist), leap_hist.ctypes.data_as(_c_int64_p)]
+        self._check(getattr(self._lib, entry)(*args))
+        out = dict(draws=draws, logp=logp, last=last, chain_mean=mean, chain_m2=m2, accept_rate=rate,
+                   step_size_history=step_hist, accept_prob=accept_hist, step_size=final.value,
+                   n_divergent=int(n_div.value))
+        if not plain:
+            out.update(moment_sum=s1, moment_m2=s2)
+        if chees:
+            out.update(traj_state=state, trajectory_history=traj_hist, n_leapfrog_history=leap_hist)
+        return out
 
     def hmc_run_metric(self, x0, metric, n_warmup, n_draws, n_leapfrog, step_size, target_accept=0.8, jitter=0.2, seed=1,
                        stream_offset=0, thin=1, keep_draws=True, moment_shift=None):
@@ -1001,41 +1030,9 @@ class Engine:
         may be 0 (a warm-up-only segment: the sampling outputs come back as None).  With ``moment_shift`` (D,) the dict
         also has ``moment_sum`` (D,) and ``moment_m2`` ((D,) or (D, D)): the sums of ``x - shift`` and of its squares /
         outer products over the chains and all iterations of the call."""
-        x0 = _f64(x0)
-        metric = _f64(metric)
-        if x0.ndim != 2:
-            raise ValueError('x0 must be (n_chains, D)')
-        c, d = x0.shape
-        if metric.shape not in ((d,), (d, d)):
-            raise ValueError('metric must have shape ({0},) or ({0}, {0})'.format(d))
-        dense = metric.ndim == 2
-        n_warmup, n_draws, thin = int(n_warmup), int(n_draws), int(thin)
-        n_iter = max(n_warmup, 0) + max(n_draws, 0)
-        n_kept = -(-max(n_draws, 0) // thin) if thin >= 1 else 0
-        sampling = n_draws > 0
-        draws = np.empty((n_kept, c, d), dtype=np.float64) if keep_draws and sampling else None
-        logp = np.empty((n_kept, c), dtype=np.float64) if sampling else None
-        last = np.empty((c, d), dtype=np.float64)
-        mean, m2 = (np.empty((c, d), dtype=np.float64) if sampling else None for _ in range(2))
-        rate = np.empty(c, dtype=np.float64) if sampling else None
-        step_hist, accept_hist = np.empty(n_iter, dtype=np.float64), np.empty(n_iter, dtype=np.float64)
-        shift = s1 = s2 = None
-        if moment_shift is not None:
-            shift = _f64(moment_shift)
-            if shift.shape != (d,):
-                raise ValueError('moment_shift must have shape ({},)'.format(d))
-            s1, s2 = np.empty(d, dtype=np.float64), np.empty((d, d) if dense else d, dtype=np.float64)
-        final = ctypes.c_double(0.0)
-        n_div = ctypes.c_int64(0)
-        opt = lambda a: None if a is None else _dptr(a)                                                       # noqa: E731
-        self._check(self._lib.vb_hmc_run_metric(
-            self._ctx, _dptr(x0), HMC_METRIC_DENSE if dense else HMC_METRIC_DIAG, _dptr(metric), c, d, n_warmup, n_draws,
-            thin, int(n_leapfrog), float(step_size), float(target_accept), float(jitter), int(seed), int(stream_offset),
-            opt(shift), opt(s1), opt(s2), opt(draws), opt(logp), _dptr(last), opt(mean), opt(m2), opt(rate),
-            _dptr(step_hist), _dptr(accept_hist), ctypes.addressof(final), ctypes.byref(n_div)))
-        return dict(draws=draws, logp=logp, last=last, chain_mean=mean, chain_m2=m2, accept_rate=rate,
-                    step_size_history=step_hist, accept_prob=accept_hist, step_size=final.value,
-                    n_divergent=int(n_div.value), moment_sum=s1, moment_m2=s2)
+        run = [int(n_warmup), int(n_draws), int(thin), int(n_leapfrog), float(step_size), float(target_accept), float(jitter),
+               int(seed), int(stream_offset)]
+        return self._hmc_call('vb_hmc_run_metric', x0, metric, run, keep_draws, moment_shift)
 
     def hmc_run_chees(self, x0, metric, n_warmup, n_draws, max_leapfrog, step_size, traj_state, trajectory_lr=0.025,
                       target_accept=0.8, jitter=0.2, seed=1, stream_offset=0, thin=1, keep_draws=True, moment_shift=None):
@@ -1044,47 +1041,9 @@ class Engine:
         m)`` -- ``(log T0, 0, log T0, 0)`` for a first call, the last call's ``traj_state`` for a continuation.  The dict
         has ``hmc_run_metric``'s entries plus ``traj_state`` (the state after the call), ``trajectory_history`` (float64)
         and ``n_leapfrog_history`` (int64), both of length ``n_warmup + n_draws``."""
-        x0 = _f64(x0)
-        metric = _f64(metric)
-        if x0.ndim != 2:
-            raise ValueError('x0 must be (n_chains, D)')
-        c, d = x0.shape
-        if metric.shape not in ((d,), (d, d)):
-            raise ValueError('metric must have shape ({0},) or ({0}, {0})'.format(d))
-        state = np.array(traj_state, dtype=np.float64)
-        if state.shape != (4,):
-            raise ValueError('traj_state must have four entries (log T, v, log T_bar, m)')
-        dense = metric.ndim == 2
-        n_warmup, n_draws, thin = int(n_warmup), int(n_draws), int(thin)
-        n_iter = max(n_warmup, 0) + max(n_draws, 0)
-        n_kept = -(-max(n_draws, 0) // thin) if thin >= 1 else 0
-        sampling = n_draws > 0
-        draws = np.empty((n_kept, c, d), dtype=np.float64) if keep_draws and sampling else None
-        logp = np.empty((n_kept, c), dtype=np.float64) if sampling else None
-        last = np.empty((c, d), dtype=np.float64)
-        mean, m2 = (np.empty((c, d), dtype=np.float64) if sampling else None for _ in range(2))
-        rate = np.empty(c, dtype=np.float64) if sampling else None
-        step_hist, accept_hist = np.empty(n_iter, dtype=np.float64), np.empty(n_iter, dtype=np.float64)
-        traj_hist, leap_hist = np.empty(n_iter, dtype=np.float64), np.zeros(n_iter, dtype=np.int64)
-        shift = s1 = s2 = None
-        if moment_shift is not None:
-            shift = _f64(moment_shift)
-            if shift.shape != (d,):
-                raise ValueError('moment_shift must have shape ({},)'.format(d))
-            s1, s2 = np.empty(d, dtype=np.float64), np.empty((d, d) if dense else d, dtype=np.float64)
-        final = ctypes.c_double(0.0)
-        n_div = ctypes.c_int64(0)
-        opt = lambda a: None if a is None else _dptr(a)                                                       # noqa: E731
-        self._check(self._lib.vb_hmc_run_chees(
-            self._ctx, _dptr(x0), HMC_METRIC_DENSE if dense else HMC_METRIC_DIAG, _dptr(metric), c, d, n_warmup, n_draws,
-            thin, int(max_leapfrog), float(trajectory_lr), float(step_size), float(target_accept), float(jitter), int(seed),
-            int(stream_offset), opt(shift), opt(s1), opt(s2), opt(draws), opt(logp), _dptr(last), opt(mean), opt(m2),
-            opt(rate), _dptr(step_hist), _dptr(accept_hist), ctypes.addressof(final), ctypes.byref(n_div), _dptr(state),
-            _dptr(traj_hist), leap_hist.ctypes.data_as(_c_int64_p)))
-        return dict(draws=draws, logp=logp, last=last, chain_mean=mean, chain_m2=m2, accept_rate=rate,
-                    step_size_history=step_hist, accept_prob=accept_hist, step_size=final.value,
-                    n_divergent=int(n_div.value), moment_sum=s1, moment_m2=s2, traj_state=state,
-                    trajectory_history=traj_hist, n_leapfrog_history=leap_hist)
+        run = [int(n_warmup), int(n_draws), int(thin), int(max_leapfrog), float(trajectory_lr), float(step_size),
+               float(target_accept), float(jitter), int(seed), int(stream_offset)]
+        return self._hmc_call('vb_hmc_run_chees', x0, metric, run, keep_draws, moment_shift, traj_state)
 
     # ------------------------------------------------------------------ AlphaDivergence, mean field
     def alpha_grad_meanfield(self, slot, n, d, theta, family, alpha, df=0.0, n_total=None):

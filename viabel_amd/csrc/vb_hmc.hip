@@ -120,6 +120,12 @@
 // D = 64 (one workgroup) and 37.4 us at D = 117 (213 us with one load in flight), chain kernel 4.9 us, velocity product
 // 6.0 / 7.4 us, adapt 6.3 us, plan 4.8 us.  Smallest ESS per gradient evaluation against n_leapfrog = 16: 2.5, 2.2 and 1.8
 // times at the logistic, multilevel and correlated-logistic shapes; at the logistic shape n_leapfrog = 4 beats it five times.
+//
+// ---- the host side ------------------------------------------------------------------------------------------------------
+// The three entries fill one request (HmcRun) and call hmc_run, whose body is the lists above: hmc_refuse, hmc_layout (one
+// named offset per workspace piece), hmc_upload, hmc_bind (the kernels' argument structs on the workspace: HmcDev), then per
+// iteration hmc_trajectory, hmc_chees_criterion (ChEES warm-up), hmc_end, hmc_window_moments (moment_shift given) and
+// hmc_adapt (ChEES: with the step-count fetches), and at last hmc_download.
 #include "vb_rows_target.h"
 #include "vb_rng.h"
 
@@ -600,12 +606,27 @@ __global__ void __launch_bounds__(256) hmc_chees_plan_kernel(const HmcCheesPlanA
   if (t == q.n_warmup) q.state[HS_EPS] = eps;
 }
 
-struct HmcChees {            // vb_hmc_run_chees's own arguments
-  int max_leapfrog;
-  double lr;
-  double* traj_state;      // in / out: log T, v, log T_bar, m
-  double* traj_hist;       // n_iter
-  int64_t* leap_hist;      // n_iter
+// ---- the host driver: one request, then the stages hmc_run lists -------------------------------------------------------------
+struct HmcRun {              // one call, as its entry states it: what differs between the entries, then what all three take
+  const char* name;        // the entry, for the messages
+  int kind;                // VB_HMC_METRIC_*
+  const double* metric;    // inv_mass[d], or the lower factor L (d x d)
+  int n_leapfrog;          // vb_hmc_run_chees: max_leapfrog, the largest step count
+  const double* moment_shift;      // the window moments: all three or none
+  double *moment_sum, *moment_m2;
+  double trajectory_lr;            // vb_hmc_run_chees's own block: traj_state given, else all zero
+  double *traj_state, *traj_hist;  // in / out: log T, v, log T_bar, m; n_iter
+  int64_t* leap_hist;              // n_iter
+  const double* x0;        // C x d
+  int64_t n_chains, d, n_warmup, n_draws, thin;
+  double step_size, target_accept, jitter;
+  uint64_t seed, stream_offset;
+  double *draws, *logp, *last_x, *chain_mean, *chain_m2, *accept_rate, *step_hist, *accept_hist, *final_step;
+  int64_t* n_divergent;
+  bool dense() const { return kind == VB_HMC_METRIC_DENSE; }
+  bool chees() const { return traj_state != nullptr; }
+  int64_t n_iter() const { return n_warmup + n_draws; }
+  int64_t n_kept() const { return (n_draws + thin - 1) / thin; }
 };
 
 constexpr int kHmcDenseMaxDim = 4096;                           // dense metric: two padded d x d factors on the device
@@ -622,272 +643,350 @@ int hmc_gram_splits(int64_t n_chains, int64_t ld) {
   return (int)((n_chains + ks - 1) / ks);
 }
 
-struct HmcCall {
-  const char* name;        // the entry, for the messages
-  int kind;                // VB_HMC_METRIC_*
-  const double* metric;    // inv_mass[d], or the lower factor L (d x d)
-  const double* moment_shift;
-  double* moment_sum;
-  double* moment_m2;
-  const HmcChees* chees;   // vb_hmc_run_chees: n_leapfrog is then the largest step count; else nullptr
-};
-
-// vb_hmc_run, vb_hmc_run_metric and vb_hmc_run_chees: the diagonal kind without moments and without ChEES enqueues exactly
-// what vb_hmc_run always did
-int hmc_run(vb_ctx* ctx, const HmcCall& hc, const double* x0, int64_t n_chains, int64_t d, int64_t n_warmup, int64_t n_draws,
-            int64_t thin, int n_leapfrog, double step_size, double target_accept, double jitter, uint64_t seed,
-            uint64_t stream_offset, double* draws, double* logp, double* last_x, double* chain_mean, double* chain_m2,
-            double* accept_rate, double* step_hist, double* accept_hist, double* final_step, int64_t* n_divergent) {
-  const bool dense = hc.kind == VB_HMC_METRIC_DENSE, moments = hc.moment_shift != nullptr;
-  const HmcChees* ch = hc.chees;
-  if (thin < 1) return fail(ctx, VB_ERR_INVALID, "thin must be at least 1");
-  if (n_leapfrog < 1) return fail(ctx, VB_ERR_INVALID, "n_leapfrog must be at least 1");
-  if (!(step_size > 0.0) || !std::isfinite(step_size)) return fail(ctx, VB_ERR_INVALID, "step_size must be positive and finite");
-  if (!(target_accept > 0.0 && target_accept < 1.0)) return fail(ctx, VB_ERR_INVALID, "target_accept must lie in (0, 1)");
-  if (!(jitter >= 0.0 && jitter < 1.0)) return fail(ctx, VB_ERR_INVALID, "jitter must lie in [0, 1)");
+// Refusals, in this order: a call that violates two conditions reports the first
+static int hmc_refuse(vb_ctx* ctx, const HmcRun& r) {
+  const int64_t d = r.d;
+  if (r.thin < 1) return fail(ctx, VB_ERR_INVALID, "thin must be at least 1");
+  if (r.n_leapfrog < 1) return fail(ctx, VB_ERR_INVALID, "n_leapfrog must be at least 1");
+  if (!(r.step_size > 0.0) || !std::isfinite(r.step_size))
+    return fail(ctx, VB_ERR_INVALID, "step_size must be positive and finite");
+  if (!(r.target_accept > 0.0 && r.target_accept < 1.0)) return fail(ctx, VB_ERR_INVALID, "target_accept must lie in (0, 1)");
+  if (!(r.jitter >= 0.0 && r.jitter < 1.0)) return fail(ctx, VB_ERR_INVALID, "jitter must lie in [0, 1)");
   const ModelDev& m = ctx->model;
   if (m.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model)");
   if (d != m.dim) return fail(ctx, VB_ERR_INVALID, "x0 has %lld columns, model dimension is %d", (long long)d, m.dim);
-  if (dense && d > kHmcDenseMaxDim)
+  if (r.dense() && d > kHmcDenseMaxDim)
     return fail(ctx, VB_ERR_UNSUPPORTED, "the dense metric takes at most %d dimensions (got %lld)", kHmcDenseMaxDim, (long long)d);
-  if (!dense) {
+  if (!r.dense()) {
     for (int64_t j = 0; j < d; ++j)
-      if (!(hc.metric[j] > 0.0) || !std::isfinite(hc.metric[j]))
+      if (!(r.metric[j] > 0.0) || !std::isfinite(r.metric[j]))
         return fail(ctx, VB_ERR_INVALID, "inv_mass[%lld] must be positive and finite", (long long)j);
   } else {
     for (int64_t i = 0; i < d; ++i) {
-      if (!(hc.metric[i * d + i] > 0.0) || !std::isfinite(hc.metric[i * d + i]))
+      if (!(r.metric[i * d + i] > 0.0) || !std::isfinite(r.metric[i * d + i]))
         return fail(ctx, VB_ERR_INVALID, "L[%lld][%lld] must be positive and finite", (long long)i, (long long)i);
       for (int64_t j = 0; j < i; ++j)
-        if (!std::isfinite(hc.metric[i * d + j]))
+        if (!std::isfinite(r.metric[i * d + j]))
           return fail(ctx, VB_ERR_INVALID, "L[%lld][%lld] must be finite", (long long)i, (long long)j);
     }
   }
   if (m.id == VB_MODEL_SOURCE && ctx->user_host_fn)
     return fail(ctx, VB_ERR_UNSUPPORTED, "%s runs without host synchronisation: a host-callback model cannot be its "
-                                         "target (write the density as a source model)", hc.name);
-  if (ctx->comm) return fail(ctx, VB_ERR_UNSUPPORTED, "%s runs on one process's engine: detach the communicator", hc.name);
-  const int64_t n_iter = n_warmup + n_draws, n_kept = (n_draws + thin - 1) / thin;
-  if (n_chains > ((int64_t)1 << 31) - 8 || n_iter > ((int64_t)1 << 40) || (double)n_chains * (double)round_up(d, 16) > 0x1p36)
+                                         "target (write the density as a source model)", r.name);
+  if (ctx->comm) return fail(ctx, VB_ERR_UNSUPPORTED, "%s runs on one process's engine: detach the communicator", r.name);
+  if (r.n_chains > ((int64_t)1 << 31) - 8 || r.n_iter() > ((int64_t)1 << 40) ||
+      (double)r.n_chains * (double)round_up(d, 16) > 0x1p36)
     return fail(ctx, VB_ERR_UNSUPPORTED, "%s takes at most 2^31 - 8 chains, 2^36 chain coordinates (n_chains x "
-                                         "round_up(d, 16)) and 2^40 iterations", hc.name);
-  if (draws && (double)n_kept * (double)n_chains * (double)d * sizeof(double) > (double)kHmcDrawBudgetBytes)
+                                         "round_up(d, 16)) and 2^40 iterations", r.name);
+  if (r.draws && (double)r.n_kept() * (double)r.n_chains * (double)d * sizeof(double) > (double)kHmcDrawBudgetBytes)
     return fail(ctx, VB_ERR_UNSUPPORTED, "the kept draws (%lld x %lld x %lld doubles) exceed the device draw buffer's budget of "
                                          "%lld bytes: raise thin or pass no draws",
-                (long long)n_kept, (long long)n_chains, (long long)d, (long long)kHmcDrawBudgetBytes);
-  VB_HIP(ctx, hipSetDevice(ctx->device));
-  VB_TRY(main_stream_write(ctx));
-  hipStream_t st = ctx->stream;
-  const int n_cu = ctx->prop.multiProcessorCount;
-  const int64_t C = n_chains, ld = round_up(d, 16), mat = C * ld;
-  const int splits = dense && moments ? hmc_gram_splits(C, ld) : 0;
-  const int64_t slab_stride = ld * ld;
+                (long long)r.n_kept(), (long long)r.n_chains, (long long)d, (long long)kHmcDrawBudgetBytes);
+  return VB_OK;
+}
+
+// Layout: the offset (in doubles) of every piece of vb_ctx::hmc_work, carved in the order of the header's piece lists
+struct HmcLayout {
+  int64_t x, g, xp, gp, p, mean, m2, f, fp, h0, a, count, inv_mass, state, step_hist, accept_hist, n_div;
+  int64_t l, lt, shift, s1, s2, xc, colsum, n_usable, crit, flag, vel, traj_hist, leap_hist;      // dense, moments, ChEES
+  int64_t draws, logp, slab;     // not zeroed
+  int64_t zeroed, total, ld;     // zeroed: the prefix every call clears (everything before the draws)
+  int splits;                    // Gram slabs of the dense moments; else 0
+};
+
+static HmcLayout hmc_layout(const HmcRun& r) {
+  const bool dense = r.dense(), moments = r.moment_shift != nullptr, ch = r.chees();
+  const int64_t C = r.n_chains, d = r.d, T = r.n_iter(), ld = round_up(d, 16), mat = C * ld;
+  HmcLayout o;
   Carver carve;
-  const int64_t o_x = carve(mat), o_g = carve(mat), o_xp = carve(mat), o_gp = carve(mat), o_p = carve(mat),
-                o_mean = carve(mat), o_m2 = carve(mat), o_f = carve(C), o_fp = carve(C), o_h0 = carve(C), o_a = carve(C),
-                o_cnt = carve(C), o_im = carve(ld), o_state = carve(HS_NUM), o_sh = carve(n_iter), o_ah = carve(n_iter),
-                o_div = carve(C), o_l = carve(dense ? ld * ld : 0), o_lt = carve(dense ? ld * ld : 0),
-                o_shift = carve(moments ? ld : 0), o_s1 = carve(moments ? ld : 0),
-                o_s2 = carve(moments ? (dense ? d * d : ld) : 0), o_xc = carve(splits ? mat : 0),
-                o_cs = carve(ch ? 2 * ld : 0), o_nu = carve(ch ? 1 : 0), o_crit = carve(ch ? C : 0),
-                o_flag = carve(ch ? (C + 1) / 2 : 0), o_vel = carve(ch && dense && n_warmup > 0 ? mat : 0),
-                o_th = carve(ch ? n_iter : 0), o_lh = carve(ch ? n_iter : 0),
-                o_draws = carve(draws ? n_kept * C * d : 0), o_logp = carve(logp ? n_kept * C : 0),
-                o_slab = carve((int64_t)splits * slab_stride);
-  VB_TRY(ensure(ctx, ctx->hmc_work, (size_t)carve.off * sizeof(double)));
+  o.ld = ld, o.splits = dense && moments ? hmc_gram_splits(C, ld) : 0;
+  o.x = carve(mat), o.g = carve(mat), o.xp = carve(mat), o.gp = carve(mat), o.p = carve(mat), o.mean = carve(mat);
+  o.m2 = carve(mat), o.f = carve(C), o.fp = carve(C), o.h0 = carve(C), o.a = carve(C), o.count = carve(C);
+  o.inv_mass = carve(ld), o.state = carve(HS_NUM), o.step_hist = carve(T), o.accept_hist = carve(T), o.n_div = carve(C);
+  o.l = carve(dense ? ld * ld : 0), o.lt = carve(dense ? ld * ld : 0), o.shift = carve(moments ? ld : 0);
+  o.s1 = carve(moments ? ld : 0), o.s2 = carve(moments ? (dense ? d * d : ld) : 0), o.xc = carve(o.splits ? mat : 0);
+  o.colsum = carve(ch ? 2 * ld : 0), o.n_usable = carve(ch ? 1 : 0), o.crit = carve(ch ? C : 0);
+  o.flag = carve(ch ? (C + 1) / 2 : 0), o.vel = carve(ch && dense && r.n_warmup > 0 ? mat : 0);
+  o.traj_hist = carve(ch ? T : 0), o.leap_hist = carve(ch ? T : 0);
+  o.draws = carve(r.draws ? r.n_kept() * C * d : 0), o.logp = carve(r.logp ? r.n_kept() * C : 0);
+  o.slab = carve((int64_t)o.splits * ld * ld), o.zeroed = o.draws, o.total = carve.off;
+  return o;
+}
+
+// Upload: the zeroed prefix, x0, the metric, the shift.  `pack` must outlive the call's last synchronisation.
+static int hmc_upload(vb_ctx* ctx, const HmcRun& r, const HmcLayout& o, std::vector<double>& pack) {
+  hipStream_t st = ctx->stream;
   double* base = (double*)ctx->hmc_work.ptr;
+  const int64_t d = r.d, ld = o.ld;
   // everything up to the draws starts from zero: pad columns, Welford sums, counts, state, the factors' pads, the moments
-  VB_HIP(ctx, hipMemsetAsync(base, 0, (size_t)o_draws * sizeof(double), st));
-  VB_HIP(ctx, hipMemcpy2DAsync(base + o_x, (size_t)ld * sizeof(double), x0, (size_t)d * sizeof(double),
-                               (size_t)d * sizeof(double), (size_t)C, hipMemcpyHostToDevice, st));
-  std::vector<double> pack;      // (lives until the synchronisation at the end)
-  if (!dense) {
-    VB_HIP(ctx, hipMemcpyAsync(base + o_im, hc.metric, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
+  VB_HIP(ctx, hipMemsetAsync(base, 0, (size_t)o.zeroed * sizeof(double), st));
+  VB_HIP(ctx, hipMemcpy2DAsync(base + o.x, (size_t)ld * sizeof(double), r.x0, (size_t)d * sizeof(double),
+                               (size_t)d * sizeof(double), (size_t)r.n_chains, hipMemcpyHostToDevice, st));
+  if (!r.dense()) {
+    VB_HIP(ctx, hipMemcpyAsync(base + o.inv_mass, r.metric, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
   } else {                       // [L | L'], each ld x ld with zeros above / below the diagonal and in the pads
     pack.assign((size_t)(2 * ld * ld), 0.0);
     for (int64_t i = 0; i < d; ++i)
       for (int64_t j = 0; j <= i; ++j) {
-        const double v = hc.metric[i * d + j];
+        const double v = r.metric[i * d + j];
         pack[(size_t)(i * ld + j)] = v;
         pack[(size_t)(ld * ld + j * ld + i)] = v;
       }
-    VB_HIP(ctx, hipMemcpyAsync(base + o_l, pack.data(), (size_t)(ld * ld) * sizeof(double), hipMemcpyHostToDevice, st));
-    VB_HIP(ctx, hipMemcpyAsync(base + o_lt, pack.data() + ld * ld, (size_t)(ld * ld) * sizeof(double), hipMemcpyHostToDevice, st));
+    VB_HIP(ctx, hipMemcpyAsync(base + o.l, pack.data(), (size_t)(ld * ld) * sizeof(double), hipMemcpyHostToDevice, st));
+    VB_HIP(ctx, hipMemcpyAsync(base + o.lt, pack.data() + ld * ld, (size_t)(ld * ld) * sizeof(double), hipMemcpyHostToDevice, st));
   }
-  if (moments)
-    VB_HIP(ctx, hipMemcpyAsync(base + o_shift, hc.moment_shift, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
+  if (r.moment_shift)
+    VB_HIP(ctx, hipMemcpyAsync(base + o.shift, r.moment_shift, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
+  return VB_OK;
+}
+
+// Binding: the kernels' argument structs on the workspace, and what every launch of the call shares
+struct HmcDev {
+  hipStream_t st;
+  int n_cu;
+  bool dense;
+  double* base;                    // vb_ctx::hmc_work, laid out by o
+  HmcLayout o;
   HmcArgs a;
-  a.x = base + o_x, a.g = base + o_g, a.f = base + o_f, a.xp = base + o_xp, a.gp = base + o_gp, a.fp = base + o_fp;
-  a.p = base + o_p, a.H0 = base + o_h0, a.a = base + o_a, a.mean = base + o_mean, a.m2 = base + o_m2;
-  a.count = base + o_cnt, a.n_div = (long long*)(base + o_div), a.inv_mass = base + o_im, a.state = base + o_state;
-  a.ld = ld, a.n_chains = C, a.d = (int)d;
-  VB_TRY(model_grad_rows(ctx, a.x, ld, C, d, a.g, a.f));      // f, g of the start: carried from here on
   HmcMomentArgs mq;
-  mq.x = a.x, mq.shift = base + o_shift, mq.s1 = base + o_s1, mq.s2 = base + o_s2, mq.xc = base + o_xc;
-  mq.slab = base + o_slab, mq.slab_stride = slab_stride, mq.ld = ld, mq.n_chains = C, mq.d = (int)d, mq.splits = splits;
-  // the products of the dense kind: K runs over the padded ld columns (zeros in the states' pads and the factors' pads)
-  auto kick = [&](const double* grad, double c) {      // r += c eps (grad L): B = L, zero for k < j
-    gemm_f64_launch<true>(st, gemm_product(grad, ld, base + o_l, ld, (int)C, (int)d, (int)ld, 3), 1, n_cu,
-                          EpiHmcKick{a.p, ld, a.state, c});
-    return hipGetLastError();
-  };
-  auto drift = [&]() {                                 // xp += eps (r L'): B = L', zero for k > j
-    gemm_f64_launch<true>(st, gemm_product(a.p, ld, base + o_lt, ld, (int)C, (int)d, (int)ld, 1), 1, n_cu,
-                          EpiHmcDrift{a.xp, ld, a.state});
-    return hipGetLastError();
-  };
-  auto velocity = [&](double* vel) {                   // v' = r L' (ChEES, warm-up): the drift's operands, stored
-    gemm_f64_launch<true>(st, gemm_product(a.p, ld, base + o_lt, ld, (int)C, (int)d, (int)ld, 1), 1, n_cu,
-                          EpiHmcVelocity{vel, ld});
-    return hipGetLastError();
-  };
+  HmcCheesBuf cb;                  // cb, cz: ChEES only
+  HmcCheesAdaptArgs cz;
+  HmcAdaptArgs q;                  // t, k1_next, w_next: hmc_adapt sets them, the keys and stream of the iteration it precedes
+  uint32_t seed_hi;
+  dim3 chain_grid, leap_grid, col_grid, block;
+};
 
-  const uint32_t k0 = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32);
-  HmcCheesBuf cb{};
-  HmcCheesAdaptArgs cz{};
-  if (ch) {
-    cb.colsum = base + o_cs, cb.n_usable = base + o_nu, cb.crit = base + o_crit, cb.flag = (int*)(base + o_flag);
-    cb.vel = dense && n_warmup > 0 ? base + o_vel : nullptr;
-    cz.crit = cb.crit, cz.flag = cb.flag, cz.traj_hist = base + o_th, cz.leap_hist = (long long*)(base + o_lh);
-    cz.log_t0 = ch->traj_state[0], cz.v0 = ch->traj_state[1], cz.log_tbar0 = ch->traj_state[2], cz.m0 = ch->traj_state[3];
-    cz.lr = ch->lr, cz.max_leapfrog = ch->max_leapfrog;
+static HmcDev hmc_bind(vb_ctx* ctx, const HmcRun& r, const HmcLayout& o) {
+  double* base = (double*)ctx->hmc_work.ptr;
+  const int64_t C = r.n_chains, ld = o.ld;
+  HmcDev v{};
+  v.st = ctx->stream, v.n_cu = ctx->prop.multiProcessorCount, v.dense = r.dense(), v.base = base, v.o = o;
+  v.seed_hi = (uint32_t)(r.seed >> 32);
+  v.chain_grid = dim3((unsigned)((C + 3) / 4)), v.leap_grid = dim3((unsigned)((C * ld + 255) / 256));
+  v.col_grid = dim3((unsigned)((r.d + 63) / 64)), v.block = dim3(256);
+  HmcArgs& a = v.a;
+  HmcMomentArgs& mq = v.mq;
+  HmcCheesBuf& cb = v.cb;
+  HmcCheesAdaptArgs& cz = v.cz;
+  HmcAdaptArgs& q = v.q;
+  a.x = base + o.x, a.g = base + o.g, a.f = base + o.f, a.xp = base + o.xp, a.gp = base + o.gp, a.fp = base + o.fp;
+  a.p = base + o.p, a.H0 = base + o.h0, a.a = base + o.a, a.mean = base + o.mean, a.m2 = base + o.m2;
+  a.count = base + o.count, a.n_div = (long long*)(base + o.n_div), a.inv_mass = base + o.inv_mass, a.state = base + o.state;
+  a.ld = ld, a.n_chains = C, a.d = (int)r.d;
+  mq.x = a.x, mq.shift = base + o.shift, mq.s1 = base + o.s1, mq.s2 = base + o.s2, mq.xc = base + o.xc;
+  mq.slab = base + o.slab, mq.slab_stride = ld * ld, mq.ld = ld, mq.n_chains = C, mq.d = (int)r.d, mq.splits = o.splits;
+  if (r.chees()) {
+    cb.colsum = base + o.colsum, cb.n_usable = base + o.n_usable, cb.crit = base + o.crit, cb.flag = (int*)(base + o.flag);
+    cb.vel = v.dense && r.n_warmup > 0 ? base + o.vel : nullptr;
+    cz.crit = cb.crit, cz.flag = cb.flag, cz.traj_hist = base + o.traj_hist, cz.leap_hist = (long long*)(base + o.leap_hist);
+    cz.log_t0 = r.traj_state[0], cz.v0 = r.traj_state[1], cz.log_tbar0 = r.traj_state[2], cz.m0 = r.traj_state[3];
+    cz.lr = r.trajectory_lr, cz.max_leapfrog = r.n_leapfrog;
   }
-  // ChEES: the step count of the iteration about to be enqueued -- fetched after every warm-up iteration (8 bytes), and for
-  // all sampling iterations at once when the warm-up has ended
-  int steps = n_leapfrog;
-  auto steps_ok = [&](double l) { return l >= 1.0 && l <= (double)n_leapfrog; };
-  HmcAdaptArgs q;
-  q.a = a.a, q.n_chains = C, q.state = a.state, q.step_hist = base + o_sh, q.accept_hist = base + o_ah;
-  q.n_warmup = n_warmup, q.n_iter = n_iter, q.step_size = step_size, q.target = target_accept, q.jitter = jitter;
-  q.mu = log(10.0 * step_size), q.k0 = k0;
-  const dim3 chain_grid((unsigned)((C + 3) / 4)), leap_grid((unsigned)((mat + 255) / 256)), block(256);
-  for (int64_t t = -1; t < n_iter; ++t) {
-    if (t >= 0) {
-      const uint64_t s = stream_offset + (uint64_t)t;
-      const uint32_t k1 = seed_hi ^ (uint32_t)(s >> 32), w = (uint32_t)s;
-      if (dense) {
-        hipLaunchKernelGGL(hmc_begin_kernel<true>, chain_grid, block, 0, st, a, k0, k1, w);
-        VB_HIP(ctx, hipGetLastError());
-        VB_HIP(ctx, kick(a.g, 0.5));
-        for (int l = 0; l < steps; ++l) {
-          VB_HIP(ctx, drift());
-          VB_TRY(model_grad_rows(ctx, a.xp, ld, C, d, a.gp, a.fp));
-          VB_HIP(ctx, kick(a.gp, l + 1 == steps ? 0.5 : 1.0));
-        }
-      } else {
-        hipLaunchKernelGGL(hmc_begin_kernel<false>, chain_grid, block, 0, st, a, k0, k1, w);
-        VB_HIP(ctx, hipGetLastError());
-        for (int l = 0; l < steps; ++l) {
-          VB_TRY(model_grad_rows(ctx, a.xp, ld, C, d, a.gp, a.fp));
-          if (l + 1 == steps) break;
-          hipLaunchKernelGGL(hmc_leap_kernel, leap_grid, block, 0, st, a);
-          VB_HIP(ctx, hipGetLastError());
-        }
-      }
-      if (ch && t < n_warmup) {      // the criterion, before the accept step overwrites x
-        if (dense) VB_HIP(ctx, velocity(base + o_vel));
-        hipLaunchKernelGGL(hmc_chees_mean_kernel, dim3((unsigned)((d + 63) / 64)), block, 0, st, a, cb);
-        VB_HIP(ctx, hipGetLastError());
-        if (dense) hipLaunchKernelGGL(hmc_chees_chain_kernel<true>, chain_grid, block, 0, st, a, cb);
-        else hipLaunchKernelGGL(hmc_chees_chain_kernel<false>, chain_grid, block, 0, st, a, cb);
-        VB_HIP(ctx, hipGetLastError());
-      }
-      HmcEndArgs e;
-      e.k0 = k0, e.k1 = k1, e.w = w;
-      const int64_t si = t - n_warmup;
-      e.sampling = si >= 0, e.k = (double)(si + 1);
-      const bool keep = si >= 0 && si % thin == 0;
-      e.draw_row = keep && draws ? base + o_draws + (si / thin) * C * d : nullptr;
-      e.logp_row = keep && logp ? base + o_logp + (si / thin) * C : nullptr;
-      if (dense) hipLaunchKernelGGL(hmc_end_kernel<true>, chain_grid, block, 0, st, a, e);
-      else hipLaunchKernelGGL(hmc_end_kernel<false>, chain_grid, block, 0, st, a, e);
+  q.a = a.a, q.n_chains = C, q.state = a.state, q.step_hist = base + o.step_hist, q.accept_hist = base + o.accept_hist;
+  q.n_warmup = r.n_warmup, q.n_iter = r.n_iter(), q.step_size = r.step_size, q.target = r.target_accept, q.jitter = r.jitter;
+  q.mu = log(10.0 * r.step_size), q.k0 = (uint32_t)r.seed;
+  return v;
+}
+
+// a product of the dense kind, rows (C x ld) times a padded factor: K runs over the ld columns (zeros in both operands' pads)
+template <class Epi>
+static hipError_t hmc_product(const HmcDev& v, const double* rows, const double* factor, int tri_mode, Epi epi) {
+  const HmcArgs& a = v.a;
+  gemm_f64_launch<true>(v.st, gemm_product(rows, a.ld, factor, a.ld, (int)a.n_chains, a.d, (int)a.ld, tri_mode), 1, v.n_cu, epi);
+  return hipGetLastError();
+}
+
+// Trajectory, both kinds: the begin kernel (dense: and the first half kick), then `steps` times the drift (diagonal:
+// hmc_leap_kernel, kick and drift in one, the first drift being the begin kernel's), the gradient, and (dense) the kick --
+// a half one after the last gradient; the diagonal kind's is the end kernel's.  Kick: r += c eps (g L), B = L, zero for
+// k < j; drift: xp += eps (r L'), B = L', zero for k > j.
+static int hmc_trajectory(vb_ctx* ctx, const HmcDev& v, int steps) {
+  const HmcArgs& a = v.a;
+  const double *l = v.base + v.o.l, *lt = v.base + v.o.lt;
+  if (v.dense) hipLaunchKernelGGL(hmc_begin_kernel<true>, v.chain_grid, v.block, 0, v.st, a, v.q.k0, v.q.k1_next, v.q.w_next);
+  else hipLaunchKernelGGL(hmc_begin_kernel<false>, v.chain_grid, v.block, 0, v.st, a, v.q.k0, v.q.k1_next, v.q.w_next);
+  VB_HIP(ctx, hipGetLastError());
+  if (v.dense) VB_HIP(ctx, hmc_product(v, a.g, l, 3, EpiHmcKick{a.p, a.ld, a.state, 0.5}));
+  for (int i = 0; i < steps; ++i) {
+    if (v.dense) {
+      VB_HIP(ctx, hmc_product(v, a.p, lt, 1, EpiHmcDrift{a.xp, a.ld, a.state}));
+    } else if (i > 0) {
+      hipLaunchKernelGGL(hmc_leap_kernel, v.leap_grid, v.block, 0, v.st, a);
       VB_HIP(ctx, hipGetLastError());
-      if (moments) {
-        const dim3 col_grid((unsigned)((d + 63) / 64));
-        if (dense) {
-          hipLaunchKernelGGL(hmc_moment_kernel<true>, col_grid, block, 0, st, mq);
-          VB_HIP(ctx, hipGetLastError());
-          gemm_f64_launch<false>(st, gemm_product(mq.xc, ld, mq.xc, ld, (int)d, (int)d, (int)C, 0), splits, n_cu,
-                                 EpiHmcSlab{mq.slab, slab_stride, ld});
-          VB_HIP(ctx, hipGetLastError());
-          hipLaunchKernelGGL(hmc_gram_add_kernel, dim3((unsigned)((d * d + 255) / 256)), block, 0, st, mq);
-        } else {
-          hipLaunchKernelGGL(hmc_moment_kernel<false>, col_grid, block, 0, st, mq);
-        }
-        VB_HIP(ctx, hipGetLastError());
-      }
     }
-    const uint64_t sn = stream_offset + (uint64_t)(t + 1);
-    q.t = t, q.k1_next = seed_hi ^ (uint32_t)(sn >> 32), q.w_next = (uint32_t)sn;
-    if (!ch) {
-      hipLaunchKernelGGL(hmc_adapt_kernel, dim3(1), block, 0, st, q);
-      VB_HIP(ctx, hipGetLastError());
-      continue;
-    }
-    hipLaunchKernelGGL(hmc_chees_adapt_kernel, dim3(1), block, 0, st, q, cz);
+    VB_TRY(model_grad_rows(ctx, a.xp, a.ld, a.n_chains, a.d, a.gp, a.fp));
+    if (v.dense) VB_HIP(ctx, hmc_product(v, a.gp, l, 3, EpiHmcKick{a.p, a.ld, a.state, i + 1 == steps ? 0.5 : 1.0}));
+  }
+  return VB_OK;
+}
+
+// ChEES criterion (warm-up only), between the last gradient and the end kernel: the accept step overwrites x.  Dense: the
+// velocity v' = r L' first, the drift's operands
+static int hmc_chees_criterion(vb_ctx* ctx, const HmcDev& v) {
+  if (v.dense) VB_HIP(ctx, hmc_product(v, v.a.p, v.base + v.o.lt, 1, EpiHmcVelocity{v.base + v.o.vel, v.a.ld}));
+  hipLaunchKernelGGL(hmc_chees_mean_kernel, v.col_grid, v.block, 0, v.st, v.a, v.cb);
+  VB_HIP(ctx, hipGetLastError());
+  if (v.dense) hipLaunchKernelGGL(hmc_chees_chain_kernel<true>, v.chain_grid, v.block, 0, v.st, v.a, v.cb);
+  else hipLaunchKernelGGL(hmc_chees_chain_kernel<false>, v.chain_grid, v.block, 0, v.st, v.a, v.cb);
+  VB_HIP(ctx, hipGetLastError());
+  return VB_OK;
+}
+
+// End kernel of iteration t: the accept step, and in the sampling phase the statistics and every thin-th draw
+static int hmc_end(vb_ctx* ctx, const HmcRun& r, const HmcDev& v, int64_t t) {
+  const int64_t C = r.n_chains, si = t - r.n_warmup;
+  HmcEndArgs e;
+  e.k0 = v.q.k0, e.k1 = v.q.k1_next, e.w = v.q.w_next;
+  e.sampling = si >= 0, e.k = (double)(si + 1);
+  const bool keep = si >= 0 && si % r.thin == 0;
+  e.draw_row = keep && r.draws ? v.base + v.o.draws + (si / r.thin) * C * r.d : nullptr;
+  e.logp_row = keep && r.logp ? v.base + v.o.logp + (si / r.thin) * C : nullptr;
+  if (v.dense) hipLaunchKernelGGL(hmc_end_kernel<true>, v.chain_grid, v.block, 0, v.st, v.a, e);
+  else hipLaunchKernelGGL(hmc_end_kernel<false>, v.chain_grid, v.block, 0, v.st, v.a, e);
+  VB_HIP(ctx, hipGetLastError());
+  return VB_OK;
+}
+
+// Window moments of the states after the accept step
+static int hmc_window_moments(vb_ctx* ctx, const HmcDev& v) {
+  const HmcMomentArgs& mq = v.mq;
+  if (v.dense) {
+    hipLaunchKernelGGL(hmc_moment_kernel<true>, v.col_grid, v.block, 0, v.st, mq);
     VB_HIP(ctx, hipGetLastError());
-    if (t + 1 < n_warmup) {
-      double l_next = 0.0;
-      const FetchSeg seg{a.state + HS_LNEXT, sizeof(double), &l_next};
-      VB_TRY(fetch_blocking(ctx, st, &seg, 1));
-      if (!steps_ok(l_next)) return fail(ctx, VB_ERR_NUMERIC, "%s: the device planned %g leapfrog steps", hc.name, l_next);
-      steps = (int)l_next;
-    } else if (t + 1 == n_warmup && n_draws > 0) {
-      HmcCheesPlanArgs pq;
-      pq.state = a.state, pq.step_hist = q.step_hist, pq.traj_hist = cz.traj_hist, pq.leap_hist = cz.leap_hist;
-      pq.n_warmup = n_warmup, pq.n_iter = n_iter, pq.jitter = jitter, pq.k0 = k0, pq.seed_hi = seed_hi;
-      pq.stream_offset = stream_offset, pq.max_leapfrog = ch->max_leapfrog;
-      hipLaunchKernelGGL(hmc_chees_plan_kernel, dim3((unsigned)((n_draws + 255) / 256)), block, 0, st, pq);
-      VB_HIP(ctx, hipGetLastError());
-      const FetchSeg seg{cz.leap_hist + n_warmup, (size_t)n_draws * sizeof(long long), ch->leap_hist + n_warmup};
-      VB_TRY(fetch_blocking(ctx, st, &seg, 1));
-      for (int64_t i = n_warmup; i < n_iter; ++i)
-        if (!steps_ok((double)ch->leap_hist[i]))
-          return fail(ctx, VB_ERR_NUMERIC, "%s: the device planned %lld leapfrog steps", hc.name, (long long)ch->leap_hist[i]);
-    }
-    if (t + 1 >= n_warmup && t + 1 < n_iter) steps = (int)ch->leap_hist[t + 1];
+    gemm_f64_launch<false>(v.st, gemm_product(mq.xc, mq.ld, mq.xc, mq.ld, mq.d, mq.d, (int)mq.n_chains, 0), mq.splits, v.n_cu,
+                           EpiHmcSlab{mq.slab, mq.slab_stride, mq.ld});
+    VB_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(hmc_gram_add_kernel, dim3((unsigned)(((int64_t)mq.d * mq.d + 255) / 256)), v.block, 0, v.st, mq);
+  } else {
+    hipLaunchKernelGGL(hmc_moment_kernel<false>, v.col_grid, v.block, 0, v.st, mq);
   }
+  VB_HIP(ctx, hipGetLastError());
+  return VB_OK;
+}
 
-  // the one synchronisation: download
-  const size_t row_bytes = (size_t)d * sizeof(double), ld_bytes = (size_t)ld * sizeof(double);
-  VB_HIP(ctx, hipMemcpy2DAsync(last_x, row_bytes, a.x, ld_bytes, row_bytes, (size_t)C, hipMemcpyDeviceToHost, st));
-  if (chain_mean)
-    VB_HIP(ctx, hipMemcpy2DAsync(chain_mean, row_bytes, a.mean, ld_bytes, row_bytes, (size_t)C, hipMemcpyDeviceToHost, st));
-  if (chain_m2)
-    VB_HIP(ctx, hipMemcpy2DAsync(chain_m2, row_bytes, a.m2, ld_bytes, row_bytes, (size_t)C, hipMemcpyDeviceToHost, st));
-  if (accept_rate) VB_HIP(ctx, hipMemcpyAsync(accept_rate, a.count, (size_t)C * sizeof(double), hipMemcpyDeviceToHost, st));
-  VB_HIP(ctx, hipMemcpyAsync(step_hist, base + o_sh, (size_t)n_iter * sizeof(double), hipMemcpyDeviceToHost, st));
-  VB_HIP(ctx, hipMemcpyAsync(accept_hist, base + o_ah, (size_t)n_iter * sizeof(double), hipMemcpyDeviceToHost, st));
-  VB_HIP(ctx, hipMemcpyAsync(final_step, a.state + HS_BASE, sizeof(double), hipMemcpyDeviceToHost, st));
-  if (draws && n_kept)
-    VB_HIP(ctx, hipMemcpyAsync(draws, base + o_draws, (size_t)(n_kept * C * d) * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (logp && n_kept)
-    VB_HIP(ctx, hipMemcpyAsync(logp, base + o_logp, (size_t)(n_kept * C) * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (moments) {
-    VB_HIP(ctx, hipMemcpyAsync(hc.moment_sum, mq.s1, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, st));
-    VB_HIP(ctx, hipMemcpyAsync(hc.moment_m2, mq.s2, (size_t)(dense ? d * d : d) * sizeof(double), hipMemcpyDeviceToHost, st));
+// Adapt step after iteration t (t = -1: before the first): the step size of iteration t + 1, whose keys and stream stay in
+// v.q for its begin and end kernels.  ChEES: also its `steps` -- fetched after every warm-up iteration but the last
+// (8 bytes), and for all sampling iterations at once, behind the plan kernel, when the warm-up has ended
+static int hmc_adapt(vb_ctx* ctx, const HmcRun& r, HmcDev& v, int64_t t, int& steps) {
+  const uint64_t sn = r.stream_offset + (uint64_t)(t + 1);
+  v.q.t = t, v.q.k1_next = v.seed_hi ^ (uint32_t)(sn >> 32), v.q.w_next = (uint32_t)sn;
+  if (r.chees()) hipLaunchKernelGGL(hmc_chees_adapt_kernel, dim3(1), v.block, 0, v.st, v.q, v.cz);
+  else hipLaunchKernelGGL(hmc_adapt_kernel, dim3(1), v.block, 0, v.st, v.q);
+  VB_HIP(ctx, hipGetLastError());
+  if (!r.chees()) return VB_OK;
+  auto steps_ok = [&](double l) { return l >= 1.0 && l <= (double)r.n_leapfrog; };
+  if (t + 1 < r.n_warmup) {
+    double l_next = 0.0;
+    const FetchSeg seg{v.a.state + HS_LNEXT, sizeof(double), &l_next};
+    VB_TRY(fetch_blocking(ctx, v.st, &seg, 1));
+    if (!steps_ok(l_next)) return fail(ctx, VB_ERR_NUMERIC, "%s: the device planned %g leapfrog steps", r.name, l_next);
+    steps = (int)l_next;
+  } else if (t + 1 == r.n_warmup && r.n_draws > 0) {
+    HmcCheesPlanArgs pq;
+    pq.state = v.a.state, pq.step_hist = v.q.step_hist, pq.traj_hist = v.cz.traj_hist, pq.leap_hist = v.cz.leap_hist;
+    pq.n_warmup = r.n_warmup, pq.n_iter = r.n_iter(), pq.jitter = r.jitter, pq.k0 = v.q.k0, pq.seed_hi = v.seed_hi;
+    pq.stream_offset = r.stream_offset, pq.max_leapfrog = r.n_leapfrog;
+    hipLaunchKernelGGL(hmc_chees_plan_kernel, dim3((unsigned)((r.n_draws + 255) / 256)), v.block, 0, v.st, pq);
+    VB_HIP(ctx, hipGetLastError());
+    const FetchSeg seg{v.cz.leap_hist + r.n_warmup, (size_t)r.n_draws * sizeof(long long), r.leap_hist + r.n_warmup};
+    VB_TRY(fetch_blocking(ctx, v.st, &seg, 1));
+    for (int64_t i = r.n_warmup; i < r.n_iter(); ++i)
+      if (!steps_ok((double)r.leap_hist[i]))
+        return fail(ctx, VB_ERR_NUMERIC, "%s: the device planned %lld leapfrog steps", r.name, (long long)r.leap_hist[i]);
   }
-  if (ch) {
-    VB_HIP(ctx, hipMemcpyAsync(ch->traj_hist, cz.traj_hist, (size_t)n_iter * sizeof(double), hipMemcpyDeviceToHost, st));
-    VB_HIP(ctx, hipMemcpyAsync(ch->leap_hist, cz.leap_hist, (size_t)n_iter * sizeof(long long), hipMemcpyDeviceToHost, st));
-    VB_HIP(ctx, hipMemcpyAsync(ch->traj_state, a.state + HS_LOG_T, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-  }
-  std::vector<long long> div((size_t)C);
-  VB_HIP(ctx, hipMemcpyAsync(div.data(), a.n_div, (size_t)C * sizeof(long long), hipMemcpyDeviceToHost, st));
+  if (t + 1 >= r.n_warmup && t + 1 < r.n_iter()) steps = (int)r.leap_hist[t + 1];
+  return VB_OK;
+}
+
+// Download: the call's one synchronisation (ChEES apart), then the host's share of the outputs
+static int hmc_download(vb_ctx* ctx, const HmcRun& r, const HmcDev& v) {
+  const HmcArgs& a = v.a;
+  hipStream_t st = v.st;
+  const size_t W = sizeof(double), C = (size_t)r.n_chains, d = (size_t)r.d, T = (size_t)r.n_iter(), kept = (size_t)r.n_kept() * C;
+  auto copy = [&](void* dst, const void* src, size_t bytes) {      // an output the caller left out, or an empty one: skipped
+    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
+  };
+  auto rows = [&](double* dst, const double* src) {                 // C x d out of C x ld
+    return dst ? hipMemcpy2DAsync(dst, d * W, src, (size_t)a.ld * W, d * W, C, hipMemcpyDeviceToHost, st) : hipSuccess;
+  };
+  VB_HIP(ctx, rows(r.last_x, a.x));
+  VB_HIP(ctx, rows(r.chain_mean, a.mean));
+  VB_HIP(ctx, rows(r.chain_m2, a.m2));
+  VB_HIP(ctx, copy(r.accept_rate, a.count, C * W));
+  VB_HIP(ctx, copy(r.step_hist, v.q.step_hist, T * W));
+  VB_HIP(ctx, copy(r.accept_hist, v.q.accept_hist, T * W));
+  VB_HIP(ctx, copy(r.final_step, a.state + HS_BASE, W));
+  VB_HIP(ctx, copy(r.draws, v.base + v.o.draws, kept * d * W));
+  VB_HIP(ctx, copy(r.logp, v.base + v.o.logp, kept * W));
+  VB_HIP(ctx, copy(r.moment_sum, v.mq.s1, d * W));
+  VB_HIP(ctx, copy(r.moment_m2, v.mq.s2, (v.dense ? d * d : d) * W));
+  VB_HIP(ctx, copy(r.traj_hist, v.cz.traj_hist, T * W));
+  VB_HIP(ctx, copy(r.leap_hist, v.cz.leap_hist, T * sizeof(long long)));
+  VB_HIP(ctx, copy(r.traj_state, a.state + HS_LOG_T, 3 * W));
+  std::vector<long long> div(C);
+  VB_HIP(ctx, copy(div.data(), a.n_div, C * sizeof(long long)));
   VB_HIP(ctx, hipStreamSynchronize(st));
   int64_t total = 0;
-  for (int64_t c = 0; c < C; ++c) {
-    total += div[(size_t)c];
-    if (accept_rate && n_draws > 0) accept_rate[c] /= (double)n_draws;
+  for (size_t c = 0; c < C; ++c) {
+    total += div[c];
+    if (r.accept_rate && r.n_draws > 0) r.accept_rate[c] /= (double)r.n_draws;
   }
-  if (n_divergent) *n_divergent = total;
-  if (ch) ch->traj_state[3] += (double)n_warmup;
+  if (r.n_divergent) *r.n_divergent = total;
+  if (r.chees()) r.traj_state[3] += (double)r.n_warmup;
+  return VB_OK;
+}
+
+// vb_hmc_run, vb_hmc_run_metric and vb_hmc_run_chees: the header's transition list.  The diagonal kind without moments and
+// without ChEES enqueues exactly what vb_hmc_run always did.
+static int hmc_run(vb_ctx* ctx, const HmcRun& r) {
+  VB_TRY(hmc_refuse(ctx, r));
+  VB_HIP(ctx, hipSetDevice(ctx->device));
+  VB_TRY(main_stream_write(ctx));
+  const HmcLayout lay = hmc_layout(r);
+  VB_TRY(ensure(ctx, ctx->hmc_work, (size_t)lay.total * sizeof(double)));
+  std::vector<double> pack;      // the dense factors' staging: lives until hmc_download's synchronisation
+  VB_TRY(hmc_upload(ctx, r, lay, pack));
+  HmcDev dev = hmc_bind(ctx, r, lay);
+  VB_TRY(model_grad_rows(ctx, dev.a.x, lay.ld, r.n_chains, r.d, dev.a.g, dev.a.f));      // f, g of the start: carried from here on
+  int steps = r.n_leapfrog;
+  VB_TRY(hmc_adapt(ctx, r, dev, -1, steps));                                             // eps_0
+  for (int64_t t = 0; t < r.n_iter(); ++t) {
+    VB_TRY(hmc_trajectory(ctx, dev, steps));
+    if (r.chees() && t < r.n_warmup) VB_TRY(hmc_chees_criterion(ctx, dev));
+    VB_TRY(hmc_end(ctx, r, dev, t));
+    if (r.moment_shift) VB_TRY(hmc_window_moments(ctx, dev));
+    VB_TRY(hmc_adapt(ctx, r, dev, t, steps));
+  }
+  return hmc_download(ctx, r, dev);
+}
+
+// what vb_hmc_run_metric and vb_hmc_run_chees refuse before anything of their own (vb_hmc_run's own checks are stricter)
+static int hmc_check_segment(vb_ctx* ctx, const HmcRun& r) {
+  if (!ctx || !r.x0 || !r.metric || !r.last_x || !r.step_hist || !r.accept_hist || !r.final_step)
+    return fail(ctx, VB_ERR_INVALID, "NULL argument");
+  if (r.kind != VB_HMC_METRIC_DIAG && r.kind != VB_HMC_METRIC_DENSE)
+    return fail(ctx, VB_ERR_INVALID, "metric_kind must be VB_HMC_METRIC_DIAG or VB_HMC_METRIC_DENSE");
+  if (r.n_chains <= 0 || r.d <= 0 || r.n_draws < 0 || r.n_warmup < 0 || r.n_warmup + r.n_draws < 1)
+    return fail(ctx, VB_ERR_INVALID, "n_chains and d must be positive, n_warmup and n_draws non-negative with at least one "
+                                     "iteration between them");
+  if (r.n_draws > 0 && (!r.chain_mean || !r.chain_m2 || !r.accept_rate || !r.n_divergent))
+    return fail(ctx, VB_ERR_INVALID, "NULL sampling output with n_draws > 0");
+  const int given = (r.moment_shift != nullptr) + (r.moment_sum != nullptr) + (r.moment_m2 != nullptr);
+  if (given != 0 && given != 3)
+    return fail(ctx, VB_ERR_INVALID, "moment_shift, moment_sum and moment_m2 go together: pass all three or none");
   return VB_OK;
 }
 
 }  // namespace vb
 
 using namespace vb;
+
+// the arguments all three entries take under one name, as HmcRun's last fields
+#define HMC_SHARED_ARGS                                                                                                  \
+  .x0 = x0, .n_chains = n_chains, .d = d, .n_warmup = n_warmup, .n_draws = n_draws, .thin = thin, .step_size = step_size, \
+  .target_accept = target_accept, .jitter = jitter, .seed = seed, .stream_offset = stream_offset, .draws = draws,        \
+  .logp = logp, .last_x = last_x, .chain_mean = chain_mean, .chain_m2 = chain_m2, .accept_rate = accept_rate,            \
+  .step_hist = step_hist, .accept_hist = accept_hist, .final_step = final_step, .n_divergent = n_divergent
 
 extern "C" {
 
@@ -901,10 +1000,8 @@ int vb_hmc_run(vb_ctx* ctx, const double* x0, const double* inv_mass, int64_t n_
     return fail(ctx, VB_ERR_INVALID, "NULL argument");
   if (n_chains <= 0 || d <= 0 || n_draws <= 0 || n_warmup < 0)
     return fail(ctx, VB_ERR_INVALID, "n_chains, d and n_draws must be positive and n_warmup non-negative");
-  const HmcCall hc{"vb_hmc_run", VB_HMC_METRIC_DIAG, inv_mass, nullptr, nullptr, nullptr, nullptr};
-  return hmc_run(ctx, hc, x0, n_chains, d, n_warmup, n_draws, thin, n_leapfrog, step_size, target_accept, jitter, seed,
-                 stream_offset, draws, logp, last_x, chain_mean, chain_m2, accept_rate, step_hist, accept_hist, final_step,
-                 n_divergent);
+  return hmc_run(ctx, HmcRun{.name = "vb_hmc_run", .kind = VB_HMC_METRIC_DIAG, .metric = inv_mass, .n_leapfrog = n_leapfrog,
+                             HMC_SHARED_ARGS});
 }
 
 int vb_hmc_run_metric(vb_ctx* ctx, const double* x0, int metric_kind, const double* metric, int64_t n_chains, int64_t d,
@@ -912,22 +1009,10 @@ int vb_hmc_run_metric(vb_ctx* ctx, const double* x0, int metric_kind, const doub
                       double jitter, uint64_t seed, uint64_t stream_offset, const double* moment_shift, double* moment_sum,
                       double* moment_m2, double* draws, double* logp, double* last_x, double* chain_mean, double* chain_m2,
                       double* accept_rate, double* step_hist, double* accept_hist, double* final_step, int64_t* n_divergent) {
-  if (!ctx || !x0 || !metric || !last_x || !step_hist || !accept_hist || !final_step)
-    return fail(ctx, VB_ERR_INVALID, "NULL argument");
-  if (metric_kind != VB_HMC_METRIC_DIAG && metric_kind != VB_HMC_METRIC_DENSE)
-    return fail(ctx, VB_ERR_INVALID, "metric_kind must be VB_HMC_METRIC_DIAG or VB_HMC_METRIC_DENSE");
-  if (n_chains <= 0 || d <= 0 || n_draws < 0 || n_warmup < 0 || n_warmup + n_draws < 1)
-    return fail(ctx, VB_ERR_INVALID, "n_chains and d must be positive, n_warmup and n_draws non-negative with at least one "
-                                     "iteration between them");
-  if (n_draws > 0 && (!chain_mean || !chain_m2 || !accept_rate || !n_divergent))
-    return fail(ctx, VB_ERR_INVALID, "NULL sampling output with n_draws > 0");
-  const int given = (moment_shift != nullptr) + (moment_sum != nullptr) + (moment_m2 != nullptr);
-  if (given != 0 && given != 3)
-    return fail(ctx, VB_ERR_INVALID, "moment_shift, moment_sum and moment_m2 go together: pass all three or none");
-  const HmcCall hc{"vb_hmc_run_metric", metric_kind, metric, moment_shift, moment_sum, moment_m2, nullptr};
-  return hmc_run(ctx, hc, x0, n_chains, d, n_warmup, n_draws, thin, n_leapfrog, step_size, target_accept, jitter, seed,
-                 stream_offset, draws, logp, last_x, chain_mean, chain_m2, accept_rate, step_hist, accept_hist, final_step,
-                 n_divergent);
+  const HmcRun r{.name = "vb_hmc_run_metric", .kind = metric_kind, .metric = metric, .n_leapfrog = n_leapfrog,
+                 .moment_shift = moment_shift, .moment_sum = moment_sum, .moment_m2 = moment_m2, HMC_SHARED_ARGS};
+  VB_TRY(hmc_check_segment(ctx, r));
+  return hmc_run(ctx, r);
 }
 
 int vb_hmc_run_chees(vb_ctx* ctx, const double* x0, int metric_kind, const double* metric, int64_t n_chains, int64_t d,
@@ -936,18 +1021,12 @@ int vb_hmc_run_chees(vb_ctx* ctx, const double* x0, int metric_kind, const doubl
                      double* moment_sum, double* moment_m2, double* draws, double* logp, double* last_x, double* chain_mean,
                      double* chain_m2, double* accept_rate, double* step_hist, double* accept_hist, double* final_step,
                      int64_t* n_divergent, double* traj_state, double* traj_hist, int64_t* leap_hist) {
-  if (!ctx || !x0 || !metric || !last_x || !step_hist || !accept_hist || !final_step || !traj_state || !traj_hist || !leap_hist)
-    return fail(ctx, VB_ERR_INVALID, "NULL argument");
-  if (metric_kind != VB_HMC_METRIC_DIAG && metric_kind != VB_HMC_METRIC_DENSE)
-    return fail(ctx, VB_ERR_INVALID, "metric_kind must be VB_HMC_METRIC_DIAG or VB_HMC_METRIC_DENSE");
-  if (n_chains <= 0 || d <= 0 || n_draws < 0 || n_warmup < 0 || n_warmup + n_draws < 1)
-    return fail(ctx, VB_ERR_INVALID, "n_chains and d must be positive, n_warmup and n_draws non-negative with at least one "
-                                     "iteration between them");
-  if (n_draws > 0 && (!chain_mean || !chain_m2 || !accept_rate || !n_divergent))
-    return fail(ctx, VB_ERR_INVALID, "NULL sampling output with n_draws > 0");
-  const int given = (moment_shift != nullptr) + (moment_sum != nullptr) + (moment_m2 != nullptr);
-  if (given != 0 && given != 3)
-    return fail(ctx, VB_ERR_INVALID, "moment_shift, moment_sum and moment_m2 go together: pass all three or none");
+  const HmcRun r{.name = "vb_hmc_run_chees", .kind = metric_kind, .metric = metric, .n_leapfrog = max_leapfrog,
+                 .moment_shift = moment_shift, .moment_sum = moment_sum, .moment_m2 = moment_m2, .trajectory_lr = trajectory_lr,
+                 .traj_state = traj_state, .traj_hist = traj_hist, .leap_hist = leap_hist, HMC_SHARED_ARGS};
+  // (its own three pointers first: any NULL argument is reported before a bad metric_kind, as ever)
+  if (!traj_state || !traj_hist || !leap_hist) return fail(ctx, VB_ERR_INVALID, "NULL argument");
+  VB_TRY(hmc_check_segment(ctx, r));
   if (max_leapfrog < 1) return fail(ctx, VB_ERR_INVALID, "max_leapfrog must be at least 1");
   if (!(trajectory_lr >= 0.0) || !std::isfinite(trajectory_lr))
     return fail(ctx, VB_ERR_INVALID, "trajectory_lr must be non-negative and finite");
@@ -957,11 +1036,7 @@ int vb_hmc_run_chees(vb_ctx* ctx, const double* x0, int metric_kind, const doubl
     return fail(ctx, VB_ERR_INVALID, "traj_state: the second moment and the iteration count must be non-negative");
   if (n_chains < 2 && n_warmup > 0)
     return fail(ctx, VB_ERR_INVALID, "the trajectory length is adapted across the chains: n_chains >= 2 with n_warmup > 0");
-  const HmcChees ch{max_leapfrog, trajectory_lr, traj_state, traj_hist, leap_hist};
-  const HmcCall hc{"vb_hmc_run_chees", metric_kind, metric, moment_shift, moment_sum, moment_m2, &ch};
-  return hmc_run(ctx, hc, x0, n_chains, d, n_warmup, n_draws, thin, max_leapfrog, step_size, target_accept, jitter, seed,
-                 stream_offset, draws, logp, last_x, chain_mean, chain_m2, accept_rate, step_hist, accept_hist, final_step,
-                 n_divergent);
+  return hmc_run(ctx, r);
 }
 
 }  // extern "C"

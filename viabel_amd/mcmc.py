@@ -4,6 +4,8 @@ The reference's documentation compares its fits with MCMC draws (``docs/source/r
 ``check_accuracy(true_mean, true_cov, var_param, approx)``); :func:`hmc` produces those draws here, from the gradient
 pipeline the objectives use (``vb_hmc_run`` / ``vb_hmc_run_metric`` / ``vb_hmc_run_chees``, ``csrc/vb_hmc.hip``;
 ``DESIGN.md`` 4.22 and 4.25)."""
+from functools import partial
+
 import numpy as np
 
 from viabel_amd import _lib
@@ -154,6 +156,71 @@ def _segments(n_warmup, n_draws, windows):
     return out + [(n_warmup - windows[-1][1], n_draws, None)]
 
 
+def _resolve_start(fit, shape, init, inv_mass, dense):
+    """``(init, inv_mass)``, ``shape = (n_chains, D)``: what the caller left out comes from ``fit = (approx, var_param)``
+    when there is one; without it the metric is the unit one."""
+    if fit is not None:
+        approx, var_param = fit
+        if inv_mass is None and dense:
+            inv_mass = np.ascontiguousarray(approx.mean_and_cov(var_param)[1], dtype=np.float64)
+            if inv_mass.shape != (shape[1], shape[1]):
+                raise ValueError('approx.mean_and_cov returned a covariance of shape {}'.format(inv_mass.shape))
+            _dense_factor(inv_mass, 'the approximation\'s covariance')
+        elif inv_mass is None:
+            inv_mass = np.ascontiguousarray(np.diag(approx.mean_and_cov(var_param)[1]), dtype=np.float64)
+            if not (np.all(inv_mass > 0.0) and np.all(np.isfinite(inv_mass))):
+                raise ValueError('the approximation has no finite positive variances to take the metric from; pass inv_mass')
+        if init is None:
+            init = np.ascontiguousarray(approx.sample(var_param, shape[0]), dtype=np.float64)
+            if init.shape != shape:
+                raise ValueError('approx.sample returned shape {}, expected ({}, {})'.format(init.shape, *shape))
+    if inv_mass is None:
+        inv_mass = np.eye(shape[1]) if dense else np.ones(shape[1])
+    return init, inv_mass
+
+
+def _run_segments(method, segments, out, inv_mass, stream):
+    """One call of ``method`` (an ``Engine.hmc_run*`` with the run's own arguments bound) per segment ``(n_warmup, n_draws,
+    window)``, each continuing from the last one's ``out`` -- states, final step, trajectory state; at first the start's --
+    and stream; a window's call also returns the moments the next metric is estimated from.  Returns the last call's
+    outputs with the histories of all calls stitched together, the sampling phase's ``inv_mass`` and ``n_calls``."""
+    dense = inv_mass.ndim == 2
+    factor, calls = np.linalg.cholesky(inv_mass) if dense else inv_mass, []
+    for n_warmup, n_draws, window in segments:
+        x, own = out['last'], ({'traj_state': out['traj_state']} if 'traj_state' in out else {})
+        if window is not None:
+            own['moment_shift'] = x.mean(axis=0)
+        out = method(x, factor, n_warmup, n_draws, step_size=out['step_size'], stream_offset=stream, **own)
+        calls.append(out)
+        if window is not None:
+            inv_mass, factor = _window_metric(out['moment_sum'], out['moment_m2'], x.shape[0] * n_warmup, dense, window)
+        stream += n_warmup + n_draws
+    for key in ('step_size_history', 'accept_prob', 'trajectory_history', 'n_leapfrog_history'):
+        if key in out:
+            out[key] = np.concatenate([call[key] for call in calls])
+    return dict(out, inv_mass=inv_mass, n_calls=len(calls))
+
+
+def _results(out, n_draws, **run):
+    """``hmc``'s result dict from the stitched outputs and the run's own entries (``run``), and the printed summary."""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        chain_var = out['chain_m2'] / (n_draws - 1.0) if n_draws > 1 else np.full_like(out['chain_m2'], np.nan)
+    mean, sd, rhat = _combine_chains(out['chain_mean'], chain_var, n_draws)
+    leap_hist = out['n_leapfrog_history']
+    results = dict({key: out[key] for key in ('draws', 'logp', 'last', 'chain_mean', 'accept_rate', 'accept_prob',
+                                              'step_size_history', 'step_size', 'n_divergent', 'inv_mass',
+                                              'trajectory_history', 'n_leapfrog_history')},
+                   chain_var=chain_var, mean=mean, sd=sd, rhat=rhat, n_grad_evals=int(leap_hist.sum()) + out['n_calls'], **run)
+    max_rhat = float(np.max(rhat[~np.isnan(rhat)])) if not np.all(np.isnan(rhat)) else float('nan')
+    print('hmc: step size = {:.4g}, T = {:.4g}, mean L = {:.1f}, mean acceptance = {:.3f}, max rhat = {:.3f}, {} divergent of '
+          '{} proposals'.format(results['step_size'], run['trajectory_length'], float(leap_hist.mean()),
+                                float(out['accept_rate'].mean()), max_rhat, results['n_divergent'], n_draws * out['last'].shape[0]))
+    if max_rhat > 1.05 or results['n_divergent'] > 0:
+        print('WARNING: rhat > 1.05 means the chains have not mixed; divergences mean the step size is too large for '
+              'parts of the posterior. Run longer, start from a better fit, or lower step_size.')
+    return results
+
+
 def hmc(model, *, n_chains=256, n_warmup=300, n_draws=300, n_leapfrog=16, step_size=None, target_accept=0.8, jitter=0.2,
         init=None, inv_mass=None, var_param=None, approx=None, seed=1, stream_offset=0, thin=1, keep_draws=True,
         metric='diag', adapt_metric=False, trajectory='fixed', max_leapfrog=256, trajectory_length=None,
@@ -207,84 +274,31 @@ def hmc(model, *, n_chains=256, n_warmup=300, n_draws=300, n_leapfrog=16, step_s
                                                  jitter, init, inv_mass, var_param, approx, thin, metric, adapt_metric,
                                                  trajectory, max_leapfrog, trajectory_length, trajectory_lr)
     dense, chees = metric == 'dense', trajectory == 'chees'
-    if var_param is not None:
-        var_param = np.asarray(var_param, dtype=np.float64)
-        if inv_mass is None and dense:
-            inv_mass = np.ascontiguousarray(approx.mean_and_cov(var_param)[1], dtype=np.float64)
-            if inv_mass.shape != (model.dim, model.dim):
-                raise ValueError('approx.mean_and_cov returned a covariance of shape {}'.format(inv_mass.shape))
-            _dense_factor(inv_mass, 'the approximation\'s covariance')
-        elif inv_mass is None:
-            inv_mass = np.ascontiguousarray(np.diag(approx.mean_and_cov(var_param)[1]), dtype=np.float64)
-            if not (np.all(inv_mass > 0.0) and np.all(np.isfinite(inv_mass))):
-                raise ValueError('the approximation has no finite positive variances to take the metric from; pass inv_mass')
-        if init is None:
-            init = np.ascontiguousarray(approx.sample(var_param, int(n_chains)), dtype=np.float64)
-            if init.shape != (n_chains, model.dim):
-                raise ValueError('approx.sample returned shape {}, expected ({}, {})'.format(init.shape, n_chains, model.dim))
-    if inv_mass is None:
-        inv_mass = np.eye(model.dim) if dense else np.ones(model.dim)
+    n_chains, n_warmup, n_draws, n_leapfrog = int(n_chains), int(n_warmup), int(n_draws), int(n_leapfrog)
+    fit = None if var_param is None else (approx, np.asarray(var_param, dtype=np.float64))
+    init, inv_mass = _resolve_start(fit, (n_chains, model.dim), init, inv_mass, dense)
     windows = _adaptation_windows(n_warmup) if adapt_metric else []
     eng = _lib.default_engine()
     if eng.n_ranks > 1:
         raise NotImplementedError('hmc runs on one process\'s engine; a sharded engine ({} ranks) is not supported'.format(
             eng.n_ranks))
     eng.set_model(model.device_spec())
-    n_calls = 1
-    if not dense and not adapt_metric and not chees:
-        out = eng.hmc_run(init, inv_mass, n_warmup, n_draws, n_leapfrog, step_size, target_accept=target_accept,
-                          jitter=jitter, seed=seed, stream_offset=stream_offset, thin=thin, keep_draws=keep_draws)
-    else:
-        # one engine call per segment, each continuing from the last one's states, final step and stream
-        factor = np.linalg.cholesky(inv_mass) if dense else inv_mass
-        segments = _segments(int(n_warmup), int(n_draws), windows) if adapt_metric else [(int(n_warmup), int(n_draws), None)]
-        x, step, stream, hist, n_calls = init, step_size, int(stream_offset), [], len(segments)
+    # the route: with neither a dense metric, nor adaptation, nor ChEES, one segment through vb_hmc_run
+    kw = dict(target_accept=target_accept, jitter=jitter, seed=seed, thin=thin, keep_draws=keep_draws)
+    start, n_iter = dict(last=init, step_size=step_size), n_warmup + n_draws
+    if chees:
         log_t0 = np.log(step_size if trajectory_length is None else float(trajectory_length))
-        traj_state = np.array([log_t0, 0.0, log_t0, 0.0])
-        for seg_warmup, seg_draws, window in segments:
-            kw = dict(target_accept=target_accept, jitter=jitter, seed=seed, stream_offset=stream, thin=thin,
-                      keep_draws=keep_draws, moment_shift=None if window is None else x.mean(axis=0))
-            if chees:
-                out = eng.hmc_run_chees(x, factor, seg_warmup, seg_draws, max_leapfrog, step, traj_state,
-                                        trajectory_lr=trajectory_lr, **kw)
-                traj_state = out['traj_state']
-                hist.append((out['step_size_history'], out['accept_prob'], out['trajectory_history'],
-                             out['n_leapfrog_history']))
-            else:
-                out = eng.hmc_run_metric(x, factor, seg_warmup, seg_draws, n_leapfrog, step, **kw)
-                hist.append((out['step_size_history'], out['accept_prob']))
-            if window is not None:
-                inv_mass, factor = _window_metric(out['moment_sum'], out['moment_m2'], int(n_chains) * seg_warmup, dense,
-                                                  window)
-            x, step, stream = out['last'], out['step_size'], stream + seg_warmup + seg_draws
-        out['step_size_history'] = np.concatenate([h[0] for h in hist])
-        out['accept_prob'] = np.concatenate([h[1] for h in hist])
-        if chees:
-            out['trajectory_history'] = np.concatenate([h[2] for h in hist])
-            out['n_leapfrog_history'] = np.concatenate([h[3] for h in hist])
-    n_iter = int(n_warmup) + int(n_draws)
-    if chees:          # (without a warm-up the length is the one given: a continuation passes it on unchanged)
-        traj_hist, leap_hist = out['trajectory_history'], out['n_leapfrog_history']
-        traj = float(traj_hist[int(n_warmup)]) if n_warmup > 0 or trajectory_length is None else float(trajectory_length)
+        start['traj_state'] = np.array([log_t0, 0.0, log_t0, 0.0])
+        method = partial(eng.hmc_run_chees, max_leapfrog=max_leapfrog, trajectory_lr=trajectory_lr, **kw)
     else:
-        traj = int(n_leapfrog) * out['step_size']
-        traj_hist, leap_hist = np.full(n_iter, traj), np.full(n_iter, int(n_leapfrog), dtype=np.int64)
-    n = int(n_draws)
-    with np.errstate(divide='ignore', invalid='ignore'):
-        chain_var = out['chain_m2'] / (n - 1.0) if n > 1 else np.full_like(out['chain_m2'], np.nan)
-    mean, sd, rhat = _combine_chains(out['chain_mean'], chain_var, n)
-    results = dict(draws=out['draws'], logp=out['logp'], last=out['last'], chain_mean=out['chain_mean'],
-                   chain_var=chain_var, mean=mean, sd=sd, rhat=rhat, accept_rate=out['accept_rate'],
-                   accept_prob=out['accept_prob'], step_size_history=out['step_size_history'], step_size=out['step_size'],
-                   n_divergent=out['n_divergent'], inv_mass=inv_mass, metric=metric, adapt_windows=windows, trajectory_length=traj,
-                   trajectory_history=traj_hist, n_leapfrog_history=leap_hist,
-                   n_grad_evals=int(leap_hist.sum()) + n_calls, seed=int(seed),
-                   next_stream=int(stream_offset) + int(n_warmup) + int(n_draws))
-    max_rhat = float(np.max(rhat[~np.isnan(rhat)])) if not np.all(np.isnan(rhat)) else float('nan')
-    print('hmc: step size = {:.4g}, T = {:.4g}, mean L = {:.1f}, mean acceptance = {:.3f}, max rhat = {:.3f}, {} divergent of '
-          '{} proposals'.format(results['step_size'], traj, float(leap_hist.mean()), float(out['accept_rate'].mean()),
-                                max_rhat, results['n_divergent'], n * int(n_chains)))
-    if max_rhat > 1.05 or results['n_divergent'] > 0:
-        print('WARNING: rhat > 1.05 means the chains have not mixed; divergences mean the step size is too large for '
-              'parts of the posterior. Run longer, start from a better fit, or lower step_size.')
-    return results
+        method = partial(eng.hmc_run_metric if dense or adapt_metric else eng.hmc_run, n_leapfrog=n_leapfrog, **kw)
+    segments = _segments(n_warmup, n_draws, windows) if adapt_metric else [(n_warmup, n_draws, None)]
+    out = _run_segments(method, segments, start, inv_mass, int(stream_offset))
+    if not chees:
+        out.update(trajectory_history=np.full(n_iter, n_leapfrog * out['step_size']),
+                   n_leapfrog_history=np.full(n_iter, n_leapfrog, dtype=np.int64))
+    traj = float(out['trajectory_history'][n_warmup])
+    if chees and n_warmup == 0 and trajectory_length is not None:      # a continuation passes the length on unchanged
+        traj = float(trajectory_length)
+    return _results(out, n_draws, metric=metric, adapt_windows=windows, trajectory_length=traj, seed=int(seed),
+                    next_stream=int(stream_offset) + n_iter)
