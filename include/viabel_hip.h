@@ -745,9 +745,10 @@ int vb_elbo_grad_mvt_chol(vb_ctx* ctx, int slot, int64_t n, int64_t d, int64_t n
  * MultivariateT.sample (approximations.py:348) -- by coupled Newton-Schulz iterations (fp64 MFMA GEMMs only).
  * With e != NULL also x = the solution of  root x + x root = e  (the derivative of the root in direction e, what
  * autograd's sqrtm VJP computes for ExclusiveKL over a MultivariateT, objectives.py:154-164); e and x may be
- * NULL.  info (3 doubles, may be NULL) = [iterations, final ||I - Z Y||_F, ||root root - a||_F / ||a||_F]:
+ * NULL.  info (3 doubles, may be NULL) = [iterations, final ||I - Z Y||_F, ||root root - a||_F / max_i sum_j |a_ij|]:
  * the caller decides from info[2] whether to keep the result or use its LAPACK path (the iteration resolves
- * condition numbers up to ~1e12). */
+ * condition numbers up to ~1e12).  Only the symmetric part (a + a') / 2 is read -- `a` itself, bit for bit, when it is
+ * exactly symmetric -- and info[2] refers to that matrix: the root of a non-symmetric `a` is not what this computes. */
 int vb_sym_sqrt(vb_ctx* ctx, const double* a, const double* e, int64_t d, double* root, double* x, double* info);
 /* the same with the inverse root a^(-1/2) (d x d, may be NULL), which the iteration produces alongside */
 int vb_sym_sqrt_inv(vb_ctx* ctx, const double* a, const double* e, int64_t d, double* root, double* x, double* info,

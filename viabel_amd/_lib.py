@@ -408,6 +408,19 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _root_arguments(a, e):
+    """``a`` (and ``e``) as contiguous doubles for ``vb_sym_sqrt``; the C side reads ``d * d`` doubles from each, so anything
+    but a non-empty square ``a`` and an ``e`` of the same shape is refused here."""
+    a = _f64(a)
+    if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] == 0:
+        raise ValueError('a must be a non-empty square matrix; got shape {}'.format(a.shape))
+    if e is not None:
+        e = _f64(e)
+        if e.shape != a.shape:
+            raise ValueError('e must have the shape of a, {}; got {}'.format(a.shape, e.shape))
+    return a, e
+
+
 def device_count():
     """GPUs visible to HIP (0 without one)."""
     n = ctypes.c_int(0)
@@ -1364,15 +1377,15 @@ class Engine:
     def sym_sqrt(self, a, e=None):
         """Symmetric square root of an SPD matrix on the device (``vb_sym_sqrt``); with ``e`` also the solution
         ``x`` of ``root x + x root = e``.  Returns ``(root, x or None, info)`` with
-        ``info = [iterations, final residual, ||root root - a|| / ||a||]``."""
-        a = _f64(a)
+        ``info = [iterations, final residual, ||root root - a||_F / max_i sum_j |a_ij|]``.  Only the symmetric part of
+        ``a`` is read.  ``ValueError`` unless ``a`` is a non-empty square matrix and ``e`` has its shape."""
+        a, e = _root_arguments(a, e)
         d = a.shape[0]
         root = np.empty((d, d), dtype=np.float64)
         info = np.zeros(3, dtype=np.float64)
         if e is None:
             self._check(self._lib.vb_sym_sqrt(self._ctx, _dptr(a), None, d, _dptr(root), None, _dptr(info)))
             return root, None, info
-        e = _f64(e)
         x = np.empty((d, d), dtype=np.float64)
         self._check(self._lib.vb_sym_sqrt(self._ctx, _dptr(a), _dptr(e), d, _dptr(root), _dptr(x), _dptr(info)))
         return root, x, info
@@ -1398,7 +1411,7 @@ class Engine:
 
     def sym_sqrt_inv(self, a):
         """``(root, inverse root, info)`` of an SPD matrix (``vb_sym_sqrt_inv``)."""
-        a = _f64(a)
+        a, _ = _root_arguments(a, None)
         d = a.shape[0]
         root, inv_root = np.empty((d, d), dtype=np.float64), np.empty((d, d), dtype=np.float64)
         info = np.zeros(3, dtype=np.float64)

@@ -6,11 +6,11 @@
 // Method: the coupled Newton-Schulz iteration (Higham, Functions of Matrices, eq. 6.35) -- only fp64 MFMA
 // GEMMs, no factorisation:
 //     Y_0 = M / c,  Z_0 = I;    T = (3 I - Z Y) / 2;    Y <- Y T,   Z <- T Z;     Y -> (M / c)^(1/2)
-// with c = ||A||_F so that the spectrum of M / c lies in (0, 1].  For the derivative the iteration runs on the
+// with c = max_i sum_j |A_ij| so that the spectrum of M / c lies in (0, 1].  For the derivative the iteration runs on the
 // block upper-triangular matrix M = [[A, E], [0, A]], whose square root is [[R, X], [0, R]] (the Frechet
 // derivative of the root in direction E, i.e. the Sylvester solution).  Three GEMMs per step; the first one's
 // epilogue forms T and reduces ||I - Z Y||_F^2, which the host reads to stop when it no longer decreases.
-// The caller checks ||R R - A||_F / ||A||_F (returned) and keeps its LAPACK path for matrices this iteration
+// The caller checks ||R R - A||_F / c (returned) and keeps its LAPACK path for matrices this iteration
 // cannot resolve (condition numbers beyond ~1e12).
 //
 // Why not LAPACK on the host as before: OpenBLAS's threaded dsyevd takes 70-95 ms for a 256 x 256 matrix on the
@@ -69,7 +69,11 @@ GemmArgs square(const double* A, const double* B, int64_t ld, int m) {
 }  // namespace
 
 // host: a (d x d, symmetric positive definite), e (d x d or nullptr) -> root, x (d x d each), info = [iterations,
-// final ||I - Z Y||_F, ||R R - A||_F / ||A||_F]
+// final ||I - Z Y||_F, ||R R - A||_F / c], c = max_i sum_j |A_ij|.
+// What is staged, scaled and rooted is the SYMMETRIC PART A = (a + a') / 2 -- bit for bit `a` itself for the exactly
+// symmetric matrices every caller passes.  The returned root is symmetrised, so for a non-symmetric `a` the iteration on
+// `a` as given would converge to its (non-symmetric) principal root, report info[2] ~ 1e-15 for THAT and return a matrix
+// whose square is off by the skew part; now info[2] refers to the matrix that was actually rooted.
 int sym_sqrt(vb_ctx* ctx, const double* a, const double* e, int64_t d, double* root, double* x, double* info,
              double* inv_root) {
   const int m = (int)(e ? 2 * d : d);
@@ -95,7 +99,7 @@ int sym_sqrt(vb_ctx* ctx, const double* a, const double* e, int64_t d, double* r
   double fro = 0.0, fro_e = 0.0;
   for (int64_t i = 0; i < d; ++i) {
     double r = 0.0;
-    for (int64_t j = 0; j < d; ++j) r += fabs(a[i * d + j]);
+    for (int64_t j = 0; j < d; ++j) r += fabs(0.5 * (a[i * d + j] + a[j * d + i]));
     if (r > fro || !(r == r)) fro = r;
   }
   if (!(fro > 0.0) || !std::isfinite(fro)) return fail(ctx, VB_ERR_NUMERIC, "matrix square root: zero or non-finite matrix");
@@ -118,7 +122,7 @@ int sym_sqrt(vb_ctx* ctx, const double* a, const double* e, int64_t d, double* r
   for (int64_t i = 0; i < m; ++i) h[i * ld + i] = 0.0;
   for (int64_t i = 0; i < d; ++i)
     for (int64_t j = 0; j < d; ++j) {
-      const double v = a[i * d + j] / fro;
+      const double v = 0.5 * (a[i * d + j] + a[j * d + i]) / fro;      // the symmetric part (see the header comment)
       h[i * ld + j] = v;
       if (e) {
         h[(i + d) * ld + (j + d)] = v;
