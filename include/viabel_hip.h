@@ -17,6 +17,11 @@
  *   - one context per GPU; calls on one context are serialised by the caller; the
  *     synchronous entry points return after the context's HIP stream has drained;
  *   - return 0 on success, a VB_ERR_* code otherwise; vb_last_error() gives the text.
+ *
+ * The Python binding (viabel_amd/_lib.py) derives its ctypes table and its constants from this file, so keep to the shape
+ * it reads: one function declaration per `;`, parameters of the scalar types used below (int, unsigned, double, int64_t,
+ * uint64_t, uint32_t, size_t, char, the opaque handles and void) or pointers / arrays of them, no function-pointer parameter
+ * except through a typedef, and integer constants as `#define VB_NAME <integer>`.
  */
 #ifndef VIABEL_HIP_H
 #define VIABEL_HIP_H

@@ -267,6 +267,32 @@ def test_async_pipeline_matches_sync(vb):
         np.testing.assert_array_equal(g, sync[s][1])     # deterministic reductions: bitwise
 
 
+def test_profile_read_reports_the_mean_field_kernel(vb):
+    """vb_profile_read after one mean-field evaluation at n = 8, d = 4: one launch covering one evaluation (every route
+    records one event pair per launch and `count` evaluations, vb_meanfield.hip), and -- read without a reset -- the
+    very record vb_profile_read_kernel(VB_PROF_MF_ACCUM) reports, its milliseconds included."""
+    import ctypes
+    from viabel_amd import _lib
+    eng = _lib.default_engine()
+    D, N = 4, 8
+    eng.set_model(vb.GaussianModel(np.zeros(D), np.ones(D)).device_spec())
+    eng.noise_generate(10, N, D, seed=1)
+    theta = _theta(D, np.random.RandomState(4))
+    eng.profile_enable(True)
+    try:
+        eng.profile_read(reset=True)
+        eng.elbo_grad_meanfield(10, N, D, theta, _lib.FAMILY_MF_GAUSSIAN)
+        launches, evals, ms = ctypes.c_int64(-1), ctypes.c_int64(-1), ctypes.c_double(-1.0)
+        eng._check(eng._lib.vb_profile_read(eng._ctx, ctypes.byref(launches), ctypes.byref(evals), ctypes.byref(ms), 0))
+        same = eng.profile_read(reset=True, kernel=_lib.PROF_MF_ACCUM)
+        after = eng.profile_read(reset=False)
+    finally:
+        eng.profile_enable(False)
+    assert (launches.value, evals.value) == (1, 1) and ms.value > 0.0
+    assert same == (1, 1, ms.value)
+    assert after == (0, 0, 0.0)
+
+
 @pytest.mark.parametrize('count,D,N', [(16, 1024, 4096), (5, 130, 77), (33, 64, 256)])
 def test_batch_matches_single(vb, count, D, N):
     """`count` evaluations sharing one launch of each kernel == the same evaluations one by one."""

@@ -5,6 +5,7 @@ no MI355X is visible, every compute call raises -- loudly -- instead of silently
 computing something else.
 """
 import ctypes
+import re
 import weakref
 import os
 import subprocess
@@ -16,20 +17,91 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # VIABEL_AMD_LIB: load another build of the same C ABI (the host-sanitizer build libviabel_hip_asan.so, `make asan`)
 LIB_PATH = os.environ.get('VIABEL_AMD_LIB') or os.path.join(_HERE, 'libviabel_hip.so')
 CSRC_DIR = os.path.join(_HERE, 'csrc')
+# the declaration of the C ABI (what csrc/Makefile compiles against): the one source of SIGNATURES and of the VB_* constants
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'viabel_hip.h')
 
-VB_OK, VB_ERR_INVALID, VB_ERR_HIP, VB_ERR_UNSUPPORTED, VB_ERR_STATE, VB_ERR_NUMERIC, VB_ERR_COMM, VB_ERR_CALLBACK = range(8)
 
-FAMILY_MF_GAUSSIAN, FAMILY_MF_STUDENT_T, FAMILY_FULLRANK_GAUSSIAN, FAMILY_MULTIVARIATE_T, FAMILY_LOWRANK_GAUSSIAN = \
-    range(5)
-MODEL_GAUSS_DIAG, MODEL_FUNNEL, MODEL_GAUSS_FULL, MODEL_LOGISTIC, MODEL_SOURCE, MODEL_SOFTMAX = range(6)
-MODEL_MULTILEVEL = 6
-MODEL_LOCSCALE = 7
-MODEL_SPARSE_GLM = 8
-MODEL_MINIBATCH_GLM = 9
+class EngineError(RuntimeError):
+    """The HIP engine is unavailable or a HIP call failed."""
+
+
+# `const double*` / `double*` parameters are declared void*: ctypes then takes the array's address as a plain integer
+# (`_dptr`), half the cost of building a POINTER(c_double) per argument on calls that last tens of microseconds
+_c_double_p = ctypes.c_void_p
+_c_int64_p = ctypes.POINTER(ctypes.c_int64)
+_ctx_p = ctypes.c_void_p
+
+# The binding's type rule.  What the header declares decides the ctypes type; a type outside the rule is an error.
+#   int, unsigned, double, int64_t, uint64_t, uint32_t, size_t      the ctypes scalar of that type
+#   double*, const double*                                          c_void_p, always: the hot path passes integer addresses
+#   vb_ctx*, vb_flow*, vb_legacy_rng*, void*, the callback typedefs  c_void_p
+#   char*, char x[N], const char*                                   c_char_p
+#   T*, T x[N] for the integer types above                          POINTER(T)
+#   T**                                                             POINTER(c_void_p)
+#   return void                                                     None
+_SCALARS = {'int': ctypes.c_int, 'unsigned': ctypes.c_uint, 'double': ctypes.c_double, 'int64_t': ctypes.c_int64,
+            'uint64_t': ctypes.c_uint64, 'uint32_t': ctypes.c_uint32, 'size_t': ctypes.c_size_t}
+_OPAQUE = ('vb_ctx', 'vb_flow', 'vb_legacy_rng', 'void')
+_CALLBACKS = ('vb_model_callback', 'vb_host_collective_fn')
+_COMMENT = re.compile(r'/\*.*?\*/', re.S)
+_DEFINE = re.compile(r'^[ \t]*#[ \t]*define[ \t]+VB_(\w+)[ \t]+(\d+)u?[ \t]*$', re.M)
+_NOT_DECLARATIONS = re.compile(r'^[ \t]*#.*$|extern\s+"C"\s*\{|\}', re.M)
+_FUNCTION = re.compile(r'(.+?)\b(vb_\w+)\s*\((.*)\)', re.S)
+_TYPE = re.compile(r'(?:const\s+)?(\w+)\s*(\**)\s*(?:\w+\s*(\[\w*\])?)?')       # [const] base [*...] [name [[N]]]
+
+
+def _ctype(text, where):
+    m = _TYPE.fullmatch(text.strip())
+    if m:
+        base, depth = m.group(1), len(m.group(2)) + (m.group(3) is not None)
+        if depth == 0 and base in _SCALARS:
+            return _SCALARS[base]
+        if (depth == 0 and base in _CALLBACKS) or (depth == 1 and (base == 'double' or base in _OPAQUE)):
+            return ctypes.c_void_p
+        if depth == 1 and base == 'char':
+            return ctypes.c_char_p
+        if depth == 1 and base in _SCALARS:
+            return ctypes.POINTER(_SCALARS[base])
+        if depth == 2 and base in _OPAQUE:
+            return ctypes.POINTER(ctypes.c_void_p)
+    raise EngineError('%s: %s: the type of `%s` is outside the binding\'s type rule (viabel_amd/_lib.py)'
+                      % (HEADER_PATH, where, ' '.join(text.split())))
+
+
+def _parse_header(path):
+    """``(signatures, constants)`` of the C header at ``path``: ``name -> (restype, argtypes)`` for every function it
+    declares, ``NAME -> value`` for every ``#define VB_NAME <integer>``."""
+    try:
+        with open(path) as f:
+            text = _COMMENT.sub(' ', f.read())
+    except OSError as exc:
+        raise EngineError('cannot read the C ABI header %s: %s' % (path, exc))
+    constants = {name: int(value) for name, value in _DEFINE.findall(text)}
+    signatures = {}
+    for decl in _NOT_DECLARATIONS.sub('', text).split(';'):
+        decl = decl.strip()
+        if not decl or decl.startswith('typedef'):
+            continue
+        m = _FUNCTION.fullmatch(decl)
+        if not m:
+            raise EngineError('%s: not a function declaration the binding can read: `%s`' % (path, ' '.join(decl.split())))
+        restype, name, params = m.groups()
+        params = [] if params.strip() in ('', 'void') else params.split(',')
+        signatures[name] = (None if restype.strip() == 'void' else _ctype(restype, name + ', return type'),
+                            [_ctype(p, '%s, parameter %d' % (name, i)) for i, p in enumerate(params)])
+    return signatures, constants
+
+
+# name -> (restype, argtypes) of every symbol include/viabel_hip.h declares, and its integer constants without their VB_
+# prefix (FAMILY_*, MODEL_*, GLM_*, NOISE_*, CV_*, OPT_*, PRIOR_*, HMC_METRIC_*, PROF_*, MAX_SLOTS, ...) as module attributes
+SIGNATURES, _CONSTANTS = _parse_header(HEADER_PATH)
+globals().update(_CONSTANTS)
+# the status codes keep the prefix as well: the package says VB_OK, VB_ERR_INVALID
+globals().update({'VB_' + name: value for name, value in _CONSTANTS.items() if name == 'OK' or name.startswith('ERR_')})
+
 # targets that hand every pipeline finished rows (f, grad f): a softmax, multilevel, location-scale or sparse regression
 # target goes wherever a source model goes; the minibatch target forms its rows the same way (the objectives decide what
 # may take a density that changes from batch to batch)
-MODEL_NEURALNET = 10
 MODELS_WITH_ROWS = (MODEL_SOURCE, MODEL_SOFTMAX, MODEL_MULTILEVEL, MODEL_LOCSCALE, MODEL_SPARSE_GLM, MODEL_MINIBATCH_GLM,
                     MODEL_NEURALNET)
 # doubles of predictor matrix one row chunk of the softmax pipeline may hold (csrc/vb_common.h: kSoftmaxChunkDoubles);
@@ -41,7 +113,6 @@ MULTILEVEL_CHUNK_DOUBLES = 16 << 20
 # ... and of the location-scale pipeline (kLocScaleChunkDoubles), whose two predictor matrices share the bound: a chunk is
 # max(8, LOCSCALE_CHUNK_DOUBLES // (2 * round_up(n_data, 16))) rows
 LOCSCALE_CHUNK_DOUBLES = 16 << 20
-LOCSCALE_GAUSSIAN, LOCSCALE_STUDENT_T = range(2)
 # entries of a row or column of a sparse design that one wave sums (csrc/vb_common.h: kSparseSegment); longer lists are cut
 # into segments of this many entries, summed by separate waves and combined in segment order
 SPARSE_SEGMENT = 256
@@ -83,278 +154,19 @@ def nn_predict_chunk(n_hidden, n_draws):
     return max(1, NN_PREDICT_DOUBLES // (int(n_hidden) * ((int(n_draws) + 15) // 16 * 16)))
 
 
-GLM_BERNOULLI_LOGIT, GLM_POISSON, GLM_GAUSSIAN = range(3)
-NOISE_NORMAL, NOISE_STUDENT_T = range(2)
-FLAG_PATH_DERIV = 1
-CV_MODES = {None: 0, 'full': 1, 'mean_only': 2, 'loo_diag_approx': 3, 'loo_direct_approx': 4}
-MAX_SLOTS = 64
+CV_MODES = {None: CV_NONE, 'full': CV_FULL, 'mean_only': CV_MEAN_ONLY, 'loo_diag_approx': CV_LOO_DIAG,
+            'loo_direct_approx': CV_LOO_DIRECT}
 # capacity of the batched smoothing kernel (csrc/vb_psis_batch.hip: kPbMaxN, kPbTailCap)
 PSIS_BATCH_MAX_N, PSIS_BATCH_MAX_TAIL = 16384, 1024
-OPT_SGD, OPT_RMSPROP, OPT_ADAM, OPT_ADAGRAD = range(4)
-PRIOR_DIAG_GAUSSIAN, PRIOR_DIAG_STUDENT_T, PRIOR_DENSE = range(3)
-HMC_METRIC_DIAG, HMC_METRIC_DENSE = range(2)      # VB_HMC_METRIC_* (vb_hmc_run_metric)
 # int fn(void* user, const double* z, int64 n, int64 d, double* f, double* grad)   (include/viabel_hip.h: vb_model_callback)
 MODEL_CALLBACK_TYPE = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_int64,
                                        ctypes.c_int64, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double))
-COMM_ID_BYTES = 128
-PROF_MF_ACCUM, PROF_FR_SAMPLE_GEMM, PROF_FR_MODEL_GEMM, PROF_FR_GRAD_GEMM = range(4)
-# the folded full-rank evaluation's gate (include/viabel_hip.h: VB_FR_FOLD_MIN_D, VB_FR_FOLD_MIN_ROWS_PER_D); read-only mirrors
-FR_FOLD_MIN_D, FR_FOLD_MIN_ROWS_PER_D = 1024, 3
-
-# `const double*` / `double*` parameters are declared void*: ctypes then takes the array's address as a plain integer
-# (`_dptr`), half the cost of building a POINTER(c_double) per argument on calls that last tens of microseconds
-_c_double_p = ctypes.c_void_p
-_c_int64_p = ctypes.POINTER(ctypes.c_int64)
-_ctx_p = ctypes.c_void_p
-
-# the parts the three vb_hmc_run* argument lists are made of
-_HMC_METRIC = [_ctx_p, _c_double_p, ctypes.c_int, _c_double_p]        # ctx, x0, metric_kind, metric
-_HMC_SIZES = [ctypes.c_int64] * 5 + [ctypes.c_int]                    # n_chains, d, n_warmup, n_draws, thin, n_leapfrog
-_HMC_SCALARS = [ctypes.c_double] * 3 + [ctypes.c_uint64] * 2          # step_size, target_accept, jitter, seed, stream_offset
-_HMC_MOMENTS = [_c_double_p] * 3                                      # moment_shift, moment_sum, moment_m2
-_HMC_OUTPUTS = [_c_double_p] * 9 + [_c_int64_p]                       # draws ... final_step, n_divergent
-
-# name -> (restype, argtypes); every symbol declared in include/viabel_hip.h
-SIGNATURES = {
-    'vb_version': (ctypes.c_char_p, []),
-    'vb_device_count': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
-    'vb_create': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(_ctx_p)]),
-    'vb_destroy': (ctypes.c_int, [_ctx_p]),
-    'vb_last_error': (ctypes.c_char_p, [_ctx_p]),
-    'vb_device_info': (ctypes.c_int, [_ctx_p, ctypes.c_char_p, ctypes.c_size_t,
-                                      ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64)]),
-    'vb_sync': (ctypes.c_int, [_ctx_p]),
-    'vb_noise_set_host': (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int64, ctypes.c_int64]),
-    'vb_noise_generate': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.c_double,
-                                         ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64,
-                                         ctypes.c_int64, ctypes.c_int64]),
-    'vb_noise_hint_seed': (ctypes.c_int, [_ctx_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64]),
-    'vb_noise_ahead_stats': (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
-    'vb_chisq_generate': (ctypes.c_int, [_ctx_p, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64,
-                                         ctypes.c_int64]),
-    'vb_chisq_get_host': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64]),
-    'vb_noise_get_host': (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, ctypes.c_int64, ctypes.c_int64]),
-    'vb_set_model': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, _c_double_p, ctypes.c_size_t,
-                                    _c_int64_p, ctypes.c_size_t]),
-    'vb_set_model_source': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_char_p, _c_double_p, ctypes.c_size_t]),
-    'vb_set_model_callback': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
-    'vb_model_logp': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
-    'vb_model_grad': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p]),
-    'vb_elbo_sums_lowrank': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                            _c_double_p, _c_double_p]),
-    'vb_elbo_grad_mvt_chol': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_double,
-                                             _c_double_p, _c_double_p, _c_double_p]),
-    'vb_dis_step_mvt_packed': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _c_double_p, ctypes.c_int64,
-                                              ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double, _c_double_p, _c_double_p,
-                                              _c_double_p, _c_double_p, _c_double_p]),
-    'vb_dis_psis_mvt': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_double]),
-    'vb_dis_weights_get': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int]),
-    'vb_noise_moments': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p]),
-    'vb_elbo_grad_meanfield': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                              ctypes.c_int64, ctypes.c_int, ctypes.c_double, _c_double_p,
-                                              ctypes.c_uint, ctypes.c_int, _c_double_p, _c_double_p]),
-    'vb_elbo_grad_meanfield_async': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                                    ctypes.c_int64, ctypes.c_int, ctypes.c_double,
-                                                    _c_double_p, ctypes.c_uint, ctypes.c_int, ctypes.c_int]),
-    'vb_elbo_grad_meanfield_batch_async': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
-                                                          ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                                          ctypes.c_int, ctypes.c_double, _c_double_p,
-                                                          ctypes.c_uint, ctypes.c_int,
-                                                          ctypes.POINTER(ctypes.c_int)]),
-    'vb_elbo_sums_mvt': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                        _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
-                                        _c_double_p]),
-    'vb_elbo_grad_lowrank': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                            ctypes.c_int64, ctypes.c_int64, _c_double_p, ctypes.c_uint, _c_double_p,
-                                            _c_double_p]),
-    'vb_sym_sqrt': (ctypes.c_int, [_ctx_p, _c_double_p, _c_double_p, ctypes.c_int64, _c_double_p, _c_double_p,
-                                   _c_double_p]),
-    'vb_alpha_grad_fullrank': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                              _c_double_p, ctypes.c_double, _c_double_p, _c_double_p]),
-    'vb_alpha_grad_mvt_chol': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                              ctypes.c_double, _c_double_p, ctypes.c_double, _c_double_p, _c_double_p]),
-    'vb_sym_sqrt_inv': (ctypes.c_int, [_ctx_p, _c_double_p, _c_double_p, ctypes.c_int64, _c_double_p, _c_double_p,
-                                       _c_double_p, _c_double_p]),
-    'vb_lowrank_path_terms': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                             ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p]),
-    'vb_mvt_path_terms': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                         ctypes.c_double, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
-    'vb_alpha_sums_mvt': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                         ctypes.c_double, ctypes.c_double, _c_double_p, _c_double_p, _c_double_p,
-                                         ctypes.c_double, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
-    'vb_elbo_grad_meanfield_philox': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                                     ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
-                                                     _c_double_p, ctypes.c_uint, ctypes.c_int, ctypes.c_uint64,
-                                                     ctypes.c_uint64, _c_double_p, _c_double_p]),
-    'vb_fit': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                              ctypes.c_int, ctypes.c_double, ctypes.c_uint, ctypes.c_int, ctypes.c_int,
-                              ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, _c_double_p,
-                              ctypes.c_int64, _c_double_p, ctypes.c_int64, _c_double_p, ctypes.c_int,
-                              _c_double_p, _c_double_p, ctypes.c_int64, _c_double_p, _c_double_p]),
-    'vb_fit_history_mean': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
-    'vb_chain_open': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_int64]),
-    'vb_chain_close': (ctypes.c_int, [_ctx_p]),
-    'vb_chain_rows': (ctypes.c_int, [_ctx_p, _c_int64_p]),
-    'vb_chain_append': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64]),
-    'vb_chain_fetch': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
-    'vb_chain_mean': (ctypes.c_int, [_ctx_p, ctypes.c_int64, _c_double_p]),
-    'vb_chain_rhat': (ctypes.c_int, [_ctx_p, _c_int64_p, ctypes.c_int, ctypes.c_double, _c_double_p, _c_double_p]),
-    'vb_chain_ess_mcse': (ctypes.c_int, [_ctx_p, ctypes.c_int64, _c_double_p, _c_double_p]),
-    'vb_mvt_route_stats': (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
-    'vb_log_weights_meanfield': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
-                                                ctypes.c_double, _c_double_p, _c_double_p]),
-    'vb_psis_smooth': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_double, _c_double_p,
-                                      _c_double_p]),
-    'vb_psis_smooth_batch': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                            ctypes.c_double, _c_double_p, _c_double_p]),
-    'vb_glm_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
-    'vb_softmax_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
-    'vb_multilevel_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
-    'vb_locscale_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
-    'vb_sparse_glm_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
-    'vb_minibatch_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
-    'vb_minibatch_set_batch': (ctypes.c_int, [_ctx_p, ctypes.c_int64]),
-    'vb_minibatch_get_batch': (ctypes.c_int, [_ctx_p, _c_int64_p]),
-    'vb_minibatch_indices': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_void_p]),
-    'vb_glm_psis_loo': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p,
-                                       ctypes.c_double, _c_double_p, _c_double_p, _c_double_p]),
-    'vb_glm_predict': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p,
-                                      ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
-                                      _c_double_p]),
-    'vb_nn_pointwise': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
-    'vb_nn_predict': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p,
-                                     ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
-                                     _c_double_p]),
-    'vb_glm_value_grad_hessian': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p]),
-    'vb_hmc_run': (ctypes.c_int, [_ctx_p, _c_double_p, _c_double_p] + _HMC_SIZES + _HMC_SCALARS + _HMC_OUTPUTS),
-    'vb_hmc_run_metric': (ctypes.c_int, _HMC_METRIC + _HMC_SIZES + _HMC_SCALARS + _HMC_MOMENTS + _HMC_OUTPUTS),
-    # (max_leapfrog in n_leapfrog's place, trajectory_lr after it; traj_state, traj_hist, leap_hist at the end)
-    'vb_hmc_run_chees': (ctypes.c_int, _HMC_METRIC + _HMC_SIZES + [ctypes.c_double] + _HMC_SCALARS + _HMC_MOMENTS +
-                         _HMC_OUTPUTS + [_c_double_p, _c_double_p, _c_int64_p]),
-    'vb_alpha_grad_meanfield': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                               ctypes.c_int, ctypes.c_double, _c_double_p, ctypes.c_double,
-                                               _c_double_p, _c_double_p]),
-    'vb_dis_clip_mvt': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_double]),
-    'vb_dis_set_temper_prior': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, _c_double_p,
-                                               _c_double_p, ctypes.c_double]),
-    'vb_dis_refresh_meanfield': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                                ctypes.c_int, ctypes.c_double, _c_double_p, _c_double_p,
-                                                ctypes.c_double, ctypes.c_double, ctypes.c_int,
-                                                _c_double_p, _c_double_p, _c_double_p, _c_double_p,
-                                                _c_double_p]),
-    'vb_dis_grad_meanfield': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                             ctypes.c_int, ctypes.c_double, _c_double_p, _c_double_p,
-                                             ctypes.c_double, _c_double_p, _c_double_p]),
-    'vb_dis_refresh_mvt': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                          ctypes.c_double,
-                                          _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
-                                          ctypes.c_double, ctypes.c_double, ctypes.c_int, _c_double_p,
-                                          _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
-    'vb_dis_scalars_get': (ctypes.c_int, [_ctx_p, _c_double_p]),
-    'vb_elbo_grad_mvt_symroot': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _c_double_p,
-                                                ctypes.POINTER(ctypes.c_double), _c_double_p, _c_double_p]),
-    'vb_alpha_grad_mvt_symroot': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_double,
-                                                 ctypes.c_double, _c_double_p, ctypes.POINTER(ctypes.c_double), _c_double_p,
-                                                 _c_double_p]),
-    'vb_elbo_grad_mvt_symroot_path': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_double,
-                                                     _c_double_p, ctypes.POINTER(ctypes.c_double), _c_double_p, _c_double_p]),
-    'vb_dis_refresh_mvt_symroot': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_double,
-                                                  _c_double_p, _c_double_p, ctypes.c_double, ctypes.c_double, ctypes.c_int,
-                                                  _c_double_p]),
-    'vb_dis_refresh_lowrank': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                              ctypes.c_int64, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p,
-                                              _c_double_p, ctypes.c_double, _c_double_p, ctypes.c_double,
-                                              ctypes.c_double, ctypes.c_int, _c_double_p, _c_double_p, _c_double_p,
-                                              _c_double_p, _c_double_p]),
-    'vb_dis_grad_lowrank': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _c_double_p,
-                                           _c_double_p, _c_double_p, _c_double_p, ctypes.c_double, _c_double_p,
-                                           _c_double_p]),
-    'vb_alpha_sums_lowrank': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                             ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _c_double_p, _c_double_p,
-                                             _c_double_p, _c_double_p, ctypes.c_double, _c_double_p, _c_double_p,
-                                             _c_double_p]),
-    'vb_dis_grad_mvt_packed': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _c_double_p,
-                                              _c_double_p, ctypes.c_double, _c_double_p, _c_double_p]),
-    'vb_dis_generation': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
-    'vb_dis_state_get': (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_int64]),
-    'vb_dis_grad_mvt': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _c_double_p,
-                                       _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
-                                       _c_double_p]),
-    'vb_elbo_grad_fullrank': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                             ctypes.c_int64, _c_double_p, ctypes.c_uint, _c_double_p,
-                                             _c_double_p]),
-    'vb_fullrank_set_theta': (ctypes.c_int, [_ctx_p, _c_double_p, ctypes.c_int64]),
-    'vb_elbo_grad_fullrank_enqueue': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                                     ctypes.c_int64, ctypes.c_uint]),
-    'vb_fullrank_get': (ctypes.c_int, [_ctx_p, _c_double_p, _c_double_p, ctypes.c_int64]),
-    'vb_result_get': (ctypes.c_int, [_ctx_p, ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_int64]),
-    'vb_legacy_rng_create': (ctypes.c_int, [ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]),
-    'vb_legacy_rng_destroy': (None, [ctypes.c_void_p]),
-    'vb_legacy_rng_randn': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64, ctypes.c_int]),
-    'vb_legacy_rng_standard_t': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, _c_double_p, ctypes.c_int64]),
-    'vb_legacy_rng_chisquare': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, _c_double_p, ctypes.c_int64]),
-    'vb_legacy_rng_random_sample': (ctypes.c_int, [ctypes.c_void_p, _c_double_p, ctypes.c_int64]),
-    'vb_legacy_rng_get_state': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int),
-                                               ctypes.POINTER(ctypes.c_int), _c_double_p]),
-    'vb_legacy_rng_set_state': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.c_int,
-                                               ctypes.c_double]),
-    'vb_legacy_rng_randn_device': (ctypes.c_int, [_ctx_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                                  ctypes.c_int64, ctypes.c_int64]),
-    'vb_legacy_rng_standard_t_device': (ctypes.c_int, [_ctx_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int64,
-                                                       ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
-    'vb_legacy_rng_chisquare_device': (ctypes.c_int, [_ctx_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int64, _c_double_p]),
-    'vb_legacy_rng_log_proven': (ctypes.c_int, []),
-    'vb_legacy_rng_uid': (ctypes.c_uint64, [ctypes.c_void_p]),
-    'vb_comm_ipc_window': (ctypes.c_int, [_ctx_p, ctypes.c_size_t, ctypes.c_char_p]),
-    'vb_comm_init_ipc': (ctypes.c_int, [_ctx_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]),
-    'vb_comm_check': (ctypes.c_int, [_ctx_p]),
-    'vb_legacy_round_end': (ctypes.c_int, [_ctx_p, ctypes.c_void_p]),
-    'vb_legacy_ahead_stats': (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
-                                            ctypes.POINTER(ctypes.c_uint64)]),
-    'vb_dis_state_park': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
-    'vb_dis_state_unpark': (ctypes.c_int, [_ctx_p, ctypes.c_void_p]),
-    'vb_dis_state_drop': (ctypes.c_int, [ctypes.c_void_p]),
-    'vb_host_alloc': (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]),
-    'vb_host_free': (ctypes.c_int, [ctypes.c_void_p]),
-    'vb_resource_counts': (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
-    'vb_comm_allreduce_time': (ctypes.c_int, [_ctx_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
-    'vb_comm_unique_id': (ctypes.c_int, [ctypes.c_char_p]),
-    'vb_comm_init': (ctypes.c_int, [_ctx_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]),
-    'vb_comm_init_host': (ctypes.c_int, [_ctx_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
-    'vb_comm_destroy': (ctypes.c_int, [_ctx_p]),
-    'vb_comm_info': (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
-    'vb_profile_enable': (ctypes.c_int, [_ctx_p, ctypes.c_int]),
-    'vb_profile_read': (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
-                                       ctypes.POINTER(ctypes.c_double), ctypes.c_int]),
-    'vb_profile_read_kernel': (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
-                                              ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double),
-                                              ctypes.c_int]),
-    'vb_flow_create': (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_int64, _c_double_p, ctypes.c_int64, _c_int64_p,
-                                      ctypes.c_int64, _c_int64_p, ctypes.POINTER(ctypes.c_void_p)]),
-    'vb_flow_destroy': (ctypes.c_int, [_ctx_p, ctypes.c_void_p]),
-    'vb_flow_param_dim': (ctypes.c_int, [_ctx_p, ctypes.c_void_p, _c_int64_p]),
-    'vb_flow_elbo_grad': (ctypes.c_int, [_ctx_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                         ctypes.c_int, ctypes.c_double, _c_double_p, _c_double_p, ctypes.c_uint,
-                                         _c_double_p]),
-    'vb_flow_sample': (ctypes.c_int, [_ctx_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
-                                      ctypes.c_double, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
-    'vb_flow_fit': (ctypes.c_int, [_ctx_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-                                   ctypes.c_int, ctypes.c_double, _c_double_p, ctypes.c_uint, ctypes.c_int,
-                                   ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, _c_double_p,
-                                   ctypes.c_int64, _c_double_p, _c_double_p, ctypes.c_int, _c_double_p, _c_double_p,
-                                   ctypes.c_int64, _c_double_p, _c_double_p]),
-}
-
-_lib = None
-_lib_lock = threading.Lock()
-
-
+# int fn(void* user, double* buf, size_t count, int op)   (include/viabel_hip.h: vb_host_collective_fn)
 HOST_COLLECTIVE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_size_t,
                                       ctypes.c_int)
 
-
-class EngineError(RuntimeError):
-    """The HIP engine is unavailable or a HIP call failed."""
+_lib = None
+_lib_lock = threading.Lock()
 
 
 def build(verbose=False):
@@ -882,7 +694,7 @@ class Engine:
         """The observation indices of batch ``t`` of the bound minibatch regression target as the index kernel computes
         them: int64 ``(batch_size,)``."""
         out = np.empty(int(batch_size), dtype=np.int64)
-        self._check(self._lib.vb_minibatch_indices(self._ctx, int(t), _dptr(out)))
+        self._check(self._lib.vb_minibatch_indices(self._ctx, int(t), out.ctypes.data_as(_c_int64_p)))
         return out
 
     def glm_psis_loo(self, x, n_data, log_ratios=None, log_w=None, reff=1.0):
@@ -1578,7 +1390,7 @@ class Engine:
         self._check(self._lib.vb_comm_init(self._ctx, unique_id, n_ranks, rank))
         self.n_ranks, self.rank = n_ranks, rank
 
-    IPC_HANDLE_BYTES = 64
+    IPC_HANDLE_BYTES = IPC_HANDLE_BYTES
 
     def comm_ipc_window(self, cap_doubles=1 << 21):
         """Allocate this rank's window of the xGMI-native transport; returns its IPC handle (64 bytes)."""
