@@ -25,7 +25,10 @@ class GLMOracle:
 
     def _terms(self, b):
         """(log-likelihood terms with their constants, d / d eta, -d^2 / d eta^2) at one point."""
-        eta = self.X @ np.asarray(b, dtype=self.dtype)
+        return self._terms_eta(self.X @ np.asarray(b, dtype=self.dtype))
+
+    def _terms_eta(self, eta):
+        """The same three at given linear predictors."""
         y = self.y
         if self.kind == 'poisson':
             mu = np.exp(eta)

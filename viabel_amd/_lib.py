@@ -154,6 +154,31 @@ def nn_predict_chunk(n_hidden, n_draws):
     return max(1, NN_PREDICT_DOUBLES // (int(n_hidden) * ((int(n_draws) + 15) // 16 * 16)))
 
 
+# doubles of the term matrix per row chunk of the flat regression target's row entries (csrc/vb_rows.hip:
+# kGlmRowsLogpDoubles of vb_model_logp, kGlmRowsGradDoubles of vb_model_grad) and the fewest rows of a chunk (kGlmRowsMinChunk)
+GLM_ROWS_LOGP_DOUBLES = 64 << 20
+GLM_ROWS_GRAD_DOUBLES = 32 << 20
+GLM_ROWS_MIN_CHUNK = 128
+
+
+def glm_rows_chunk(n_data, grad):
+    """Rows per chunk of ``vb_model_grad`` (``grad``) or ``vb_model_logp`` on a flat regression target of ``n_data``
+    observations; a call of fewer rows is one chunk.  Must equal the chunk arithmetic of ``model_grad_rows`` and
+    ``logistic_rows`` in ``csrc/vb_rows.hip``."""
+    doubles = GLM_ROWS_GRAD_DOUBLES if grad else GLM_ROWS_LOGP_DOUBLES
+    return max(GLM_ROWS_MIN_CHUNK, doubles // ((int(n_data) + 15) // 16 * 16))
+
+
+def glm_grad_splits(rows, d, n_data, n_cu):
+    """Slabs into which the gradient product ``[rows x d x n_data]`` of one row chunk splits its observations on a device
+    of ``n_cu`` compute units (1: one launch that writes the gradient itself).  Must equal ``glm_grad_splits`` in
+    ``csrc/vb_rows.hip``."""
+    tiles = ((int(rows) + 63) // 64) * ((int(d) + 63) // 64)
+    if tiles >= n_cu:
+        return 1
+    return max(1, min(2 * int(n_cu) // tiles, int(n_data) // 128, 64))
+
+
 CV_MODES = {None: CV_NONE, 'full': CV_FULL, 'mean_only': CV_MEAN_ONLY, 'loo_diag_approx': CV_LOO_DIAG,
             'loo_direct_approx': CV_LOO_DIRECT}
 # capacity of the batched smoothing kernel (csrc/vb_psis_batch.hip: kPbMaxN, kPbTailCap)

@@ -262,14 +262,21 @@ static int gauss_full_rows(vb_ctx* ctx, const double* x_dev, int64_t ld, int64_t
   return VB_OK;
 }
 
+// doubles of the rows x round_up(n_data, 16) term matrix per row chunk of the flat regression target's row entries: the
+// log-density entry holds the terms (512 MB), the gradient entry the terms and the residuals (256 MB each); a chunk is
+// never fewer than kGlmRowsMinChunk rows (mirrored by _lib.glm_rows_chunk)
+constexpr int64_t kGlmRowsLogpDoubles = (int64_t)64 << 20;
+constexpr int64_t kGlmRowsGradDoubles = (int64_t)32 << 20;
+constexpr int64_t kGlmRowsMinChunk = 128;
+
 // logistic: f(b) = sum_i [y_i eta_i - log(1 + exp(eta_i))] - |b|^2 / (2 sd^2) + c0, eta = X b; row chunks bound
 // the n x n_data term matrix to 512 MB
 static int logistic_rows(vb_ctx* ctx, const double* x_dev, int64_t ld, int64_t n, int64_t d, double* out_dev) {
   const ModelDev& m = ctx->model;
   hipStream_t st = ctx->stream;
   const int64_t ldt = m.ldq;
-  int64_t chunk = ((int64_t)64 << 20) / ldt;
-  chunk = chunk < 128 ? 128 : (chunk > n ? n : chunk);
+  int64_t chunk = kGlmRowsLogpDoubles / ldt;
+  chunk = chunk < kGlmRowsMinChunk ? kGlmRowsMinChunk : (chunk > n ? n : chunk);
   VB_TRY(ensure(ctx, ctx->rows_work, (size_t)chunk * ldt * sizeof(double)));
   double* T = (double*)ctx->rows_work.ptr;
   for (int64_t r0 = 0; r0 < n; r0 += chunk) {
@@ -287,6 +294,19 @@ static int logistic_rows(vb_ctx* ctx, const double* x_dev, int64_t ld, int64_t n
   return VB_OK;
 }
 
+// few output tiles and a long contraction: split the observations so that every CU gets a workgroup or two, at least 128
+// observations per split and at most 64 splits (mirrored by _lib.glm_grad_splits)
+inline int glm_grad_splits(int64_t rows, int d, int64_t n_data, int n_cu) {
+  const int64_t tiles = gemm_max_blocks(rows, d);
+  if (tiles >= n_cu) return 1;
+  int splits = (int)(2 * n_cu / tiles);
+  const int max_splits = (int)(n_data / 128);
+  if (splits > max_splits) splits = max_splits;
+  if (splits > 64) splits = 64;
+  if (splits < 1) splits = 1;
+  return splits;
+}
+
 int glm_grad_enqueue(vb_ctx* ctx, hipStream_t st, const ModelDev& m, const double* R, int64_t ldr, const double* Z,
                      double* G, int64_t ldz, int64_t n, int d) {
   const int n_cu = ctx->prop.multiProcessorCount;
@@ -300,16 +320,7 @@ int glm_grad_enqueue(vb_ctx* ctx, hipStream_t st, const ModelDev& m, const doubl
   gg.K = (int)m.n_data;
   gg.tri_mode = 0;
   const double ivp = 1.0 / (m.tau * m.tau);
-  // few output tiles and a long contraction: split the observations so that every CU gets a workgroup or two
-  const int64_t tiles = gemm_max_blocks(n, d);
-  int splits = 1;
-  if (tiles < n_cu) {
-    splits = (int)(2 * n_cu / tiles);
-    const int max_splits = (int)(m.n_data / 128);
-    if (splits > max_splits) splits = max_splits;
-    if (splits > 64) splits = 64;
-    if (splits < 1) splits = 1;
-  }
+  const int splits = glm_grad_splits(n, d, m.n_data, n_cu);
   if (splits == 1) {
     gemm_f64_launch<true>(st, gg, 1, n_cu, EpiGlmGradDirect{G, ldz, Z, ivp});
     VB_HIP(ctx, hipGetLastError());
@@ -445,8 +456,8 @@ int model_grad_rows(vb_ctx* ctx, const double* x_dev, int64_t ld, int64_t n, int
   }
   if (m.id == VB_MODEL_LOGISTIC) {        // eta = x X' -> terms and residuals -> f, G = R X - x / sd^2; row chunks
     const int64_t ldt = m.ldq;
-    int64_t chunk = ((int64_t)32 << 20) / ldt;
-    chunk = chunk < 128 ? 128 : (chunk > n ? n : chunk);
+    int64_t chunk = kGlmRowsGradDoubles / ldt;
+    chunk = chunk < kGlmRowsMinChunk ? kGlmRowsMinChunk : (chunk > n ? n : chunk);
     VB_TRY(ensure(ctx, ctx->rows_work, (size_t)2 * chunk * ldt * sizeof(double)));
     double* T = (double*)ctx->rows_work.ptr;
     double* R = T + chunk * ldt;
