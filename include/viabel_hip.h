@@ -734,6 +734,16 @@ int vb_fullrank_set_theta(vb_ctx* ctx, const double* theta, int64_t d);
 int vb_elbo_grad_fullrank_enqueue(vb_ctx* ctx, int slot, int64_t n, int64_t d, int64_t n_total,
                                   unsigned flags);
 int vb_fullrank_get(vb_ctx* ctx, double* value, double* grad, int64_t p);
+/* The folded evaluation (VB_FR_FOLD_MIN_D below) forms M = L' P on the device.  vb_fullrank_fold_get_m copies the M of the
+ * last folded evaluation to the host (d x d, row-major; blocks until it is there); VB_ERR_STATE if the context's last
+ * full-rank evaluation did not take the fold or had another dimension.
+ * vb_fold_m_team_plan (host only, no context): the slab program of the workgroups that form it, two four-wave teams on a
+ * pair of 64-row blocks (csrc/vb_gemm_f64.h, gemm_f64_team_plan).  out8 = [H, slab iterations of every workgroup | n_h,
+ * n_l: 16-deep slabs of the heavy and of the light tile | slabs team 0 and team 1 multiply | the sequence index at which
+ * team 0 goes from the light tile to the heavy one | barriers a wave of team 0 and of team 1 executes].  VB_ERR_INVALID
+ * unless d is a positive multiple of 16 and 0 <= pair < ceil(ceil(d / 64) / 2).                                     */
+int vb_fullrank_fold_get_m(vb_ctx* ctx, double* M_host, int64_t d);
+int vb_fold_m_team_plan(int d, int pair, int* out8);
 
 /* ---- ExclusiveKL for the multivariate t, throughput mode (approximations.py:342-354, objectives.py:160-164) --------
  * Samples through the CHOLESKY factor, x_n = mu + (L z_n) / s_n with s_n = sqrt(chi_n / df) from the device chi-square

@@ -1210,6 +1210,12 @@ class Engine:
         self._check(self._lib.vb_fullrank_get(self._ctx, ctypes.byref(value), _dptr(grad), p))
         return value.value, grad
 
+    def fullrank_fold_m(self, d):
+        """``M = L' P`` (d x d) of the last folded full-rank evaluation (``vb_fullrank_fold_get_m``)."""
+        m = np.empty((d, d), dtype=np.float64)
+        self._check(self._lib.vb_fullrank_fold_get_m(self._ctx, _dptr(m), d))
+        return m
+
     # ------------------------------------------------------------------ small dense linear algebra
     def sym_sqrt(self, a, e=None):
         """Symmetric square root of an SPD matrix on the device (``vb_sym_sqrt``); with ``e`` also the solution

@@ -401,6 +401,8 @@ struct vb_ctx {
   vb::DeviceBuffer fr_theta;            // full-rank: resident flat parameter
   vb::DeviceBuffer fr_out;              // full-rank: [value | grad] on the device
   int64_t fr_p = 0;                     // length of the resident full-rank parameter
+  const double* fr_fold_m = nullptr;    // M = L' P of the last full-rank evaluation if it took the fold (in fr_work, row stride
+  int64_t fr_fold_d = 0, fr_fold_ld = 0;   // fr_fold_ld), and its dimension; nullptr / 0 after any other evaluation
   // numpy's legacy normal stream on the device (vb_legacy_dev.hip): scratch; where the jump polynomials were uploaded
   vb::DeviceBuffer alpha_g;             // AlphaDivergence, correlated-Gaussian target: G of the samples (see FrWeighted::g_ready)
   vb::DeviceBuffer legacy_work;

@@ -400,12 +400,15 @@ __global__ void __launch_bounds__(256) fr_colsum_kernel(const double* __restrict
 // b = P c -- a D x D x D product that does not depend on the number of samples instead of the N x D x D sampling product
 // (and G itself is never formed: fr_route).
 // The Gram product of the noise leaves the lower tiles of E' E in `gsplits` slabs (pieces of the sample axis) and one row
-// of column sums of E per slab.  fr_fold_msum_kernel, ONE launch behind it, runs four kinds of workgroups that do not
-// depend on each other, in this order:
-//   [0, nb_m): the M = L' P product on paired row blocks (gemm_f64_dma_pair_tiles: 64 x 32 tiles, three LDS stages, row
-//     blocks b and T - 1 - b of a column tile, each over its whole k range).  They follow the parameter alone, are the
-//     longest pieces of the launch and bound by their operands' latency with one wave per SIMD, so they are dispatched first
-//     (D = 1024: 256 of them, one per CU) and the memory-bound blocks behind them take the wave slots they leave free;
+// of column sums of E per slab.  fr_fold_msum_team_kernel or fr_fold_msum_kernel, ONE launch behind it, runs four kinds of
+// workgroups that do not depend on each other, in this order:
+//   [0, nb_m): the M = L' P product on paired row blocks: 64 x 32 tiles, row blocks b and T - 1 - b of a column tile, each
+//     over its whole k range.  They follow the parameter alone and are the longest pieces of the launch, so they are
+//     dispatched first and the memory-bound blocks behind them take the wave slots they leave free.  While there are fewer
+//     than two of them per CU (D = 1024: 256, one per CU) a workgroup is two four-wave teams with two LDS stages each
+//     (gemm_f64_dma_team_pair_tiles: two waves per SIMD, half the chain of slab iterations); from two per CU on it is one
+//     four-wave team with three stages that runs the two tiles one after the other (gemm_f64_dma_pair_tiles; D = 2048: 1 024
+//     workgroups, four per CU).  The rule and its two measurements: gemm_f64_team_pair_plan;
 //   the next nb_b, 8 columns each: b[j] = sum_k P[k][j] c[k] (P is symmetric: its column j).  Thread (pair p = t & 3, k
 //     group t >> 2) sums its 64th of the k range, sixteen rows per pass, and the groups are combined through LDS in fixed
 //     order;
@@ -415,50 +418,55 @@ __global__ void __launch_bounds__(256) fr_colsum_kernel(const double* __restrict
 //     symmetric, and both stores are contiguous runs.  Of a diagonal tile only the entries j <= i are read (the product's
 //     waves that lie above the diagonal store zeros there).  Only the lower tiles are dispatched; the tile comes from the
 //     block index by arithmetic that is uniform over the block, and no thread divides.
-// The launch's LDS is the M tiles' three stages, dynamic (36.9 KB); the other kinds carve their arrays out of the same
-// allocation, so that four workgroups fit a CU -- an M tile and three of the others.  No launch bound beyond the block size:
-// bounded to four waves per SIMD the sum code spills; it stays below 128 registers by itself.
+// The launch's LDS is the M tiles' stages, dynamic; the other kinds carve their arrays out of the same allocation.
+//   One team: three stages, 36.9 KB, four workgroups per CU.  256 threads per block, no launch bound beyond that: bounded to
+//     four waves per SIMD the sum code spills; it stays below 128 registers by itself.
+//   Two teams: 512 threads per block, and the other kinds remain the 256-thread blocks they are (fr_fold_sum_blocks).  TWO
+//     stages per team, 49.2 KB, three workgroups per CU -- an M tile and two of the others: the launch takes 30.6 us at
+//     D = 1024; with three stages per team (73.7 KB, an M tile and one other) 31.8; with one team 38.7.
+//     110 registers, no scratch.
 // colsum(G), which needs M and s and b, is formed by fr_fold_csg_blocks in a later launch; nobody reads it before the reduction.
 // Everything is added in a fixed order: the same inputs give the same bits.
-struct FoldMsumNoDep : GemmNoDep {};      // (a Dep type of this kernel's own: see gemm_f64_dma_pair_tiles)
 
-__global__ void __launch_bounds__(256) fr_fold_msum_kernel(const GemmArgs gm, const EpiSplitSlab em, int nb_m,
-                                                           const double* __restrict__ Spart, int gsplits, int64_t slab, int d,
-                                                           int64_t ldl, const double* __restrict__ colpart, int64_t ldz,
-                                                           const double* __restrict__ P, int64_t ldp,
-                                                           const double* __restrict__ mu, const double* __restrict__ mean,
-                                                           int nb_b, int nb_s, double* __restrict__ S,
-                                                           double* __restrict__ svec, double* __restrict__ b) {
-  extern __shared__ double fold_lds[];      // (the dynamic allocation the tile body calls gemm_lds)
-  if ((int)blockIdx.x < nb_m) {
-    gemm_f64_dma_pair_tiles<2, 4, 3, EpiSplitSlab, FoldMsumNoDep>(gm, em, FoldMsumNoDep{}, (int)blockIdx.x, nb_m);
-    return;
-  }
-  const int blk = (int)blockIdx.x - nb_m;
+// The blocks of b, s and S (`blk` counts from the first of them) in a launch of THREADS threads per block, 256 or 512.  They
+// are 256-thread blocks: in the 512-thread launch threads 256 .. 511 read, add and store nothing -- every sum keeps its order
+// of additions.  Those threads stay to the block's one barrier instead of ending in front of it, so that the barrier's count is
+// the block's size.
+template <int THREADS>
+__device__ __forceinline__ void fr_fold_sum_blocks(const int blk, double* fold_lds, const double* __restrict__ Spart, int gsplits,
+                                                   int64_t slab, int d, int64_t ldl, const double* __restrict__ colpart,
+                                                   int64_t ldz, const double* __restrict__ P, int64_t ldp,
+                                                   const double* __restrict__ mu, const double* __restrict__ mean, int nb_b,
+                                                   int nb_s, double* __restrict__ S, double* __restrict__ svec,
+                                                   double* __restrict__ b) {
+  static_assert(THREADS == 256 || THREADS == 512, "256 workers, with or without a second idle half");
+  const bool worker = THREADS == 256 || threadIdx.x < 256;
   if (blk < nb_b) {
     fr_d2(*part)[4] = reinterpret_cast<fr_d2(*)[4]>(fold_lds);      // [64][4]
     const int p = threadIdx.x & 3, kg = threadIdx.x >> 2;
     const int col = blk * 8 + 2 * p;
-    const int colc = col < d ? col : 0;                        // (rows of P have an even stride >= d)
-    const int kper = (d + 63) / 64;
-    const int k0 = kg * kper, k1 = k0 + kper < d ? k0 + kper : d;
-    fr_d2 bacc = (fr_d2){0.0, 0.0};
-    for (int kb = k0; kb < k1; kb += 16) {      // sixteen rows in flight
-      fr_d2 v[16];
-      double c[16];
+    if (worker) {
+      const int colc = col < d ? col : 0;                        // (rows of P have an even stride >= d)
+      const int kper = (d + 63) / 64;
+      const int k0 = kg * kper, k1 = k0 + kper < d ? k0 + kper : d;
+      fr_d2 bacc = (fr_d2){0.0, 0.0};
+      for (int kb = k0; kb < k1; kb += 16) {      // sixteen rows in flight
+        fr_d2 v[16];
+        double c[16];
 #pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const int k = kb + u < k1 ? kb + u : k1 - 1;
-        v[u] = *reinterpret_cast<const fr_d2*>(P + (int64_t)k * ldp + colc);
-        c[u] = mu[k] - mean[k];
+        for (int u = 0; u < 16; ++u) {
+          const int k = kb + u < k1 ? kb + u : k1 - 1;
+          v[u] = *reinterpret_cast<const fr_d2*>(P + (int64_t)k * ldp + colc);
+          c[u] = mu[k] - mean[k];
+        }
+#pragma unroll
+        for (int u = 0; u < 16; ++u)
+          if (kb + u < k1) bacc += v[u] * c[u];
       }
-#pragma unroll
-      for (int u = 0; u < 16; ++u)
-        if (kb + u < k1) bacc += v[u] * c[u];
+      part[kg][p] = bacc;
     }
-    part[kg][p] = bacc;
     __syncthreads();
-    if (kg == 0) {
+    if (worker && kg == 0) {
       fr_d2 btot = part[0][p];
 #pragma unroll 16
       for (int q = 1; q < 64; ++q) btot += part[q][p];
@@ -467,9 +475,9 @@ __global__ void __launch_bounds__(256) fr_fold_msum_kernel(const GemmArgs gm, co
     }
     return;
   }
-  if (blk < nb_b + nb_s) {
+  if (blk < nb_b + nb_s) {      // (no barrier in these blocks)
     const int k = (blk - nb_b) * 256 + (int)threadIdx.x;
-    if (k >= ldz) return;
+    if (!worker || k >= ldz) return;
     double s = 0.0;
     if (k < d) {
       s = colpart[k];
@@ -481,32 +489,35 @@ __global__ void __launch_bounds__(256) fr_fold_msum_kernel(const GemmArgs gm, co
   int bi = 0, bj = blk - nb_b - nb_s;                    // lower tiles only, row by row: tile row bi has bi + 1 of them
   while (bj > bi) bj -= ++bi;                            // (uniform over the block: scalar arithmetic)
   double(*tile)[33] = reinterpret_cast<double(*)[33]>(fold_lds);      // [32][33]
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int tx = threadIdx.x & 31, ty = (threadIdx.x >> 5) & 7;
   const int i0 = bi * 32, j0 = bj * 32;
   double v[4];
-  int64_t idx[4];
+  if (worker) {
+    int64_t idx[4];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int i = i0 + ty + 8 * q, j = j0 + tx;
-    idx[q] = (i < d && j <= i) ? (int64_t)i * ldl + j : 0;      // (not read by the sum: clamped, not predicated)
-    v[q] = 0.0;
+    for (int q = 0; q < 4; ++q) {
+      const int i = i0 + ty + 8 * q, j = j0 + tx;
+      idx[q] = (i < d && j <= i) ? (int64_t)i * ldl + j : 0;      // (not read by the sum: clamped, not predicated)
+      v[q] = 0.0;
+    }
+    for (int zb = 0; zb < gsplits; zb += 8) {      // eight slabs in flight, added in slab order
+      double w[8][4];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) w[u][q] = Spart[(zb + u < gsplits ? zb + u : gsplits - 1) * slab + idx[q]];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (zb + u < gsplits) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) v[q] = (zb + u == 0) ? w[u][q] : v[q] + w[u][q];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) tile[ty + 8 * q][tx] = v[q];
   }
-  for (int zb = 0; zb < gsplits; zb += 8) {      // eight slabs in flight, added in slab order
-    double w[8][4];
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) w[u][q] = Spart[(zb + u < gsplits ? zb + u : gsplits - 1) * slab + idx[q]];
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (zb + u < gsplits) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = (zb + u == 0) ? w[u][q] : v[q] + w[u][q];
-      }
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) tile[ty + 8 * q][tx] = v[q];
   __syncthreads();
+  if (!worker) return;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int r = ty + 8 * q;
@@ -521,6 +532,40 @@ __global__ void __launch_bounds__(256) fr_fold_msum_kernel(const GemmArgs gm, co
     }
   }
 }
+
+struct FoldMsumNoDep : GemmNoDep {};      // (a Dep type of this kernel's own: see gemm_f64_dma_pair_tiles)
+struct FoldMsumTeamNoDep : GemmNoDep {};
+constexpr int kFoldTeamStages = 2;
+
+#define VB_FOLD_MSUM_PARAMS                                                                                                  \
+  const GemmArgs gm, const EpiSplitSlab em, int nb_m, const double *__restrict__ Spart, int gsplits, int64_t slab, int d,     \
+      int64_t ldl, const double *__restrict__ colpart, int64_t ldz, const double *__restrict__ P, int64_t ldp,                \
+      const double *__restrict__ mu, const double *__restrict__ mean, int nb_b, int nb_s, double *__restrict__ S,             \
+      double *__restrict__ svec, double *__restrict__ b
+#define VB_FOLD_MSUM_SUM_ARGS Spart, gsplits, slab, d, ldl, colpart, ldz, P, ldp, mu, mean, nb_b, nb_s, S, svec, b
+
+// one four-wave team per M workgroup: two or more of them per CU (fr_grad_folded)
+__global__ void __launch_bounds__(256) fr_fold_msum_kernel(VB_FOLD_MSUM_PARAMS) {
+  extern __shared__ double fold_lds[];      // (the dynamic allocation the tile body calls gemm_lds)
+  if ((int)blockIdx.x < nb_m) {
+    gemm_f64_dma_pair_tiles<2, 4, 3, EpiSplitSlab, FoldMsumNoDep>(gm, em, FoldMsumNoDep{}, (int)blockIdx.x, nb_m);
+    return;
+  }
+  fr_fold_sum_blocks<256>((int)blockIdx.x - nb_m, fold_lds, VB_FOLD_MSUM_SUM_ARGS);
+}
+
+// two four-wave teams per M workgroup: about one of them per CU
+__global__ void __launch_bounds__(512) fr_fold_msum_team_kernel(VB_FOLD_MSUM_PARAMS) {
+  extern __shared__ double fold_lds[];
+  if ((int)blockIdx.x < nb_m) {
+    gemm_f64_dma_team_pair_tiles<2, 4, kFoldTeamStages, EpiSplitSlab, FoldMsumTeamNoDep>(gm, em, FoldMsumTeamNoDep{},
+                                                                                         (int)blockIdx.x);
+    return;
+  }
+  fr_fold_sum_blocks<512>((int)blockIdx.x - nb_m, fold_lds, VB_FOLD_MSUM_SUM_ARGS);
+}
+#undef VB_FOLD_MSUM_PARAMS
+#undef VB_FOLD_MSUM_SUM_ARGS
 
 // colsum(G)[j] = -sum_k s[k] M[k][j] - n b[j], eight columns per block `blk`: the arithmetic the b blocks above use, with
 // s[k] added up from the rows of `colpart` in row order by the thread that needs it and b[j] read from the vector an
@@ -575,7 +620,7 @@ __global__ void __launch_bounds__(256) fr_fold_csg_kernel(const double* __restri
 // x / gx -- the linear order of the launcher's (gx, 1, splits) grid -- and the blocks behind take the free slots.  Neither
 // kind reads what the other writes.  `part` is carved out of the tiles' dynamic LDS, and a thread keeps eight rows in flight:
 // with sixteen the kernel needs scratch under the tile's bound of four workgroups per CU.
-struct FoldCsgNoDep : GemmNoDep {};      // (a Dep type of this kernel's own: see gemm_f64_dma_pair_tiles)
+struct FoldCsgNoDep : GemmNoDep {};      // (a Dep type of this kernel's own: see gemm_f64_dma_team_pair_tiles)
 
 __global__ void __launch_bounds__(256, 4) fr_fold_ctile_csg_kernel(const GemmArgs g, const EpiFoldSlabF epi, int gx, int nb_tiles,
                                                                    const double* __restrict__ colpart, int gsplits, int64_t ldz,
@@ -1841,25 +1886,34 @@ static int fr_grad_folded(vb_ctx* ctx, const FrRoute& r, const FrBufs& b, const 
   gemm_f64_launch<false>(st, gs, r.splits, r.n_cu, EpiSplitSlabCs{b.Cpart, r.ldl, r.slab, b.colpart, r.ldz}, r.cfg3);
   VB_HIP(ctx, hipGetLastError());
   // M[r][j] = sum_{k >= r} Lt[r][k] P[k][j]: 64 x 32 tiles, row blocks b and T - 1 - b by one workgroup -- equal work per
-  // workgroup with the k range unsplit, so the launch writes M itself (D = 1024: 256 workgroups, one per CU).  Three LDS
-  // stages: a workgroup has little but its own prefetch to cover the operands' latency (two stages: 4 us more per
-  // evaluation when it was a launch of its own)
+  // workgroup with the k range unsplit, so the launch writes M itself.  Two four-wave teams per workgroup while there are
+  // fewer than two workgroups per CU (D = 1024: 256), one team from there on (gemm_f64_team_pair_plan)
   GemmArgs gm = gemm_product(b.Lt, r.ldl, m.p1, m.ldp, D, D, D, 4);
-  const unsigned nb_m = gemm_f64_pair_plan(&gm);
+  const unsigned nb_team = gemm_f64_team_pair_plan(&gm, r.n_cu);
+  const unsigned nb_m = nb_team ? nb_team : gemm_f64_pair_plan(&gm);
   if (nb_m == 0) return fail(ctx, VB_ERR_STATE, "folded evaluation: D = %d does not go to the LDS-DMA product", D);
   const int nb_cs = (D + 7) / 8, nb_s = (int)((r.ldz + 255) / 256), tiles = (D + 31) / 32;
-  constexpr size_t msum_lds = gemm_f64_dma_pair_lds<2, 4, 3>();
-  static_assert(msum_lds >= 64 * 4 * sizeof(fr_d2) && msum_lds >= 32 * 33 * sizeof(double), "the sum blocks' LDS is the tiles'");
+  constexpr size_t pair_lds = gemm_f64_dma_pair_lds<2, 4, 3>(), team_lds = gemm_f64_dma_team_pair_lds<2, 4, kFoldTeamStages>();
+  static_assert(pair_lds >= 64 * 4 * sizeof(fr_d2) && pair_lds >= 32 * 33 * sizeof(double) && team_lds >= pair_lds,
+                "the sum blocks' LDS is the tiles'");
   static bool configured = false;
   if (!configured) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fr_fold_msum_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)msum_lds);
+                              (int)pair_lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fr_fold_msum_team_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)team_lds);
     configured = true;
   }
-  hipLaunchKernelGGL(fr_fold_msum_kernel, dim3(nb_m + (unsigned)(nb_cs + nb_s + tiles * (tiles + 1) / 2)), dim3(256), msum_lds, st,
-                     gm, EpiSplitSlab{b.Mf, r.ldz, r.slab}, (int)nb_m, (const double*)b.Cpart, r.splits, r.slab, D, r.ldl,
-                     (const double*)b.colpart, r.ldz, m.p1, (int64_t)m.ldp, (const double*)b.mu, m.p0, nb_cs, nb_s, b.Sg, b.svec,
-                     b.bvec);
+  const dim3 msum_grid(nb_m + (unsigned)(nb_cs + nb_s + tiles * (tiles + 1) / 2));
+  const EpiSplitSlab em{b.Mf, r.ldz, r.slab};
+  if (nb_team)
+    hipLaunchKernelGGL(fr_fold_msum_team_kernel, msum_grid, dim3(512), team_lds, st, gm, em, (int)nb_m, (const double*)b.Cpart,
+                       r.splits, r.slab, D, r.ldl, (const double*)b.colpart, r.ldz, m.p1, (int64_t)m.ldp, (const double*)b.mu,
+                       m.p0, nb_cs, nb_s, b.Sg, b.svec, b.bvec);
+  else
+    hipLaunchKernelGGL(fr_fold_msum_kernel, msum_grid, dim3(256), pair_lds, st, gm, em, (int)nb_m, (const double*)b.Cpart,
+                       r.splits, r.slab, D, r.ldl, (const double*)b.colpart, r.ldz, m.p1, (int64_t)m.ldp, (const double*)b.mu,
+                       m.p0, nb_cs, nb_s, b.Sg, b.svec, b.bvec);
   VB_HIP(ctx, hipGetLastError());
   // C[i][j] = sum_k M[k][i] S[k][j]: the gradient product's form, lower tiles, split over k
   GemmArgs gc = gemm_product(M, r.ldz, b.Sg, r.ldl, D, D, D, 2);
@@ -2066,6 +2120,8 @@ int fr_pipeline_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, 
   FrBufs b;
   VB_TRY(fr_stream_plan(ctx, r, &set));
   VB_TRY(fr_carve(ctx, r, ns, set, &b));
+  ctx->fr_fold_m = r.fold ? b.Mf : nullptr;      // (vb_fullrank_fold_get_m)
+  ctx->fr_fold_d = r.fold ? d : 0, ctx->fr_fold_ld = r.fold ? r.ldz : 0;
 
   if (mvt) VB_TRY(fr_prepare_mvt(ctx, r, b, mu_dev, root_dev));
   else VB_TRY(fr_prepare_dense(ctx, r, &b, theta_dev));
@@ -2110,6 +2166,7 @@ int fr_sample_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, co
   hipStream_t st = ctx->stream;
   const double* E = (const double*)ns.buf.ptr;
   const int n_cu = ctx->prop.multiProcessorCount;
+  ctx->fr_fold_m = nullptr, ctx->fr_fold_d = ctx->fr_fold_ld = 0;      // (fr_work is rewritten)
   if (theta_dev) {
     VB_TRY(ensure(ctx, ctx->fr_work, (size_t)(ldz + d * ldl) * sizeof(double)));
     double* mu = (double*)ctx->fr_work.ptr;
@@ -2132,3 +2189,28 @@ int fr_elbo_grad_enqueue(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d,
 }
 
 }  // namespace vb
+
+// ---- C ABI: a look at the folded evaluation's M = L' P and at the slab program of its tiles (include/viabel_hip.h) ---------
+int vb_fullrank_fold_get_m(vb_ctx* ctx, double* M_host, int64_t d) {
+  using namespace vb;
+  if (!ctx || !M_host) return fail(ctx, VB_ERR_INVALID, "NULL argument");
+  if (!ctx->fr_fold_m || ctx->fr_fold_d != d)
+    return fail(ctx, VB_ERR_STATE, "the last full-rank evaluation was no folded one of dimension %lld", (long long)d);
+  VB_HIP(ctx, hipSetDevice(ctx->device));
+  VB_TRY(main_stream_write(ctx));
+  VB_HIP(ctx, hipMemcpy2DAsync(M_host, (size_t)d * sizeof(double), ctx->fr_fold_m, (size_t)ctx->fr_fold_ld * sizeof(double),
+                               (size_t)d * sizeof(double), (size_t)d, hipMemcpyDeviceToHost, ctx->stream));
+  VB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return VB_OK;
+}
+
+int vb_fold_m_team_plan(int d, int pair, int* out8) {
+  using namespace vb;
+  if (!out8 || d <= 0 || d % kGemmBK != 0) return VB_ERR_INVALID;
+  const int tiles_m = gemm_tiles(d, 64);
+  if (pair < 0 || pair >= (tiles_m + 1) / 2) return VB_ERR_INVALID;
+  const GemmTeamPlan p = gemm_f64_team_plan(d, d, tiles_m, pair);
+  const int out[8] = {p.H, p.n_h, p.n_l, p.cnt0, p.cnt1, p.sw, gemm_f64_team_barriers(p, 0), gemm_f64_team_barriers(p, 1)};
+  for (int i = 0; i < 8; ++i) out8[i] = out[i];
+  return VB_OK;
+}

@@ -53,9 +53,9 @@ struct GemmArgs {
                     // 3: B[k][j] == 0 for k < j (the mirror image of 1; LDS-DMA kernel, otherwise computed densely)
                     // 4: A[m][k] == 0 for k < m, A given as A[m][k] (an upper-triangular left factor: M = L' P of the
                     //    folded full-rank evaluation): the k range of row block bm starts at its first row rounded down
-                    //    to a slab, row block 0 -- the longest range -- is dispatched first.  gemm_f64_dma_pair_tiles
+                    //    to a slab, row block 0 -- the longest range -- is dispatched first.  gemm_f64_dma_team_pair_tiles
                     //    gives one workgroup row blocks b and tiles_m - 1 - b of a column tile, whose k ranges add up to
-                    //    the same length for every b (gemm_f64_pair_plan).  (LDS-DMA kernel, otherwise computed
+                    //    the same length for every b (gemm_f64_team_plan).  (LDS-DMA kernel, otherwise computed
                     //    densely)
   int k_split = 0;  // K range per blockIdx.z (multiple of kGemmBK); splits = gridDim.z
   // batch mode (batch != 0): blockIdx.z selects one of gridDim.z independent products of the same shape -- operand
@@ -382,6 +382,43 @@ __global__ void __launch_bounds__(256, AF * NB > 32 ? 1 : 2) gemm_f64_kernel(con
   }
 }
 
+// An unsplit tri_mode 4 product on paired row blocks, two four-wave teams per workgroup (gemm_f64_dma_team_pair_tiles,
+// vb_gemm_f64_dma.h): the slab program of workgroup (pair, column tile), one function for the host and the device.  Row
+// block `pair` is the heavy tile (n_h slabs of kGemmBK from its first row to K), row block tiles_m - 1 - pair the light
+// one (n_l slabs; 0 for the middle block of an odd tiles_m, which has no partner), and every workgroup runs
+// H = ceil((n_h + n_l) / 2) slab iterations:
+//   team 0, sequence index s in [0, H):     s < sw: light slab s;  s >= sw: heavy slab s - sw        (sw = n_l, cnt0 = H)
+//   team 1, sequence index s in [0, cnt1):  heavy slab h0 + s, h0 = H - n_l                           (cnt1 = H or H - 1)
+// n_h + n_l = (2 K - 64 (tiles_m - 1)) / 16 for every pair, so H does not depend on the pair; n_h - n_l >= 4 for a true
+// pair, so team 0 always has heavy slabs left after the light tile (sw < H).
+struct GemmTeamPlan {
+  int H, n_h, n_l, cnt0, cnt1, sw, h0;
+};
+__host__ __device__ inline GemmTeamPlan gemm_f64_team_plan(int M, int K, int tiles_m, int pair) {
+  (void)M;
+  const int mirror = tiles_m - 1 - pair;
+  auto slabs = [K](int bm) {      // (tri_mode 4: the k range of row block bm starts at its first row)
+    const int k0 = bm * 64 < K ? bm * 64 : K;
+    return (K - k0) / kGemmBK;
+  };
+  GemmTeamPlan p;
+  p.n_h = slabs(pair);
+  p.n_l = mirror > pair ? slabs(mirror) : 0;
+  p.H = (p.n_h + p.n_l + 1) / 2;
+  p.sw = p.n_l;
+  p.h0 = p.H - p.n_l;
+  p.cnt0 = p.H;
+  p.cnt1 = p.n_h - p.h0;
+  return p;
+}
+// s_barrier instructions a wave of `team` executes in gemm_f64_dma_team_pair_tiles: one behind the first slab, one per
+// iteration of the team's loop, one in front of the hand-off and one behind it.  Both teams loop H times whatever they
+// multiply -- the invariant of that function.
+__host__ __device__ inline int gemm_f64_team_barriers(const GemmTeamPlan& p, int team) {
+  const int multiplied = team == 0 ? p.cnt0 : p.cnt1, idled = p.H - multiplied;      // (team 1, cnt1 = H - 1: one idle pass)
+  return p.H > 0 ? 1 + (multiplied + idled) + 2 : 0;
+}
+
 }  // namespace vb
 
 #include "vb_gemm_f64_dma.h"
@@ -421,6 +458,25 @@ inline bool gemm_uses_dma(const GemmArgs& g) {
 // and returns their number, 0 if the shape does not go to the LDS-DMA kernel.
 inline unsigned gemm_f64_pair_plan(GemmArgs* g) {
   if (g->tri_mode != 4 || g->batch || !gemm_uses_dma(*g)) return 0;
+  g->k_split = gemm_tiles(g->K, kGemmBK) * kGemmBK;
+  g->tiles_m = gemm_tiles(g->M, 64);
+  g->tiles_n = gemm_tiles(g->N, 32);
+  g->xcd_group = 0;
+  g->prio_div = 0;      // (triangular k ranges: no priority alternation, as the launcher below)
+  return (unsigned)((g->tiles_m + 1) / 2 * g->tiles_n);
+}
+
+// The same product with two four-wave teams per workgroup (gemm_f64_dma_team_pair_tiles<2, 4, STAGES, ...>: the same pairs of
+// 64 x 32 tiles by one 512-thread workgroup; slab program: gemm_f64_team_plan above), likewise for the caller's own kernel
+// (fr_fold_msum_team_kernel).  Returns the number of workgroups, or 0 where the caller takes gemm_f64_pair_plan instead: a shape
+// that does not go to the LDS-DMA kernel, or TWO OR MORE WORKGROUPS PER CU.  The teams put a second wave on every SIMD and
+// halve the chain of slab iterations, which pays while a CU has one such workgroup (D = 1024, 256 workgroups: the launch
+// 38.7 -> 30.6 us); with four per CU the pair function's workgroups fill the SIMDs by themselves and the teams' lock step
+// and hand-off only cost (D = 2048, 1 024 workgroups: 163.5 -> 175.6 us).  Between the two (D = 1040 .. 2032) nothing is
+// timed: the bound is the count at which the pair function itself has two waves per SIMD on every CU (D >= 1424).
+inline unsigned gemm_f64_team_pair_plan(GemmArgs* g, int n_cu) {
+  if (g->tri_mode != 4 || g->batch || !gemm_uses_dma(*g) || g->M > g->K) return 0;
+  if ((long)((gemm_tiles(g->M, 64) + 1) / 2) * gemm_tiles(g->N, 32) >= 2L * n_cu) return 0;
   g->k_split = gemm_tiles(g->K, kGemmBK) * kGemmBK;
   g->tiles_m = gemm_tiles(g->M, 64);
   g->tiles_n = gemm_tiles(g->N, 32);

@@ -578,4 +578,265 @@ constexpr size_t gemm_f64_dma_pair_lds() {
   return (size_t)STAGES * (32 * AF * kGemmBK + kGemmBK * 8 * NB) * sizeof(double);
 }
 
+// The same paired row blocks on TWO four-wave teams, for products with about one such workgroup per CU: a 512-thread workgroup
+// (pair, column tile), team = threadIdx.x >> 8, each team with LDS stages of its own.  One wave per SIMD gets less than half of
+// the SIMD's matrix pipe out of a chain of dependent slab iterations however many slabs are in flight (the pair
+// function above, 68 iterations at D = 1024, 38.7 us for the launch it rides in; the teams, 34 iterations with two waves on
+// every SIMD, 30.6).  Where the pair function's workgroups already share their CUs four at a time, the teams' lock step costs
+// more than it gains (D = 2048: 163.5 against 175.6 us).  With the slab program of gemm_f64_team_plan (vb_gemm_f64.h):
+//     team 0:  the light tile (row block tiles_m - 1 - pair), all n_l slabs -> its epilogue -> the first H - n_l slabs of the
+//              heavy tile (row block pair)
+//     team 1:  the remaining H or H - 1 slabs of the heavy tile
+// and at the end team 1 hands its accumulators to team 0 through its own, by then idle, stages: heavy = acc0 + acc1, always in
+// that order.  The middle block of an odd tiles_m has no light tile: the teams take the halves of its k range.  Tile, swizzle,
+// fragment arrangement and k order are those of gemm_f64_dma_tile<true, AF, NB, STAGES>: a light tile has the bits that tile
+// body gives it, each half of a heavy tile the bits it would give the same slabs.  No atomics, every order fixed.
+//
+// INVARIANT (what can hang): the eight waves share one s_barrier, so every wave of the workgroup executes the SAME NUMBER OF
+// BARRIERS -- one behind the first slab, one per pass of the slab loop, one in front of the hand-off, one behind it
+// (gemm_f64_team_barriers) -- whatever its team, its pair or the raggedness of its tile.  The loop runs H passes for both
+// teams; a team with fewer slabs (team 1 with H - 1, or with none) fetches its last slab again and multiplies nothing in the
+// passes it has no slab for.  No barrier stands under a condition that depends on the team: the team only decides which
+// sources are fetched, whether a pass multiplies, and who stores.
+// The pipeline of a team runs THROUGH team 0's tile switch: the slab fetched in pass s goes to the stage read in pass s - 1,
+// whose readers are past that pass's barrier, whichever tile either slab belongs to -- no DMA lands in a stage that a wave of
+// the team still reads.  Counted vmcnt waits count a wave's own DMAs only: the stores of the light tile's epilogue, issued at
+// the top of pass sw, sit on the same counter, so that one pass ends with vmcnt(0) instead of the counted wait.
+//
+// `block` = pair * tiles_n + column tile.  The caller's kernel has 512 threads and provides the dynamic LDS of both teams
+// (gemm_f64_dma_team_pair_lds).  `Dep`: a type of the calling kernel's own (see above); only its cache policy is consulted.
+template <int AF, int NB, int STAGES, class Epi, class Dep>
+__device__ __forceinline__ void gemm_f64_dma_team_pair_tiles(const GemmArgs& g, const Epi& epi, const Dep&, const int block) {
+  static_assert(!EpiReduces<Epi>::value && !EpiColsum<Epi>::value && !EpiRowSums<Epi>::value,
+                "the epilogue inside the slab loop must leave LDS alone");
+  static_assert(STAGES == 2 || STAGES == 3, "two or three LDS stages per team");
+  static_assert(AF == 2, "gemm_f64_team_plan counts the slabs of 64-row blocks");
+  static_assert(NB % 2 == 0, "fragments are read in pairs");
+  constexpr int BM = 32 * AF, BN = 8 * NB;
+  constexpr int kStages = STAGES, kAhead = STAGES - 1;
+  constexpr int kATile = BM * kGemmBK, kBTile = kGemmBK * BN;
+  constexpr int kAUnits = kATile / 128, kBUnits = kBTile / 128;
+  static_assert(kAUnits % 4 == 0 && kBUnits % 4 == 0, "whole rounds of A and of B units over the 4 waves of a team");
+  constexpr int UA = kAUnits / 4, UPW = (kAUnits + kBUnits) / 4;      // wave-loads per wave and slab: UA of A, then those of B
+  constexpr int kTeamLds = kStages * (kATile + kBTile);              // doubles
+  constexpr int KS = kGemmBK / 4;
+  extern __shared__ double gemm_lds[];
+  const int t = threadIdx.x & 255;
+  const int lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int team = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);
+  double* lds = gemm_lds + team * kTeamLds;
+  double* As = lds;                              // [kStages][kATile]
+  double* Bs = lds + kStages * kATile;           // [kStages][kBTile]
+  const int wm = wave >> 1, wn = wave & 1;
+
+  // ---- the pair of tiles and this team's slab program ---------------------------------------------------------------
+  const int pair = block / g.tiles_n, bn = block % g.tiles_n;
+  const GemmTeamPlan pl = gemm_f64_team_plan(g.M, g.K, g.tiles_m, pair);
+  const int H = pl.H;
+  if (H <= 0) return;                            // (uniform over the workgroup)
+  const int cnt = team == 0 ? pl.cnt0 : pl.cnt1; // slabs this team multiplies
+  const int sw = team == 0 ? pl.sw : 0;          // sequence index at which team 0 changes tiles (0: never)
+  const int m0_h = pair * BM, m0_l = (g.tiles_m - 1 - pair) * BM, n0 = bn * BN;
+  const int kb_h = (m0_h < g.K ? m0_h : g.K) / kGemmBK, kb_l = m0_l / kGemmBK;      // first k slab of either tile
+
+  double acc[AF][NB];
+#pragma unroll
+  for (int i = 0; i < AF; ++i)
+#pragma unroll
+    for (int j = 0; j < NB; ++j) acc[i][j] = 0.0;
+
+  // ---- global sources of this wave's units (as gemm_f64_dma_tile, A[m][k]): u < UA the A tile, then the B tile ----------
+  const double* src[UPW];
+  const int64_t step_b = (int64_t)kGemmBK * g.ldb;
+  auto set_sources = [&](int m0, int ks) __attribute__((always_inline)) {      // k slab `ks` of the tile of row block m0 / BM
+#pragma unroll
+    for (int u = 0; u < UPW; ++u) {
+      if (u < UA) {            // 8 rows x 8 pairs per unit
+        const int q = u * 4 + wave;
+        const int row = q * 8 + (lane >> 3), p = lane & 7;
+        const int kp = p ^ ((row >> 1) & 7);
+        int m = m0 + row;
+        m = m < g.M ? m : g.M - 1;
+        src[u] = g.A + (int64_t)m * g.lda + (int64_t)ks * kGemmBK + 2 * kp;
+      } else {
+        const int qb = (u - UA) * 4 + wave;
+        constexpr int PPR = BN / 2, RPU = 64 / PPR > 0 ? 64 / PPR : 1;
+        constexpr int UPR = PPR >= 64 ? PPR / 64 : 1;
+        const int krow = (PPR >= 64) ? qb / UPR : qb * RPU + lane / PPR;
+        const int p = (PPR >= 64) ? (qb % UPR) * 64 + lane : lane % PPR;
+        int64_t col = n0 + 2 * p;
+        col = col < g.ldb - 1 ? col : g.ldb - 2;
+        src[u] = g.B + ((int64_t)ks * kGemmBK + krow) * g.ldb + col;
+      }
+    }
+  };
+  if (team == 0) set_sources(sw > 0 ? m0_l : m0_h, sw > 0 ? kb_l : kb_h);
+  else set_sources(m0_h, kb_h + (cnt > 0 ? pl.h0 : pl.n_h - 1));      // (nothing to multiply: an in-range slab all the same)
+  auto issue = [&](int st) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < UPW; ++u) {
+      if (u < UA) {
+        double* dst = lds + (u * 4 + wave) * 128 + st * kATile;
+        __builtin_amdgcn_global_load_lds((gemm_gptr)src[u], (gemm_lptr)dst, 16, 0, Dep::kAuxA);
+      } else {
+        double* dst = lds + kStages * kATile + ((u - UA) * 4 + wave) * 128 + st * kBTile;
+        __builtin_amdgcn_global_load_lds((gemm_gptr)src[u], (gemm_lptr)dst, 16, 0, 0);
+      }
+    }
+  };
+  // make src point at sequence index `next` (called with next = previous + 1 < cnt)
+  auto advance_to = [&](int next) __attribute__((always_inline)) {
+    if (sw > 0 && next == sw) {
+      set_sources(m0_h, kb_h);
+    } else {
+#pragma unroll
+      for (int u = 0; u < UPW; ++u) src[u] += u < UA ? (int64_t)kGemmBK : step_b;
+    }
+  };
+
+  // ---- fragment addresses and the k-step (as gemm_f64_dma_tile, A[m][k] tile) ---------------------------------------------
+  const int fi = lane & 15, fk = lane >> 4;
+  const int fblk = (lane >> 2) & 3, fj = lane & 3;
+  auto frag_row = [&](int a, int i) __attribute__((always_inline)) { return wm * (16 * AF) + a * 16 + i; };
+  auto frag_col = [&](int r, int blk, int j) __attribute__((always_inline)) {
+    return wn * (4 * NB) + 8 * ((blk + (r >> 1)) & (NB / 2 - 1)) + 2 * j + (r & 1);
+  };
+  int a_off[KS], b_off[NB];
+#pragma unroll
+  for (int kk = 0; kk < KS; ++kk) {
+    const int k = 4 * kk + fk;
+    const int row = wm * (16 * AF) + fi;
+    a_off[kk] = row * kGemmBK + 2 * ((k >> 1) ^ ((row >> 1) & 7)) + (k & 1);
+  }
+#pragma unroll
+  for (int r = 0; r < NB; ++r) b_off[r] = fk * BN + frag_col(r, fblk, fj);
+
+  double fa[2][AF], fb[2][NB];
+  auto load_frags = [&](int st, int kk, int set) __attribute__((always_inline)) {
+    const double* as = As + st * kATile;
+    const double* bs = Bs + st * kBTile;
+#pragma unroll
+    for (int a = 0; a < AF; ++a) fa[set][a] = as[a_off[kk] + a * (16 * kGemmBK)];
+#pragma unroll
+    for (int r = 0; r < NB; r += 2) {
+      const d2v v = *reinterpret_cast<const d2v*>(bs + b_off[r] + 4 * kk * BN);
+      fb[set][r] = v.x, fb[set][r + 1] = v.y;
+    }
+  };
+  auto mfma_step = [&](int set) __attribute__((always_inline)) {
+#pragma unroll
+    for (int a = 0; a < AF; ++a)
+#pragma unroll
+      for (int r = 0; r < NB; ++r)
+        acc[a][r] = __builtin_amdgcn_mfma_f64_4x4x4f64(fa[set][a], fb[set][r], acc[a][r], 0, 0, 0);
+  };
+  constexpr int kReads = AF / 2 + NB / 2, kMfma = AF * NB, kPer = kMfma / kReads;
+  auto interleave = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < kReads; ++i) {
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, kPer, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x008, kMfma - kPer * kReads, 0);
+  };
+  auto wait_vm = [&](auto n) __attribute__((always_inline)) {      // s_waitcnt vmcnt(n) only (as gemm_f64_dma_tile)
+    constexpr int N = decltype(n)::value;
+    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
+  };
+
+  // ---- plain-store epilogue of the tile of row block m0 / BM (team 0 only; as gemm_f64_dma_tile) --------------------------
+  auto store_tile = [&](int m0) __attribute__((always_inline)) {
+#pragma unroll
+    for (int a = 0; a < AF; ++a)
+#pragma unroll
+      for (int r = 0; r < NB; r += 2) {
+        const int row = m0 + frag_row(a, 4 * fblk + fk);
+        const int col = n0 + frag_col(r, fblk, fj);
+        if constexpr (EpiPairs<Epi>::value) {
+          if (row < g.M && col + 1 < g.N) {
+            epi.pair(0, row, col, acc[a][r], acc[a][r + 1]);
+            continue;
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+          if (row < g.M && col + q < g.N) epi(0, row, col + q, acc[a][r + q]);
+      }
+  };
+
+  issue(0);                              // sequence index 0
+  if (kAhead == 2) {
+    if (1 < cnt) advance_to(1);
+    issue(1);                            // index 1 (or index 0 again: keeps the vmcnt arithmetic uniform)
+  }
+  wait_vm(std::integral_constant<int, UPW*(kAhead - 1)>());
+  __asm__ volatile("" ::: "memory");
+  __builtin_amdgcn_s_barrier();          // barrier 1 of H + 3
+  __asm__ volatile("" ::: "memory");
+  if (0 < cnt) load_frags(0, 0, 0);
+  int st = 0;
+  for (int s = 0; s < H; ++s) {          // H passes for BOTH teams
+    const int st1 = st == kStages - 1 ? 0 : st + 1;
+    const int st_new = kAhead == 2 ? (st1 == kStages - 1 ? 0 : st1 + 1) : st1;      // the stage index s + kAhead goes to
+    const bool switching = sw > 0 && s == sw;      // team 0: the light tile is complete -- store it, start the heavy one
+    if (switching) {
+      store_tile(m0_l);
+#pragma unroll
+      for (int i = 0; i < AF; ++i)
+#pragma unroll
+        for (int j = 0; j < NB; ++j) acc[i][j] = 0.0;
+      __asm__ volatile("" ::: "memory");               // (the stores stay in this pass, in front of its vmcnt(0))
+    }
+    if (s + kAhead < cnt) advance_to(s + kAhead);      // beyond the end: re-fetch the last slab into the free stage
+    issue(st_new);
+    const bool on = s < cnt;
+    if (on) {
+#pragma unroll
+      for (int kk = 0; kk < KS - 1; ++kk) {
+        load_frags(st, kk + 1, (kk + 1) & 1);
+        mfma_step(kk & 1);
+        interleave();
+      }
+    }
+    // index s + 1 has landed (this wave's share); in the switching pass the epilogue's stores are on the counter too
+    if (switching) wait_vm(std::integral_constant<int, 0>());
+    else wait_vm(std::integral_constant<int, UPW*(kAhead - 1)>());
+    __builtin_amdgcn_s_waitcnt(0xC07F);              // lgkmcnt(0): this wave's reads of stage st are done
+    __asm__ volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();                    // barriers 2 .. H + 1
+    __asm__ volatile("" ::: "memory");
+    if (on) {
+      load_frags(st1, 0, KS & 1);
+      mfma_step((KS - 1) & 1);
+      interleave();
+    }
+    st = st1;
+  }
+  __builtin_amdgcn_s_waitcnt(0);         // nothing in flight into LDS, no read outstanding: the stages are free
+  __builtin_amdgcn_s_barrier();          // barrier H + 2
+  __asm__ volatile("" ::: "memory");
+  // team 1's part of the heavy tile to team 0: [wave][fragment][lane] in team 1's stages
+  static_assert(4 * AF * NB * 64 <= kTeamLds, "the hand-off buffer fits a team's stages");
+  double* xch = gemm_lds + kTeamLds + wave * (AF * NB * 64) + lane;
+  if (team == 1) {
+#pragma unroll
+    for (int a = 0; a < AF; ++a)
+#pragma unroll
+      for (int r = 0; r < NB; ++r) xch[(a * NB + r) * 64] = acc[a][r];
+  }
+  __syncthreads();                       // barrier H + 3
+  if (team == 0) {
+#pragma unroll
+    for (int a = 0; a < AF; ++a)
+#pragma unroll
+      for (int r = 0; r < NB; ++r) acc[a][r] = acc[a][r] + xch[(a * NB + r) * 64];
+    store_tile(m0_h);
+  }
+}
+
+template <int AF, int NB, int STAGES>
+constexpr size_t gemm_f64_dma_team_pair_lds() {
+  return (size_t)2 * STAGES * (32 * AF * kGemmBK + kGemmBK * 8 * NB) * sizeof(double);
+}
+
 }  // namespace vb
