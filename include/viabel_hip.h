@@ -611,6 +611,39 @@ int vb_nn_predict(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const doub
  * context usable.                                                                                                        */
 int vb_glm_value_grad_hessian(vb_ctx* ctx, const double* x, int64_t d, double* f, double* grad, double* hess);
 
+/* ---- kernel Stein discrepancy of weighted draws (csrc/vb_ksd.hip) ------------------------------------------------
+ * vb_ksd: the squared kernel Stein discrepancy (Gorham & Mackey 2017) of the s host draws x (s x d, row-major) against the
+ * density whose scores g_i = grad log p(x_i) are given or come from the bound model, with the inverse multiquadric base
+ * kernel k(x, y) = (c^2 + |x - y|^2)^beta.  With x~ = x / scale, g~ = g * scale (the discrepancy in rescaled coordinates)
+ * and, per pair, sums over the d coordinates
+ *   r2 = sum (x~_i - x~_j)^2     a = sum g~_i g~_j     b = sum (g~_i - g~_j)(x~_i - x~_j)     u = c^2 + r2
+ *   k_p(i, j)  = a u^beta - 2 beta u^(beta-1) (b + d) - 4 beta (beta - 1) r2 u^(beta-2)
+ *   rowsums[i] = sum_j w_j k_p(i, j)              *ksd2 = sum_i w_i rowsums[i]
+ * r2 and b are accumulated from the differences themselves (never from Gram products), so duplicate draws give r2 = 0
+ * and the rounding error does not depend on where the draws sit.
+ *   scores   s x d host scores: no model needs to be bound and d is free.  NULL: the bound model's gradient at the draws,
+ *            evaluated on the device by the pipeline behind vb_model_grad (it never crosses the bus): VB_ERR_STATE without a
+ *            bound model, VB_ERR_INVALID when d is not its dimension, VB_ERR_UNSUPPORTED for a host-callback model and
+ *            for VB_MODEL_MINIBATCH_GLM.
+ *   log_w    NULL: uniform weights.  Otherwise s log weights, normalised here as vb_glm_predict normalises them (the same
+ *            VB_ERR_INVALID for "no finite weight"); a weight of -inf adds nothing.
+ *   scale    NULL: ones.  Otherwise d positive finite values.
+ *   c, beta  c > 0 finite, -1 < beta < 0, else VB_ERR_INVALID.
+ *   ksd2     one double, required;  rowsums: s doubles, or NULL.
+ * 1 <= s <= 65536 (VB_ERR_INVALID below, VB_ERR_UNSUPPORTED above).  A staging kernel, the pair kernel (one 256-thread
+ * workgroup per 64 draws and column split, 4 x 4 pairs per thread, operands through LDS; nothing of order s^2 is stored) and
+ * a finishing kernel; every sum has a fixed order and there are no floating-point atomics: two calls with the same inputs
+ * return the same bits.  A non-finite *ksd2 (a draw or its score was not finite) returns VB_ERR_NUMERIC.  A failing call
+ * leaves the context and the bound model usable.  Runs on the calling process's engine only: no all-reduce (like
+ * vb_glm_psis_loo).
+ * vb_ksd_plan (host only, no context): the pair kernel's launch shape on a device of n_cu compute units, out = {row blocks
+ * = ceil(s / 64), column splits}.  Split k of n takes the column tiles [k * tiles / n, (k + 1) * tiles / n) (integer
+ * division; tiles = row blocks): contiguous ranges whose lengths differ by at most one.  VB_ERR_INVALID for out == NULL,
+ * s outside [1, 65536] or n_cu < 1.                                                                                   */
+int vb_ksd(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const double* scores, const double* log_w,
+           const double* scale, double c, double beta, double* ksd2, double* rowsums);
+int vb_ksd_plan(int64_t s, int n_cu, int out[2]);
+
 /* ---- Hamiltonian Monte Carlo on the device gradients -----------------------------------
  * vb_hmc_run: n_chains chains of HMC on the bound model, advanced in lock-step as one batch of the gradient pipeline
  * (what vb_model_grad evaluates), from the host starts x0 (n_chains x d, row-major) under the diagonal metric

@@ -179,6 +179,63 @@ def glm_grad_splits(rows, d, n_data, n_cu):
     return max(1, min(2 * int(n_cu) // tiles, int(n_data) // 128, 64))
 
 
+KSD_MAX_DRAWS = 65536      # capacity of vb_ksd (csrc/vb_ksd.hip: kKsdMaxDraws)
+
+
+def ksd_plan(s, n_cu):
+    """``(row blocks, column splits)`` of the pair kernel of ``vb_ksd`` for ``s`` draws on a device of ``n_cu`` compute
+    units (``vb_ksd_plan``: the host function the launch uses; no GPU needed).  ``ValueError`` for what it rejects."""
+    out = (ctypes.c_int * 2)()
+    if load().vb_ksd_plan(int(s), int(n_cu), out) != VB_OK:
+        raise ValueError('ksd_plan needs 1 <= s <= {} and n_cu >= 1; got s = {}, n_cu = {}'.format(KSD_MAX_DRAWS, s, n_cu))
+    return int(out[0]), int(out[1])
+
+
+def ksd_split_tiles(tiles, splits):
+    """The column tiles ``[first, last)`` of every split of the pair kernel: the rule of ``vb_ksd_plan`` in
+    ``include/viabel_hip.h`` (split ``k`` of ``n`` takes ``[k * tiles // n, (k + 1) * tiles // n)``)."""
+    return [(k * int(tiles) // int(splits), (k + 1) * int(tiles) // int(splits)) for k in range(int(splits))]
+
+
+def ksd_arguments(x, scores=None, log_w=None, scale=None, c=1.0, beta=-0.5):
+    """The arguments of ``vb_ksd`` checked and made contiguous doubles: ``(x, scores, log_w, scale, c, beta)``.
+    ``ValueError`` for a wrong shape, non-finite draws or scores, no finite log weight, a scale that is not positive and
+    finite, ``c`` not positive and finite and ``beta`` outside (-1, 0); ``NotImplementedError`` for more than
+    ``KSD_MAX_DRAWS`` draws.  Touches no engine."""
+    c, beta = float(c), float(beta)
+    if not (c > 0.0 and np.isfinite(c)):
+        raise ValueError('c must be positive and finite')
+    if not (-1.0 < beta < 0.0):
+        raise ValueError('beta must lie in (-1, 0)')
+    x = _f64(x)
+    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError('x must be (S, D) with S >= 1 and D >= 1; got shape {}'.format(x.shape))
+    s, d = x.shape
+    if s > KSD_MAX_DRAWS:
+        raise NotImplementedError('ksd takes at most {} draws; got {}'.format(KSD_MAX_DRAWS, s))
+    if not np.all(np.isfinite(x)):
+        raise ValueError('the draws must be finite')
+    if scores is not None:
+        scores = _f64(scores)
+        if scores.shape != (s, d):
+            raise ValueError('scores must have the shape of x, {}; got {}'.format((s, d), scores.shape))
+        if not np.all(np.isfinite(scores)):
+            raise ValueError('the scores must be finite')
+    if log_w is not None:
+        if np.shape(log_w) != (s,):
+            raise ValueError('log_w must have shape ({},)'.format(s))
+        log_w = _f64(log_w)
+        if np.any(np.isnan(log_w)) or np.any(log_w == np.inf) or not np.any(np.isfinite(log_w)):
+            raise ValueError('no log weight is finite (or one is NaN or +inf)')
+    if scale is not None:
+        if np.shape(scale) != (d,):
+            raise ValueError('scale must have shape ({},)'.format(d))
+        scale = _f64(scale)
+        if not np.all(np.isfinite(scale) & (scale > 0.0)):
+            raise ValueError('scale must be positive and finite')
+    return x, scores, log_w, scale, c, beta
+
+
 CV_MODES = {None: CV_NONE, 'full': CV_FULL, 'mean_only': CV_MEAN_ONLY, 'loo_diag_approx': CV_LOO_DIAG,
             'loo_direct_approx': CV_LOO_DIRECT}
 # capacity of the batched smoothing kernel (csrc/vb_psis_batch.hip: kPbMaxN, kPbTailCap)
@@ -807,6 +864,22 @@ class Engine:
         self._check(self._lib.vb_glm_value_grad_hessian(self._ctx, _dptr(x), d, ctypes.addressof(f), _dptr(grad),
                                                         None if hess is None else _dptr(hess)))
         return f.value, grad, hess
+
+    def ksd(self, x, scores=None, log_w=None, scale=None, c=1.0, beta=-0.5):
+        """Squared kernel Stein discrepancy of the weighted draws ``x`` (S x D) with the IMQ kernel
+        ``(c^2 + |x - y|^2)^beta`` (``vb_ksd``): ``(ksd2, rowsums)``, ``rowsums`` (S,) with
+        ``ksd2 = sum_i w_i rowsums[i]``.  ``scores`` (S x D): ``grad log p`` at the draws; None: the bound model's,
+        evaluated on the device.  ``log_w`` (S,; None: uniform; normalised by the entry), ``scale`` (D,; None: ones): the
+        discrepancy is that of ``x / scale`` with scores ``scores * scale``.  The arguments are checked before the call
+        (:func:`ksd_arguments`)."""
+        x, scores, log_w, scale, c, beta = ksd_arguments(x, scores, log_w, scale, c, beta)
+        s, d = x.shape
+        ksd2 = ctypes.c_double(0.0)
+        rowsums = np.empty(s, dtype=np.float64)
+        self._check(self._lib.vb_ksd(self._ctx, _dptr(x), s, d, None if scores is None else _dptr(scores),
+                                     None if log_w is None else _dptr(log_w), None if scale is None else _dptr(scale), c,
+                                     beta, ctypes.addressof(ksd2), _dptr(rowsums)))
+        return ksd2.value, rowsums
 
     def hmc_run(self, x0, inv_mass, n_warmup, n_draws, n_leapfrog, step_size, target_accept=0.8, jitter=0.2, seed=1,
                 stream_offset=0, thin=1, keep_draws=True):

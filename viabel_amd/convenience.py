@@ -12,12 +12,12 @@ from . import _lib
 from ._psis import _tail_size, batch_capacity, psislw, psisloo
 from .approximations import FullRankGaussian, MFGaussian, MFStudentT, NVPFlow
 from .diagnostics import all_diagnostics
-from .models import CallableModel, DeviceModel, LogisticRegressionModel, SourceModel, refuse_minibatch
+from .models import CallableModel, DeviceModel, LogisticRegressionModel, SourceModel, ksd_results, refuse_minibatch
 from .objectives import ExclusiveKL, _stage_prior_noise
 from .optimization import FASO, RAABBVI, RMSProp
 
 __all__ = ['bbvi', 'vi_diagnostics', 'psis_correction', 'samples_and_log_weights', 'loo', 'psisloo', 'predict',
-           'laplace_approximation']
+           'laplace_approximation', 'ksd']
 
 
 def bbvi(dimension, *, n_iters=10000, num_mc_samples=10, log_density=None, approx=None, objective=None,
@@ -286,6 +286,115 @@ def predict(var_param, *, objective=None, model=None, approx=None, X_new=None, y
             results['elpd'], results['se_elpd'], m, results['elpd'] / m))
     else:
         print('predicted {} observations from {} draws (no response: no elpd)'.format(m, int(n_samples)))
+    if khat is not None:
+        print('Pareto k is estimated to be khat = {:.2f}'.format(khat))
+        if khat > 0.7:
+            print('WARNING: khat > 0.7 means importance sampling is not feasible.')
+    return results
+
+
+def ksd(var_param=None, *, objective=None, model=None, approx=None, samples=None, log_weights=None, scores=None,
+        n_samples=4096, weights='psis', Reff=1.0, scale='auto', c=1.0, beta=-0.5):
+    """Kernel Stein discrepancy (Gorham & Mackey 2017, inverse multiquadric kernel ``(c^2 + |x - y|^2)^beta``) of a
+    weighted sample against a target, from the target's scores ``grad log p`` alone: no normalising constant, no density
+    ratio, no reference sample.  All ``S^2`` pairs are summed on the device (``vb_ksd``); nothing of that order is stored.
+
+    What the number is for: COMPARING samples of ONE target at the same ``scale``, ``c`` and ``beta`` -- a mean-field
+    fit against a full-rank one, raw draws against PSIS-corrected ones, each of them against an ``hmc()`` baseline of the
+    same size.  Smaller is closer; an exact sample of ``S`` draws does not give 0 but a value that shrinks like
+    ``1 / sqrt(S)``.  It is not an absolute threshold.
+
+    Exactly one of ``var_param`` and ``samples`` is given.
+
+    **From a fit**: ``var_param`` with ``objective``, or with ``model`` and ``approx`` (the rules of :func:`predict`).
+    ``n_samples`` draws and their log ratios come from :func:`samples_and_log_weights`; ``weights='psis'`` smooths the
+    ratios (``psislw``) and reports ``khat``, ``weights=None`` takes the draws as they are.  ``scale='auto'``: the
+    approximation's standard deviations (``approx.mean_and_cov(var_param)``).  The scores are the model's device
+    gradient.
+
+    **From draws**: ``samples`` (S x D) -- ``hmc()``'s draws reshaped to ``(chains * draws, D)``, or draws produced
+    elsewhere -- with optional ``log_weights`` (S,) and either ``model`` (device scores) or ``scores`` (S x D, given).
+    ``scale='auto'``: the weighted standard deviations of the draws.
+
+    In both modes ``scale=None`` means ones and an array is taken as given.  Returns a dict: ``ksd``, ``ksd2``,
+    ``rowsums`` (``ksd2 = sum_i w_i rowsums[i]``), ``ess`` (``1 / sum w^2``), ``n_samples``, ``c``, ``beta``, ``khat``
+    (None without smoothing) and ``scale``.  Argument errors raise ``ValueError`` before the engine is touched.  Runs on
+    the calling process's engine."""
+    if (var_param is None) == (samples is None):
+        raise ValueError('exactly one of var_param (a fit) and samples (draws) must be given')
+    c, beta = float(c), float(beta)
+    if not (c > 0.0 and np.isfinite(c)):
+        raise ValueError('c must be positive and finite')
+    if not (-1.0 < beta < 0.0):
+        raise ValueError('beta must lie in (-1, 0)')
+    auto = isinstance(scale, str)
+    if auto and scale != 'auto':
+        raise ValueError("scale must be 'auto', None or an array")
+    khat = None
+    if samples is None:
+        if objective is None:
+            if model is None or approx is None:
+                raise ValueError('either objective or both model and approx must be specified')
+        elif model is not None or approx is not None:
+            raise ValueError('model and/or approx cannot be specified if objective is')
+        else:
+            model, approx = objective.model, objective.approx
+        if log_weights is not None or scores is not None:
+            raise ValueError('log_weights and scores go with samples; a fit supplies its own')
+        if n_samples < 1:
+            raise ValueError('n_samples must be positive')
+        if weights not in ('psis', None):
+            raise ValueError("weights must be 'psis' or None")
+        if weights == 'psis' and n_samples < 2:
+            raise ValueError('n_samples must be at least 2 to smooth the weights')
+        if not (Reff > 0):
+            raise ValueError('Reff must be positive')
+        if not auto and scale is not None:
+            _lib.ksd_arguments(np.zeros((1, approx.dim)), scale=scale)
+        if not isinstance(model, DeviceModel):
+            raise TypeError('ksd needs a viabel_amd device model (its scores are device code); got {}. For other targets '
+                            'pass samples= and scores='.format(type(model).__name__))
+        model._refuse_ksd()
+        var_param = np.asarray(var_param, dtype=np.float64)
+        if auto:
+            scale = np.sqrt(np.diag(approx.mean_and_cov(var_param)[1]))
+        samples, log_ratios = samples_and_log_weights(var_param, model, approx, n_samples)
+        if weights == 'psis':
+            log_weights, khat = psislw(log_ratios, Reff=Reff)
+            khat = float(khat)
+    else:
+        if objective is not None or approx is not None:
+            raise ValueError('objective and approx go with var_param; with samples give model or scores')
+        if (model is None) == (scores is None):
+            raise ValueError('with samples exactly one of model and scores must be given')
+        if model is not None and not isinstance(model, DeviceModel):
+            raise TypeError('model must be a viabel_amd device model; got {}. Pass scores= instead'.format(
+                type(model).__name__))
+        samples, scores, log_weights, scale_arr, _, _ = _lib.ksd_arguments(samples, scores, log_weights,
+                                                                           None if auto else scale, c, beta)
+        if model is not None:
+            if samples.shape[1] != model.dim:
+                raise ValueError('samples must have shape (S, {})'.format(model.dim))
+            model._refuse_ksd()
+        if auto:
+            w = np.full(samples.shape[0], 1.0 / samples.shape[0]) if log_weights is None else \
+                np.exp(log_weights - np.max(log_weights))
+            w = w / np.sum(w)
+            mean = w @ samples
+            scale = np.sqrt(w @ (samples - mean) ** 2)
+            if not np.all(np.isfinite(scale) & (scale > 0.0)):
+                raise ValueError("scale='auto' needs draws that vary in every coordinate; pass scale=None or an array")
+        else:
+            scale = scale_arr
+    scale = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64)
+    if scores is None:
+        results = model.ksd_from_draws(samples, log_weights=log_weights, scale=scale, c=c, beta=beta)
+    else:
+        ksd2, rowsums = _lib.default_engine().ksd(samples, scores, log_weights, scale, c, beta)
+        results = ksd_results(ksd2, rowsums, log_weights, c, beta)
+    results.update(khat=khat, scale=scale)
+    print('KSD = {:.4g} (squared: {:.4g}) from {} draws, effective sample size {:.1f}'.format(
+        results['ksd'], results['ksd2'], results['n_samples'], results['ess']))
     if khat is not None:
         print('Pareto k is estimated to be khat = {:.2f}'.format(khat))
         if khat > 0.7:

@@ -44,6 +44,19 @@ class Model(object):
         raise NotImplementedError()
 
 
+def ksd_results(ksd2, rowsums, log_weights, c, beta):
+    """The dict ``ksd_from_draws`` and ``viabel_amd.ksd`` return, from what ``Engine.ksd`` gives."""
+    n = rowsums.shape[0]
+    if log_weights is None:
+        ess = float(n)
+    else:
+        w = np.exp(log_weights - np.max(log_weights))
+        ess = float(np.sum(w) ** 2 / np.sum(w * w))
+    ksd2 = float(ksd2)
+    return dict(ksd=float(np.sqrt(max(ksd2, 0.0))), ksd2=ksd2, rowsums=rowsums, ess=ess, n_samples=int(n), c=float(c),
+                beta=float(beta))
+
+
 class DeviceModel(Model):
     """A target whose log density / gradient / Hessian products are HIP device code."""
 
@@ -106,6 +119,26 @@ class DeviceModel(Model):
         eng.set_model(self.device_spec())
         g = eng.model_grad(x)[1]
         return g[0] if one else g
+
+    def ksd_from_draws(self, x, log_weights=None, scale=None, c=1.0, beta=-0.5):
+        """Kernel Stein discrepancy of the weighted draws ``x`` (S x D) against this model (Gorham & Mackey 2017; inverse
+        multiquadric kernel ``(c^2 + |x - y|^2)^beta``): how far the draws are from the target, from the target's scores
+        alone -- no normalising constant, no reference sample.  The scores are this model's device gradient at the
+        draws and stay on the device (``vb_ksd``, ``Engine.ksd``).  ``log_weights`` (S,; None: uniform; normalised by the
+        entry), ``scale`` (D,; None: ones): the discrepancy is that of ``x / scale``.  Returns a dict: ``ksd``
+        (``sqrt(max(ksd2, 0))``), ``ksd2``, ``rowsums`` (S,; ``ksd2 = sum_i w_i rowsums[i]``), ``ess``
+        (``1 / sum w^2``), ``n_samples``, ``c``, ``beta``."""
+        self._refuse_ksd()
+        x, _, log_weights, scale, c, beta = _lib.ksd_arguments(x, None, log_weights, scale, c, beta)
+        if x.shape[1] != self._dim:
+            raise ValueError('x must have shape (S, {})'.format(self._dim))
+        eng = _lib.default_engine()
+        eng.set_model(self.device_spec())
+        ksd2, rowsums = eng.ksd(x, None, log_weights, scale, c, beta)
+        return ksd_results(ksd2, rowsums, log_weights, c, beta)
+
+    def _refuse_ksd(self):
+        """Hook: ``NotImplementedError`` from the models whose scores the device cannot supply."""
 
     def check_gradient(self, x, step=1e-6):
         """Largest deviation of the device gradient from central differences of the device log density at the rows of
@@ -312,6 +345,11 @@ class CallableModel(DeviceModel):
     def _build_spec(self):
         empty = np.zeros(0)
         return (_lib.MODEL_SOURCE, self._dim, empty, np.zeros(0, dtype=np.int64), self._callback, self._error)
+
+    def _refuse_ksd(self):
+        raise NotImplementedError(
+            'ksd_from_draws evaluates the scores on the device; a CallableModel has them on the host only. Evaluate '
+            'scores = model.grad(x) and call viabel_amd.ksd(samples=x, scores=scores) (or Engine.ksd(x, scores=scores))')
 
 
 def as_device_model(model, dim):
@@ -1236,6 +1274,9 @@ class MinibatchRegressionModel(DeviceModel):
 
     def hessian(self, x):
         refuse_minibatch(self, 'hessian()')
+
+    def _refuse_ksd(self):
+        refuse_minibatch(self, 'ksd_from_draws()')
 
     def _value_grad_hessian(self, x, want_hessian=True):
         refuse_minibatch(self, 'find_mode() / laplace_approximation()')
