@@ -644,6 +644,51 @@ int vb_ksd(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const double* sco
            const double* scale, double c, double beta, double* ksd2, double* rowsums);
 int vb_ksd_plan(int64_t s, int n_cu, int out[2]);
 
+/* ---- Stein variational gradient descent (csrc/vb_svgd.hip) ---------------------------------------------------------
+ * vb_svgd_direction: the SVGD direction (Liu & Wang 2016) of the n host particles x (n x d, row-major) with the RBF kernel
+ * in rescaled, centred coordinates.  With c the column means of x (summed in a fixed order),
+ *   y_i = (x_i - c) / scale          g_i = score_i * scale
+ *   r2_ij = sum_k (y_ik - y_jk)^2    kappa_ij = exp(-r2_ij / h)
+ *   phi_y(i) = 1/n [ sum_j kappa_ij g_j + (2/h) ( y_i sum_j kappa_ij - sum_j kappa_ij y_j ) ]      phi(i) = phi_y(i) / scale
+ * (centred first, then scaled: the result does not depend on where the particles sit).  r2 is accumulated from the
+ * differences themselves (never from a Gram product): r2_ij == r2_ji bit for bit, duplicates give exactly 0, kappa_ii == 1.
+ *   scores     n x d host scores: no model needs to be bound and d is free.  NULL: the bound model's gradient at the
+ *              particles, evaluated on the device by the pipeline behind vb_model_grad: VB_ERR_STATE without a bound model,
+ *              VB_ERR_INVALID when d is not its dimension, VB_ERR_UNSUPPORTED for a host-callback model and for
+ *              VB_MODEL_MINIBATCH_GLM.
+ *   scale      NULL: ones.  Otherwise d positive finite values.
+ *   bandwidth  > 0: h itself.  0: the median rule h = m / log(n + 1), m the lower median of the n (n - 1) / 2 values r2_ij,
+ *              i < j (the element of 0-based rank (n (n - 1) / 2 - 1) / 2), selected exactly on the device by a radix
+ *              selection on the 64-bit patterns with integer counting; h = 1 when n = 1 or m = 0.  Negative or not
+ *              finite: VB_ERR_INVALID.
+ *   phi        n x d, required;  logp: n doubles or NULL, the model's log density at the particles (written only when the
+ *              model supplies the scores);  h_used: one double, required.
+ * 1 <= n <= 8192 (VB_ERR_INVALID below, VB_ERR_UNSUPPORTED above: the n x n kernel matrix is stored, 512 MiB at the
+ * capacity).  Stages: column means; B = [g | y] (rows padded to 64, columns to 16, zeros elsewhere); the pair kernel (one
+ * 256-thread workgroup per 64 x 64 tile on or below the diagonal, 4 x 4 pairs per thread, operands through LDS, the tile
+ * stored and mirrored); the selection; K = exp(-r2 / h) in place with its row sums; one fp64 MFMA product K [g | y]; a
+ * finishing kernel.  Every sum has a fixed order and there are no floating-point atomics: two calls with the same inputs
+ * return the same bits.  A non-finite direction or bandwidth returns VB_ERR_NUMERIC.  A failing call leaves the context
+ * and the bound model usable.
+ * vb_svgd_run: n_iters iterations of SVGD on the bound model from the host starts x0 (n x d): the scores at the particles,
+ * the direction as above, one optimiser step on the particle block with gradient -phi (the step of vb_fit: opt_kind one of
+ * VB_OPT_SGD / RMSPROP / ADAM / ADAGRAD, hyper = {learning rate, beta or beta1, beta2, jitter}, the arithmetic of the
+ * Python optimisers; for every kind but SGD the jitter must be positive).  Everything is enqueued on the context's
+ * stream, h stays in device memory, the host synchronises once, for the download.
+ *   state      in/out optimiser state [second moment (n x d) | momentum (n x d)], or NULL; read when has_state != 0
+ *              (a continued run), else the optimiser starts fresh; written whenever it is not NULL.
+ *   x, logp    the final particles (n x d) and their log densities (n).
+ *   h_hist, rms_hist, logp_hist   n_iters doubles each: the bandwidth, sqrt(mean phi^2) and the mean log density of the
+ *              particles at the START of every iteration.  A non-finite entry returns VB_ERR_NUMERIC.
+ * Refusals as vb_hmc_run: VB_ERR_STATE without a bound model, VB_ERR_UNSUPPORTED for a host-callback model, for
+ * VB_MODEL_MINIBATCH_GLM, for an attached communicator and for n > 8192, VB_ERR_INVALID for bad arguments; a refused
+ * call leaves the context and the bound model usable.                                                                 */
+int vb_svgd_direction(vb_ctx* ctx, const double* x, int64_t n, int64_t d, const double* scores, const double* scale,
+                      double bandwidth, double* phi, double* logp, double* h_used);
+int vb_svgd_run(vb_ctx* ctx, const double* x0, int64_t n, int64_t d, const double* scale, double bandwidth, int opt_kind,
+                const double hyper[4], int64_t n_iters, double* state, int has_state, double* x, double* logp,
+                double* h_hist, double* rms_hist, double* logp_hist);
+
 /* ---- Hamiltonian Monte Carlo on the device gradients -----------------------------------
  * vb_hmc_run: n_chains chains of HMC on the bound model, advanced in lock-step as one batch of the gradient pipeline
  * (what vb_model_grad evaluates), from the host starts x0 (n_chains x d, row-major) under the diagonal metric

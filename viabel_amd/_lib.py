@@ -236,6 +236,46 @@ def ksd_arguments(x, scores=None, log_w=None, scale=None, c=1.0, beta=-0.5):
     return x, scores, log_w, scale, c, beta
 
 
+SVGD_MAX_PARTICLES = 8192      # capacity of vb_svgd_direction / vb_svgd_run (csrc/vb_svgd.hip: kSvgdMaxParticles)
+
+
+def svgd_arguments(x, scores=None, scale=None, bandwidth='median'):
+    """The arguments of ``vb_svgd_direction`` / ``vb_svgd_run`` checked and made contiguous doubles:
+    ``(x, scores, scale, bandwidth)`` with ``bandwidth`` as the C entries take it (0.0: the median rule).  ``ValueError``
+    for a wrong shape, non-finite particles or scores, a scale that is not positive and finite and a bandwidth that is
+    neither ``'median'`` nor positive and finite; ``NotImplementedError`` for more than ``SVGD_MAX_PARTICLES`` particles.
+    Touches no engine."""
+    if isinstance(bandwidth, str):
+        if bandwidth != 'median':
+            raise ValueError("bandwidth must be 'median' or a positive number")
+        bandwidth = 0.0
+    else:
+        bandwidth = float(bandwidth)
+        if not (bandwidth > 0.0 and np.isfinite(bandwidth)):
+            raise ValueError("bandwidth must be 'median' or a positive finite number")
+    x = _f64(x)
+    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError('x must be (n, D) with n >= 1 and D >= 1; got shape {}'.format(x.shape))
+    n, d = x.shape
+    if n > SVGD_MAX_PARTICLES:
+        raise NotImplementedError('svgd takes at most {} particles; got {}'.format(SVGD_MAX_PARTICLES, n))
+    if not np.all(np.isfinite(x)):
+        raise ValueError('the particles must be finite')
+    if scores is not None:
+        scores = _f64(scores)
+        if scores.shape != (n, d):
+            raise ValueError('scores must have the shape of x, {}; got {}'.format((n, d), scores.shape))
+        if not np.all(np.isfinite(scores)):
+            raise ValueError('the scores must be finite')
+    if scale is not None:
+        if np.shape(scale) != (d,):
+            raise ValueError('scale must have shape ({},)'.format(d))
+        scale = _f64(scale)
+        if not np.all(np.isfinite(scale) & (scale > 0.0)):
+            raise ValueError('scale must be positive and finite')
+    return x, scores, scale, bandwidth
+
+
 CV_MODES = {None: CV_NONE, 'full': CV_FULL, 'mean_only': CV_MEAN_ONLY, 'loo_diag_approx': CV_LOO_DIAG,
             'loo_direct_approx': CV_LOO_DIRECT}
 # capacity of the batched smoothing kernel (csrc/vb_psis_batch.hip: kPbMaxN, kPbTailCap)
@@ -880,6 +920,50 @@ class Engine:
                                      None if log_w is None else _dptr(log_w), None if scale is None else _dptr(scale), c,
                                      beta, ctypes.addressof(ksd2), _dptr(rowsums)))
         return ksd2.value, rowsums
+
+    def svgd_direction(self, x, scores=None, scale=None, bandwidth='median'):
+        """One SVGD direction (``vb_svgd_direction``) of the particles ``x`` (n x D) with the RBF kernel of
+        ``(x - mean) / scale``: ``(phi, h, logp)``.  ``scores`` (n x D): ``grad log p`` at the particles; None: the bound
+        model's, evaluated on the device (``logp`` (n,) is then its log density, else None).  ``scale`` (D,; None: ones);
+        ``bandwidth``: ``'median'`` (``h = median r2 / log(n + 1)``, selected exactly on the device) or a positive number.
+        The arguments are checked before the call (:func:`svgd_arguments`)."""
+        x, scores, scale, bandwidth = svgd_arguments(x, scores, scale, bandwidth)
+        n, d = x.shape
+        phi = np.empty((n, d), dtype=np.float64)
+        logp = np.empty(n, dtype=np.float64) if scores is None else None
+        h = ctypes.c_double(0.0)
+        self._check(self._lib.vb_svgd_direction(self._ctx, _dptr(x), n, d, None if scores is None else _dptr(scores),
+                                                None if scale is None else _dptr(scale), bandwidth, _dptr(phi),
+                                                None if logp is None else _dptr(logp), ctypes.addressof(h)))
+        return phi, h.value, logp
+
+    def svgd_run(self, x0, n_iters, opt_kind, hyper, state=None, scale=None, bandwidth='median'):
+        """``n_iters`` iterations of SVGD on the bound model in one call (``vb_svgd_run``): the scores, the direction of
+        :meth:`svgd_direction` and one optimiser step (``opt_kind`` one of ``OPT_SGD`` / ``OPT_RMSPROP`` / ``OPT_ADAM`` /
+        ``OPT_ADAGRAD``, ``hyper = [learning rate, beta or beta1, beta2, jitter]``) per iteration, without host
+        synchronisation in between.  ``state``: the optimiser state ``[second moment (n D) | momentum (n D)]`` of an
+        earlier run (None: fresh).  Returns a dict: ``particles`` (n x D), ``logp`` (n,), ``state`` (2 n D,) and
+        ``bandwidth_history``, ``phi_rms_history``, ``logp_history`` (n_iters,; at the start of every iteration)."""
+        x0, _, scale, bandwidth = svgd_arguments(x0, None, scale, bandwidth)
+        n, d = x0.shape
+        n_iters = int(n_iters)
+        if n_iters < 1:
+            raise ValueError('n_iters must be positive')
+        hyper = np.array(hyper, dtype=np.float64)
+        if hyper.shape != (4,):
+            raise ValueError('hyper must have four entries (learning rate, beta / beta1, beta2, jitter)')
+        has_state = state is not None
+        state = np.array(state, dtype=np.float64).ravel() if has_state else np.zeros(2 * n * d, dtype=np.float64)
+        if state.shape != (2 * n * d,):
+            raise ValueError('state must have {} entries'.format(2 * n * d))
+        x = np.empty((n, d), dtype=np.float64)
+        logp = np.empty(n, dtype=np.float64)
+        h_hist, rms_hist, logp_hist = (np.empty(n_iters, dtype=np.float64) for _ in range(3))
+        self._check(self._lib.vb_svgd_run(self._ctx, _dptr(x0), n, d, None if scale is None else _dptr(scale), bandwidth,
+                                          int(opt_kind), _dptr(hyper), n_iters, _dptr(state), int(has_state), _dptr(x),
+                                          _dptr(logp), _dptr(h_hist), _dptr(rms_hist), _dptr(logp_hist)))
+        return dict(particles=x, logp=logp, state=state, bandwidth_history=h_hist, phi_rms_history=rms_hist,
+                    logp_history=logp_hist)
 
     def hmc_run(self, x0, inv_mass, n_warmup, n_draws, n_leapfrog, step_size, target_accept=0.8, jitter=0.2, seed=1,
                 stream_offset=0, thin=1, keep_draws=True):

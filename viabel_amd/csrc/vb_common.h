@@ -375,6 +375,8 @@ struct vb_ctx {
   vb::DeviceBuffer loo_work;            // batched smoothing / PSIS-LOO (vb_psis_batch.hip): vectors, draws, per-vector results
   vb::DeviceBuffer ksd_work;            // vb_ksd (vb_ksd.hip): staged draws and scores, weights, partials; laid out by every call
                                         // (its own buffer: model_grad_rows and the bound target run while it holds the draws)
+  vb::DeviceBuffer svgd_work;           // vb_svgd_direction / vb_svgd_run (vb_svgd.hip): particles, scores, [G | Y], the n x n kernel
+                                        // matrix, the selection's state, the optimiser's state and the histories; laid out by every call
   vb::PinnedBuffer pin;                 // device-mapped staging (vb_linalg.hip; ensure_pinned)
   vb::DeviceBuffer fit_work;            // device-resident fit: laid out by FitRun (vb_fit_run.h) alone
   int64_t fit_out_off = 0;

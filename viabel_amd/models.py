@@ -140,6 +140,25 @@ class DeviceModel(Model):
     def _refuse_ksd(self):
         """Hook: ``NotImplementedError`` from the models whose scores the device cannot supply."""
 
+    def svgd_direction(self, x, scale=None, bandwidth='median'):
+        """One Stein variational gradient descent direction (Liu & Wang 2016) of the particles ``x`` (n x D) towards this
+        model: ``phi(x_i) = 1/n sum_j [k(x_j, x_i) grad log p(x_j) + grad_{x_j} k(x_j, x_i)]`` with the RBF kernel
+        ``exp(-|y - y'|^2 / h)`` of ``y = (x - mean) / scale``.  The scores are this model's device gradient and stay on
+        the device (``vb_svgd_direction``, ``Engine.svgd_direction``).  ``scale`` (D,; None: ones); ``bandwidth``:
+        ``'median'`` (``h`` = the lower median of the squared pair distances over ``log(n + 1)``) or a positive number.
+        Returns a dict: ``phi`` (n x D), ``bandwidth`` (the ``h`` used) and ``logp`` (n,)."""
+        self._refuse_svgd('svgd_direction()')
+        x, _, scale, bandwidth = _lib.svgd_arguments(x, None, scale, bandwidth)
+        if x.shape[1] != self._dim:
+            raise ValueError('x must have shape (n, {})'.format(self._dim))
+        eng = _lib.default_engine()
+        eng.set_model(self.device_spec())
+        phi, h, logp = eng.svgd_direction(x, None, scale, 'median' if bandwidth == 0.0 else bandwidth)
+        return dict(phi=phi, bandwidth=h, logp=logp)
+
+    def _refuse_svgd(self, what):
+        """Hook: ``NotImplementedError`` from the models whose scores the device cannot supply."""
+
     def check_gradient(self, x, step=1e-6):
         """Largest deviation of the device gradient from central differences of the device log density at the rows of
         ``x``, relative to the largest gradient entry there: the check the reference runs on its models with
@@ -350,6 +369,11 @@ class CallableModel(DeviceModel):
         raise NotImplementedError(
             'ksd_from_draws evaluates the scores on the device; a CallableModel has them on the host only. Evaluate '
             'scores = model.grad(x) and call viabel_amd.ksd(samples=x, scores=scores) (or Engine.ksd(x, scores=scores))')
+
+    def _refuse_svgd(self, what):
+        raise NotImplementedError(
+            '{} evaluates the scores on the device; a CallableModel has them on the host only. Write the density as a '
+            'SourceModel, or evaluate scores = model.grad(x) and call Engine.svgd_direction(x, scores=scores)'.format(what))
 
 
 def as_device_model(model, dim):
@@ -1277,6 +1301,9 @@ class MinibatchRegressionModel(DeviceModel):
 
     def _refuse_ksd(self):
         refuse_minibatch(self, 'ksd_from_draws()')
+
+    def _refuse_svgd(self, what):
+        refuse_minibatch(self, what)
 
     def _value_grad_hessian(self, x, want_hessian=True):
         refuse_minibatch(self, 'find_mode() / laplace_approximation()')
