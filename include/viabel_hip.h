@@ -689,6 +689,49 @@ int vb_svgd_run(vb_ctx* ctx, const double* x0, int64_t n, int64_t d, const doubl
                 const double hyper[4], int64_t n_iters, double* state, int has_state, double* x, double* logp,
                 double* h_hist, double* rms_hist, double* logp_hist);
 
+/* ---- Adaptive tempered sequential Monte Carlo with HMC moves (csrc/vb_smc.hip) ------------------------------------
+ * Base q0 = N(loc, diag(scale^2)), normalised; target the bound model's log p = f, unnormalised; path
+ * log pi_beta = beta f + (1 - beta) log q0, beta from 0 to exactly 1 (Del Moral, Doucet & Jasra 2006; adaptive
+ * temperatures, Jasra et al. 2011; HMC moves, Buchholz, Chopin & Jacob 2021).  u_i = f(x_i) - log q0(x_i).
+ * vb_smc_reweight: one stage's reweight and resample on the n host log weights u, by the kernels the run uses.
+ *   v_i = u_i - max u, E(delta) = (sum e^{delta v_i})^2 / (n sum e^{2 delta v_i}).  If E(1 - beta_prev) >= ess_target,
+ *   delta = 1 - beta_prev and the new beta is exactly 1.0; otherwise 40 halvings of [lo, hi] = [0, 1 - beta_prev]
+ *   (lo = mid when E(mid) >= ess_target, else hi = mid), delta = lo, beta = beta_prev + delta.
+ *   out = {beta, delta max u + log(1/n sum e^{delta v_i}), n E(delta)}.  Systematic resampling: w_i = e^{delta v_i}
+ *   (0 for u_i = -inf), C the inclusive prefix sums of w over their total, t_i = (i + uniform) / n,
+ *   ancestors[i] = min(#{j : C_j <= t_i}, n - 1): non-decreasing, and a zero-weight particle is never an ancestor.
+ *   VB_ERR_INVALID: NULL pointers, n <= 0, ess_target outside (0, 1), beta_prev outside [0, 1), uniform outside [0, 1).
+ *   VB_ERR_UNSUPPORTED: n > 65 536.  VB_ERR_NUMERIC: a NaN or +inf u, every u = -inf, delta = 0 after the search
+ *   (fewer than ess_target of the particles carry weight).  No model needs to be bound.
+ * vb_smc_run: the whole sampler on the bound model.  Start: x = loc + scale z, z the normals
+ *   vb_noise_generate(seed, stream stream_offset) puts at (row = particle, col = coordinate); f and its gradient once.
+ *   Stage k = 1, 2, ... while beta < 1: reweight and resample as above with uniform = the v uniform of Philox stream
+ *   stream_offset + 1 + (k - 1) n_moves (row 2^64 - 1 of pseudo column 0xFFFFFFFE, as vb_hmc_run defines it), every stage;
+ *   then n_moves HMC transitions on pi_beta at the new beta, metric inv_mass = scale^2, n_leapfrog steps each, momenta
+ *   and accept uniforms of transition j from stream stream_offset + 1 + (k - 1) n_moves + j laid out as vb_hmc_run's,
+ *   divergence and rejection as vb_hmc_run's, no jitter; after every transition
+ *   log eps += adapt_rate (mean acceptance probability - target_accept), in device memory.
+ *   The host synchronises once per stage (16 bytes) and once for the download.  Every sum has a fixed order, there are
+ *   no floating-point atomics: two calls with equal arguments return equal bits.
+ *   Outputs: x (n x d), logp (n), log_base (n; log q0 at the particles), *log_evidence (the sum of the increments:
+ *   an unbiased estimate of the normalising constant on the log scale), *n_stages; beta_hist, log_z_hist, ess_hist
+ *   (max_stages each; the first *n_stages entries are set, the rest zero); accept_hist, step_hist, n_accepted_hist
+ *   (max_stages x n_moves: mean acceptance probability, the step size used, accepted particles); *final_step;
+ *   *n_divergent; ancestors_hist (max_stages x n, the first *n_stages rows set) or NULL.
+ *   VB_ERR_INVALID, before any device work: NULL required pointers, non-positive n, d, n_moves, n_leapfrog or max_stages,
+ *   ess_target or target_accept outside (0, 1), a non-finite loc, a scale or step_size that is not positive and finite, a
+ *   negative adapt_rate, d different from the model's dimension.  VB_ERR_STATE without a bound model.
+ *   VB_ERR_UNSUPPORTED: a host-callback model, an attached communicator, n > 65 536.  VB_ERR_NUMERIC: the reweight's
+ *   cases above at any stage, beta < 1 after max_stages stages, a non-finite log evidence.  A refused or failing call
+ *   leaves the context and the bound model usable.                                                                     */
+int vb_smc_reweight(vb_ctx* ctx, const double* u, int64_t n, double beta_prev, double ess_target, double uniform,
+                    double out[3], int64_t* ancestors);
+int vb_smc_run(vb_ctx* ctx, const double* loc, const double* scale, int64_t n, int64_t d, double ess_target, int n_moves,
+               int n_leapfrog, double step_size, double target_accept, double adapt_rate, int64_t max_stages, uint64_t seed,
+               uint64_t stream_offset, double* x, double* logp, double* log_base, double* log_evidence, int64_t* n_stages,
+               double* beta_hist, double* log_z_hist, double* ess_hist, double* accept_hist, double* step_hist,
+               int64_t* n_accepted_hist, double* final_step, int64_t* n_divergent, int64_t* ancestors_hist);
+
 /* ---- Hamiltonian Monte Carlo on the device gradients -----------------------------------
  * vb_hmc_run: n_chains chains of HMC on the bound model, advanced in lock-step as one batch of the gradient pipeline
  * (what vb_model_grad evaluates), from the host starts x0 (n_chains x d, row-major) under the diagonal metric

@@ -965,6 +965,58 @@ class Engine:
         return dict(particles=x, logp=logp, state=state, bandwidth_history=h_hist, phi_rms_history=rms_hist,
                     logp_history=logp_hist)
 
+    def smc_reweight(self, u, beta_prev, ess_target, uniform):
+        """One stage's reweight and resample of tempered SMC on the host log weights ``u`` (n,) (``vb_smc_reweight``, the
+        kernels ``smc_run`` uses): the next temperature by the 40-step bisection on the effective sample size (exactly 1.0
+        when ``1 - beta_prev`` already keeps ``ess_target``), the log-evidence increment, and the systematic resampling's
+        ancestors for the uniform ``uniform`` in [0, 1).  Returns ``(beta, log_z_inc, ess, ancestors (n,) int64)``.
+        ``ValueError`` for a NaN or ``+inf`` weight, for all ``-inf`` and when fewer than ``ess_target`` of the particles
+        carry weight; no model needs to be bound."""
+        u = _f64(u)
+        if u.ndim != 1 or u.size < 1:
+            raise ValueError('u must be (n,) with n >= 1; got shape {}'.format(u.shape))
+        out = np.zeros(3, dtype=np.float64)
+        ancestors = np.zeros(u.size, dtype=np.int64)
+        self._check(self._lib.vb_smc_reweight(self._ctx, _dptr(u), u.size, float(beta_prev), float(ess_target), float(uniform),
+                                              _dptr(out), ancestors.ctypes.data_as(_c_int64_p)))
+        return float(out[0]), float(out[1]), float(out[2]), ancestors
+
+    def smc_run(self, loc, scale, n, ess_target=0.5, n_moves=2, n_leapfrog=8, step_size=1.0, target_accept=0.8,
+                adapt_rate=0.5, max_stages=200, seed=1, stream_offset=0, keep_ancestors=False):
+        """Adaptive tempered SMC with HMC moves on the bound model (``vb_smc_run``) from the base ``N(loc, diag(scale^2))``:
+        ``n`` particles, per stage the temperature search, systematic resampling and ``n_moves`` HMC transitions of
+        ``n_leapfrog`` steps under the metric ``scale^2``, the step size adapted in device memory; one 16-byte host round
+        trip per stage.  Returns a dict: ``particles`` (n x D), ``logp`` and ``log_base`` (n,), ``log_evidence``,
+        ``n_stages``, ``betas``, ``log_z_increments``, ``ess`` (n_stages,), ``accept_prob``, ``step_size_history`` and
+        ``n_accepted`` (n_stages x n_moves), ``step_size`` (after the last update), ``n_divergent`` and ``ancestors``
+        (n_stages x n, int64; None without ``keep_ancestors``)."""
+        loc, scale = _f64(loc), _f64(scale)
+        if loc.ndim != 1 or loc.size < 1 or scale.shape != loc.shape:
+            raise ValueError('loc and scale must be (D,) with D >= 1; got shapes {} and {}'.format(loc.shape, scale.shape))
+        n, d, n_moves, max_stages = int(n), loc.size, int(n_moves), int(max_stages)
+        if n < 1 or n_moves < 1 or max_stages < 1:
+            raise ValueError('n, n_moves and max_stages must be positive')
+        x = np.empty((n, d), dtype=np.float64)
+        logp, log_base = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
+        beta_hist, log_z_hist, ess_hist = (np.zeros(max_stages, dtype=np.float64) for _ in range(3))
+        accept_hist, step_hist = (np.zeros((max_stages, n_moves), dtype=np.float64) for _ in range(2))
+        n_acc_hist = np.zeros((max_stages, n_moves), dtype=np.int64)
+        anc_hist = np.zeros((max_stages, n), dtype=np.int64) if keep_ancestors else None
+        log_ev, final = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        n_stages, n_div = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self._lib.vb_smc_run(
+            self._ctx, _dptr(loc), _dptr(scale), n, d, float(ess_target), n_moves, int(n_leapfrog), float(step_size),
+            float(target_accept), float(adapt_rate), max_stages, int(seed), int(stream_offset), _dptr(x), _dptr(logp),
+            _dptr(log_base), ctypes.addressof(log_ev), ctypes.byref(n_stages), _dptr(beta_hist), _dptr(log_z_hist),
+            _dptr(ess_hist), _dptr(accept_hist), _dptr(step_hist), n_acc_hist.ctypes.data_as(_c_int64_p),
+            ctypes.addressof(final), ctypes.byref(n_div),
+            None if anc_hist is None else anc_hist.ctypes.data_as(_c_int64_p)))
+        k = int(n_stages.value)
+        return dict(particles=x, logp=logp, log_base=log_base, log_evidence=log_ev.value, n_stages=k, betas=beta_hist[:k].copy(),
+                    log_z_increments=log_z_hist[:k].copy(), ess=ess_hist[:k].copy(), accept_prob=accept_hist[:k].copy(),
+                    step_size_history=step_hist[:k].copy(), n_accepted=n_acc_hist[:k].copy(), step_size=final.value,
+                    n_divergent=int(n_div.value), ancestors=None if anc_hist is None else anc_hist[:k].copy())
+
     def hmc_run(self, x0, inv_mass, n_warmup, n_draws, n_leapfrog, step_size, target_accept=0.8, jitter=0.2, seed=1,
                 stream_offset=0, thin=1, keep_draws=True):
         """Many-chain HMC on the bound model (``vb_hmc_run``): ``x0`` (C x D) starts, ``inv_mass`` (D,) the diagonal

@@ -377,6 +377,8 @@ struct vb_ctx {
                                         // (its own buffer: model_grad_rows and the bound target run while it holds the draws)
   vb::DeviceBuffer svgd_work;           // vb_svgd_direction / vb_svgd_run (vb_svgd.hip): particles, scores, [G | Y], the n x n kernel
                                         // matrix, the selection's state, the optimiser's state and the histories; laid out by every call
+  vb::DeviceBuffer smc_work;            // vb_smc_run / vb_smc_reweight (vb_smc.hip): two particle-state buffers, the move's proposal,
+                                        // weights, prefix sums, ancestors, the device-resident state and the histories; laid out by every call
   vb::PinnedBuffer pin;                 // device-mapped staging (vb_linalg.hip; ensure_pinned)
   vb::DeviceBuffer fit_work;            // device-resident fit: laid out by FitRun (vb_fit_run.h) alone
   int64_t fit_out_off = 0;

@@ -86,6 +86,43 @@ def _dense_factor(cov, what):
         raise ValueError('{} must be positive definite'.format(what))
 
 
+# ---- argument checks hmc() shares with smc() (viabel_amd/smc.py): none of them touches an engine -----------------------------
+def _require_device_target(model, what, moved):
+    """``TypeError`` unless ``model`` is a device model, ``NotImplementedError`` for a host callback; ``what`` is the calling
+    function's name, ``moved`` what it advances ('chains', 'particles')."""
+    if not isinstance(model, DeviceModel):
+        raise TypeError('{} needs a viabel_amd device model (its gradient is device code); got {}'.format(
+            what, type(model).__name__))
+    if isinstance(model, CallableModel):
+        raise NotImplementedError('{} advances the {} without host synchronisation: a CallableModel (a host callback) '
+                                  'cannot be its target; write the density as a SourceModel'.format(what, moved))
+
+
+def _require_integers(*triples):
+    """Every ``(name, value, lowest)``: an integer (no bool) that is at least ``lowest``."""
+    for name, v, low in triples:
+        if isinstance(v, bool) or int(v) != v or v < low:
+            raise ValueError('{} must be an integer >= {}'.format(name, low))
+
+
+def _require_open_unit(name, v):
+    if not (0.0 < v < 1.0):
+        raise ValueError('{} must lie in (0, 1)'.format(name))
+
+
+def _require_fit_pair(var_param, approx):
+    if (var_param is None) != (approx is None):
+        raise ValueError('var_param and approx must be given together')
+
+
+def _resolve_step_size(step_size, d):
+    """``step_size`` as a float, ``D ** -0.25`` for None; positive and finite."""
+    step_size = d ** -0.25 if step_size is None else float(step_size)
+    if not (step_size > 0.0 and np.isfinite(step_size)):
+        raise ValueError('step_size must be positive and finite')
+    return step_size
+
+
 def _check_arguments(model, n_chains, n_warmup, n_draws, n_leapfrog, step_size, target_accept, jitter, init, inv_mass,
                      var_param, approx, thin, metric='diag', adapt_metric=False, trajectory='fixed', max_leapfrog=256,
                      trajectory_length=None, trajectory_lr=0.025):
@@ -100,33 +137,22 @@ def _check_arguments(model, n_chains, n_warmup, n_draws, n_leapfrog, step_size, 
         raise ValueError('trajectory_length must be positive and finite')
     if not (trajectory_lr >= 0.0 and np.isfinite(trajectory_lr)):
         raise ValueError('trajectory_lr must be non-negative and finite')
-    if not isinstance(model, DeviceModel):
-        raise TypeError('hmc needs a viabel_amd device model (its gradient is device code); got {}'.format(
-            type(model).__name__))
-    if isinstance(model, CallableModel):
-        raise NotImplementedError('hmc advances the chains without host synchronisation: a CallableModel (a host callback) '
-                                  'cannot be its target; write the density as a SourceModel')
-    for name, v, low in (('n_chains', n_chains, 1), ('n_warmup', n_warmup, 0), ('n_draws', n_draws, 1),
-                         ('n_leapfrog', n_leapfrog, 1), ('thin', thin, 1)):
-        if isinstance(v, bool) or int(v) != v or v < low:
-            raise ValueError('{} must be an integer >= {}'.format(name, low))
+    _require_device_target(model, 'hmc', 'chains')
+    _require_integers(('n_chains', n_chains, 1), ('n_warmup', n_warmup, 0), ('n_draws', n_draws, 1),
+                      ('n_leapfrog', n_leapfrog, 1), ('thin', thin, 1))
     if trajectory == 'chees' and n_chains < 2 and n_warmup > 0:
         raise ValueError('trajectory=\'chees\' adapts the trajectory length across the chains: it needs n_chains >= 2 '
                          '(or n_warmup = 0)')
-    if not (0.0 < target_accept < 1.0):
-        raise ValueError('target_accept must lie in (0, 1)')
+    _require_open_unit('target_accept', target_accept)
     if not (0.0 <= jitter < 1.0):
         raise ValueError('jitter must lie in [0, 1)')
-    if (var_param is None) != (approx is None):
-        raise ValueError('var_param and approx must be given together')
+    _require_fit_pair(var_param, approx)
     if var_param is None and init is None:
         raise ValueError('either init or both var_param and approx must be given')
     if adapt_metric and n_warmup < MIN_ADAPT_WARMUP:
         raise ValueError('adapt_metric needs n_warmup >= {}'.format(MIN_ADAPT_WARMUP))
     d = model.dim
-    step_size = d ** -0.25 if step_size is None else float(step_size)
-    if not (step_size > 0.0 and np.isfinite(step_size)):
-        raise ValueError('step_size must be positive and finite')
+    step_size = _resolve_step_size(step_size, d)
     if init is not None:
         init = np.ascontiguousarray(init, dtype=np.float64)
         if init.shape != (n_chains, d):
