@@ -866,6 +866,26 @@ int vb_fullrank_get(vb_ctx* ctx, double* value, double* grad, int64_t p);
 int vb_fullrank_fold_get_m(vb_ctx* ctx, double* M_host, int64_t d);
 int vb_fold_m_team_plan(int d, int pair, int* out8);
 
+/* ---- the fp64 GEMM launcher's decisions (host only, no context; csrc/vb_gemm_f64.h) ----------------------------------
+ * vb_gemm_plan: what gemm_f64_launch decides for an m x n product with contraction length k in `splits` k pieces on a
+ * device of n_cu compute units -- gemm_f64_plan, the function the launcher itself calls.  tri_mode 0 .. 4 and batch as in
+ * GemmArgs; a_kcontig: A is given as A[m][k] (row-major), 0: as A[k][m]; narrow_ok, narrow_auto: whether the epilogue
+ * admits the 64 x 32 tiles on request / by the automatic rule (the launcher's kNarrowOk, kNarrowAuto); cfg 0: automatic,
+ * 1 .. 8: the caller's choice; flags bit 0: force the register-staged kernel.
+ * out6 = [cfg after the downgrades: 1 = 128 x 128, 2 = 128 x 64, 3 = 64 x 64 (three LDS stages), 4 = 64 x 64, 5 = 128 x 64,
+ * 6 = 128 x 128 (two stages), 7, 8 = 64 x 32 (three, two stages) | 1: the LDS-DMA kernel, 0: the register-staged one |
+ * rows, columns of a tile | k range of a split, a multiple of 16 | tiles per split: gridDim.x].  A split whose range starts
+ * at or beyond k writes a slab of zeros.  VB_ERR_INVALID for out6 == NULL, m, n, k, splits or n_cu < 1, tri_mode outside
+ * 0 .. 4, cfg outside 0 .. 8, batch or flags < 0.
+ * vb_gram_splits_plan: the k splits of the lower-tile Gram product of an n x d matrix (vb_noise_moments, the full-rank and
+ * multivariate-t gradients, the GLM Hessian): min(n_cu / lower 128 x 128 tiles, n / 256), at least 1.
+ * vb_lowrank_splits_plan: the k splits of the low-rank family's products over n samples (vb_lowrank_path_terms,
+ * vb_elbo_sums_lowrank): min(32, n / 256), at least 1.  Both: VB_ERR_INVALID for splits == NULL or an argument < 1.    */
+int vb_gemm_plan(int m, int n, int k, int splits, int n_cu, int tri_mode, int batch, int a_kcontig, int narrow_ok,
+                 int narrow_auto, int cfg, int flags, int* out6);
+int vb_gram_splits_plan(int d, int64_t n, int n_cu, int* splits);
+int vb_lowrank_splits_plan(int64_t n, int* splits);
+
 /* ---- ExclusiveKL for the multivariate t, throughput mode (approximations.py:342-354, objectives.py:160-164) --------
  * Samples through the CHOLESKY factor, x_n = mu + (L z_n) / s_n with s_n = sqrt(chi_n / df) from the device chi-square
  * draws of vb_chisq_generate (same distribution as the reference's symmetric root, :348, which parity mode keeps): with

@@ -191,6 +191,43 @@ def ksd_plan(s, n_cu):
     return int(out[0]), int(out[1])
 
 
+def gemm_plan(m, n, k, splits=1, n_cu=256, tri_mode=0, batch=0, a_kcontig=True, narrow_ok=None, narrow_auto=None, cfg=0,
+              flags=0):
+    """What the fp64 GEMM launcher decides for an ``m x n`` product of contraction length ``k`` in ``splits`` k pieces on a
+    device of ``n_cu`` compute units (``vb_gemm_plan``: the host function the launcher calls; no GPU needed): a dict of
+    ``cfg`` (1 .. 8), ``dma`` (the LDS-DMA kernel, else the register-staged one), ``bm_rows``, ``bn_cols``, ``k_split``
+    and ``grid_x``.  ``narrow_ok`` and ``narrow_auto`` default to what a plain-store epilogue gives: ``a_kcontig``.
+    ``ValueError`` for what the function rejects."""
+    narrow_ok = bool(a_kcontig) if narrow_ok is None else bool(narrow_ok)
+    narrow_auto = narrow_ok if narrow_auto is None else bool(narrow_auto)
+    out = (ctypes.c_int * 6)()
+    args = (int(m), int(n), int(k), int(splits), int(n_cu), int(tri_mode), int(batch), int(bool(a_kcontig)), int(narrow_ok),
+            int(narrow_auto), int(cfg), int(flags))
+    if load().vb_gemm_plan(*args, out) != VB_OK:
+        raise ValueError('gemm_plan rejects (m, n, k, splits, n_cu, tri_mode, batch, a_kcontig, narrow_ok, narrow_auto, cfg, '
+                         'flags) = {}'.format(args))
+    return {'cfg': int(out[0]), 'dma': bool(out[1]), 'bm_rows': int(out[2]), 'bn_cols': int(out[3]), 'k_split': int(out[4]),
+            'grid_x': int(out[5])}
+
+
+def gram_splits(d, n, n_cu):
+    """k splits of the lower-tile Gram product of an ``n x d`` matrix on a device of ``n_cu`` compute units
+    (``vb_gram_splits_plan``: the rule behind ``Engine.noise_moments``)."""
+    out = ctypes.c_int(0)
+    if load().vb_gram_splits_plan(int(d), int(n), int(n_cu), ctypes.byref(out)) != VB_OK:
+        raise ValueError('gram_splits needs d, n, n_cu >= 1; got {}'.format((d, n, n_cu)))
+    return int(out.value)
+
+
+def lowrank_splits(n):
+    """k splits of the low-rank family's products over ``n`` samples (``vb_lowrank_splits_plan``: the rule behind
+    ``Engine.lowrank_path_terms``)."""
+    out = ctypes.c_int(0)
+    if load().vb_lowrank_splits_plan(int(n), ctypes.byref(out)) != VB_OK:
+        raise ValueError('lowrank_splits needs n >= 1; got {}'.format(n))
+    return int(out.value)
+
+
 def ksd_split_tiles(tiles, splits):
     """The column tiles ``[first, last)`` of every split of the pair kernel: the rule of ``vb_ksd_plan`` in
     ``include/viabel_hip.h`` (split ``k`` of ``n`` takes ``[k * tiles // n, (k + 1) * tiles // n)``)."""

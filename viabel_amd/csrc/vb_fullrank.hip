@@ -1313,12 +1313,7 @@ int noise_moments(vb_ctx* ctx, const NoiseSlot& ns, int64_t n, int64_t d, double
 }
 
 int gram_splits(vb_ctx* ctx, int d, int64_t n) {
-  const int tiles = gemm_tiles(d, 128);
-  const int lower_tiles = tiles * (tiles + 1) / 2;
-  int splits = ctx->prop.multiProcessorCount / lower_tiles;
-  const int max_splits = (int)(n / 256) > 0 ? (int)(n / 256) : 1;
-  if (splits > max_splits) splits = max_splits;
-  return splits < 1 ? 1 : splits;
+  return gemm_gram_splits(d, n, ctx->prop.multiProcessorCount);
 }
 
 // ---- XCD-aware tile order of the lower-triangular product C = G' E ------------------------------------------
@@ -2212,5 +2207,29 @@ int vb_fold_m_team_plan(int d, int pair, int* out8) {
   const GemmTeamPlan p = gemm_f64_team_plan(d, d, tiles_m, pair);
   const int out[8] = {p.H, p.n_h, p.n_l, p.cnt0, p.cnt1, p.sw, gemm_f64_team_barriers(p, 0), gemm_f64_team_barriers(p, 1)};
   for (int i = 0; i < 8; ++i) out8[i] = out[i];
+  return VB_OK;
+}
+
+int vb_gemm_plan(int m, int n, int k, int splits, int n_cu, int tri_mode, int batch, int a_kcontig, int narrow_ok,
+                 int narrow_auto, int cfg, int flags, int* out6) {
+  using namespace vb;
+  if (!out6 || m <= 0 || n <= 0 || k <= 0 || splits <= 0 || n_cu <= 0) return VB_ERR_INVALID;
+  if (tri_mode < 0 || tri_mode > 4 || batch < 0 || cfg < 0 || cfg > 8 || flags < 0) return VB_ERR_INVALID;
+  const GemmPlan p = gemm_f64_plan(m, n, k, splits, n_cu, tri_mode, batch, a_kcontig != 0, narrow_ok != 0, narrow_auto != 0, cfg,
+                                   flags);
+  const int out[6] = {p.cfg, p.dma ? 1 : 0, p.bm_rows, p.bn_cols, p.k_split, (int)p.grid_x};
+  for (int i = 0; i < 6; ++i) out6[i] = out[i];
+  return VB_OK;
+}
+
+int vb_gram_splits_plan(int d, int64_t n, int n_cu, int* splits) {
+  if (!splits || d <= 0 || n <= 0 || n_cu <= 0) return VB_ERR_INVALID;
+  *splits = vb::gemm_gram_splits(d, n, n_cu);
+  return VB_OK;
+}
+
+int vb_lowrank_splits_plan(int64_t n, int* splits) {
+  if (!splits || n <= 0) return VB_ERR_INVALID;
+  *splits = vb::gemm_lr_splits(n);
   return VB_OK;
 }

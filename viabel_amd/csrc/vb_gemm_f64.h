@@ -499,22 +499,46 @@ inline unsigned gemm_f64_tri2_small_plan(GemmArgs* g, int splits, int n_cu) {
   return (unsigned)gemm_count_blocks(*g, 64, 64);
 }
 
-// returns gridDim.x of the launch (the number of output tiles; reducing epilogues write one partial per tile and split)
-template <bool A_KCONTIG, class Epi>
-inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu, const Epi& epi, int cfg = 0,
-                                int flags = 0) {
-  // 64 x 32 tiles: only where the result cannot depend on the tiling (no per-tile partial sums, no column sums)
-  // (round 6: a REDUCING epilogue may take them too when the caller asks for it by cfg = 7 / 8 -- its per-tile partial sums
-  // are then grouped by 64 x 32 tiles: another, equally fixed, summation order)
-  constexpr bool kNarrowOk = A_KCONTIG && !EpiColsum<Epi>::value;
-  constexpr bool kNarrowAuto = kNarrowOk && !EpiReduces<Epi>::value && !EpiRowSums<Epi>::value;
+// k splits of the lower-tile Gram product A'B (d x d, contraction over n rows; gram_splits of vb_common.h): one 128 x 128
+// tile's worth of workgroups per CU, at least 256 rows per split
+inline int gemm_gram_splits(int d, int64_t n, int n_cu) {
+  const int tiles = gemm_tiles(d, 128);
+  const int lower_tiles = tiles * (tiles + 1) / 2;
+  int splits = n_cu / lower_tiles;
+  const int max_splits = (int)(n / 256) > 0 ? (int)(n / 256) : 1;
+  if (splits > max_splits) splits = max_splits;
+  return splits < 1 ? 1 : splits;
+}
+
+// k splits of the low-rank family's products over the samples (lr_path_terms, lr_elbo_sums_any_rank): min(32, n / 256)
+inline int gemm_lr_splits(int64_t n) {
+  int splits = (int)(n / 256);
+  if (splits > 32) splits = 32;
   if (splits < 1) splits = 1;
+  return splits;
+}
+
+// The launcher's decision, a pure host function of the shape, the split count, the CU count and what the epilogue allows
+// (gemm_f64_launch below calls it; vb_gemm_plan exports it for the tests): the tile configuration, the kernel, the k range
+// of a split and the tile count.  narrow_ok / narrow_auto: the launcher's kNarrowOk / kNarrowAuto.  splits >= 1.
+struct GemmPlan {
+  int cfg;            // 1 .. 8 as listed above, after the downgrades
+  bool dma;           // the LDS-DMA kernel (vb_gemm_f64_dma.h), else the register-staged one
+  int tri_mode;       // 3 and 4 fall back to 0 where the kernel taken does not skip the zeros
+  int bm_rows, bn_cols, k_split;
+  unsigned grid_x;    // tiles per split of the chosen tile (a tile_map launch has its own count)
+};
+inline GemmPlan gemm_f64_plan(int M, int N, int K, int splits, int n_cu, int tri_mode, int batch, bool a_kcontig,
+                              bool narrow_ok, bool narrow_auto, int cfg, int flags) {
+  GemmArgs g;         // (the shape only: what gemm_count_blocks and gemm_uses_dma read)
+  g.M = M, g.N = N, g.K = K, g.tri_mode = tri_mode, g.batch = batch;
+  GemmPlan p;
   int ks = g.batch ? g.K : gemm_tiles(g.K, splits);   // batch mode: `splits` is the number of products
-  g.k_split = gemm_tiles(ks, kGemmBK) * kGemmBK;
+  p.k_split = gemm_tiles(ks, kGemmBK) * kGemmBK;
   // operands straight into LDS (vb_gemm_f64_dma.h) when every k range is a whole number of slabs
   const bool dma = gemm_uses_dma(g) && !(flags & 1);
   if (g.tri_mode == 3 && (!dma || splits != 1 || g.batch)) g.tri_mode = 0;      // the zeros are multiplied instead of skipped
-  if (g.tri_mode == 4 && (!dma || !A_KCONTIG || g.batch)) g.tri_mode = 0;
+  if (g.tri_mode == 4 && (!dma || !a_kcontig || g.batch)) g.tri_mode = 0;
   if (cfg == 0) {
     if (dma && (g.tri_mode == 1 || g.tri_mode == 3) && splits == 1 && gemm_count_blocks(g, 128, 64) < 4L * n_cu) {
       // k ranges grow with the column block: with only a couple of tiles per CU the long ones finish alone.  The
@@ -528,7 +552,7 @@ inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu
       // as wide a tile halves the MFMAs of every slab of it -- 4096 x 256 x 256: 15.2 -> 11.9 us, 4096 x 512 x 512:
       // 28.9 -> 26.9 us; with more tiles per CU it loses (16 384 x 256 x 256: 29.3 -> 30.8 us, D = 1024: 82 -> 92 us)
       // (tools/tile32_probe.sh)
-      if (kNarrowAuto && !g.batch && gemm_count_blocks(g, 64, 64) <= 2L * n_cu) cfg = 8;
+      if (narrow_auto && !g.batch && gemm_count_blocks(g, 64, 64) <= 2L * n_cu) cfg = 8;
     } else if (dma && g.tri_mode == 0 && g.batch == 0 && gemm_count_blocks(g, 128, 128) * splits >= 2L * n_cu) {
       // large dense products: 128 x 128 tiles with TWO LDS stages (64 KB: two workgroups per CU).  Per MFMA a third
       // fewer fragment reads and LDS-DMA pieces than 128 x 64: 69.3 - 70.2 against 66.0 - 67.5 TFLOP/s on
@@ -545,16 +569,38 @@ inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu
       cfg = 3;
       // dense products with at most one 64 x 64 tile per CU: 4096 x 256 x 256 17.2 -> 15.8 us (at two per CU it loses:
       // 4096 x 512 x 512 42.9 -> 45.4 us)
-      if (kNarrowAuto && dma && g.tri_mode == 0 && !g.batch && gemm_count_blocks(g, 64, 64) * splits <= (long)n_cu) cfg = 7;
+      if (narrow_auto && dma && g.tri_mode == 0 && !g.batch && gemm_count_blocks(g, 64, 64) * splits <= (long)n_cu) cfg = 7;
     }
   }
-  if (!kNarrowOk && cfg >= 7) cfg = 4;
+  if (!narrow_ok && cfg >= 7) cfg = 4;
   if (!dma && cfg > 3) cfg = (cfg == 4 || cfg >= 7) ? 3 : cfg == 6 ? 1 : 2;
-  const int bm_rows = (cfg == 3 || cfg == 4 || cfg >= 7) ? 64 : 128, bn_cols = cfg >= 7 ? 32 : (cfg == 1 || cfg == 6) ? 128 : 64;
+  p.bm_rows = (cfg == 3 || cfg == 4 || cfg >= 7) ? 64 : 128, p.bn_cols = cfg >= 7 ? 32 : (cfg == 1 || cfg == 6) ? 128 : 64;
+  p.cfg = cfg, p.dma = dma, p.tri_mode = g.tri_mode;
+  p.grid_x = (unsigned)gemm_count_blocks(g, p.bm_rows, p.bn_cols);
+  return p;
+}
+
+// returns gridDim.x of the launch (the number of output tiles; reducing epilogues write one partial per tile and split)
+template <bool A_KCONTIG, class Epi>
+inline unsigned gemm_f64_launch(hipStream_t st, GemmArgs g, int splits, int n_cu, const Epi& epi, int cfg = 0,
+                                int flags = 0) {
+  // 64 x 32 tiles: only where the result cannot depend on the tiling (no per-tile partial sums, no column sums)
+  // (round 6: a REDUCING epilogue may take them too when the caller asks for it by cfg = 7 / 8 -- its per-tile partial sums
+  // are then grouped by 64 x 32 tiles: another, equally fixed, summation order)
+  constexpr bool kNarrowOk = A_KCONTIG && !EpiColsum<Epi>::value;
+  constexpr bool kNarrowAuto = kNarrowOk && !EpiReduces<Epi>::value && !EpiRowSums<Epi>::value;
+  if (splits < 1) splits = 1;
+  const GemmPlan plan = gemm_f64_plan(g.M, g.N, g.K, splits, n_cu, g.tri_mode, g.batch, A_KCONTIG, kNarrowOk, kNarrowAuto, cfg,
+                                      flags);
+  const bool dma = plan.dma;
+  const int bm_rows = plan.bm_rows, bn_cols = plan.bn_cols;
+  cfg = plan.cfg;
+  g.k_split = plan.k_split;
+  g.tri_mode = plan.tri_mode;
   g.tiles_m = gemm_tiles(g.M, bm_rows);
   g.tiles_n = gemm_tiles(g.N, bn_cols);
   if (splits % 8 != 0 || g.batch) g.xcd_group = 0;
-  dim3 grid(g.tile_map ? (unsigned)g.tile_blocks : (unsigned)gemm_count_blocks(g, bm_rows, bn_cols), 1, (unsigned)splits);
+  dim3 grid(g.tile_map ? (unsigned)g.tile_blocks : plan.grid_x, 1, (unsigned)splits);
   // (triangular k ranges: the tiles of a CU differ in length anyway, and the alternation costs 1 - 3 us there --
   // 4096 x 768 x 768: 55.5 -> 52.7 us, 512: 30.1 -> 29.1 us, 1024: unchanged, tools/gemm_bench.hip with it switched off)
   g.prio_div = (g.tri_mode != 1 && g.tri_mode != 3 && g.tri_mode != 4) ? n_cu : 0;

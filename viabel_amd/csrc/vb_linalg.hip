@@ -582,9 +582,7 @@ int lr_path_terms(vb_ctx* ctx, const NoiseSlot& ns, const NoiseSlot& nz, int64_t
   const int k2 = (int)(2 * k);
   const int64_t ldk = round_up(k, 16), ldt = round_up(2 * k, 16) < 32 ? 32 : round_up(2 * k, 16);   // row strides of sw (d x k), T (n x 2k)
   const int n_rb = (int)((n + 127) / 128);
-  int splits = (int)(n / 256);
-  if (splits > 32) splits = 32;
-  if (splits < 1) splits = 1;
+  const int splits = gemm_lr_splits(n);
   const int64_t slab_et = d * ldt, slab_tt = (int64_t)k2 * ldt;
   const int64_t out_len = d * k2 + (int64_t)k2 * k2 + 2 * d + k2;
   int64_t off = 0;

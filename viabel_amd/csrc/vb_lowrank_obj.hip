@@ -718,8 +718,7 @@ int lr_elbo_sums_any_rank(vb_ctx* ctx, const NoiseSlot& ns, const NoiseSlot& nz,
   const int64_t ld = round_up(d, 16), kp = round_up(k, 16);
   if (nz.ld < kp) return fail(ctx, VB_ERR_STATE, "low-rank noise slot row stride %lld < %lld", (long long)nz.ld, (long long)kp);
   const int n_rb = (int)((n + 127) / 128);
-  int splits = (int)(n / 256);
-  splits = splits > 32 ? 32 : (splits < 1 ? 1 : splits);
+  const int splits = gemm_lr_splits(n);
   const int64_t p = 2 * d + d * k, n_out = 1 + p;
   int64_t off = 0;
   auto carve = [&off](int64_t doubles) {
