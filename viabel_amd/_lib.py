@@ -234,6 +234,39 @@ def ksd_split_tiles(tiles, splits):
     return [(k * int(tiles) // int(splits), (k + 1) * int(tiles) // int(splits)) for k in range(int(splits))]
 
 
+def _pair_arguments(x, scores, scale, entry, noun, axis, cap, log_w=None):
+    """What :func:`ksd_arguments` and :func:`svgd_arguments` share, in the order both report it: ``x`` (two axes, at most
+    ``cap`` rows, finite), ``scores`` (the shape of ``x``, finite), ksd's ``log_w`` and ``scale`` (one positive finite
+    entry per column).  ``noun`` and ``axis`` name the rows in the messages.  Returns ``(x, scores, log_w, scale)``."""
+    x = _f64(x)
+    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError('x must be ({0}, D) with {0} >= 1 and D >= 1; got shape {1}'.format(axis, x.shape))
+    n, d = x.shape
+    if n > cap:
+        raise NotImplementedError('{} takes at most {} {}; got {}'.format(entry, cap, noun, n))
+    if not np.all(np.isfinite(x)):
+        raise ValueError('the {} must be finite'.format(noun))
+    if scores is not None:
+        scores = _f64(scores)
+        if scores.shape != (n, d):
+            raise ValueError('scores must have the shape of x, {}; got {}'.format((n, d), scores.shape))
+        if not np.all(np.isfinite(scores)):
+            raise ValueError('the scores must be finite')
+    if log_w is not None:
+        if np.shape(log_w) != (n,):
+            raise ValueError('log_w must have shape ({},)'.format(n))
+        log_w = _f64(log_w)
+        if np.any(np.isnan(log_w)) or np.any(log_w == np.inf) or not np.any(np.isfinite(log_w)):
+            raise ValueError('no log weight is finite (or one is NaN or +inf)')
+    if scale is not None:
+        if np.shape(scale) != (d,):
+            raise ValueError('scale must have shape ({},)'.format(d))
+        scale = _f64(scale)
+        if not np.all(np.isfinite(scale) & (scale > 0.0)):
+            raise ValueError('scale must be positive and finite')
+    return x, scores, log_w, scale
+
+
 def ksd_arguments(x, scores=None, log_w=None, scale=None, c=1.0, beta=-0.5):
     """The arguments of ``vb_ksd`` checked and made contiguous doubles: ``(x, scores, log_w, scale, c, beta)``.
     ``ValueError`` for a wrong shape, non-finite draws or scores, no finite log weight, a scale that is not positive and
@@ -244,32 +277,7 @@ def ksd_arguments(x, scores=None, log_w=None, scale=None, c=1.0, beta=-0.5):
         raise ValueError('c must be positive and finite')
     if not (-1.0 < beta < 0.0):
         raise ValueError('beta must lie in (-1, 0)')
-    x = _f64(x)
-    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError('x must be (S, D) with S >= 1 and D >= 1; got shape {}'.format(x.shape))
-    s, d = x.shape
-    if s > KSD_MAX_DRAWS:
-        raise NotImplementedError('ksd takes at most {} draws; got {}'.format(KSD_MAX_DRAWS, s))
-    if not np.all(np.isfinite(x)):
-        raise ValueError('the draws must be finite')
-    if scores is not None:
-        scores = _f64(scores)
-        if scores.shape != (s, d):
-            raise ValueError('scores must have the shape of x, {}; got {}'.format((s, d), scores.shape))
-        if not np.all(np.isfinite(scores)):
-            raise ValueError('the scores must be finite')
-    if log_w is not None:
-        if np.shape(log_w) != (s,):
-            raise ValueError('log_w must have shape ({},)'.format(s))
-        log_w = _f64(log_w)
-        if np.any(np.isnan(log_w)) or np.any(log_w == np.inf) or not np.any(np.isfinite(log_w)):
-            raise ValueError('no log weight is finite (or one is NaN or +inf)')
-    if scale is not None:
-        if np.shape(scale) != (d,):
-            raise ValueError('scale must have shape ({},)'.format(d))
-        scale = _f64(scale)
-        if not np.all(np.isfinite(scale) & (scale > 0.0)):
-            raise ValueError('scale must be positive and finite')
+    x, scores, log_w, scale = _pair_arguments(x, scores, scale, 'ksd', 'draws', 'S', KSD_MAX_DRAWS, log_w)
     return x, scores, log_w, scale, c, beta
 
 
@@ -290,26 +298,7 @@ def svgd_arguments(x, scores=None, scale=None, bandwidth='median'):
         bandwidth = float(bandwidth)
         if not (bandwidth > 0.0 and np.isfinite(bandwidth)):
             raise ValueError("bandwidth must be 'median' or a positive finite number")
-    x = _f64(x)
-    if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError('x must be (n, D) with n >= 1 and D >= 1; got shape {}'.format(x.shape))
-    n, d = x.shape
-    if n > SVGD_MAX_PARTICLES:
-        raise NotImplementedError('svgd takes at most {} particles; got {}'.format(SVGD_MAX_PARTICLES, n))
-    if not np.all(np.isfinite(x)):
-        raise ValueError('the particles must be finite')
-    if scores is not None:
-        scores = _f64(scores)
-        if scores.shape != (n, d):
-            raise ValueError('scores must have the shape of x, {}; got {}'.format((n, d), scores.shape))
-        if not np.all(np.isfinite(scores)):
-            raise ValueError('the scores must be finite')
-    if scale is not None:
-        if np.shape(scale) != (d,):
-            raise ValueError('scale must have shape ({},)'.format(d))
-        scale = _f64(scale)
-        if not np.all(np.isfinite(scale) & (scale > 0.0)):
-            raise ValueError('scale must be positive and finite')
+    x, scores, _, scale = _pair_arguments(x, scores, scale, 'svgd', 'particles', 'n', SVGD_MAX_PARTICLES)
     return x, scores, scale, bandwidth
 
 

@@ -125,17 +125,15 @@
 // The three entries fill one request (HmcRun) and call hmc_run, whose body is the lists above: hmc_refuse, hmc_layout (one
 // named offset per workspace piece), hmc_upload, hmc_bind (the kernels' argument structs on the workspace: HmcDev), then per
 // iteration hmc_trajectory, hmc_chees_criterion (ChEES warm-up), hmc_end, hmc_window_moments (moment_shift given) and
-// hmc_adapt (ChEES: with the step-count fetches), and at last hmc_download.
-#include "vb_rows_target.h"
+// hmc_adapt (ChEES: with the step-count fetches), and at last hmc_download.  A StreamDrain declared before the upload
+// synchronises the stream on every way out.  It, the model refusals, the row copies, the uniforms' pseudo column and the
+// divergence threshold are vb_particles.h's, shared with vb_smc.hip, vb_svgd.hip and vb_ksd.hip.
+#include "vb_particles.h"
 #include "vb_rng.h"
-
-#include <cmath>
 
 namespace vb {
 
 constexpr int64_t kHmcDrawBudgetBytes = (int64_t)1 << 30;      // the device copy of the kept draws
-constexpr uint32_t kHmcUniformCol = 0xFFFFFFFEu;               // pseudo column of the accept / jitter uniforms
-constexpr double kHmcDivergence = 1000.0;                      // an energy error above this is a divergence
 constexpr double kHmcGamma = 0.05, kHmcT0 = 10.0, kHmcKappa = 0.75;
 
 // state[]: what the adapt kernel carries from one iteration to the next
@@ -239,8 +237,8 @@ __global__ void __launch_bounds__(256) hmc_end_kernel(const HmcArgs a, const Hmc
   const double fprop = a.fp[c];
   const double h0 = a.H0[c], h1 = -fprop + 0.5 * ke;
   const double dh = h0 - h1;
-  const bool divergent = !isfinite(dh) || h1 - h0 > kHmcDivergence;
-  const Philox4 o = philox_sub((uint64_t)c, kHmcUniformCol, e.w, 0, e.k0, e.k1);
+  const bool divergent = !isfinite(dh) || h1 - h0 > kDivergence;
+  const Philox4 o = philox_sub((uint64_t)c, kUniformCol, e.w, 0, e.k0, e.k1);
   const bool accept = !divergent && log(u01(o.x, o.y)) < dh;
   const double* xs = accept ? a.xp : a.x;
   for (int col = lane; col < a.d; col += 64) {
@@ -310,7 +308,7 @@ __global__ void __launch_bounds__(256) hmc_adapt_kernel(const HmcAdaptArgs q) {
   }
   q.state[HS_BASE] = base;
   if (q.t + 1 < q.n_iter) {
-    const Philox4 o = philox_sub(~(uint64_t)0, kHmcUniformCol, q.w_next, 0, q.k0, q.k1_next);
+    const Philox4 o = philox_sub(~(uint64_t)0, kUniformCol, q.w_next, 0, q.k0, q.k1_next);
     const double eps = base * (1.0 + q.jitter * (2.0 * u01(o.z, o.w) - 1.0));
     q.state[HS_EPS] = eps;
     q.step_hist[q.t + 1] = eps;
@@ -564,7 +562,7 @@ __global__ void __launch_bounds__(256) hmc_chees_adapt_kernel(const HmcAdaptArgs
   }
   if (q.t + 1 >= q.n_iter) return;
   if (q.t + 1 < q.n_warmup) {
-    const Philox4 o = philox_sub(~(uint64_t)0, kHmcUniformCol, q.w_next, 0, q.k0, q.k1_next);
+    const Philox4 o = philox_sub(~(uint64_t)0, kUniformCol, q.w_next, 0, q.k0, q.k1_next);
     const double eps = base * (1.0 + q.jitter * (2.0 * u01(o.z, o.w) - 1.0));
     const double traj = exp(q.state[HS_LOG_T]);
     const long long n_leap = chees_steps(chees_halton(q.w_next + 1u) * traj, eps, z.max_leapfrog);
@@ -597,7 +595,7 @@ __global__ void __launch_bounds__(256) hmc_chees_plan_kernel(const HmcCheesPlanA
   if (t >= q.n_iter) return;
   const uint64_t s = q.stream_offset + (uint64_t)t;
   const double base = q.state[HS_BASE];
-  const Philox4 o = philox_sub(~(uint64_t)0, kHmcUniformCol, (uint32_t)s, 0, q.k0, q.seed_hi ^ (uint32_t)(s >> 32));
+  const Philox4 o = philox_sub(~(uint64_t)0, kUniformCol, (uint32_t)s, 0, q.k0, q.seed_hi ^ (uint32_t)(s >> 32));
   const double eps = base * (1.0 + q.jitter * (2.0 * u01(o.z, o.w) - 1.0));
   const double traj = exp(q.state[HS_LOG_TBAR]);
   q.step_hist[t] = eps;
@@ -652,15 +650,11 @@ static int hmc_refuse(vb_ctx* ctx, const HmcRun& r) {
     return fail(ctx, VB_ERR_INVALID, "step_size must be positive and finite");
   if (!(r.target_accept > 0.0 && r.target_accept < 1.0)) return fail(ctx, VB_ERR_INVALID, "target_accept must lie in (0, 1)");
   if (!(r.jitter >= 0.0 && r.jitter < 1.0)) return fail(ctx, VB_ERR_INVALID, "jitter must lie in [0, 1)");
-  const ModelDev& m = ctx->model;
-  if (m.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model)");
-  if (d != m.dim) return fail(ctx, VB_ERR_INVALID, "x0 has %lld columns, model dimension is %d", (long long)d, m.dim);
+  VB_TRY(model_bound_refuse(ctx, r.name, "x0", d));
   if (r.dense() && d > kHmcDenseMaxDim)
     return fail(ctx, VB_ERR_UNSUPPORTED, "the dense metric takes at most %d dimensions (got %lld)", kHmcDenseMaxDim, (long long)d);
   if (!r.dense()) {
-    for (int64_t j = 0; j < d; ++j)
-      if (!(r.metric[j] > 0.0) || !std::isfinite(r.metric[j]))
-        return fail(ctx, VB_ERR_INVALID, "inv_mass[%lld] must be positive and finite", (long long)j);
+    VB_TRY(positive_finite(ctx, r.name, "inv_mass", r.metric, d));
   } else {
     for (int64_t i = 0; i < d; ++i) {
       if (!(r.metric[i * d + i] > 0.0) || !std::isfinite(r.metric[i * d + i]))
@@ -670,10 +664,7 @@ static int hmc_refuse(vb_ctx* ctx, const HmcRun& r) {
           return fail(ctx, VB_ERR_INVALID, "L[%lld][%lld] must be finite", (long long)i, (long long)j);
     }
   }
-  if (m.id == VB_MODEL_SOURCE && ctx->user_host_fn)
-    return fail(ctx, VB_ERR_UNSUPPORTED, "%s runs without host synchronisation: a host-callback model cannot be its "
-                                         "target (write the density as a source model)", r.name);
-  if (ctx->comm) return fail(ctx, VB_ERR_UNSUPPORTED, "%s runs on one process's engine: detach the communicator", r.name);
+  VB_TRY(model_device_refuse(ctx, r.name, false, true));
   if (r.n_chains > ((int64_t)1 << 31) - 8 || r.n_iter() > ((int64_t)1 << 40) ||
       (double)r.n_chains * (double)round_up(d, 16) > 0x1p36)
     return fail(ctx, VB_ERR_UNSUPPORTED, "%s takes at most 2^31 - 8 chains, 2^36 chain coordinates (n_chains x "
@@ -713,15 +704,14 @@ static HmcLayout hmc_layout(const HmcRun& r) {
   return o;
 }
 
-// Upload: the zeroed prefix, x0, the metric, the shift.  `pack` must outlive the call's last synchronisation.
+// Upload: the zeroed prefix, x0, the metric, the shift.  `pack` is read until the stream is next drained.
 static int hmc_upload(vb_ctx* ctx, const HmcRun& r, const HmcLayout& o, std::vector<double>& pack) {
   hipStream_t st = ctx->stream;
   double* base = (double*)ctx->hmc_work.ptr;
   const int64_t d = r.d, ld = o.ld;
   // everything up to the draws starts from zero: pad columns, Welford sums, counts, state, the factors' pads, the moments
   VB_HIP(ctx, hipMemsetAsync(base, 0, (size_t)o.zeroed * sizeof(double), st));
-  VB_HIP(ctx, hipMemcpy2DAsync(base + o.x, (size_t)ld * sizeof(double), r.x0, (size_t)d * sizeof(double),
-                               (size_t)d * sizeof(double), (size_t)r.n_chains, hipMemcpyHostToDevice, st));
+  VB_TRY(upload_rows(ctx, base + o.x, r.x0, r.n_chains, d, ld, false));
   if (!r.dense()) {
     VB_HIP(ctx, hipMemcpyAsync(base + o.inv_mass, r.metric, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
   } else {                       // [L | L'], each ld x ld with zeros above / below the diagonal and in the pads
@@ -907,7 +897,7 @@ static int hmc_download(vb_ctx* ctx, const HmcRun& r, const HmcDev& v) {
     return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
   };
   auto rows = [&](double* dst, const double* src) {                 // C x d out of C x ld
-    return dst ? hipMemcpy2DAsync(dst, d * W, src, (size_t)a.ld * W, d * W, C, hipMemcpyDeviceToHost, st) : hipSuccess;
+    return dst ? download_rows(ctx, dst, src, r.n_chains, r.d, a.ld) : hipSuccess;
   };
   VB_HIP(ctx, rows(r.last_x, a.x));
   VB_HIP(ctx, rows(r.chain_mean, a.mean));
@@ -944,7 +934,8 @@ static int hmc_run(vb_ctx* ctx, const HmcRun& r) {
   VB_TRY(main_stream_write(ctx));
   const HmcLayout lay = hmc_layout(r);
   VB_TRY(ensure(ctx, ctx->hmc_work, (size_t)lay.total * sizeof(double)));
-  std::vector<double> pack;      // the dense factors' staging: lives until hmc_download's synchronisation
+  std::vector<double> pack;      // the dense factors' staging
+  StreamDrain drain{ctx->stream};
   VB_TRY(hmc_upload(ctx, r, lay, pack));
   HmcDev dev = hmc_bind(ctx, r, lay);
   VB_TRY(model_grad_rows(ctx, dev.a.x, lay.ld, r.n_chains, r.d, dev.a.g, dev.a.f));      // f, g of the start: carried from here on

@@ -11,19 +11,15 @@
 //   ksd_pair_kernel    one workgroup per (row block of 64 draws, column split): the hot path, one partial per (row, split)
 //   ksd_finish_kernel  rowsums = the partials in split order, ksd2 = sum_i w_i rowsums[i] in one workgroup's fixed tree
 // Nothing of order S^2 is stored, no floating-point atomics: two calls with the same inputs return the same bits.
+// The pair tile's constants and draw order (pair_draw), the 256-thread sum and the host's refusals, row copies, workspace
+// carver and stream guard are vb_particles.h's, shared with vb_svgd.hip.
 #include <cmath>
 #include <vector>
 
-#include "vb_common.h"
-#include "vb_psis_util.h"
+#include "vb_particles.h"
 
 namespace vb {
 
-constexpr int kKsdTile = 64;              // draws per row block and per column tile
-constexpr int kKsdK = 16;                 // coordinates per LDS step
-constexpr int kKsdLdsRow = kKsdTile + 2;  // doubles per coordinate in LDS: the two more keep the staging stores (four
-                                          // coordinates 2 q apart per 16 lanes) on distinct banks; reads have one coordinate
-                                          // per instruction and do not care
 constexpr int64_t kKsdMaxDraws = 65536;
 
 struct KsdStageArgs {
@@ -64,10 +60,6 @@ struct KsdPairArgs {
   double c2, beta, dim;     // c^2, beta, D as a double
 };
 
-// the thread's four draws of a 64-draw tile: two adjacent pairs 32 apart, so that the 16 lanes of one ds_read_b128 group
-// read 256 contiguous bytes (threads along the tile) or two adjacent 16-byte pieces (threads across it, broadcast)
-__device__ __forceinline__ int ksd_draw(int t, int q) { return (q >> 1) * 32 + t * 2 + (q & 1); }
-
 // tiles [first, last) of column split `split`: contiguous ranges whose lengths differ by at most one
 __host__ __device__ __forceinline__ int ksd_split_first(int split, int tiles, int splits) {
   return (int)((int64_t)split * tiles / splits);
@@ -75,19 +67,19 @@ __host__ __device__ __forceinline__ int ksd_split_first(int split, int tiles, in
 
 __global__ void __launch_bounds__(256) ksd_pair_kernel(const KsdPairArgs a) {
   // [Xi | Gi | Xj | Gj][coordinate][draw]
-  __shared__ __attribute__((aligned(16))) double sh[4][kKsdK][kKsdLdsRow];
+  __shared__ __attribute__((aligned(16))) double sh[4][kPairK][kPairLdsRow];
   const int tid = threadIdx.x;
   const int tx = tid & 15, ty = tid >> 4;       // columns / rows of the thread's 4 x 4 pairs
   const int lr = tid >> 2, lq = tid & 3;        // staging: draw lr of the tile, coordinates 2 lq, 2 lq + 1, 8 + 2 lq, 9 + 2 lq
   const int rb = blockIdx.x, split = blockIdx.y;
   const int t0 = ksd_split_first(split, a.tiles, a.splits), t1 = ksd_split_first(split + 1, a.tiles, a.splits);
-  const int nk = (int)(a.ld / kKsdK);
-  const int64_t off_i = ((int64_t)rb * kKsdTile + lr) * a.ld + 2 * lq;
+  const int nk = (int)(a.ld / kPairK);
+  const int64_t off_i = ((int64_t)rb * kPairTile + lr) * a.ld + 2 * lq;
   const double mb2 = -2.0 * a.beta, mb4 = -4.0 * a.beta * (a.beta - 1.0), bm2 = a.beta - 2.0;
 
   double rowacc[4] = {0.0, 0.0, 0.0, 0.0};
   for (int t = t0; t < t1; ++t) {
-    const int64_t off_j = ((int64_t)t * kKsdTile + lr) * a.ld + 2 * lq;
+    const int64_t off_j = ((int64_t)t * kPairTile + lr) * a.ld + 2 * lq;
     double r2[4][4], aa[4][4], bb[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -96,7 +88,7 @@ __global__ void __launch_bounds__(256) ksd_pair_kernel(const KsdPairArgs a) {
 
     double2 pre[4][2];                          // the next step's 16 doubles of this thread
     auto fetch = [&](int ks) {
-      const int64_t k0 = (int64_t)ks * kKsdK;
+      const int64_t k0 = (int64_t)ks * kPairK;
       const double* src[4] = {a.X + off_i + k0, a.G + off_i + k0, a.X + off_j + k0, a.G + off_j + k0};
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
@@ -117,7 +109,7 @@ __global__ void __launch_bounds__(256) ksd_pair_kernel(const KsdPairArgs a) {
       __syncthreads();
       if (ks + 1 < nk) fetch(ks + 1);
 #pragma unroll 4
-      for (int k = 0; k < kKsdK; ++k) {
+      for (int k = 0; k < kPairK; ++k) {
         double xi[4], gi[4], xj[4], gj[4];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -146,7 +138,7 @@ __global__ void __launch_bounds__(256) ksd_pair_kernel(const KsdPairArgs a) {
     // share the rows in a fixed butterfly (every lane ends with the same bits)
     double wj[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) wj[j] = a.w[(int64_t)t * kKsdTile + ksd_draw(tx, j)];
+    for (int j = 0; j < 4; ++j) wj[j] = a.w[(int64_t)t * kPairTile + pair_draw(tx, j)];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       double v = 0.0;
@@ -163,18 +155,10 @@ __global__ void __launch_bounds__(256) ksd_pair_kernel(const KsdPairArgs a) {
     }
   }
   if (tx == 0) {
-    double* out = a.partial + (int64_t)split * a.sp + (int64_t)rb * kKsdTile;
+    double* out = a.partial + (int64_t)split * a.sp + (int64_t)rb * kPairTile;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) out[ksd_draw(ty, i)] = rowacc[i];
+    for (int i = 0; i < 4; ++i) out[pair_draw(ty, i)] = rowacc[i];
   }
-}
-
-__device__ __forceinline__ double ksd_block_sum(double x, double* sh) {      // 256 threads, a fixed tree
-  x = ps_wave_sum(x);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
 // one workgroup: rowsums[i] = the row's partials in split order; ksd2 = sum_i w_i rowsums[i], thread t taking rows
@@ -190,7 +174,7 @@ __global__ void __launch_bounds__(256) ksd_finish_kernel(const double* __restric
     rowsums[i] = r;
     acc = fma(w[i], r, acc);
   }
-  acc = ksd_block_sum(acc, sh);
+  acc = block_sum(acc, sh);
   if (threadIdx.x == 0) *ksd2 = acc;
 }
 
@@ -201,7 +185,7 @@ struct KsdLayout {
   int64_t o_x, o_g, o_w, o_f, o_scale, o_part, o_rows, o_out, total;
 };
 static void ksd_plan(int64_t s, int n_cu, int* row_blocks, int* splits) {
-  const int64_t tiles = (s + kKsdTile - 1) / kKsdTile;
+  const int64_t tiles = (s + kPairTile - 1) / kPairTile;
   // two workgroups per compute unit (what the pair kernel's registers allow) when the column tiles can be dealt that far
   int64_t sp = (2 * (int64_t)n_cu + tiles - 1) / tiles;
   sp = sp < 1 ? 1 : (sp > tiles ? tiles : sp);
@@ -209,17 +193,12 @@ static void ksd_plan(int64_t s, int n_cu, int* row_blocks, int* splits) {
 }
 static KsdLayout ksd_layout(int64_t s, int64_t d, int n_cu) {
   KsdLayout L;
-  L.sp = round_up(s, kKsdTile), L.ld = round_up(d, 16);
+  L.sp = round_up(s, kPairTile), L.ld = round_up(d, 16);
   ksd_plan(s, n_cu, &L.tiles, &L.splits);
-  int64_t off = 0;
-  auto carve = [&off](int64_t doubles) {
-    const int64_t o = off;
-    off += round_up(doubles, 16);
-    return o;
-  };
+  Carver carve;
   L.o_x = carve(L.sp * L.ld), L.o_g = carve(L.sp * L.ld), L.o_w = carve(L.sp), L.o_f = carve(L.sp), L.o_scale = carve(L.ld),
   L.o_part = carve((int64_t)L.splits * L.sp), L.o_rows = carve(L.sp), L.o_out = carve(16);
-  L.total = off;
+  L.total = carve.off;
   return L;
 }
 
@@ -244,44 +223,29 @@ int vb_ksd(vb_ctx* ctx, const double* x, int64_t s, int64_t d, const double* sco
   if (d < 1 || d > 0x7fffffffll - 16) return fail(ctx, VB_ERR_INVALID, "the dimension must be positive");
   if (!(c > 0.0) || !std::isfinite(c)) return fail(ctx, VB_ERR_INVALID, "c must be positive and finite");
   if (!(beta > -1.0 && beta < 0.0)) return fail(ctx, VB_ERR_INVALID, "beta must lie in (-1, 0)");
-  if (scale)
-    for (int64_t j = 0; j < d; ++j)
-      if (!(scale[j] > 0.0) || !std::isfinite(scale[j]))
-        return fail(ctx, VB_ERR_INVALID, "scale must be positive and finite (entry %lld)", (long long)j);
+  if (scale) VB_TRY(positive_finite(ctx, "vb_ksd", "scale", scale, d));
   if (!scores) {
-    const ModelDev& m = ctx->model;
-    if (m.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model) and no scores given");
-    if (d != m.dim) return fail(ctx, VB_ERR_INVALID, "x has %lld columns, model dimension is %d", (long long)d, m.dim);
-    if (m.id == VB_MODEL_SOURCE && ctx->user_host_fn)
-      return fail(ctx, VB_ERR_UNSUPPORTED, "vb_ksd evaluates the scores on the device: a host-callback model cannot supply "
-                                           "them (pass scores)");
-    if (m.id == VB_MODEL_MINIBATCH_GLM)
-      return fail(ctx, VB_ERR_UNSUPPORTED, "vb_ksd needs the scores of the whole target: the minibatch target's change from "
-                                           "batch to batch (bind the full-data model, or pass scores)");
+    VB_TRY(model_bound_refuse(ctx, "vb_ksd", "x", d, ", or pass scores"));
+    VB_TRY(model_device_refuse(ctx, "vb_ksd", true, false, ", or pass scores"));
   }
   std::vector<double> wv;
   if (!predict_weights(log_w, s, wv)) return fail(ctx, VB_ERR_INVALID, "no log weight is finite (or one is NaN or +inf)");
   VB_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  struct Drain {      // the host buffers of the asynchronous uploads outlive them on every way out
-    hipStream_t st;
-    ~Drain() { (void)hipStreamSynchronize(st); }
-  } drain{st};
+  StreamDrain drain{st};
   const KsdLayout L = ksd_layout(s, d, ctx->prop.multiProcessorCount);
   VB_TRY(ensure(ctx, ctx->ksd_work, (size_t)L.total * sizeof(double)));
   double* base = (double*)ctx->ksd_work.ptr;
   double *X = base + L.o_x, *G = base + L.o_g, *w = base + L.o_w;
-  const size_t row_bytes = (size_t)d * sizeof(double), ld_bytes = (size_t)L.ld * sizeof(double);
-  // the s live rows: padding columns zero for the model's row kernels (the staging kernel zeroes them again, and the rows
-  // past s)
-  if (L.ld != d) VB_HIP(ctx, hipMemsetAsync(X, 0, (size_t)s * ld_bytes, st));
-  VB_HIP(ctx, hipMemcpy2DAsync(X, ld_bytes, x, row_bytes, row_bytes, (size_t)s, hipMemcpyHostToDevice, st));
+  // the s live rows: padding columns zero for the model's row kernels; the staging kernel zeroes them again, and the rows
+  // past s, and is the first to read the scores' pads
+  VB_TRY(upload_rows(ctx, X, x, s, d, L.ld));
   if (scores)
-    VB_HIP(ctx, hipMemcpy2DAsync(G, ld_bytes, scores, row_bytes, row_bytes, (size_t)s, hipMemcpyHostToDevice, st));
+    VB_TRY(upload_rows(ctx, G, scores, s, d, L.ld, false));
   else
     VB_TRY(model_grad_rows(ctx, X, L.ld, s, d, G, base + L.o_f));
   VB_HIP(ctx, hipMemcpyAsync(w, wv.data(), (size_t)s * sizeof(double), hipMemcpyHostToDevice, st));
-  if (scale) VB_HIP(ctx, hipMemcpyAsync(base + L.o_scale, scale, row_bytes, hipMemcpyHostToDevice, st));
+  if (scale) VB_HIP(ctx, hipMemcpyAsync(base + L.o_scale, scale, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
 
   const KsdStageArgs sa{X, G, w, scale ? base + L.o_scale : nullptr, s, L.sp, L.ld, (int)d};
   hipLaunchKernelGGL(ksd_stage_kernel, dim3((unsigned)L.sp), dim3(256), 0, st, sa);

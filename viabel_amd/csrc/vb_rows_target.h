@@ -1,6 +1,7 @@
-// What the rows targets share (vb_softmax.hip, vb_multilevel.hip, vb_locscale.hip, vb_sparse.hip, vb_neuralnet.hip): the
-// plain-store GEMM epilogue, the wave and workgroup sums in their fixed order, the per-observation constant of a GLM
-// likelihood, and the host pieces of a layout, of the argument checks and of vb_set_model.  Not part of the C ABI.
+// What the rows targets share (vb_softmax.hip, vb_multilevel.hip, vb_locscale.hip, vb_sparse.hip, vb_neuralnet.hip) and,
+// through vb_particles.h, the particle entries: the plain-store GEMM epilogue, the wave and workgroup sums in their fixed
+// order, the per-observation constant of a GLM likelihood, and the host pieces of a layout, of the argument checks and of
+// vb_set_model.  Not part of the C ABI.
 #pragma once
 
 #include "vb_common.h"
@@ -25,6 +26,11 @@ struct EpiStorePlain {       // Y = acc
 __device__ __forceinline__ double wave_sum(double x) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+  return x;
+}
+__device__ __forceinline__ double wave_max(double x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x = fmax(x, __shfl_down(x, off, 64));
   return x;
 }
 

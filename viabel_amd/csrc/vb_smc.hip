@@ -39,7 +39,9 @@
 //                        three kernels above read it.  No jitter.
 // 4 + n_moves (3 + (n_leapfrog - 1)) launches of this file per stage beside the n_moves n_leapfrog gradient evaluations and
 // one start kernel per run.  No floating-point atomics; every sum has a fixed order: two runs with equal arguments return
-// equal bits.  vb_hmc.hip's kernels and entries are untouched (nothing is shared but vb_rng.h and wave_sum).
+// equal bits.  Shared with vb_hmc.hip through vb_particles.h: wave_sum and wave_max, the uniforms' pseudo column and the
+// divergence threshold of the Metropolis decision, and the host's refusals, row copies and stream guard.  The leapfrog
+// kernels are this file's own: the tempered gradient is another formula than vb_hmc.hip's.
 //
 // Workspace: vb_ctx::smc_work, laid out from scratch by every call -- [state A | state B (each x | g (n x ld) | f | lq (n)) |
 // xp | gp | p (n x ld) | fp | H0 | a (n) | flags (n, int) | w | cdf (n) | block totals (64) | anc (n, int64) | loc | scale |
@@ -64,10 +66,8 @@
 // passes of 1.9 us: latency-bound), scan 5.0, search 5.3, gather 5.0, begin 6.1, leap 5.0, end 5.2, control 4.8 us: reweight +
 // resample + gather (94 us) are below one gradient evaluation at the logistic shape and above one (76 us) at the multilevel
 // shape.  The numpy loop around vb_model_grad takes 10.95 / 8.81 ms per stage (n = 1024).
-#include "vb_rows_target.h"
+#include "vb_particles.h"
 #include "vb_rng.h"
-
-#include <cmath>
 
 namespace vb {
 
@@ -75,9 +75,6 @@ constexpr int64_t kSmcMaxParticles = 65536;
 constexpr int kSmcScanPerThread = 4, kSmcScanBlock = 256 * kSmcScanPerThread;      // 1024 weights per scan workgroup
 constexpr int kSmcMaxScanBlocks = (int)(kSmcMaxParticles / kSmcScanBlock);         // 64
 constexpr int kSmcBisections = 40;
-constexpr uint32_t kSmcUniformCol = 0xFFFFFFFEu;               // pseudo column of the accept / stage uniforms (as vb_hmc.hip)
-constexpr double kSmcDivergence = 1000.0;
-constexpr double kSmcHalfLog2Pi = 0.91893853320467274178;
 
 // state[]: what the kernels carry in device memory (SS_BETA and SS_STATUS adjacent: the stage's one fetch);
 // SS_LQ_CONST = -sum_j log scale_j - d/2 log 2 pi, formed once on the host
@@ -137,12 +134,6 @@ struct SmcReweightArgs {
   double ess_target;
 };
 
-__device__ __forceinline__ double smc_wave_max(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x = fmax(x, __shfl_down(x, off, 64));
-  return x;
-}
-
 // (sum e^{delta v}, sum e^{2 delta v}) over the particles, broadcast to every thread; optionally the weights stored
 template <bool STORE>
 __device__ __forceinline__ void smc_weight_sums(double* v, int64_t n, double delta, double (*sh)[16], double* bc, double* s1,
@@ -186,7 +177,7 @@ __global__ void __launch_bounds__(1024) smc_reweight_kernel(const SmcReweightArg
     q.w[i] = u;
   }
   if (bad) bad_any = 1;            // (every writer stores the same value)
-  m = smc_wave_max(m);
+  m = wave_max(m);
   if ((t & 63) == 0) sh[0][t >> 6] = m;
   __syncthreads();
   if (t == 0) {
@@ -289,7 +280,7 @@ __global__ void __launch_bounds__(256) smc_search_kernel(const SmcResampleArgs q
   if (i >= q.n) return;
   double U = q.uniform;
   if (q.from_stream) {
-    const Philox4 o = philox_sub(~(uint64_t)0, kSmcUniformCol, q.wlo, 0, q.k0, q.k1);
+    const Philox4 o = philox_sub(~(uint64_t)0, kUniformCol, q.wlo, 0, q.k0, q.k1);
     U = u01(o.z, o.w);
   }
   const double total = boff[q.n_blocks];
@@ -408,8 +399,8 @@ __global__ void __launch_bounds__(256) smc_end_kernel(const SmcMoveArgs a, uint3
   const double fprop = a.fp[c];
   const double h0 = a.H0[c], h1 = -(beta * fprop + omb * lqp) + 0.5 * ke;
   const double dh = h0 - h1;
-  const bool divergent = !isfinite(dh) || h1 - h0 > kSmcDivergence;
-  const Philox4 o = philox_sub((uint64_t)c, kSmcUniformCol, w, 0, k0, k1);
+  const bool divergent = !isfinite(dh) || h1 - h0 > kDivergence;
+  const Philox4 o = philox_sub((uint64_t)c, kUniformCol, w, 0, k0, k1);
   const bool accept = !divergent && log(u01(o.x, o.y)) < dh;
   if (accept)
     for (int col = lane; col < a.d; col += 64) {
@@ -553,6 +544,7 @@ int vb_smc_reweight(vb_ctx* ctx, const double* u, int64_t n, double beta_prev, d
   SmcParticles s = smc_particles(base + o.sa, n, o.mat);
   double state[SS_NUM] = {0.0};
   state[SS_BETA] = beta_prev;
+  StreamDrain drain{st};
   VB_HIP(ctx, hipMemcpyAsync(base + o.state, state, sizeof(state), hipMemcpyHostToDevice, st));
   VB_HIP(ctx, hipMemcpyAsync(s.f, u, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
   SmcResampleArgs rs{};
@@ -581,18 +573,13 @@ int vb_smc_run(vb_ctx* ctx, const double* loc, const double* scale, int64_t n, i
   if (!(step_size > 0.0) || !std::isfinite(step_size)) return fail(ctx, VB_ERR_INVALID, "step_size must be positive and finite");
   if (!(target_accept > 0.0 && target_accept < 1.0)) return fail(ctx, VB_ERR_INVALID, "target_accept must lie in (0, 1)");
   if (!(adapt_rate >= 0.0) || !std::isfinite(adapt_rate)) return fail(ctx, VB_ERR_INVALID, "adapt_rate must be non-negative and finite");
-  const ModelDev& m = ctx->model;
-  if (m.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model)");
-  if (d != m.dim) return fail(ctx, VB_ERR_INVALID, "loc has %lld entries, model dimension is %d", (long long)d, m.dim);
+  VB_TRY(model_bound_refuse(ctx, name, "loc", d));
   for (int64_t j = 0; j < d; ++j) {
-    if (!std::isfinite(loc[j])) return fail(ctx, VB_ERR_INVALID, "loc[%lld] must be finite", (long long)j);
+    if (!std::isfinite(loc[j])) return fail(ctx, VB_ERR_INVALID, "%s: loc[%lld] must be finite", name, (long long)j);
     if (!(scale[j] > 0.0) || !std::isfinite(scale[j]))
-      return fail(ctx, VB_ERR_INVALID, "scale[%lld] must be positive and finite", (long long)j);
+      return fail(ctx, VB_ERR_INVALID, "%s: scale[%lld] must be positive and finite", name, (long long)j);
   }
-  if (m.id == VB_MODEL_SOURCE && ctx->user_host_fn)
-    return fail(ctx, VB_ERR_UNSUPPORTED, "%s moves the particles on the device: a host-callback model cannot be its target "
-                                         "(write the density as a source model)", name);
-  if (ctx->comm) return fail(ctx, VB_ERR_UNSUPPORTED, "%s runs on one process's engine: detach the communicator", name);
+  VB_TRY(model_device_refuse(ctx, name, false, true));
   if (n > kSmcMaxParticles)
     return fail(ctx, VB_ERR_UNSUPPORTED, "%s takes at most %lld particles (got %lld)", name, (long long)kSmcMaxParticles, (long long)n);
   if ((double)n * (double)round_up(d, 16) > 0x1p36 || (double)max_stages * (double)n_moves > 0x1p31 ||
@@ -608,7 +595,8 @@ int vb_smc_run(vb_ctx* ctx, const double* loc, const double* scale, int64_t n, i
   const int64_t ld = o.ld, T = max_stages * n_moves;
   const uint32_t k0 = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32);
 
-  // upload: everything but the ancestor history starts from zero (pads, state, histories); loc | scale | scale^2; the state
+  // upload: everything but the ancestor history starts from zero (pads, state, histories); loc | scale | scale^2; the state.
+  // pack and state are read until the stream is drained: the guard does that on every way out
   std::vector<double> pack((size_t)(3 * round_up(ld, 32)), 0.0);
   const int64_t stride = round_up(ld, 32);
   for (int64_t j = 0; j < ld; ++j) {
@@ -619,7 +607,8 @@ int vb_smc_run(vb_ctx* ctx, const double* loc, const double* scale, int64_t n, i
   double state[SS_NUM] = {0.0};
   state[SS_EPS] = step_size, state[SS_LOG_EPS] = log(step_size);
   for (int64_t j = 0; j < d; ++j) state[SS_LQ_CONST] -= log(scale[j]);
-  state[SS_LQ_CONST] -= (double)d * kSmcHalfLog2Pi;
+  state[SS_LQ_CONST] -= (double)d * kHalfLog2Pi;
+  StreamDrain drain{st};
   VB_HIP(ctx, hipMemsetAsync(base, 0, (size_t)o.zeroed * sizeof(double), st));
   VB_HIP(ctx, hipMemcpyAsync(base + o.loc, pack.data(), pack.size() * sizeof(double), hipMemcpyHostToDevice, st));
   VB_HIP(ctx, hipMemcpyAsync(base + o.state, state, sizeof(state), hipMemcpyHostToDevice, st));
@@ -695,7 +684,7 @@ int vb_smc_run(vb_ctx* ctx, const double* loc, const double* scale, int64_t n, i
 
   // download: the run's one other synchronisation
   const size_t W = sizeof(double);
-  VB_HIP(ctx, hipMemcpy2DAsync(x, (size_t)d * W, cur.x, (size_t)ld * W, (size_t)d * W, (size_t)n, hipMemcpyDeviceToHost, st));
+  VB_HIP(ctx, download_rows(ctx, x, cur.x, n, d, ld));
   VB_HIP(ctx, hipMemcpyAsync(logp, cur.f, (size_t)n * W, hipMemcpyDeviceToHost, st));
   VB_HIP(ctx, hipMemcpyAsync(log_base, cur.lq, (size_t)n * W, hipMemcpyDeviceToHost, st));
   VB_HIP(ctx, hipMemcpyAsync(beta_hist, base + o.beta_hist, (size_t)max_stages * W, hipMemcpyDeviceToHost, st));

@@ -21,19 +21,15 @@
 //   svgd_stats_kernel     (the run) mean log p, h and rms(phi) of the iteration into the histories
 // No floating-point atomics, every sum in a fixed order: two calls with the same inputs return the same bits, and the run
 // enqueues exactly what the direction entry enqueues, followed by fit_step_enqueue.
+// The pair tile's constants and draw order (pair_draw), the 256-thread sum and the host's refusals, row copies, workspace
+// carver and stream guard are vb_particles.h's, shared with vb_ksd.hip.
 #include <cmath>
 #include <vector>
 
-#include "vb_common.h"
-#include "vb_gemm_f64.h"
-#include "vb_psis_util.h"
-#include "vb_rows_target.h"
+#include "vb_particles.h"
 
 namespace vb {
 
-constexpr int kSvgdTile = 64;               // particles per row block and per column tile
-constexpr int kSvgdK = 16;                  // coordinates per LDS step
-constexpr int kSvgdLdsRow = kSvgdTile + 2;  // as vb_ksd.hip's kKsdLdsRow: the staging stores on distinct banks
 constexpr int64_t kSvgdMaxParticles = 8192; // the n x n matrix is stored: 512 MiB at the capacity
 constexpr int kSvgdBins = 8192;             // bins of one selection pass (13 bits)
 constexpr int kSvgdPasses = 5;
@@ -47,14 +43,6 @@ struct SvgdSel {                            // the selection's state, in device 
   double h;
   unsigned long long unused;
 };
-
-__device__ __forceinline__ double svgd_block_sum(double x, double* sh) {      // 256 threads, a fixed tree
-  x = ps_wave_sum(x);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
 
 constexpr int kSvgdMeanChunk = 256;          // rows per workgroup of the column-sum kernel
 
@@ -116,9 +104,6 @@ __global__ void __launch_bounds__(256) svgd_stage_kernel(const SvgdStageArgs a) 
   }
 }
 
-// the thread's four particles of a 64-particle tile (vb_ksd.hip's ksd_draw): two adjacent pairs 32 apart
-__device__ __forceinline__ int svgd_draw(int t, int q) { return (q >> 1) * 32 + t * 2 + (q & 1); }
-
 struct SvgdPairArgs {
   const double* Y;          // staged particles: row stride ldy (the right half of B)
   double* R;                // [np x np] squared distances
@@ -128,9 +113,9 @@ struct SvgdPairArgs {
 
 // grid = tiles (tiles + 1) / 2: workgroup t computes tile (rb, cb), cb <= rb, t = rb (rb + 1) / 2 + cb, and stores it at
 // (rb, cb) and, transposed, at (cb, rb) -- the same doubles, so the stored matrix is symmetric bit for bit.  256 threads,
-// 4 x 4 pairs per thread, operands through LDS.
+// 4 x 4 pairs per thread, operands through LDS: vb_ksd.hip's tiling with two operand streams in place of four.
 __global__ void __launch_bounds__(256) svgd_pair_kernel(const SvgdPairArgs a) {
-  __shared__ __attribute__((aligned(16))) double sh[2][kSvgdK][kSvgdLdsRow];      // [Yi | Yj][coordinate][particle]
+  __shared__ __attribute__((aligned(16))) double sh[2][kPairK][kPairLdsRow];      // [Yi | Yj][coordinate][particle]
   const int tid = threadIdx.x;
   const int tx = tid & 15, ty = tid >> 4;
   const int lr = tid >> 2, lq = tid & 3;        // staging: particle lr, coordinates 2 lq, 2 lq + 1, 8 + 2 lq, 9 + 2 lq
@@ -139,8 +124,8 @@ __global__ void __launch_bounds__(256) svgd_pair_kernel(const SvgdPairArgs a) {
   while ((rb + 1) * (rb + 2) / 2 <= t) ++rb;
   while (rb * (rb + 1) / 2 > t) --rb;
   const int cb = t - rb * (rb + 1) / 2;
-  const int64_t off_i = ((int64_t)rb * kSvgdTile + lr) * a.ldy + 2 * lq;
-  const int64_t off_j = ((int64_t)cb * kSvgdTile + lr) * a.ldy + 2 * lq;
+  const int64_t off_i = ((int64_t)rb * kPairTile + lr) * a.ldy + 2 * lq;
+  const int64_t off_j = ((int64_t)cb * kPairTile + lr) * a.ldy + 2 * lq;
 
   double r2[4][4];
 #pragma unroll
@@ -149,7 +134,7 @@ __global__ void __launch_bounds__(256) svgd_pair_kernel(const SvgdPairArgs a) {
     for (int j = 0; j < 4; ++j) r2[i][j] = 0.0;
   double2 pre[2][2];
   auto fetch = [&](int ks) {
-    const int64_t k0 = (int64_t)ks * kSvgdK;
+    const int64_t k0 = (int64_t)ks * kPairK;
     const double* src[2] = {a.Y + off_i + k0, a.Y + off_j + k0};
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -170,7 +155,7 @@ __global__ void __launch_bounds__(256) svgd_pair_kernel(const SvgdPairArgs a) {
     __syncthreads();
     if (ks + 1 < a.nk) fetch(ks + 1);
 #pragma unroll 4
-    for (int k = 0; k < kSvgdK; ++k) {
+    for (int k = 0; k < kPairK; ++k) {
       double yi[4], yj[4];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -188,15 +173,15 @@ __global__ void __launch_bounds__(256) svgd_pair_kernel(const SvgdPairArgs a) {
         }
     }
   }
-  // rows svgd_draw(ty, i), columns svgd_draw(tx, j): q = 0, 1 and q = 2, 3 are adjacent, 16-byte stores both ways
-  const int64_t row0 = (int64_t)rb * kSvgdTile, col0 = (int64_t)cb * kSvgdTile;
+  // rows pair_draw(ty, i), columns pair_draw(tx, j): q = 0, 1 and q = 2, 3 are adjacent, 16-byte stores both ways
+  const int64_t row0 = (int64_t)rb * kPairTile, col0 = (int64_t)cb * kPairTile;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int jp = 0; jp < 2; ++jp) {
       double2 v;
       v.x = r2[i][2 * jp], v.y = r2[i][2 * jp + 1];
-      *reinterpret_cast<double2*>(a.R + (row0 + svgd_draw(ty, i)) * a.np + col0 + svgd_draw(tx, 2 * jp)) = v;
+      *reinterpret_cast<double2*>(a.R + (row0 + pair_draw(ty, i)) * a.np + col0 + pair_draw(tx, 2 * jp)) = v;
     }
   if (rb != cb) {
 #pragma unroll
@@ -205,7 +190,7 @@ __global__ void __launch_bounds__(256) svgd_pair_kernel(const SvgdPairArgs a) {
       for (int ip = 0; ip < 2; ++ip) {
         double2 v;
         v.x = r2[2 * ip][j], v.y = r2[2 * ip + 1][j];
-        *reinterpret_cast<double2*>(a.R + (col0 + svgd_draw(tx, j)) * a.np + row0 + svgd_draw(ty, 2 * ip)) = v;
+        *reinterpret_cast<double2*>(a.R + (col0 + pair_draw(tx, j)) * a.np + row0 + pair_draw(ty, 2 * ip)) = v;
       }
   }
 }
@@ -303,7 +288,7 @@ __global__ void __launch_bounds__(256) svgd_map_kernel(double* __restrict__ R, i
     r[j] = v;
     acc += v;
   }
-  acc = svgd_block_sum(acc, sh);
+  acc = block_sum(acc, sh);
   if (threadIdx.x == 0) rowsum[row] = acc;
 }
 
@@ -338,7 +323,7 @@ __global__ void __launch_bounds__(256) svgd_finish_kernel(const SvgdFinishArgs a
     }
     acc = fma(v, v, acc);
   }
-  acc = svgd_block_sum(acc, sh);
+  acc = block_sum(acc, sh);
   if (threadIdx.x == 0) a.rowsq[row] = acc;
 }
 
@@ -351,8 +336,8 @@ __global__ void __launch_bounds__(256) svgd_stats_kernel(const double* __restric
   __shared__ double sh[4];
   double sq = 0.0, lp = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += 256) sq += rowsq[i], lp += f[i];
-  sq = svgd_block_sum(sq, sh);
-  lp = svgd_block_sum(lp, sh);
+  sq = block_sum(sq, sh);
+  lp = block_sum(lp, sh);
   if (threadIdx.x == 0) {
     value[0] = lp / (double)n;
     h_hist[k] = sel->h;
@@ -368,21 +353,16 @@ struct SvgdLayout {
 };
 static SvgdLayout svgd_layout(int64_t n, int64_t d, int64_t n_iters) {
   SvgdLayout L;
-  L.n = n, L.d = d, L.np = round_up(n, kSvgdTile), L.ld = round_up(d, 16);
-  int64_t off = 0;
-  auto carve = [&off](int64_t doubles) {
-    const int64_t o = off;
-    off += round_up(doubles, 32);
-    return o;
-  };
+  L.n = n, L.d = d, L.np = round_up(n, kPairTile), L.ld = round_up(d, 16);
+  Carver carve;
   L.o_x = carve(L.np * L.ld), L.o_g = carve(L.np * L.ld), L.o_f = carve(L.np), L.o_c = carve(L.ld), L.o_scale = carve(L.ld);
-  L.o_cpart = carve((L.np / kSvgdTile + 3) / 4 * L.ld);      // one row of column sums per 256-row chunk
+  L.o_cpart = carve((L.np / kPairTile + 3) / 4 * L.ld);      // one row of column sums per 256-row chunk
   L.o_b = carve(L.np * 2 * L.ld), L.o_r = carve(L.np * L.np), L.o_rowsum = carve(L.np), L.o_p = carve(L.np * 2 * L.ld);
   L.o_rowsq = carve(L.np), L.o_sel = carve(sizeof(SvgdSel) / sizeof(double)), L.o_hist = carve(kSvgdBins / 2);
   L.o_out = carve(1 + L.np * L.ld);      // [value | -phi]: fit_step_enqueue's (value, gradient)
   L.o_s1 = carve(n_iters ? n * L.ld : 0), L.o_s2 = carve(n_iters ? n * L.ld : 0);
   L.o_val = carve(n_iters), L.o_hh = carve(n_iters), L.o_hr = carve(n_iters);
-  L.total = off;
+  L.total = carve.off;
   return L;
 }
 
@@ -407,8 +387,8 @@ static int svgd_direction_enqueue(vb_ctx* ctx, const SvgdLayout& L, bool has_sca
   const SvgdStageArgs sa{base + L.o_x, base + L.o_g, base + L.o_c, scale, B, n, ld, (int)L.d};
   hipLaunchKernelGGL(svgd_stage_kernel, dim3((unsigned)np), dim3(256), 0, st, sa);
   VB_HIP(ctx, hipGetLastError());
-  const int tiles = (int)(np / kSvgdTile);
-  const SvgdPairArgs pa{B + ld, R, 2 * ld, np, (int)(ld / kSvgdK)};
+  const int tiles = (int)(np / kPairTile);
+  const SvgdPairArgs pa{B + ld, R, 2 * ld, np, (int)(ld / kPairK)};
   hipLaunchKernelGGL(svgd_pair_kernel, dim3((unsigned)(tiles * (tiles + 1) / 2)), dim3(256), 0, st, pa);
   VB_HIP(ctx, hipGetLastError());
 
@@ -449,42 +429,8 @@ static int svgd_check(vb_ctx* ctx, const char* name, int64_t n, int64_t d, const
   if (d < 1 || d > (1 << 24)) return fail(ctx, VB_ERR_INVALID, "the dimension must lie in [1, 2^24]");
   if (!(bandwidth >= 0.0) || !std::isfinite(bandwidth))
     return fail(ctx, VB_ERR_INVALID, "bandwidth must be positive and finite, or 0 for the median rule");
-  if (scale)
-    for (int64_t j = 0; j < d; ++j)
-      if (!(scale[j] > 0.0) || !std::isfinite(scale[j]))
-        return fail(ctx, VB_ERR_INVALID, "scale must be positive and finite (entry %lld)", (long long)j);
+  if (scale) VB_TRY(positive_finite(ctx, name, "scale", scale, d));
   return VB_OK;
-}
-
-// the bound model can supply the scores of `d` columns on the device
-static int svgd_check_model(vb_ctx* ctx, const char* name, int64_t d) {
-  const ModelDev& m = ctx->model;
-  if (m.id < 0) return fail(ctx, VB_ERR_STATE, "no model bound (vb_set_model)");
-  if (d != m.dim) return fail(ctx, VB_ERR_INVALID, "x has %lld columns, model dimension is %d", (long long)d, m.dim);
-  if (m.id == VB_MODEL_SOURCE && ctx->user_host_fn)
-    return fail(ctx, VB_ERR_UNSUPPORTED, "%s evaluates the scores on the device: a host-callback model cannot supply them", name);
-  if (m.id == VB_MODEL_MINIBATCH_GLM)
-    return fail(ctx, VB_ERR_UNSUPPORTED, "%s needs the scores of the whole target: the minibatch target's change from batch "
-                                         "to batch (bind the full-data model)", name);
-  return VB_OK;
-}
-
-struct SvgdDrain {      // the host buffers of the asynchronous uploads outlive them on every way out
-  hipStream_t st;
-  ~SvgdDrain() { (void)hipStreamSynchronize(st); }
-};
-
-// rows of d doubles into rows of ld doubles at `dst`, the padding columns zeroed
-static int svgd_upload_rows(vb_ctx* ctx, double* dst, const double* src, int64_t n, int64_t d, int64_t ld) {
-  const size_t row_bytes = (size_t)d * sizeof(double), ld_bytes = (size_t)ld * sizeof(double);
-  if (ld != d) VB_HIP(ctx, hipMemsetAsync(dst, 0, (size_t)n * ld_bytes, ctx->stream));
-  VB_HIP(ctx, hipMemcpy2DAsync(dst, ld_bytes, src, row_bytes, row_bytes, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  return VB_OK;
-}
-static hipError_t svgd_download_rows(vb_ctx* ctx, double* dst, const double* src, int64_t n, int64_t d, int64_t ld) {
-  const size_t row_bytes = (size_t)d * sizeof(double);
-  return hipMemcpy2DAsync(dst, row_bytes, src, (size_t)ld * sizeof(double), row_bytes, (size_t)n, hipMemcpyDeviceToHost,
-                          ctx->stream);
 }
 
 }  // namespace vb
@@ -497,24 +443,27 @@ int vb_svgd_direction(vb_ctx* ctx, const double* x, int64_t n, int64_t d, const 
                       double bandwidth, double* phi, double* logp, double* h_used) {
   if (!ctx || !x || !phi || !h_used) return fail(ctx, VB_ERR_INVALID, "NULL argument");
   VB_TRY(svgd_check(ctx, "vb_svgd_direction", n, d, scale, bandwidth));
-  if (!scores) VB_TRY(svgd_check_model(ctx, "vb_svgd_direction", d));
+  if (!scores) {
+    VB_TRY(model_bound_refuse(ctx, "vb_svgd_direction", "x", d));
+    VB_TRY(model_device_refuse(ctx, "vb_svgd_direction", true, false));
+  }
   VB_HIP(ctx, hipSetDevice(ctx->device));
   VB_TRY(main_stream_write(ctx));
   hipStream_t st = ctx->stream;
-  SvgdDrain drain{st};
+  StreamDrain drain{st};
   const SvgdLayout L = svgd_layout(n, d, 0);
   VB_TRY(ensure(ctx, ctx->svgd_work, (size_t)L.total * sizeof(double)));
   double* base = (double*)ctx->svgd_work.ptr;
-  VB_TRY(svgd_upload_rows(ctx, base + L.o_x, x, n, d, L.ld));
+  VB_TRY(upload_rows(ctx, base + L.o_x, x, n, d, L.ld));
   if (scores)
-    VB_TRY(svgd_upload_rows(ctx, base + L.o_g, scores, n, d, L.ld));
+    VB_TRY(upload_rows(ctx, base + L.o_g, scores, n, d, L.ld));
   else
     VB_TRY(model_grad_rows(ctx, base + L.o_x, L.ld, n, d, base + L.o_g, base + L.o_f));
   if (scale)
     VB_HIP(ctx, hipMemcpyAsync(base + L.o_scale, scale, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
   VB_TRY(svgd_direction_enqueue(ctx, L, scale != nullptr, bandwidth));
   SvgdSel sel{};
-  VB_HIP(ctx, svgd_download_rows(ctx, phi, base + L.o_out + 1, n, d, L.ld));
+  VB_HIP(ctx, download_rows(ctx, phi, base + L.o_out + 1, n, d, L.ld));
   VB_HIP(ctx, hipMemcpyAsync(&sel, base + L.o_sel, sizeof(SvgdSel), hipMemcpyDeviceToHost, st));
   if (logp && !scores) VB_HIP(ctx, hipMemcpyAsync(logp, base + L.o_f, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
   VB_HIP(ctx, hipStreamSynchronize(st));
@@ -541,26 +490,26 @@ int vb_svgd_run(vb_ctx* ctx, const double* x0, int64_t n, int64_t d, const doubl
   // the step runs over the padded particle block, whose padding columns have gradient 0: 0 / sqrt(jitter + 0) must be 0
   if (opt_kind != VB_OPT_SGD && !(hyper[3] > 0.0))
     return fail(ctx, VB_ERR_INVALID, "the optimiser's jitter must be positive");
-  VB_TRY(svgd_check_model(ctx, "vb_svgd_run", d));
-  if (ctx->comm) return fail(ctx, VB_ERR_UNSUPPORTED, "vb_svgd_run runs on one process's engine: detach the communicator");
+  VB_TRY(model_bound_refuse(ctx, "vb_svgd_run", "x0", d));
+  VB_TRY(model_device_refuse(ctx, "vb_svgd_run", true, true));
   VB_HIP(ctx, hipSetDevice(ctx->device));
   VB_TRY(main_stream_write(ctx));
   hipStream_t st = ctx->stream;
-  SvgdDrain drain{st};
+  StreamDrain drain{st};
   const SvgdLayout L = svgd_layout(n, d, n_iters);
   VB_TRY(ensure(ctx, ctx->svgd_work, (size_t)L.total * sizeof(double)));
   double* base = (double*)ctx->svgd_work.ptr;
   double *X = base + L.o_x, *G = base + L.o_g, *F = base + L.o_f;
   const int64_t p = n * L.ld;
-  VB_TRY(svgd_upload_rows(ctx, X, x0, n, d, L.ld));
+  VB_TRY(upload_rows(ctx, X, x0, n, d, L.ld));
   if (scale)
     VB_HIP(ctx, hipMemcpyAsync(base + L.o_scale, scale, (size_t)d * sizeof(double), hipMemcpyHostToDevice, st));
   // the optimiser state: [second moment (n x d) | momentum (n x d)] on the host, two n x ld blocks here; what is not
   // uploaded (no state, the padding) is zero
   VB_HIP(ctx, hipMemsetAsync(base + L.o_s1, 0, (size_t)(L.o_val - L.o_s1) * sizeof(double), st));
   if (has_state) {
-    VB_TRY(svgd_upload_rows(ctx, base + L.o_s1, state, n, d, L.ld));
-    VB_TRY(svgd_upload_rows(ctx, base + L.o_s2, state + n * d, n, d, L.ld));
+    VB_TRY(upload_rows(ctx, base + L.o_s1, state, n, d, L.ld));
+    VB_TRY(upload_rows(ctx, base + L.o_s2, state + n * d, n, d, L.ld));
   }
   FitStep step;
   step.kind = opt_kind;
@@ -588,7 +537,7 @@ int vb_svgd_run(vb_ctx* ctx, const double* x0, int64_t n, int64_t d, const doubl
     VB_TRY(fit_step_enqueue(ctx, step));
   }
   VB_TRY(model_grad_rows(ctx, X, L.ld, n, d, G, F));      // log p of the final particles
-  VB_HIP(ctx, svgd_download_rows(ctx, x, X, n, d, L.ld));
+  VB_HIP(ctx, download_rows(ctx, x, X, n, d, L.ld));
   auto fetch = [&](double* dst, const double* src, int64_t doubles) {
     return hipMemcpyAsync(dst, src, (size_t)doubles * sizeof(double), hipMemcpyDeviceToHost, st);
   };
@@ -597,8 +546,8 @@ int vb_svgd_run(vb_ctx* ctx, const double* x0, int64_t n, int64_t d, const doubl
   VB_HIP(ctx, fetch(rms_hist, base + L.o_hr, n_iters));
   VB_HIP(ctx, fetch(logp_hist, base + L.o_val, n_iters));
   if (state) {
-    VB_HIP(ctx, svgd_download_rows(ctx, state, base + L.o_s1, n, d, L.ld));
-    VB_HIP(ctx, svgd_download_rows(ctx, state + n * d, base + L.o_s2, n, d, L.ld));
+    VB_HIP(ctx, download_rows(ctx, state, base + L.o_s1, n, d, L.ld));
+    VB_HIP(ctx, download_rows(ctx, state + n * d, base + L.o_s2, n, d, L.ld));
   }
   VB_HIP(ctx, hipStreamSynchronize(st));      // the run's one synchronisation
   for (int64_t k = 0; k < n_iters; ++k)
