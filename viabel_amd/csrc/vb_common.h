@@ -372,6 +372,7 @@ struct vb_ctx {
   int64_t psis_n = 0;                   // number of device-resident log weights (0: none)
   vb::DeviceBuffer psis_work;           // the multi-workgroup smoothing's exchange area (barrier counter, histograms, tail lists)
   unsigned long long psis_bar_base = 0; // value of that counter before the next launch
+  int psis_grid_per_cu[3] = {-1, -1, -1};   // its workgroups one CU of this device takes, per variant (-1: not asked yet)
   vb::DeviceBuffer loo_work;            // batched smoothing / PSIS-LOO (vb_psis_batch.hip): vectors, draws, per-vector results
   vb::DeviceBuffer ksd_work;            // vb_ksd (vb_ksd.hip): staged draws and scores, weights, partials; laid out by every call
                                         // (its own buffer: model_grad_rows and the bound target run while it holds the draws)

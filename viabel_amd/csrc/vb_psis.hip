@@ -9,8 +9,12 @@
 // Zhang-Stephens empirical-Bayes GPD fit (30 + sqrt(M) quadrature points), replacement of the tail by the
 // fitted quantiles, truncation at 0 and log-sum-exp normalisation.  Integer atomics only (histogram, gather
 // counter); the sorted order is by (value, index), so the result does not depend on the gather order.
+//
+// The steps themselves are vb_psis_util.h's (shared with vb_psis_batch.hip).  This file holds the two kernels' passes over
+// the N weights, what only one of them does -- psis_kernel's small-tail sort on all waves; psis_grid_kernel's grid
+// barriers, 12-bit global histogram, candidate lists, per-workgroup ranking and quadrature shares -- and the host side.
 #include "vb_common.h"
-#include "vb_psis_util.h"      // ps_wave_sum / ps_wave_max, ps_key / ps_unkey, ps_after
+#include "vb_psis_util.h"
 
 #include <cfloat>
 #include <cmath>
@@ -19,30 +23,9 @@
 namespace vb {
 
 constexpr int kPsisThreads = 1024;
+constexpr int kPsisWaves = kPsisThreads / 64;
 constexpr int kPsisTailCap = 4096;     // tail values sorted in LDS (M <= 4096  <=>  N <= 1.86e6 at Reff = 1)
 constexpr int kPsisQuadCap = 128;      // 30 + sqrt(4096) = 94 quadrature points at most
-
-// block-wide sum / max over 1024 threads; every thread gets the result (sh: 16 doubles + 1)
-__device__ double ps_block_sum(double x, double* sh) {
-  x = ps_wave_sum(x);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < kPsisThreads / 64; ++w) t += sh[w];
-  return t;
-}
-__device__ double ps_block_max(double x, double* sh) {
-  x = ps_wave_max(x);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-  __syncthreads();
-  double t = sh[0];
-#pragma unroll
-  for (int w = 1; w < kPsisThreads / 64; ++w) t = fmax(t, sh[w]);
-  return t;
-}
 
 // lw = f - b + sum(log sigma): the log importance weights log p(z_n) - log q(z_n) of the mean-field families
 __global__ void __launch_bounds__(256) psis_lw_kernel(const double* __restrict__ f, const double* __restrict__ b,
@@ -102,10 +85,10 @@ __global__ void __launch_bounds__(kPsisThreads) psis_kernel(double* __restrict__
   __shared__ int tail_count;
   __shared__ double tv[kPsisTailCap];
   __shared__ int ti[kPsisTailCap];
-  __shared__ double q_bs[kPsisQuadCap], q_ks[kPsisQuadCap], q_L[kPsisQuadCap], q_w[kPsisQuadCap];
+  __shared__ double q_bs[kPsisQuadCap], q_L[kPsisQuadCap], q_w[kPsisQuadCap];
   __shared__ int rank_sh[kPsisThreads / 2];
   __shared__ double bc[4];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x, wave = t >> 6;
 #ifdef VB_PSIS_CLOCK
   int dbg_k = 4;
 #define PSIS_MARK() do { __syncthreads(); if (t == 0) out[dbg_k] = (double)wall_clock64(); ++dbg_k; } while (0)
@@ -125,7 +108,7 @@ __global__ void __launch_bounds__(kPsisThreads) psis_kernel(double* __restrict__
   }
   double mx = -INFINITY;
   ps_each<REGS>(r, x, n, [&](int64_t, double v) { mx = fmax(mx, v); });
-  mx = ps_block_max(mx, sh);
+  mx = ps_block_max<kPsisWaves>(mx, sh);
   if constexpr (REGS) {
 #pragma unroll
     for (int u = 0; u < kPsisRegs; ++u) {
@@ -154,27 +137,11 @@ __global__ void __launch_bounds__(kPsisThreads) psis_kernel(double* __restrict__
     const unsigned long long prefix = sel_prefix;
     const unsigned long long mask = pass == 7 ? 0ull : (~0ull << (8 * (pass + 1)));
     if constexpr (REGS) {
-      // the top bytes of log weights are sign and exponent: a wave's 64 keys fall into one or two bins, and 64 LDS
-      // atomics on one address are served one after the other.  Two rounds of "the first lane's bin: everybody in it
-      // is counted by one add"; what is left (the low bytes' spread-out bins) goes lane by lane.
 #pragma unroll
       for (int u = 0; u < kPsisRegs; ++u) {
         const int64_t i = t + (int64_t)u * kPsisThreads;
         const unsigned long long k = ps_key(r[u]);
-        const int bin = (int)((k >> (8 * pass)) & 255ull);
-        bool act = i < n && (k & mask) == prefix;
-#pragma unroll
-        for (int round = 0; round < 2; ++round) {
-          const unsigned long long todo = __ballot(act);
-          if (!todo) break;
-          const int leader = __builtin_ctzll(todo);
-          const int b = __shfl(bin, leader, 64);
-          const bool same = act && bin == b;
-          const unsigned long long m = __ballot(same);
-          if (lane == leader) atomicAdd(&hist[b], __builtin_popcountll(m));
-          act = act && !same;
-        }
-        if (act) atomicAdd(&hist[bin], 1);
+        ps_hist_add(hist, (int)((k >> (8 * pass)) & 255ull), i < n && (k & mask) == prefix);
       }
     } else {
       ps_each<REGS>(r, x, n, [&](int64_t, double v) {
@@ -183,31 +150,7 @@ __global__ void __launch_bounds__(kPsisThreads) psis_kernel(double* __restrict__
       });
     }
     __syncthreads();
-    if (wave == 0) {
-      // the bin that holds rank r: wave 0 scans the 256 counts, four consecutive bins per lane (a serial walk by one
-      // thread was 3.5 us of every pass)
-      const long long r = sel_rank;
-      const int c0 = hist[4 * lane], c1 = hist[4 * lane + 1], c2 = hist[4 * lane + 2], c3 = hist[4 * lane + 3];
-      long long incl = (long long)c0 + c1 + c2 + c3;          // inclusive prefix over lanes
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const long long up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-      }
-      const long long excl = incl - ((long long)c0 + c1 + c2 + c3);
-      // exactly one lane has excl <= r < incl (the total is > r); the last lane also takes r beyond the total's reach
-      const bool mine = (excl <= r && r < incl) || (lane == 63 && r >= incl);
-      if (mine) {
-        long long rr = r - excl;
-        int bin = 4 * lane, cb = c0;
-        if (rr >= c0 && bin < 255) { rr -= c0; ++bin; cb = c1;
-          if (rr >= c1 && bin < 255) { rr -= c1; ++bin; cb = c2;
-            if (rr >= c2 && bin < 255) { rr -= c2; ++bin; cb = c3; } } }
-        sel_rank = rr;
-        sel_prefix = prefix | ((unsigned long long)bin << (8 * pass));
-        sel_bin_count = cb;
-      }
-    }
+    if (wave == 0) ps_scan_hist256(hist, prefix, 8 * pass, &sel_prefix, &sel_rank, &sel_bin_count);
     __syncthreads();
     pass_done = pass;
     if (pass > 0 && sel_bin_count <= kPsisThreads) break;      // (uniform: a shared value read behind the barrier)
@@ -218,45 +161,19 @@ __global__ void __launch_bounds__(kPsisThreads) psis_kernel(double* __restrict__
     if (t == 0) tail_count = 0;
     __syncthreads();
     const unsigned long long prefix = sel_prefix, mask = ~0ull << (8 * pass_done);
-    ps_each<REGS>(r, x, n, [&](int64_t, double v) {
-      const unsigned long long k = ps_key(v);
-      if ((k & mask) == prefix) {
-        const int p = atomicAdd(&tail_count, 1);
-        if (p < kPsisThreads) bk[p] = k;
-      }
-    });
+    ps_each<REGS>(r, x, n, [&](int64_t, double v) { ps_bin_put<kPsisThreads>(v, prefix, mask, bk, &tail_count); });
     __syncthreads();
-    const int nb = tail_count < kPsisThreads ? tail_count : kPsisThreads;
-    const long long want = sel_rank;
-    if (t < nb) {
-      const unsigned long long mk = bk[t];
-      int lt = 0, le = 0;
-      for (int j = 0; j < nb; ++j) {
-        const unsigned long long o = bk[j];
-        lt += o < mk ? 1 : 0;
-        le += o <= mk ? 1 : 0;
-      }
-      if (lt <= want && want < le) sel_prefix = mk;      // (every thread that holds this key writes the same value)
-    }
+    ps_rank_among(bk, tail_count < kPsisThreads ? tail_count : kPsisThreads, &sel_prefix, &sel_rank);
     __syncthreads();
   }
   PSIS_MARK();
-  const double cutoffmin = log(DBL_MIN);                       // :159
-  const double xcutoff = fmax(ps_unkey(sel_prefix), cutoffmin);
-  const double expxc = exp(xcutoff);
+  double expxc;
+  const double xcutoff = ps_cutoff(sel_prefix, &expxc);
 
   // 3. right tail: x > xcutoff   (:175-177)
   if (t == 0) tail_count = 0;
   __syncthreads();
-  ps_each<REGS>(r, x, n, [&](int64_t i, double v) {
-    if (v > xcutoff) {
-      const int p = atomicAdd(&tail_count, 1);
-      if (p < kPsisTailCap) {
-        tv[p] = v;
-        ti[p] = (int)i;
-      }
-    }
-  });
+  ps_each<REGS>(r, x, n, [&](int64_t i, double v) { ps_tail_put<kPsisTailCap>((int)i, v, xcutoff, tv, ti, &tail_count); });
   __syncthreads();
   const int n2 = tail_count < kPsisTailCap ? tail_count : kPsisTailCap;
   PSIS_MARK();
@@ -265,7 +182,6 @@ __global__ void __launch_bounds__(kPsisThreads) psis_kernel(double* __restrict__
     // 4. order of the tail samples by (value, index): every element counts the elements before it (n2^2 / 1024
     // comparisons per thread on LDS broadcasts: 0.15 M in all at n2 = 384) and moves to that position -- two
     // barriers instead of the 45 of a bitonic network
-    constexpr int kPerThread = kPsisTailCap / kPsisThreads;
     if (n2 <= kPsisThreads / 2) {
       // few tail values (n2 = 384 at N = 16 384): the counting is a chain of dependent compare / select instructions,
       // so it goes to ALL waves -- R = 1024 / round_up(n2, 64) threads per element, thread (e, rep) counts the comparands
@@ -307,125 +223,59 @@ __global__ void __launch_bounds__(kPsisThreads) psis_kernel(double* __restrict__
       }
       __syncthreads();
     } else {
-    double my_v[kPerThread];
-    int my_i[kPerThread], my_r[kPerThread];
+      // (spelled out here and in psis_batch_kernel: as a shared function the same loop spilled scalar registers in both)
+      constexpr int kPerThread = kPsisTailCap / kPsisThreads;
+      double my_v[kPerThread];
+      int my_i[kPerThread], my_r[kPerThread];
 #pragma unroll
-    for (int u = 0; u < kPerThread; ++u) {
-      const int e = t + u * kPsisThreads;
-      my_v[u] = e < n2 ? tv[e] : INFINITY;
-      my_i[u] = e < n2 ? ti[e] : 0x7fffffff;
-      my_r[u] = 0;
-    }
-    // eight comparands are read from LDS before the first comparison; beyond n2 a sentinel nothing comes after
-    for (int j0 = 0; j0 < n2; j0 += 8) {
-      double v8[8];
-      int i8[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int jx = j0 + q;
-        const int jc = jx < n2 ? jx : n2 - 1;
-        const double vv = tv[jc];
-        const int ii = ti[jc];
-        v8[q] = jx < n2 ? vv : INFINITY;
-        i8[q] = jx < n2 ? ii : 0x7fffffff;
+      for (int u = 0; u < kPerThread; ++u) {
+        const int e = t + u * kPsisThreads;
+        my_v[u] = e < n2 ? tv[e] : INFINITY;
+        my_i[u] = e < n2 ? ti[e] : 0x7fffffff;
+        my_r[u] = 0;
       }
+      // eight comparands are read from LDS before the first comparison; beyond n2 a sentinel nothing comes after
+      for (int j0 = 0; j0 < n2; j0 += 8) {
+        double v8[8];
+        int i8[8];
 #pragma unroll
-      for (int q = 0; q < 8; ++q)
+        for (int q = 0; q < 8; ++q) {
+          const int jx = j0 + q;
+          const int jc = jx < n2 ? jx : n2 - 1;
+          const double vv = tv[jc];
+          const int ii = ti[jc];
+          v8[q] = jx < n2 ? vv : INFINITY;
+          i8[q] = jx < n2 ? ii : 0x7fffffff;
+        }
 #pragma unroll
-        for (int u = 0; u < kPerThread; ++u)
-          if (u * kPsisThreads < n2) my_r[u] += ps_after(my_v[u], my_i[u], v8[q], i8[q]) ? 1 : 0;     // (uniform condition)
-    }
-    __syncthreads();
+        for (int q = 0; q < 8; ++q)
 #pragma unroll
-    for (int u = 0; u < kPerThread; ++u) {
-      if (t + u * kPsisThreads < n2) {
-        tv[my_r[u]] = my_v[u];
-        ti[my_r[u]] = my_i[u];
+          for (int u = 0; u < kPerThread; ++u)
+            if (u * kPsisThreads < n2) my_r[u] += ps_after(my_v[u], my_i[u], v8[q], i8[q]) ? 1 : 0;     // (uniform condition)
       }
-    }
-    __syncthreads();
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < kPerThread; ++u) {
+        if (t + u * kPsisThreads < n2) {
+          tv[my_r[u]] = my_v[u];
+          ti[my_r[u]] = my_i[u];
+        }
+      }
+      __syncthreads();
     }
     PSIS_MARK();
-    // x2 = exp(x2) - exp(xcutoff)   (:185-186)
-    for (int i = t; i < n2; i += kPsisThreads) tv[i] = exp(tv[i]) - expxc;
-    __syncthreads();
+    ps_tail_exp<kPsisThreads>(tv, n2, expxc);
 
     PSIS_MARK();
-    // 5. gpdfitnew (:266-325): PRIOR = 3, m = 30 + int(sqrt(n2))
-    const int m = 30 + (int)sqrt((double)n2);
-    const double xq = tv[(int)(n2 / 4.0 + 0.5) - 1], xl = tv[n2 - 1];
-    if (t < m) q_bs[t] = (1.0 - sqrt((double)m / ((double)(t + 1) - 0.5))) / (3.0 * xq) + 1.0 / xl;
-    __syncthreads();
-    // sixteen lanes per quadrature point (64 points at a time: m <= 94), each a fixed stride of the tail, combined by a
-    // fixed butterfly -- the m n2 log1p evaluations spread over the whole workgroup instead of one wave per point
-    const int grp = t >> 4, gl = t & 15;
-    for (int j = grp; j < m; j += kPsisThreads / 16) {          // ks_j = mean log1p(-bs_j x)
-      const double nb = -q_bs[j];
-      double s = 0.0;
-      // log(1 + y) for log1p(y): the ABSOLUTE error of a term is what the mean sees, and that is one rounding of 1 + y
-      // (<= 1.1e-16) either way; log costs half of what log1p does, and these m n2 evaluations are the phase's time
-      // four logarithms in flight per lane (independent chains: the evaluation is latency-bound), added in the same order
-      int i = gl;
-      for (; i + 48 < n2; i += 64) {
-        const double l0 = log(fma(nb, tv[i], 1.0)), l1 = log(fma(nb, tv[i + 16], 1.0)), l2 = log(fma(nb, tv[i + 32], 1.0)),
-                     l3 = log(fma(nb, tv[i + 48], 1.0));
-        s += l0;
-        s += l1;
-        s += l2;
-        s += l3;
-      }
-      for (; i < n2; i += 16) s += log(fma(nb, tv[i], 1.0));
-#pragma unroll
-      for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-      if (gl == 0) {
-        const double ks = s / n2;
-        q_ks[j] = ks;
-        q_L[j] = n2 * (log(-(q_bs[j] / ks)) - ks - 1.0);
-      }
-    }
-    __syncthreads();
-    for (int j = grp; j < m; j += kPsisThreads / 16) {
-      const double lj = q_L[j];
-      double s = 0.0;
-      for (int i = gl; i < m; i += 16) s += exp(q_L[i] - lj);
-#pragma unroll
-      for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-      if (gl == 0) {
-        const double w = 1.0 / s;
-        q_w[j] = w >= 10.0 * DBL_EPSILON ? w : 0.0;              // remove negligible weights
-      }
-    }
-    __syncthreads();
-    if (t == 0) {
-      double ws = 0.0, bsum = 0.0;
-      for (int i = 0; i < m; ++i) ws += q_w[i];
-      for (int i = 0; i < m; ++i) bsum += q_bs[i] * (q_w[i] / ws);
-      bc[0] = bsum;                                              // posterior mean of b
-    }
-    __syncthreads();
-    const double b = bc[0];
-    double s = 0.0;
-    for (int i = t; i < n2; i += kPsisThreads) s += log1p(-b * tv[i]);
-    s = ps_block_sum(s, sh);
-    k = s / n2;
-    sigma = -k / b;
-    k = k * n2 / (n2 + 10.0) + 10.0 * 0.5 / (n2 + 10.0);        // weakly informative prior, a = 10
+    // 5. gpdfitnew (:266-325)
+    const int m = ps_quad_points(tv, n2, q_bs);
+    ps_quad_ks<kPsisThreads>(tv, n2, m, q_bs, q_L);
+    k = ps_gpd_fit<kPsisThreads>(tv, n2, m, q_bs, q_L, q_w, bc, sh, &sigma);
 
     PSIS_MARK();
     // 6. smoothed tail (:188-199): order statistics of the fitted GPD, truncated at the largest raw weight
-    if (k >= 1.0 / 3.0 && !isinf(k)) {
-      for (int i = t; i < n2; i += kPsisThreads) {
-        const double p = ((double)i + 0.5) / n2;
-        double qq = NAN;
-        if (sigma > 0.0) {
-          const double l = log1p(-p);
-          qq = (fabs(k) < DBL_EPSILON ? -l : expm1(-k * l) / k) * sigma;
-        }
-        double v = log(qq + expxc);
-        if (v > 0.0) v = 0.0;
-        x[ti[i]] = v;
-      }
-    }
+    if (k >= 1.0 / 3.0 && !isinf(k))
+      for (int i = t; i < n2; i += kPsisThreads) x[ti[i]] = ps_quantile(i, n2, k, sigma, expxc);
   }
   __syncthreads();
 
@@ -440,10 +290,10 @@ __global__ void __launch_bounds__(kPsisThreads) psis_kernel(double* __restrict__
   }
   double m2 = -INFINITY;
   ps_each<REGS>(r, x, n, [&](int64_t, double v) { m2 = fmax(m2, v); });
-  m2 = ps_block_max(m2, sh);
+  m2 = ps_block_max<kPsisWaves>(m2, sh);
   double se = 0.0;
   ps_each<REGS>(r, x, n, [&](int64_t, double v) { se += exp(v - m2); });
-  se = ps_block_sum(se, sh);
+  se = ps_block_sum<kPsisWaves>(se, sh);
   const double lse = log(se) + m2;
   ps_each<REGS>(r, x, n, [&](int64_t i, double v) { x[i] = v - lse; });
   PSIS_MARK();
@@ -522,9 +372,6 @@ struct PgBarrier {
     if (threadIdx.x == 0) {
       target += (unsigned long long)g_count;
       ++used;
-#ifdef VB_PSIS_FENCE
-      __threadfence();
-#endif
       atomicAdd(bar, 1ull);
       int spins = 0;
       while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
@@ -534,9 +381,6 @@ struct PgBarrier {
           break;
         }
       }
-#ifdef VB_PSIS_FENCE
-      __threadfence();
-#endif
     }
     __syncthreads();
   }
@@ -615,7 +459,7 @@ __global__ void __launch_bounds__(kPsisThreads) psis_grid_kernel(double* __restr
     }
     if (i < n) mx = fmax(mx, r[u]);
   }
-  mx = ps_block_max(mx, sh);
+  mx = ps_block_max<kPsisWaves>(mx, sh);
   if (t == 0) pg_st(&wgval[g], mx);
   if (io.w_in) {      // this workgroup's share of sum w: the wave by shuffles, the sixteen waves in order (mvt_psis_prep_kernel's)
 #pragma unroll
@@ -661,19 +505,7 @@ __global__ void __launch_bounds__(kPsisThreads) psis_grid_kernel(double* __restr
       const int64_t i = i0 + t + (int64_t)u * kPsisThreads;
       const unsigned long long k = ps_key(r[u]);
       const int bin = (int)((k >> shift) & ((1ull << width) - 1ull));
-      bool act = i < n && (k & fixed_mask) == prefix;
-#pragma unroll
-      for (int round = 0; round < 2; ++round) {      // (see psis_kernel: a wave's keys share their top bits)
-        const unsigned long long todo = __ballot(act);
-        if (!todo) break;
-        const int leader = __builtin_ctzll(todo);
-        const int b = __shfl(bin, leader, 64);
-        const bool same = act && bin == b;
-        const unsigned long long m = __ballot(same);
-        if (lane == leader) atomicAdd(&hist[b], __builtin_popcountll(m));
-        act = act && !same;
-      }
-      if (act) atomicAdd(&hist[bin], 1);
+      ps_hist_add(hist, bin, i < n && (k & fixed_mask) == prefix);
     }
     __syncthreads();
     int* gh = ghist + pass * kPgBins;
@@ -685,12 +517,7 @@ __global__ void __launch_bounds__(kPsisThreads) psis_grid_kernel(double* __restr
       const long long want = sel_rank;
       const int c0 = pg_ld(&gh[4 * t]), c1 = pg_ld(&gh[4 * t + 1]), c2 = pg_ld(&gh[4 * t + 2]), c3 = pg_ld(&gh[4 * t + 3]);
       const long long mine4 = (long long)c0 + c1 + c2 + c3;
-      long long incl = mine4;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const long long up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-      }
+      long long incl = ps_wave_prefix(mine4);
       long long* wtot = reinterpret_cast<long long*>(tv);       // 16 wave totals (tv is free here)
       __syncthreads();
       if (lane == 63) wtot[wave] = incl;
@@ -698,18 +525,8 @@ __global__ void __launch_bounds__(kPsisThreads) psis_grid_kernel(double* __restr
       long long before = 0;
       for (int w = 0; w < wave; ++w) before += wtot[w];
       incl += before;
-      const long long excl = incl - mine4;
-      const bool last_thread = t == kPsisThreads - 1;
-      if ((excl <= want && want < incl) || (last_thread && want >= incl)) {
-        long long rr = want - excl;
-        int bin = 4 * t, cb = c0;
-        if (rr >= c0 && bin < kPgBins - 1) { rr -= c0; ++bin; cb = c1;
-          if (rr >= c1 && bin < kPgBins - 1) { rr -= c1; ++bin; cb = c2;
-            if (rr >= c2 && bin < kPgBins - 1) { rr -= c2; ++bin; cb = c3; } } }
-        sel_rank = rr;
-        sel_prefix = prefix | ((unsigned long long)bin << shift);
-        sel_bin_count = cb;
-      }
+      ps_pick_bin(want, incl - mine4, incl, t == kPsisThreads - 1, c0, c1, c2, c3, 4 * t, kPgBins - 1, prefix, shift,
+                  &sel_prefix, &sel_rank, &sel_bin_count);
       __syncthreads();
     }
     shift_done = shift;
@@ -757,24 +574,13 @@ __global__ void __launch_bounds__(kPsisThreads) psis_grid_kernel(double* __restr
     if (need_bin) {
       if (t < nb) bk[t] = pg_ld(&gbk[t]), bi[t] = pg_ld(&gbi[t]);
       __syncthreads();
-      const long long want = sel_rank;
-      if (t < nb) {
-        const unsigned long long mk = bk[t];
-        int lt = 0, le = 0;
-        for (int j = 0; j < nb; ++j) {
-          const unsigned long long o = bk[j];
-          lt += o < mk ? 1 : 0;
-          le += o <= mk ? 1 : 0;
-        }
-        if (lt <= want && want < le) sel_prefix = mk;
-      }
+      ps_rank_among(bk, nb, &sel_prefix, &sel_rank);
       __syncthreads();
     }
   }
   PG_MARK();
-  const double cutoffmin = log(DBL_MIN);                       // :159
-  const double xcutoff = fmax(ps_unkey(sel_prefix), cutoffmin);
-  const double expxc = exp(xcutoff);
+  double expxc;
+  const double xcutoff = ps_cutoff(sel_prefix, &expxc);
   // right tail: x > xcutoff (:175-177): the candidates above the bin, and the bin's members above the cut-off
   int na = pg_ld(&gcnt[1]);
   na = na < kPsisTailCap ? na : kPsisTailCap;
@@ -854,11 +660,8 @@ __global__ void __launch_bounds__(kPsisThreads) psis_grid_kernel(double* __restr
       ti[i] = pg_ld(&gsi[i]);
     }
     __syncthreads();
-    // 5. gpdfitnew (:266-325): PRIOR = 3, m = 30 + int(sqrt(n2)); point j on workgroup j mod G
-    const int m = 30 + (int)sqrt((double)n2);
-    const double xq = tv[(int)(n2 / 4.0 + 0.5) - 1], xl = tv[n2 - 1];
-    if (t < m) q_bs[t] = (1.0 - sqrt((double)m / ((double)(t + 1) - 0.5))) / (3.0 * xq) + 1.0 / xl;
-    __syncthreads();
+    // 5. gpdfitnew (:266-325); point j on workgroup j mod G
+    const int m = ps_quad_points(tv, n2, q_bs);
     const int grp = t >> 4, gl = t & 15;
     // ks_j = mean log1p(-bs_j x) for the points j = g, g + G, ...: the logarithms by all threads into LDS (as many points
     // at a time as fit), then sixteen lanes per point add them in psis_kernel's order (lane l takes i = l, l + 16, ..., a
@@ -898,50 +701,18 @@ __global__ void __launch_bounds__(kPsisThreads) psis_grid_kernel(double* __restr
     PG_MARK();
     if (t < m) q_L[t] = pg_ld(&gq[t]);
     __syncthreads();
-    for (int j = grp; j < m; j += kPsisThreads / 16) {
-      const double lj = q_L[j];
-      double s = 0.0;
-      for (int i = gl; i < m; i += 16) s += exp(q_L[i] - lj);
-#pragma unroll
-      for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-      if (gl == 0) {
-        const double w = 1.0 / s;
-        q_w[j] = w >= 10.0 * DBL_EPSILON ? w : 0.0;              // remove negligible weights
-      }
-    }
-    __syncthreads();
-    if (t == 0) {
-      double ws = 0.0, bsum = 0.0;
-      for (int i = 0; i < m; ++i) ws += q_w[i];
-      for (int i = 0; i < m; ++i) bsum += q_bs[i] * (q_w[i] / ws);
-      bc[0] = bsum;                                              // posterior mean of b
-    }
-    __syncthreads();
-    const double b = bc[0];
-    double s = 0.0;
-    for (int i = t; i < n2; i += kPsisThreads) s += log1p(-b * tv[i]);
-    s = ps_block_sum(s, sh);
-    k = s / n2;
-    sigma = -k / b;
-    k = k * n2 / (n2 + 10.0) + 10.0 * 0.5 / (n2 + 10.0);        // weakly informative prior, a = 10
+    k = ps_gpd_fit<kPsisThreads>(tv, n2, m, q_bs, q_L, q_w, bc, sh, &sigma);
 
     // 6. smoothed tail (:188-199); every workgroup forms all of it and keeps what falls into its slice
     if (k >= 1.0 / 3.0 && !isinf(k)) {
       double vmax = -INFINITY;
       for (int i = t; i < n2; i += kPsisThreads) {
-        const double p = ((double)i + 0.5) / n2;
-        double qq = NAN;
-        if (sigma > 0.0) {
-          const double l = log1p(-p);
-          qq = (fabs(k) < DBL_EPSILON ? -l : expm1(-k * l) / k) * sigma;
-        }
-        double v = log(qq + expxc);
-        if (v > 0.0) v = 0.0;
-        vmax = fmax(vmax, v);          // (fmax drops a NaN: the reference's max of the vector would not -- sigma <= 0 only)
+        const double v = ps_quantile(i, n2, k, sigma, expxc);
+        vmax = fmax(vmax, v);         // (fmax drops a NaN: the reference's max of the vector would not -- sigma <= 0 only)
         const int64_t idx = ti[i];
         if (idx >= i0 && idx < i0 + slice) x[idx] = v;
       }
-      new_max = ps_block_max(vmax, sh);
+      new_max = ps_block_max<kPsisWaves>(vmax, sh);
       // the untouched weights are <= xcutoff <= every smoothed value (the quantiles are >= 0); without a tail to the
       // right of the cut-off the old maximum (0) stays
       if (!(new_max > -INFINITY)) new_max = 0.0;
@@ -961,7 +732,7 @@ __global__ void __launch_bounds__(kPsisThreads) psis_grid_kernel(double* __restr
     const int64_t i = i0 + t + (int64_t)u * kPsisThreads;
     if (i < n) se += exp(r[u] - new_max);
   }
-  se = ps_block_sum(se, sh);
+  se = ps_block_sum<kPsisWaves>(se, sh);
   if (t == 0) pg_st(&wgval[kPgMaxWg + g], se);
   barrier.wait();
   double tot = 0.0;
@@ -987,10 +758,6 @@ __global__ void __launch_bounds__(kPsisThreads) psis_grid_kernel(double* __restr
     out[1] = poisoned ? NAN : (double)tail_count;      // (k-hat AND the tail count NaN: the poison's signature)
     out[2] = xcutoff;
     out[3] = sigma;
-#ifdef VB_PSIS_DEBUG
-    out[4] = n2, out[5] = pg_ld(&gcnt[1]), out[6] = pg_ld(&gcnt[0]), out[7] = shift_done, out[8] = (double)sel_rank;
-    out[9] = mx, out[10] = new_max, out[11] = tot;
-#endif
   }
   // the barriers this launch did not need (the select leaves early): the counter advances by the same amount every launch
   if (t == 0 && barrier.used < kPgBarriers) atomicAdd(bar, (unsigned long long)(kPgBarriers - barrier.used));
@@ -1048,16 +815,15 @@ int psis_enqueue(vb_ctx* ctx, int64_t n, double reff, const double* weights_in, 
   // ~115 KB-LDS workgroups one CU takes (once per context and variant) and keep to the single-workgroup kernel when the
   // grid would not fit -- other streams' work or another process can still delay residency, which the bounded polls turn
   // into a poisoned (NaN) result and vb_psis_smooth into VB_ERR_STATE, not into a hang.
-  static int per_cu[3] = {-1, -1, -1};
+  using GridKernel = void (*)(double*, int64_t, int, double*, char*, unsigned long long, PsisWeightsIo);
+  static const GridKernel grid_kernels[3] = {psis_grid_kernel<1>, psis_grid_kernel<2>, psis_grid_kernel<4>};      // 1, 2, 4 weights per thread
   const int variant = per_thread == 1 ? 0 : (per_thread == 2 ? 1 : 2);
-  if (grid_env && wgs > 1 && per_thread <= kPgRegs && per_cu[variant] < 0) {
+  int& per_cu = ctx->psis_grid_per_cu[variant];
+  if (grid_env && wgs > 1 && per_thread <= kPgRegs && per_cu < 0) {
     int nb = 0;
-    hipError_t e = variant == 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, psis_grid_kernel<1>, kPsisThreads, 0)
-                   : variant == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, psis_grid_kernel<2>, kPsisThreads, 0)
-                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, psis_grid_kernel<4>, kPsisThreads, 0);
-    per_cu[variant] = e == hipSuccess ? nb : 0;
+    per_cu = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, grid_kernels[variant], kPsisThreads, 0) == hipSuccess ? nb : 0;
   }
-  if (grid_env && wgs > 1 && per_thread <= kPgRegs && (int64_t)wgs <= (int64_t)per_cu[variant] * ctx->prop.multiProcessorCount) {
+  if (grid_env && wgs > 1 && per_thread <= kPgRegs && (int64_t)wgs <= (int64_t)per_cu * ctx->prop.multiProcessorCount) {
     if (!ctx->psis_work.ptr) {
       VB_TRY(ensure(ctx, ctx->psis_work, kPgBytes));
       VB_HIP(ctx, hipMemsetAsync(ctx->psis_work.ptr, 0, 64, ctx->stream));        // barrier counter, poison
@@ -1068,12 +834,7 @@ int psis_enqueue(vb_ctx* ctx, int64_t n, double reff, const double* weights_in, 
     double* out = lw + round_up(n, 16);
     PsisWeightsIo io;
     if (weights_in) io.w_in = weights_in, io.w_out = weights_out, io.khat_out = khat_out;
-    if (per_thread == 1)
-      hipLaunchKernelGGL(psis_grid_kernel<1>, dim3(wgs), dim3(kPsisThreads), 0, ctx->stream, lw, n, m_tail, out, work, bar_base, io);
-    else if (per_thread == 2)
-      hipLaunchKernelGGL(psis_grid_kernel<2>, dim3(wgs), dim3(kPsisThreads), 0, ctx->stream, lw, n, m_tail, out, work, bar_base, io);
-    else
-      hipLaunchKernelGGL(psis_grid_kernel<4>, dim3(wgs), dim3(kPsisThreads), 0, ctx->stream, lw, n, m_tail, out, work, bar_base, io);
+    hipLaunchKernelGGL(grid_kernels[variant], dim3(wgs), dim3(kPsisThreads), 0, ctx->stream, lw, n, m_tail, out, work, bar_base, io);
     VB_HIP(ctx, hipGetLastError());
     ctx->psis_bar_base += (unsigned long long)wgs * kPgBarriers;      // (a launch that did not happen adds nothing)
     if (fused_out) *fused_out = io.w_in != nullptr;

@@ -6,7 +6,8 @@
 // it does what psis_kernel does, in the same order: max shift, exact selection of the cut-off (the (M+1)-th largest,
 // M = ceil(min(0.2 S, 3 sqrt(S / Reff)))) by a byte-wise radix select on order-preserving keys, tail gathered and ordered
 // by (value, index), Zhang-Stephens fit with 30 + floor(sqrt(n_tail)) points, quantile replacement when k >= 1/3,
-// truncation at 0, log-sum-exp normalisation; k = inf when the tail has at most 4 values.
+// truncation at 0, log-sum-exp normalisation; k = inf when the tail has at most 4 values.  The steps themselves are
+// vb_psis_util.h's, the ones vb_psis.hip's kernels run; this file holds the kernel's register passes and its closing sums.
 //   * capacity: S <= 16 384 (VPT = 4, 16 or 64 values per thread, held in registers from the load to the end: the
 //     loads of a vector are contiguous and all issued before the first use) and a tail of at most 1024 values
 //     (384 at S = 16 384, Reff = 1; 62 quadrature points at most).  Longer vectors / tails keep the column loop.
@@ -19,7 +20,7 @@
 //     weights log_w, lpd[j] = logsumexp_s(log_w[s] + A[j][s]) leave instead: three doubles per vector.
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; scratch 0 in all three variants;
 // LDS 14 920 B per workgroup: ten workgroups' worth in a CU's 160 KiB, so LDS never bounds the occupancy):
-//     VPT  4 (S <= 1024):    88 VGPRs -> 5 workgroups per CU
+//     VPT  4 (S <= 1024):    90 VGPRs -> 5 workgroups per CU
 //     VPT 16 (S <= 4096):   117 VGPRs -> 4 workgroups per CU
 //     VPT 64 (S <= 16 384): 256 VGPRs + 88 AGPRs -> 1 workgroup per CU (the vector alone is 128 registers; a fully
 //                           unrolled pass over it, its exponentials inlined, keeps the rest busy)
@@ -58,7 +59,6 @@ constexpr int kPbTailCap = 1024;       // tail values sorted in LDS
 constexpr int kPbQuadCap = 64;         // 30 + sqrt(1024) = 62 quadrature points at most
 constexpr int kPbMaxVpt = 64;
 constexpr int64_t kPbMaxN = (int64_t)kPbMaxVpt * kPbThreads;      // 16 384
-constexpr int kPbBinCap = kPbThreads;  // the radix select ends by counting once the wanted rank's bin has one key per thread
 // device memory a call may hold for the n_data x S likelihood matrix (or the vectors of vb_psis_smooth_batch): larger
 // problems go through in chunks of observations
 constexpr size_t kLooBudgetBytes = (size_t)1 << 30;
@@ -76,21 +76,6 @@ struct PsisBatchArgs {
   double* lpd_out;            // [m] (loo, with log_w)
 };
 
-__device__ __forceinline__ double pb_block_sum(double x, double* sh) {
-  x = ps_wave_sum(x);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-__device__ __forceinline__ double pb_block_max(double x, double* sh) {
-  x = ps_wave_max(x);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
-  __syncthreads();
-  return fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
-}
-
 // running log-sum-exp of one thread: sum = s * exp(m)
 struct PbLse {
   double m = -INFINITY, s = 0.0;
@@ -106,9 +91,9 @@ struct PbLse {
     m = mn;
   }
   __device__ __forceinline__ double total(double* sh) const {      // over the workgroup, in a fixed order
-    const double M = pb_block_max(m, sh);
+    const double M = ps_block_max<kPbWaves>(m, sh);
     const double part = (m == -INFINITY) ? 0.0 : s * exp(m - M);
-    return log(pb_block_sum(part, sh)) + M;
+    return log(ps_block_sum<kPbWaves>(part, sh)) + M;
   }
 };
 
@@ -124,7 +109,7 @@ __global__ void __launch_bounds__(kPbThreads) psis_batch_kernel(const PsisBatchA
   __shared__ int ti[kPbTailCap];
   __shared__ double q_bs[kPbQuadCap], q_L[kPbQuadCap], q_w[kPbQuadCap];
   __shared__ double bc[2];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x, wave = t >> 6;
   const int n = a.n;
   double* __restrict__ row = a.A + (int64_t)blockIdx.x * a.ld;
 
@@ -169,7 +154,7 @@ __global__ void __launch_bounds__(kPbThreads) psis_batch_kernel(const PsisBatchA
   // 1. improve numerical accuracy: x -= max(x)   (_psis.py:166)
   double mx = -INFINITY;
   each([&](int, double v) { mx = fmax(mx, v); });
-  mx = pb_block_max(mx, sh);
+  mx = ps_block_max<kPbWaves>(mx, sh);
 #pragma unroll
   for (int u = 0; u < VPT; ++u) r[u] -= mx;
 
@@ -184,52 +169,16 @@ __global__ void __launch_bounds__(kPbThreads) psis_batch_kernel(const PsisBatchA
     __syncthreads();
     const unsigned long long prefix = sel_prefix;
     const unsigned long long mask = pass == 7 ? 0ull : (~0ull << (8 * (pass + 1)));
-    // the top bytes of log weights are sign and exponent: a wave's 64 keys fall into one or two bins (psis_kernel): two
-    // rounds of "the first lane's bin is counted by one add", the rest lane by lane
 #pragma unroll
     for (int u = 0; u < VPT; ++u) {
       const unsigned long long k = ps_key(r[u]);
-      const int bin = (int)((k >> (8 * pass)) & 255ull);
-      bool act = (k & mask) == prefix;
-#pragma unroll
-      for (int round = 0; round < 2; ++round) {
-        const unsigned long long todo = __ballot(act);
-        if (!todo) break;
-        const int leader = __builtin_ctzll(todo);
-        const int b = __shfl(bin, leader, 64);
-        const bool same = act && bin == b;
-        const unsigned long long mm = __ballot(same);
-        if (lane == leader) atomicAdd(&hist[b], __builtin_popcountll(mm));
-        act = act && !same;
-      }
-      if (act) atomicAdd(&hist[bin], 1);
+      ps_hist_add(hist, (int)((k >> (8 * pass)) & 255ull), (k & mask) == prefix);
     }
     __syncthreads();
-    if (wave == 0) {      // the bin that holds the wanted rank: four consecutive bins per lane
-      const long long want = sel_rank;
-      const int c0 = hist[4 * lane], c1 = hist[4 * lane + 1], c2 = hist[4 * lane + 2], c3 = hist[4 * lane + 3];
-      long long incl = (long long)c0 + c1 + c2 + c3;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const long long up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-      }
-      const long long excl = incl - ((long long)c0 + c1 + c2 + c3);
-      const bool mine = (excl <= want && want < incl) || (lane == 63 && want >= incl);
-      if (mine) {
-        long long rr = want - excl;
-        int bin = 4 * lane, cb = c0;
-        if (rr >= c0 && bin < 255) { rr -= c0; ++bin; cb = c1;
-          if (rr >= c1 && bin < 255) { rr -= c1; ++bin; cb = c2;
-            if (rr >= c2 && bin < 255) { rr -= c2; ++bin; cb = c3; } } }
-        sel_rank = rr;
-        sel_prefix = prefix | ((unsigned long long)bin << (8 * pass));
-        sel_bin_count = cb;
-      }
-    }
+    if (wave == 0) ps_scan_hist256(hist, prefix, 8 * pass, &sel_prefix, &sel_rank, &sel_bin_count);
     __syncthreads();
     pass_done = pass;
-    if (pass > 0 && sel_bin_count <= kPbBinCap) break;      // (uniform: a shared value read behind the barrier)
+    if (pass > 0 && sel_bin_count <= kPbThreads) break;      // (uniform: a shared value read behind the barrier)
   }
   if (pass_done > 0) {
     // the members of the selected bin, one per thread, counted against each other
@@ -237,51 +186,26 @@ __global__ void __launch_bounds__(kPbThreads) psis_batch_kernel(const PsisBatchA
     if (t == 0) tail_count = 0;
     __syncthreads();
     const unsigned long long prefix = sel_prefix, mask = ~0ull << (8 * pass_done);
-    each([&](int, double v) {
-      const unsigned long long k = ps_key(v);
-      if ((k & mask) == prefix) {
-        const int p = atomicAdd(&tail_count, 1);
-        if (p < kPbBinCap) bk[p] = k;
-      }
-    });
+    each([&](int, double v) { ps_bin_put<kPbThreads>(v, prefix, mask, bk, &tail_count); });
     __syncthreads();
-    const int nb = tail_count < kPbBinCap ? tail_count : kPbBinCap;
-    const long long want = sel_rank;
-    if (t < nb) {
-      const unsigned long long mk = bk[t];
-      int lt = 0, le = 0;
-      for (int j = 0; j < nb; ++j) {
-        const unsigned long long o = bk[j];
-        lt += o < mk ? 1 : 0;
-        le += o <= mk ? 1 : 0;
-      }
-      if (lt <= want && want < le) sel_prefix = mk;      // (every thread that holds this key writes the same value)
-    }
+    ps_rank_among(bk, tail_count < kPbThreads ? tail_count : kPbThreads, &sel_prefix, &sel_rank);
     __syncthreads();
   }
-  const double cutoffmin = log(DBL_MIN);                       // :159
-  const double xcutoff = fmax(ps_unkey(sel_prefix), cutoffmin);
-  const double expxc = exp(xcutoff);
+  double expxc;
+  const double xcutoff = ps_cutoff(sel_prefix, &expxc);
 
   // 3. right tail: x > xcutoff   (:175-177)
   __syncthreads();
   if (t == 0) tail_count = 0;
   __syncthreads();
-  each([&](int i, double v) {
-    if (v > xcutoff) {
-      const int p = atomicAdd(&tail_count, 1);
-      if (p < kPbTailCap) {
-        tv[p] = v;
-        ti[p] = i;
-      }
-    }
-  });
+  each([&](int i, double v) { ps_tail_put<kPbTailCap>(i, v, xcutoff, tv, ti, &tail_count); });
   __syncthreads();
   const int n2 = tail_count < kPbTailCap ? tail_count : kPbTailCap;
   double k = INFINITY, sigma = NAN;
   bool replaced = false;
   if (n2 > 4) {                                                 // :178-180
     // 4. order of the tail by (value, index): every element counts the elements before it and moves to that position
+    // (psis_kernel's generic branch, spelled out in both: see there)
     constexpr int kPer = kPbTailCap / kPbThreads;
     double my_v[kPer];
     int my_i[kPer], my_r[kPer];
@@ -319,82 +243,19 @@ __global__ void __launch_bounds__(kPbThreads) psis_batch_kernel(const PsisBatchA
       }
     }
     __syncthreads();
-    // x2 = exp(x2) - exp(xcutoff)   (:185-186)
-    for (int i = t; i < n2; i += kPbThreads) tv[i] = exp(tv[i]) - expxc;
-    __syncthreads();
+    ps_tail_exp<kPbThreads>(tv, n2, expxc);      // x2 = exp(x2) - exp(xcutoff)   (:185-186)
 
-    // 5. gpdfitnew (:266-325): PRIOR = 3, m = 30 + int(sqrt(n2))
-    const int m = 30 + (int)sqrt((double)n2);
-    const double xq = tv[(int)(n2 / 4.0 + 0.5) - 1], xl = tv[n2 - 1];
-    if (t < m) q_bs[t] = (1.0 - sqrt((double)m / ((double)(t + 1) - 0.5))) / (3.0 * xq) + 1.0 / xl;
-    __syncthreads();
-    // sixteen lanes per quadrature point, each a fixed stride of the tail, combined by a fixed butterfly: psis_kernel's
-    // order of additions (log(1 + y) for log1p(y): see there)
-    const int grp = t >> 4, gl = t & 15;
-    for (int j = grp; j < m; j += kPbThreads / 16) {          // ks_j = mean log1p(-bs_j x)
-      const double nb = -q_bs[j];
-      double s = 0.0;
-      int i = gl;
-      for (; i + 48 < n2; i += 64) {
-        const double l0 = log(fma(nb, tv[i], 1.0)), l1 = log(fma(nb, tv[i + 16], 1.0)), l2 = log(fma(nb, tv[i + 32], 1.0)),
-                     l3 = log(fma(nb, tv[i + 48], 1.0));
-        s += l0;
-        s += l1;
-        s += l2;
-        s += l3;
-      }
-      for (; i < n2; i += 16) s += log(fma(nb, tv[i], 1.0));
-#pragma unroll
-      for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-      if (gl == 0) {
-        const double ks = s / n2;
-        q_L[j] = n2 * (log(-(q_bs[j] / ks)) - ks - 1.0);
-      }
-    }
-    __syncthreads();
-    for (int j = grp; j < m; j += kPbThreads / 16) {
-      const double lj = q_L[j];
-      double s = 0.0;
-      for (int i = gl; i < m; i += 16) s += exp(q_L[i] - lj);
-#pragma unroll
-      for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-      if (gl == 0) {
-        const double w = 1.0 / s;
-        q_w[j] = w >= 10.0 * DBL_EPSILON ? w : 0.0;              // remove negligible weights
-      }
-    }
-    __syncthreads();
-    if (t == 0) {
-      double ws = 0.0, bsum = 0.0;
-      for (int i = 0; i < m; ++i) ws += q_w[i];
-      for (int i = 0; i < m; ++i) bsum += q_bs[i] * (q_w[i] / ws);
-      bc[0] = bsum;                                              // posterior mean of b
-    }
-    __syncthreads();
-    const double b = bc[0];
-    double s = 0.0;
-    for (int i = t; i < n2; i += kPbThreads) s += log1p(-b * tv[i]);
-    s = pb_block_sum(s, sh);
-    k = s / n2;
-    sigma = -k / b;
-    k = k * n2 / (n2 + 10.0) + 10.0 * 0.5 / (n2 + 10.0);        // weakly informative prior, a = 10
+    // 5. gpdfitnew (:266-325), in psis_kernel's order of additions
+    const int m = ps_quad_points(tv, n2, q_bs);
+    ps_quad_ks<kPbThreads>(tv, n2, m, q_bs, q_L);
+    k = ps_gpd_fit<kPbThreads>(tv, n2, m, q_bs, q_L, q_w, bc, sh, &sigma);
 
     // 6. smoothed tail (:188-199): order statistics of the fitted GPD, truncated at the largest raw weight; left in
     // tv (sorted order) beside the element indices ti
     replaced = k >= 1.0 / 3.0 && !isinf(k);
     if (replaced) {
       __syncthreads();
-      for (int i = t; i < n2; i += kPbThreads) {
-        const double p = ((double)i + 0.5) / n2;
-        double qq = NAN;
-        if (sigma > 0.0) {
-          const double l = log1p(-p);
-          qq = (fabs(k) < DBL_EPSILON ? -l : expm1(-k * l) / k) * sigma;
-        }
-        double v = log(qq + expxc);
-        if (v > 0.0) v = 0.0;
-        tv[i] = v;
-      }
+      for (int i = t; i < n2; i += kPbThreads) tv[i] = ps_quantile(i, n2, k, sigma, expxc);
     }
   }
   __syncthreads();
@@ -406,14 +267,14 @@ __global__ void __launch_bounds__(kPbThreads) psis_batch_kernel(const PsisBatchA
   });
   if (replaced)
     for (int i = t; i < n2; i += kPbThreads) m2 = fmax(m2, tv[i]);
-  m2 = pb_block_max(m2, sh);
+  m2 = ps_block_max<kPbWaves>(m2, sh);
   double se = 0.0;
   each([&](int, double v) {
     if (!(replaced && v > xcutoff)) se += exp(v - m2);
   });
   if (replaced)
     for (int i = t; i < n2; i += kPbThreads) se += exp(tv[i] - m2);
-  se = pb_block_sum(se, sh);
+  se = ps_block_sum<kPbWaves>(se, sh);
   const double lse = log(se) + m2;
   if (t == 0) a.khat[blockIdx.x] = k;
 
@@ -617,7 +478,7 @@ static int glm_pointwise_enqueue(vb_ctx* ctx, hipStream_t st, const GlmLayout& L
 // read: the second pass comes from the cache).  Pass 1: the weighted sums of eta, mu(eta), V(eta) and the running
 // log-sum-exp of log w + log p(y | eta) (glm_predict_term: one exponential per element for all three).  Pass 2: the
 // weighted squared deviations of eta and mu from those means -- never E[x^2] - E[x]^2.  Thread t takes the elements
-// t + 256 k in order, the workgroup's sums are pb_block_sum's fixed tree: bit-reproducible.  An element of weight 0 adds
+// t + 256 k in order, the workgroup's sums are ps_block_sum's fixed tree: bit-reproducible.  An element of weight 0 adds
 // nothing, whatever its value (the guard keeps 0 * inf out of the sums).
 template <int LINK>
 __global__ void __launch_bounds__(kPbThreads) glm_predict_kernel(const PredictArgs a) {
@@ -652,9 +513,9 @@ __global__ void __launch_bounds__(kPbThreads) glm_predict_kernel(const PredictAr
     }
     if (has_y) lse.add(tl);
   }
-  const double eta_mean = pb_block_sum(s_eta, sh);
-  const double mean = pb_block_sum(s_mu, sh);
-  const double within = pb_block_sum(s_v, sh);
+  const double eta_mean = ps_block_sum<kPbWaves>(s_eta, sh);
+  const double mean = ps_block_sum<kPbWaves>(s_mu, sh);
+  const double within = ps_block_sum<kPbWaves>(s_v, sh);
 
   double d_eta = 0.0, d_mu = 0.0;
   for (int64_t i0 = t; i0 < n; i0 += CH * kPbThreads) {
@@ -675,8 +536,8 @@ __global__ void __launch_bounds__(kPbThreads) glm_predict_kernel(const PredictAr
       d_mu += live ? w[q] * (dm * dm) : 0.0;
     }
   }
-  const double eta_var = pb_block_sum(d_eta, sh);
-  const double between = pb_block_sum(d_mu, sh);
+  const double eta_var = ps_block_sum<kPbWaves>(d_eta, sh);
+  const double between = ps_block_sum<kPbWaves>(d_mu, sh);
   if (t == 0) {
     a.eta_mean[blockIdx.x] = eta_mean;
     a.eta_var[blockIdx.x] = eta_var;
